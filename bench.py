@@ -2,15 +2,20 @@
 """Headline benchmark: NeRF-SH training rays/sec (800x800 images, 64 coarse + 128 fine samples)
 on N MI355X, BASELINE.json configs[1] (chair-shaped SH16 workload, 4096 rays per GPU per step).
 
-    python bench.py                      # 1 GPU, 100 timed steps
+    python bench.py                      # 1 GPU, 100 timed steps, headline only
+    python bench.py --full               # + per-kernel table, CPU baseline and every other record
     python bench.py --gpus 8             # spawns 8 ranks itself (torch.distributed.run, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one full train_step (nerf_sh/train.py:51-121) on a synthetic batch: batch sampling,
 coarse level forward + reverse, fine level forward + reverse (incl. the 10k-point sparsity branch),
 the gradient exchange (N > 1: two RCCL all-reduces, MLP_0's half of the 4.05 MB arena under the fine level,
-MLP_1's half + stats at the end), Adam + weight re-pack.  Rank 0 prints ONE JSON line; besides the headline it
-carries records of the other BASELINE configs and of the metric's second half:
+MLP_1's half + stats at the end), Adam + weight re-pack.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, the warm-up steps, the timed steps, the outputs of the last timed
+step (`--dump-outputs DIR`: DIR/<name>.npy, float32) and the line.  With `--full` the line also carries the
+per-kernel table (a few untimed steps of their own), the CPU baseline, and records of the other BASELINE configs and of
+the metric's second half:
 `converge` (eval PSNR on held-out 800x800 views after a fixed training budget), `strong512` (configs[2] strong-scaling
 shape), `tt_sh25` (configs[3] shape), `coarse64` (configs[0] shape: 64 coarse samples only), `render_fwd` (the eval
 path), `grid512` (configs[4]), `octree` (the PlenOctree-side kernels with their HBM rooflines) and the two
@@ -54,8 +59,12 @@ def parse(argv=None):
     p.add_argument("--batch", type=int, default=4096, help="rays per GPU per step (weak) / global (strong)")
     p.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     p.add_argument("--preset", choices=["blender", "tt"], default="blender")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="headline only")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: the per-kernel table, the CPU baseline and the --extras records (off: headline only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (parameters, Adam moments, gradient, stats) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    p.add_argument("--no-extras", action="store_true", help="with --full: leave the --extras records out")
     p.add_argument("--extras", default=",".join(ALL_EXTRAS), help="comma-separated subset of " + ",".join(ALL_EXTRAS + OPT_IN_EXTRAS))
     p.add_argument("--force-dist", action="store_true",
                    help="initialise RCCL and issue the per-step collectives even with one rank (exercises the "
@@ -273,7 +282,7 @@ class Job:
         self.ranks_seen = 1
         self.pdist = pdist
         self.exchange = self.world > 1 or a.force_dist       # do the legs other than strong512 exchange gradients?
-        want_strong = self.cuda and not a.no_extras and "strong512" in a.extras.split(",")
+        want_strong = self.cuda and a.full and not a.no_extras and "strong512" in a.extras.split(",")
         if self.exchange or want_strong:
             # the group (and with it RCCL's high-priority stream) is created BEFORE any kernel runs: created after the
             # headline leg, the same stream made the 512-ray step 26 % slower (4.55 vs 3.60 ms, profiles/r04h_late_group.txt)
@@ -334,11 +343,13 @@ def read_kernels(ops, deg):
     return kernels
 
 
-def run_train(job, preset, steps, warmup, per_gpu=None, snapshot_step=None, events=True, exchange=None, **flag_over):
+def run_train(job, preset, steps, warmup, per_gpu=None, snapshot_step=None, events=True, exchange=None, outputs=False,
+              **flag_over):
     """W untimed + K timed train steps of `preset`; returns a dict with elapsed (max over ranks), kernels, stats.
     snapshot_step: a copy of the parameters after exactly that many steps from the fixed-seed initialisation is kept
     (taken inside the run if it gets that far, by untimed extra steps otherwise), so that the records evaluated on
-    "a trained-ish network" do not depend on --steps / --warmup."""
+    "a trained-ish network" do not depend on --steps / --warmup.
+    outputs: host copies of what the last timed step left in the train state (before any untimed step) under "outputs"."""
     from plenoctree_amd import ops
     from plenoctree_amd.nerf_sh.nerf import datasets, models, utils
     a = job.a
@@ -378,9 +389,13 @@ def run_train(job, preset, steps, warmup, per_gpu=None, snapshot_step=None, even
     elapsed = job.max_over_ranks(elapsed)
     deg = model.cfg.sh_deg
     stats = dict(zip(utils.Stats._fields, state.stats.cpu().tolist()))
+    captured = None
+    if outputs:
+        captured = {"params": state.params, "adam_m": state.m, "adam_v": state.v, "grads": state.grads, "stats": state.stats}
+        captured = {k: t.detach().to("cpu", torch.float32, copy=True) for k, t in captured.items()}
     dom = read_kernels(ops, deg)
     kernels = dom
-    if events and not a.no_kernel_events and job.cuda:
+    if events and a.full and not a.no_kernel_events and job.cuda:
         # the table of the other kernels: a few more steps, untimed, every tag bracketed (mlp_fwd's row stays the timed one)
         extra = min(10, max(steps, 1))
         ops.profile_enable(True)
@@ -394,7 +409,7 @@ def run_train(job, preset, steps, warmup, per_gpu=None, snapshot_step=None, even
     out = {"elapsed": elapsed, "per_gpu": per_gpu, "deg": deg, "kernels": kernels,
            "stats": stats, "args": args,
            "model": model, "state": state, "dataset": dataset, "one_step": one_step,
-           "collectives_per_step": 2 if reducer.active else 0}
+           "collectives_per_step": 2 if reducer.active else 0, "outputs": captured}
     if snapshot_step is not None:
         for s in range(state.step, snapshot_step):          # untimed: a short run did not get there
             one_step(s)
@@ -682,6 +697,14 @@ def run_octree(job, a):
     return rec
 
 
+def dump_outputs(out_dir, outputs):
+    """What the last timed step computed, one float32 DIR/<name>.npy per array (~16 MB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     a = parse(argv)
@@ -717,12 +740,18 @@ def main(argv=None):
                 ops.set_tuning(knobs[k], int(v))
             tuning[k] = int(v)
 
-    want = [] if a.no_extras else [e for e in a.extras.split(",") if e]
+    want = [e for e in a.extras.split(",") if e]
     unknown = [e for e in want if e not in ALL_EXTRAS + OPT_IN_EXTRAS]
     if unknown:
         raise SystemExit(f"bench.py --extras: unknown record(s) {unknown}")
+    if a.no_extras or not a.full:
+        want = []
     need_snapshot = any(e in want for e in ("render_fwd", "grid512", "bf16x3", "bf16x6"))
-    tr = run_train(job, a.preset, a.steps, a.warmup, snapshot_step=a.eval_step if need_snapshot else None)
+    tr = run_train(job, a.preset, a.steps, a.warmup, snapshot_step=a.eval_step if need_snapshot else None,
+                   outputs=a.dump_outputs is not None)
+    if a.dump_outputs is not None and rank == 0:
+        dump_outputs(a.dump_outputs, tr["outputs"])
+    tr["outputs"] = None
     extras = {}
     if "strong512" in want:
         extras["strong512"] = run_strong(job, a)
@@ -779,7 +808,7 @@ def main(argv=None):
     # since round 6) run at N = 1 only: at N > 1 the other ranks sit in the closing barrier's collective meanwhile, next to its
     # watchdog, so they get the two B = 1024 shapes (~1 minute, as in round 5) and the line says which were left out
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(a, head["args"], job.device, long_legs=world == 1)
     if rank == 0:
         per_gpu, deg, kernels = head["per_gpu"], head["deg"], head["kernels"]

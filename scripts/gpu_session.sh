@@ -25,7 +25,8 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 R=$PWD
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-HEAD_ARGS="--no-cpu-baseline --no-extras"
+HEAD_ARGS="--full --no-cpu-baseline --no-extras"      # headline + per-kernel table
+BENCH_ARGS="--full ${BENCH_ARGS:-}"                    # the bench stage records the whole line (every record, CPU baseline)
 PROF_HEAD_ARGS="$HEAD_ARGS --no-kernel-events"      # under rocprofv3 the HIP-event brackets are only extra barrier packets
 nproc > gpurun_out/device.txt; rocminfo 2>/dev/null | grep -E "Marketing Name|Compute Unit|Max Clock" | head -8 >> gpurun_out/device.txt
 

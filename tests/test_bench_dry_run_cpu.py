@@ -14,6 +14,7 @@ import socket
 import sys
 import tempfile
 
+import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
@@ -23,7 +24,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-ARGS = ["--backend", "gloo", "--batch", "8", "--steps", "2", "--warmup", "1", "--strong-rays", "4", "--grid-reso", "8",
+ARGS = ["--backend", "gloo", "--full", "--batch", "8", "--steps", "2", "--warmup", "1", "--strong-rays", "4", "--grid-reso", "8",
         "--eval-step", "2", "--converge-steps", "2", "--converge-views", "1", "--image-factor", "100",
         "--sparsity-npoints", "16", "--cpu-rays", "8", "--cpu-steps", "1", "--cpu-warmup", "1", "--no-cpu-full", "--per-host-image",
         "--extras", "converge,strong512,render_fwd,grid512,coarse64,tt_sh25"]
@@ -37,7 +38,7 @@ def _free_port():
     return port
 
 
-def _worker(rank, world, port, outdir):
+def _worker(rank, world, port, outdir, args=ARGS):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     torch.set_num_threads(2)
@@ -55,7 +56,7 @@ def _worker(rank, world, port, outdir):
     dist.all_reduce = counting_all_reduce
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        rc = bench.main(ARGS + ["--gpus", str(world)])
+        rc = bench.main(args + ["--gpus", str(world)])
     with open(os.path.join(outdir, f"rank{rank}.json"), "w") as f:
         json.dump({"rc": rc, "stdout": buf.getvalue(), "calls": calls, "all_reduce_calls": n_collectives["n"]}, f)
 
@@ -91,3 +92,40 @@ def test_bench_two_rank_dry_run():
     # both ranks did the same work: every stand-in was reached the same number of times, cameras were sharded
     assert res[0]["calls"] == res[1]["calls"] and res[0]["calls"]["grid_weight_render"] == 1
     assert res[0]["all_reduce_calls"] == res[1]["all_reduce_calls"] > 0
+
+
+PLAIN_ARGS = ["--backend", "gloo", "--batch", "8", "--steps", "3", "--warmup", "1", "--image-factor", "100",
+              "--sparsity-npoints", "16", "--per-host-image"]
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_headline_only_and_dumps_outputs():
+    """Without --full: the warm-up and exactly --steps timed steps, no other record, no CPU baseline; --dump-outputs writes
+    the train state the last timed step left, identical from run to run with the same arguments."""
+    dumps = []
+    with tempfile.TemporaryDirectory() as outdir:
+        for run in range(2):
+            dump = os.path.join(outdir, f"dump{run}")
+            mp.spawn(_worker, args=(1, _free_port(), outdir, PLAIN_ARGS + ["--dump-outputs", dump]), nprocs=1, join=True)
+            res = json.load(open(os.path.join(outdir, "rank0.json")))
+            assert res["rc"] == 0
+            assert res["calls"]["train_fwd_bwd"] == 1 + 3                  # warm-up + timed, nothing after them
+            assert res["calls"]["render_fwd"] == res["calls"]["grid_sigma"] == 0
+            lines = [l for l in res["stdout"].splitlines() if l.strip()]
+            assert len(lines) == 1, lines
+            out = json.loads(lines[0])
+            for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+                assert k in out
+            assert out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+            assert "cpu_baseline" not in out and not set(out) & {"converge", "strong512", "render_fwd", "grid512", "coarse64",
+                                                                  "tt_sh25", "octree", "opt_in_bf16x6_training"}
+            names = sorted(os.listdir(dump))
+            assert names == ["adam_m.npy", "adam_v.npy", "grads.npy", "params.npy", "stats.npy"]
+            arrs = {n[:-4]: np.load(os.path.join(dump, n)) for n in names}
+            assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in arrs.values())
+            assert arrs["params"].shape == arrs["grads"].shape == arrs["adam_m"].shape and arrs["stats"].shape == (6,)
+            assert sum(v.nbytes for v in arrs.values()) <= 64 << 20
+            assert np.isclose(arrs["stats"][0], out["final_stats"]["loss"])
+            dumps.append(arrs)
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n])

@@ -103,45 +103,23 @@ def test_sigma_grid_matches_reference_point_list_and_mesh_scaling(tmp_path):
     assert gen_mesh._triple("5", int) == [5, 5, 5] and gen_mesh._triple("1 2 3", float) == [1.0, 2.0, 3.0]
 
 
-def _reference_function(path, name):
-    """Source of one top-level function of a reference file, compiled on its own (the file's imports - jax, flax,
-    mcubes - are not needed by the functions taken this way)."""
-    import ast
+def test_save_obj_and_grid_match_the_references_own_code(tmp_path, golden_dir):
+    """nerf_sh/gen_mesh.py's own `save_obj` (:133-158) and `marching_cubes` (:105-129, executed with the sigma evaluation and
+    PyMCubes replaced by stand-ins) were run on the inputs below by tests/golden/make_golden_consumers.py: ours writes
+    byte-identical files, with and without vertex colours, and gives the same vertices and faces."""
     import os
-    import pytest
-    if not os.path.exists(path):
-        pytest.skip("needs /root/reference")
-    src = open(path).read()
-    fn = next(n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == name)
-    ns = {"np": np}
-    exec(compile(ast.Module([fn], []), path, "exec"), ns)
-    return ns[name]
-
-
-def test_save_obj_and_grid_match_the_references_own_code(tmp_path):
-    """nerf_sh/gen_mesh.py's own `save_obj` (:133-158) run next to ours on the same mesh: byte-identical files, with and
-    without vertex colours; and the reference's grid construction + vertex rescaling (:105-111, :126-129, executed with the
-    sigma evaluation and PyMCubes replaced by stand-ins) gives the same vertices as `gen_mesh.marching_cubes`."""
-    ref_save = _reference_function("/root/reference/nerf_sh/gen_mesh.py", "save_obj")
-    rng = np.random.default_rng(3)
-    verts = rng.normal(size=(57, 3)) * 3.0
-    faces = rng.integers(0, 57, size=(101, 3))
-    cols = rng.random(size=(57, 3))
-    for c in (None, cols):
-        a, b = str(tmp_path / "ref.obj"), str(tmp_path / "ours.obj")
-        ref_save(verts, faces, a, vert_rgb=c)
+    import sys
+    z = np.load(os.path.join(golden_dir, "reference_consumers.npz"))
+    sys.path.insert(0, golden_dir)
+    try:
+        from make_golden_consumers import MC_ARGS, _mc_field, mesh_inputs
+    finally:
+        sys.path.remove(golden_dir)
+    verts, faces, cols = mesh_inputs()
+    for tag, c in (("plain", None), ("rgb", cols)):
+        b = str(tmp_path / "ours.obj")
         gen_mesh.save_obj(verts, faces, b, vert_rgb=c)
-        assert open(a, "rb").read() == open(b, "rb").read()
-    # marching_cubes(): the reference's body with its three externals stubbed
-    import types
-    ref_mc = _reference_function("/root/reference/nerf_sh/gen_mesh.py", "marching_cubes")
-    field = lambda p: (1.0 - p.norm(dim=-1, keepdim=True)) * 3.0
-    c1, c2, reso = [-2.0, -1.0, -1.5], [2.0, 1.0, 1.5], [21, 17, 13]
-    g = ref_mc.__globals__
-    g["h0print"] = lambda *a, **k: None
-    g["utils"] = types.SimpleNamespace(eval_points=lambda fn, grid, chunk: (None, fn(torch.from_numpy(np.ascontiguousarray(grid))).numpy()))
-    g["jax"] = types.SimpleNamespace(host_id=lambda: 0)
-    g["mcubes"] = types.SimpleNamespace(marching_cubes=lambda vol, iso: isosurface.marching_cubes(vol, iso))
-    v_ref, f_ref = ref_mc(field, c1, c2, reso, 0.0, 1000)
-    v_our, f_our = gen_mesh.marching_cubes(field, c1, c2, reso, 0.0, 1000, torch.device("cpu"))
-    assert np.array_equal(f_ref, f_our) and np.allclose(v_ref, v_our, rtol=0, atol=1e-12)
+        assert open(b, "rb").read() == z[f"obj_{tag}"].tobytes()
+    c1, c2, reso, iso, chunk = MC_ARGS
+    v_our, f_our = gen_mesh.marching_cubes(_mc_field, c1, c2, reso, iso, chunk, torch.device("cpu"))
+    assert np.array_equal(z["mc_faces"], f_our) and np.allclose(z["mc_verts"], v_our, rtol=0, atol=1e-12)

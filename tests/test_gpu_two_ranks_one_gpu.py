@@ -115,7 +115,7 @@ def test_bench_two_ranks_sharing_the_gpu():
     real kernels under the real multi-rank control flow -- 2 collectives per step, strong512 inside the existing group, x-slab
     sharded 64^3 grid + all-gather, camera-sharded weight mask + max-all-reduce, sharded eval render -- one JSON line."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--full",
            "--steps", "4", "--warmup", "1", "--batch", "1024", "--grid-reso", "64", "--eval-step", "6", "--converge-steps", "30",
            "--converge-views", "1", "--image-factor", "8", "--no-cpu-baseline", "--extras", "converge,strong512,render_fwd,grid512"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=800)
