@@ -296,7 +296,8 @@ def piecewise_constant_pdf(bins, weights, num_samples, u):
         weight_sum = weight_sum + padding
         pdf = weights / weight_sum
         cdf = torch.clamp(torch.cumsum(pdf[..., :-1], dim=-1), max=1)
-        cdf = torch.cat([torch.zeros_like(cdf[..., :1]), cdf, torch.ones_like(cdf[..., :1])], -1)
+        # (zeros / ones of shape [..., 1] even when cdf is empty: one bin between three coarse samples)
+        cdf = torch.cat([cdf.new_zeros(*cdf.shape[:-1], 1), cdf, cdf.new_ones(*cdf.shape[:-1], 1)], -1)
         if u is None:
             u = torch.linspace(0.0, 1.0 - float(np.finfo(np.float32).eps), num_samples, dtype=dt)
             u = u.expand(*cdf.shape[:-1], num_samples)

@@ -578,6 +578,9 @@ __global__ __launch_bounds__(kYThreads, 2) void mlp_fwd_x6_kernel(
   }
 }
 
+// The reduce of the bias partials (launch_mlp_bwd_weights, wgrad_kernels.hip) counts this kernel's tile slots with
+// mlp_bwd_partials(M), i.e. tile_sched(M, mlp_grid(M)).  That is this launch's schedule only while mlp_grid == x6_grid.
+static_assert(kMlpWgPerCu == 1, "x6_grid launches one workgroup per CU: mlp_bwd_partials must count this grid's slots");
 static unsigned x6_grid(int64_t M) {
   const int64_t tiles = num_tiles(M), cap = (int64_t)num_cus();
   return (unsigned)(tiles < cap ? tiles : cap);

@@ -266,7 +266,8 @@ def _oracle_composite(cfg, rays, raw_rgb, raw_sigma, z):
 
 
 @pytest.mark.parametrize("deg,S,white,opaque", [(3, 64, True, False), (3, 192, True, False), (4, 192, True, True),
-                                                  (1, 40, False, False), (0, 7, True, False), (2, 130, True, True)])
+                                                  (1, 40, False, False), (0, 7, True, False), (2, 130, True, True),
+                                                  (3, 256, True, False), (4, 255, False, False)])
 def test_shade_composite_fwd_bwd(deg, S, white, opaque):
     ops = _ops(); dev = _gpu()
     cfg = O.Cfg(sh_deg=deg, white_bkgd=white)
@@ -290,7 +291,8 @@ def test_shade_composite_fwd_bwd(deg, S, white, opaque):
     close("d_raw_sigma", d_sigma, rs.grad.reshape(-1), rtol=2e-4, atol=1e-6 * max(1.0, float(rs.grad.abs().max())))
 
 
-@pytest.mark.parametrize("deg,S,white,n_sp", [(3, 64, True, 0), (3, 192, True, 1000), (4, 192, True, 257), (1, 40, False, 3)])
+@pytest.mark.parametrize("deg,S,white,n_sp", [(3, 64, True, 0), (3, 192, True, 1000), (4, 192, True, 257), (1, 40, False, 3),
+                                              (3, 256, True, 100), (4, 255, False, 0)])
 def test_shade_composite_train_fused(deg, S, white, n_sp):
     """The one-launch training form (compositing + pixel loss + reverse + sparsity rows) against the loss of
     nerf_sh/train.py:77-98 differentiated by autograd on the oracle, and against the separate fwd / bwd kernels."""
@@ -377,7 +379,7 @@ def test_composite_known_answers():
     assert torch.all(comp == 1.0) and torch.all(acc == 0.0) and torch.all(disp == 1e10)   # empty space, white bg
 
 
-@pytest.mark.parametrize("Nc,Nf", [(64, 128), (16, 8), (64, 192)])
+@pytest.mark.parametrize("Nc,Nf", [(64, 128), (16, 8), (64, 192), (128, 128), (3, 1)])
 def test_sample_pdf(Nc, Nf):
     ops = _ops(); dev = _gpu()
     B = 101
