@@ -298,8 +298,9 @@ int pxo_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const flo
                                void* stream);
 
 /* How much of the last pxo_train_fwd_bwd call's reverse pass was live: 16-row chunks with a non-zero upstream gradient
- * out of all chunks of both levels (with cfg->skip_zero_rows = 0 both numbers are the total).  Reads the flags the call
- * left in `ws`; synchronises `stream`.  Reporting only (bench.py's `converge` record, tests). */
+ * out of all chunks of both levels (with cfg->skip_zero_rows = 0, or when the call ran dense, both numbers are the total).
+ * Reads the record and the flags the call left in `ws` (PXO_ERR_ARG: no call has left a record there); synchronises
+ * `stream`.  Reporting only (bench.py's `converge` record, tests). */
 int pxo_train_backward_work(const PxoCfg* cfg, int64_t B, void* ws, size_t ws_bytes, int64_t* live_chunks,
                             int64_t* total_chunks, void* stream);
 
@@ -322,8 +323,9 @@ int pxo_grid_sigma(const PxoCfg* cfg, const float* packed_fwd, int reso, int x0,
                    const float offset[3], const float scale[3], float* sigma_out, void* stream);
 
 /* ---- run-time choices between implementations of the same result ----------------------- */
-/* Process-wide, and not synchronised with steps in flight on other host threads: a step reads each knob once when it is
- * enqueued (and records what it decided: pxo_train_backward_work reports for the step that ran, not for today's knobs).
+/* Process-wide, and not synchronised with steps in flight on other host threads: a call reads all knobs once, when it is
+ * enqueued, and decides from that one snapshot; a train step records its zero-row mode in its workspace
+ * (pxo_train_backward_work reports for the step that ran there, not for today's knobs).
  * The tile schedule leaves every bit unchanged; the split-K ranges change the (still fixed) order of the
  * weight-gradient sums, i.e. float32 round-off (tests/test_gpu_parity.py holds both).  Used by A/B sessions (bench.py --tune)
  * and equality tests; nothing is read from the environment.
@@ -338,9 +340,10 @@ int pxo_grid_sigma(const PxoCfg* cfg, const float* packed_fwd, int reso, int x0,
 #define PXO_TUNE_WGRAD_RANGES 1
 #define PXO_TUNE_WGRAD_SKINNY_RANGES 2   /* the same for the two skinny products (enc-based pair, heads): 1 .. 2 x number of CUs */
 /*   PXO_TUNE_COARSE_REVERSE_STREAM  0 (default): every launch of pxo_train_fwd_bwd* on the caller's stream.  1: the reverse pass of
- *                          the coarse level runs on an internal low-priority side stream (created on first use) beside the fine
- *                          level's forward and joins the caller's stream before the fine weight gradients; `grads0_ready` is
- *                          then recorded on that side stream.  Bits unchanged; +0.2 % / +0.7 % at 512 / 4096 rays (r06b). */
+ *                          the coarse level runs on an internal low-priority side stream (one per host thread and device,
+ *                          created on first use) beside the fine level's forward and joins the caller's stream before the
+ *                          fine weight gradients, or on any early return; `grads0_ready` is then recorded on that side
+ *                          stream.  Bits unchanged; +0.2 % / +0.7 % at 512 / 4096 rays (r06b). */
 #define PXO_TUNE_COARSE_REVERSE_STREAM 3
 /*   PXO_TUNE_X6_WGRAD      with PXO_MLP_BF16X6 only.  1 (default): the 256x256 weight-gradient products of Dense_1..7 run in bf16x6
  *                          too (wgrad_x6_kernels.hip); 0: on the float32 MFMA pipe like the float32 path (A/B). */

@@ -753,7 +753,7 @@ __device__ __forceinline__ bool bwd_subtile_x6(__bf16* __restrict__ planes, floa
       }
     }
     // bias gradient of layer l: column sums over the sub-tile's samples (= lanes), fixed order.  !db_all: Dense_1..7's come
-    // from the weight-gradient kernel, which sums the columns of dz_1..7 while it streams them (pxo_common.h kBiasFromWgrad)
+    // from the weight-gradient kernel, which sums the columns of dz_1..7 while it streams them (pxo_common.h StepPlan::bias_from_wgrad)
     if (db_all || l == 0) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {

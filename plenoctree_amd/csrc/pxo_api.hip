@@ -5,9 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "pxo_common.h"
@@ -49,8 +47,8 @@ int num_cus() {
 // run-time choices between implementations of the same result (pxo_set_tuning)
 // tile schedule: the device counter by default (r05b: 3.548 vs 3.556 ms per step at 512 rays, 23.78 vs 23.84 at 4096 in one
 // process, profiles/r05b_tune_ab.jsonl; and a workgroup that starts late is not the launch's tail, r05b_contention_probe.jsonl)
-// (atomics: a knob may be set from one host thread while another enqueues a step; each step reads a knob at most once per
-// decision and records what it decided, see g_step_skipped below)
+// (atomics: a knob may be set from one host thread while another enqueues a step; an entry point reads them all ONCE, through
+// tuning_snapshot, and passes down what it decided from that snapshot -- pxo_common.h StepPlan)
 static std::atomic<int> g_tune_tile_sched{1};
 static std::atomic<int> g_tune_wgrad_ranges{0};
 static std::atomic<int> g_tune_wgrad_skinny_ranges{0};
@@ -62,32 +60,54 @@ static std::atomic<int> g_tune_x6_wgrad{1};
 // and per-kernel HIP-event times stop meaning anything (the fine forward shares the GPU with the coarse reverse: 4.83 ms
 // "per launch" instead of 3.95), so the measured default stays the single stream.
 static std::atomic<int> g_tune_coarse_stream{0};
-static hipStream_t g_side_stream = nullptr;           // created on first use, lives for the process
-static hipEvent_t g_ev_fork = nullptr, g_ev_join = nullptr;
-static std::mutex g_side_mu;
-static bool side_stream_ready() {
-  std::lock_guard<std::mutex> lk(g_side_mu);
-  if (g_side_stream) return true;
+static Tuning tuning_snapshot() {
+  return Tuning{g_tune_tile_sched.load(), g_tune_wgrad_ranges.load(), g_tune_wgrad_skinny_ranges.load(),
+                g_tune_coarse_stream.load(), g_tune_x6_wgrad.load()};
+}
+
+// The side stream of that mode and its fork / join events: one set per host thread and device, created on first use and kept
+// for the thread's life (steps enqueued from different threads or for different devices never share them).
+struct SideStream { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
+static SideStream* side_stream() {
+  static thread_local std::vector<SideStream> per_device;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return nullptr;
+  if ((size_t)dev >= per_device.size()) per_device.resize(dev + 1);
+  SideStream& x = per_device[dev];
+  if (x.stream) return &x;
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-  if (hipStreamCreateWithPriority(&g_side_stream, hipStreamNonBlocking, lo) != hipSuccess) { g_side_stream = nullptr; return false; }
-  if (hipEventCreateWithFlags(&g_ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&g_ev_join, hipEventDisableTiming) != hipSuccess) {
-    (void)hipStreamDestroy(g_side_stream);
-    g_side_stream = nullptr;
-    return false;
+  if (hipStreamCreateWithPriority(&x.stream, hipStreamNonBlocking, lo) != hipSuccess) { x.stream = nullptr; return nullptr; }
+  if (hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&x.join, hipEventDisableTiming) != hipSuccess) {
+    (void)hipStreamDestroy(x.stream);
+    x.stream = nullptr;
+    return nullptr;
   }
-  return true;
+  return &x;
 }
-// Did the last pxo_train_fwd_bwd* call on a workspace run its reverse pass in skipping mode?  Decided once per step from the
-// cfg AND the split-K tuning in force at that moment; pxo_train_backward_work reports for THAT decision, whatever
-// pxo_set_tuning did since.
-static std::mutex g_step_mu;
-static std::unordered_map<const void*, bool> g_step_skipped;
-int tune_tile_sched() { return g_tune_tile_sched; }
-int tune_wgrad_ranges() { return g_tune_wgrad_ranges; }
-int tune_wgrad_skinny_ranges() { return g_tune_wgrad_skinny_ranges; }
-int tune_x6_wgrad() { return g_tune_x6_wgrad; }
+
+// The fork of the coarse reverse pass: it goes to `sc`, the side stream when `fork` and one is there (else `s`: the same kernels
+// in stream order, the same bits).  join() makes `s` wait for everything enqueued on `sc` so far; the destructor joins as
+// well, so that no return path leaves `s` running ahead of work still queued on the side stream.
+struct SideFork {
+  hipStream_t s, sc;
+  SideStream* side = nullptr;
+  SideFork(hipStream_t s_, bool fork) : s(s_), sc(s_) {
+    SideStream* x = fork ? side_stream() : nullptr;
+    if (x && hipEventRecord(x->fork, s) == hipSuccess && hipStreamWaitEvent(x->stream, x->fork, 0) == hipSuccess) {
+      side = x;
+      sc = x->stream;
+    }
+  }
+  ~SideFork() { (void)join(); }
+  bool join() {
+    if (!side) return true;
+    SideStream* x = side;
+    side = nullptr;
+    return hipEventRecord(x->join, sc) == hipSuccess && hipStreamWaitEvent(s, x->join, 0) == hipSuccess;
+  }
+};
 
 int validate_cfg(const PxoCfg* cfg) {
   PXO_REQUIRE(cfg != nullptr, "cfg is NULL");
@@ -177,6 +197,13 @@ static void carve_pass(Carver& c, PassBuffers& p, int64_t B, int S, int64_t extr
   }
 }
 
+// The scalars block of a train workspace (128 words): [0, kSumsqBlocks) parameter-norm partials, [96, 98) the live-chunk count
+// of pxo_train_backward_work, then the words the step's first launch writes (launch_uniform_jobs step_words): at 98 the step's
+// record, kStepRecord | (1 if its reverse pass skipped zero rows), at [100, 104) the tile counters of its MLP launches.
+constexpr int kStepWordsAt = 98;
+constexpr int kStepWords = 6;
+constexpr unsigned int kStepRecord = 0x5E7D5700u;
+
 struct TrainWs {
   PassBuffers c, f;
   float *t_rand, *u, *sp, *scalars, *sp_exp;
@@ -227,8 +254,8 @@ struct Draws { const float* t_rand; const float* u; bool noisy; uint64_t seed; }
 // every uniform draw of the step in one launch (jax.random.uniform call sites model_utils.py:135,262, train.py:79)
 static int prepare_draws(const PxoCfg* cfg, TrainWs& t, int64_t B, int randomized, const float* t_rand, const float* u,
                          const float* sp_points, uint64_t seed, hipStream_t s, Draws& out, const float* params = nullptr,
-                         int64_t n_params = 0, float* sumsq_partial = nullptr, unsigned int* zero_words = nullptr,
-                         int n_zero = 0) {
+                         int64_t n_params = 0, float* sumsq_partial = nullptr, unsigned int* step_words = nullptr,
+                         int n_words = 0, unsigned int first_word = 0) {
   const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
   PassBuffers& last = Nf > 0 ? t.f : t.c;
   UniformJob jobs[3];
@@ -250,7 +277,7 @@ static int prepare_draws(const PxoCfg* cfg, TrainWs& t, int64_t B, int randomize
   out.t_rand = t_rand; out.u = u;
   out.noisy = randomized != 0 && cfg->noise_std > 0.f;     // (noise_std is not None) and randomized, model_utils.py:329
   out.seed = seed;
-  return launch_uniform_jobs(seed, jobs, nj, s, params, n_params, sumsq_partial, zero_words, n_zero);
+  return launch_uniform_jobs(seed, jobs, nj, s, params, n_params, sumsq_partial, step_words, n_words, first_word);
 }
 
 static int forward_coarse(const PxoCfg* cfg, TrainWs& t, const float* pk0, const float* o, const float* d, const float* v,
@@ -404,7 +431,7 @@ int pxo_mlp_bwd_data(const PxoCfg* cfg, const float* packed_bwd, const float* d_
   PXO_REQUIRE(M >= 0 && packed_bwd && d_raw_rgb && d_raw_sigma && relu_mask && dz && dbias_partial,
               "pxo_mlp_bwd_data: bad arguments");
   return launch_mlp_bwd_data(cfg, packed_bwd, d_raw_rgb, d_raw_sigma, (const uint32_t*)relu_mask, M, dz,
-                             dbias_partial, nullptr, nullptr, (hipStream_t)stream);
+                             dbias_partial, nullptr, nullptr, (hipStream_t)stream, false);
 }
 
 int pxo_wgrad_workspace_bytes(const PxoCfg* cfg, int64_t M, size_t* bytes) {
@@ -420,8 +447,9 @@ int pxo_mlp_bwd_weights(const PxoCfg* cfg, const float* acts, const float* enc, 
   PXO_TRY(validate_cfg(cfg));
   PXO_REQUIRE(M >= 0 && acts && enc && dz && d_raw_rgb && d_raw_sigma && dbias_partial && grads && ws,
               "pxo_mlp_bwd_weights: bad arguments");
+  const StepPlan plan = plan_step(*cfg, M, 0, num_cus(), tuning_snapshot());
   return launch_mlp_bwd_weights(cfg, acts, enc, dz, d_raw_rgb, d_raw_sigma, dbias_partial, M, grads, ws, ws_bytes,
-                                nullptr, (hipStream_t)stream);
+                                nullptr, (hipStream_t)stream, plan.split_c, plan.x6_main, false);
 }
 
 int pxo_shade_composite_fwd(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, const float* z_vals,
@@ -597,75 +625,57 @@ int pxo_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const flo
   const int deg = cfg->sh_deg;
   const int64_t n_mlp = mlp_param_count(deg);
   const float wd_coef = 2.f * cfg->weight_decay_mult / (float)(2 * n_mlp);   // d/dp of weight_decay_mult * sum(p^2)/n (train.py:101-114)
-  // weight_l2 = sum(p^2) / n (train.py:101-108) depends on the parameters only: its partial sums ride in the step's first
-  // launch, together with every uniform draw
-  float* const sumsq_partial = t.scalars;
-  // Tile counters of the step's four persistent MLP launches (forward / backward(data) of each level), zeroed by the step's
-  // first launch: the dense kernels take their tiles from them when PXO_TUNE_TILE_SCHED = 1, the skipping backward always
-  unsigned int* const counters = reinterpret_cast<unsigned int*>(t.scalars + 100);
-  const bool dyn = tune_tile_sched() != 0;
-  unsigned int* const cnt_fwd_c = dyn ? counters + 0 : nullptr;
-  unsigned int* const cnt_fwd_f = dyn ? counters + 2 : nullptr;
-  unsigned int* const cnt_bwd_c = (dyn || cfg->skip_zero_rows) ? counters + 1 : nullptr;
-  unsigned int* const cnt_bwd_f = (dyn || cfg->skip_zero_rows) ? counters + 3 : nullptr;
   const int Nf = cfg->num_fine_samples;
+  // everything the step decides, from one snapshot of the tuning knobs, before its first launch
+  const StepPlan plan = plan_step(*cfg, t.c.M, Nf > 0 ? t.f.M : 0, num_cus(), tuning_snapshot());
+  // weight_l2 = sum(p^2) / n (train.py:101-108) depends on the parameters only: its partial sums ride in the step's first
+  // launch, together with every uniform draw and the step words: the step's record (what pxo_train_backward_work reports)
+  // and the tile counters of its four persistent MLP launches (forward / backward(data) of each level), zeroed -- the dense
+  // kernels take their tiles from them when plan.dyn, the skipping backward always
+  float* const sumsq_partial = t.scalars;
+  unsigned int* const step_words = reinterpret_cast<unsigned int*>(t.scalars + kStepWordsAt);
+  unsigned int* const counters = step_words + 2;
+  unsigned int* const cnt_fwd_c = plan.dyn ? counters + 0 : nullptr;
+  unsigned int* const cnt_fwd_f = plan.dyn ? counters + 2 : nullptr;
+  unsigned int* const cnt_bwd_c = (plan.dyn || cfg->skip_zero_rows) ? counters + 1 : nullptr;
+  unsigned int* const cnt_bwd_f = (plan.dyn || cfg->skip_zero_rows) ? counters + 3 : nullptr;
   Draws dr;
-  PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, sp_points, seed, s, dr, params, 2 * n_mlp, sumsq_partial, counters, 4));
+  PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, sp_points, seed, s, dr, params, 2 * n_mlp, sumsq_partial, step_words,
+                        kStepWords, kStepRecord | (plan.skip ? 1u : 0u)));
   // coarse level: forward, losses (train.py:77-98), reverse of the compositing, reverse through MLP_0.  Nothing of the fine
   // level feeds MLP_0's gradient (the fine sample positions carry no gradient, model_utils.py:286), so it is complete here
   // -- a quarter into the step -- and its all-reduce can ride under the fine level.
   PXO_TRY(forward_coarse(cfg, t, packed_fwd0, origins, directions, viewdirs, B, dr, pixels, nullptr, nullptr, nullptr, s,
                          cnt_fwd_c));
   // skip_zero_rows: rows with an exactly zero upstream gradient are left out of the reverse pass (bit-identical gradients)
-  // (a pass whose weight-gradient row ranges would not fit the kernels' live-chunk lists -- > 32,768 rows per range, i.e.
-  // more than 8.4 M sample rows on 256 CUs -- makes the whole reverse pass dense: same bits, no saving)
-  const bool skip = cfg->skip_zero_rows != 0 && wgrad_skip_supported(t.c.M) && (Nf == 0 || wgrad_skip_supported(t.f.M));
-  {
-    std::lock_guard<std::mutex> lk(g_step_mu);
-    g_step_skipped[ws] = skip;
-  }
-  uint8_t* const live_c = skip ? t.c.live : nullptr;
-  uint8_t* const live_f = skip ? t.f.live : nullptr;
+  uint8_t* const live_c = plan.skip ? t.c.live : nullptr;
+  uint8_t* const live_f = plan.skip ? t.f.live : nullptr;
   // The coarse reverse pass touches nothing the fine forward reads or writes (its own workspace slices, the MLP_0 half of
-  // `grads`; the weight-gradient slabs are shared with the fine pass, which therefore waits for it): with a fine level it runs
+  // `grads`; the weight-gradient slabs are shared with the fine pass, which therefore waits for it): with plan.fork it runs
   // on the side stream, beside sample_pdf / the fine forward, and joins before the fine weight gradients.
-  // bf16x6 with its own weight-gradient kernel: that kernel also sums the columns of dz_1..7 (the bias gradients of Dense_1..7)
-  // while it streams them, and backward(data) leaves its per-layer lane reductions for those layers out (read ONCE per step: the
-  // two launches of a pass must agree)
-  const int bias_flags = cfg->mlp_precision == PXO_MLP_BF16X6 && tune_x6_wgrad() != 0 ? kBiasFromWgrad : 0;
-  const bool fork = Nf > 0 && g_tune_coarse_stream.load() != 0 && side_stream_ready();
-  hipStream_t sc = s;
-  if (fork) {
-    if (hipEventRecord(g_ev_fork, s) != hipSuccess || hipStreamWaitEvent(g_side_stream, g_ev_fork, 0) != hipSuccess) {
-      set_error("pxo_train_fwd_bwd: fork to the side stream failed");
-      return PXO_ERR_HIP;
-    }
-    sc = g_side_stream;
-  }
+  SideFork fk(s, plan.fork);
   PXO_TRY(launch_mlp_bwd_data(cfg, packed_bwd0, t.c.d_raw_rgb, t.c.d_raw_sigma, t.c.mask, t.c.M, t.c.dz, t.c.dbias, live_c,
-                              cnt_bwd_c, sc, true, bias_flags));
+                              cnt_bwd_c, fk.sc, plan.bias_from_wgrad));
   PXO_TRY(launch_mlp_bwd_weights(cfg, t.c.acts, t.c.enc, t.c.dz, t.c.d_raw_rgb, t.c.d_raw_sigma, t.c.dbias, t.c.M,
-                                 grads, t.wgrad_ws, t.wgrad_bytes, live_c, sc, bias_flags));
-  if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads, params, n_mlp, wd_coef, sc));
-  if (grads0_ready && hipEventRecord((hipEvent_t)grads0_ready, sc) != hipSuccess) {
+                                 grads, t.wgrad_ws, t.wgrad_bytes, live_c, fk.sc, plan.split_c, plan.x6_main,
+                                 plan.bias_from_wgrad));
+  if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads, params, n_mlp, wd_coef, fk.sc));
+  if (grads0_ready && hipEventRecord((hipEvent_t)grads0_ready, fk.sc) != hipSuccess) {
     set_error("pxo_train_fwd_bwd: hipEventRecord(grads0_ready) failed");
-    return PXO_ERR_HIP;
-  }
-  if (fork && hipEventRecord(g_ev_join, sc) != hipSuccess) {
-    set_error("pxo_train_fwd_bwd: hipEventRecord(join) failed");
     return PXO_ERR_HIP;
   }
   if (Nf > 0) {
     PXO_TRY(forward_fine(cfg, t, packed_fwd1, origins, directions, viewdirs, B, dr, pixels, nullptr, nullptr, nullptr, s,
                          cnt_fwd_f));
     PXO_TRY(launch_mlp_bwd_data(cfg, packed_bwd1, t.f.d_raw_rgb, t.f.d_raw_sigma, t.f.mask, t.f.M, t.f.dz, t.f.dbias, live_f,
-                                cnt_bwd_f, s, true, bias_flags));
-    if (fork && hipStreamWaitEvent(s, g_ev_join, 0) != hipSuccess) {       // the slabs are the coarse pass's until here
+                                cnt_bwd_f, s, plan.bias_from_wgrad));
+    if (!fk.join()) {                                         // the slabs are the coarse pass's until here
       set_error("pxo_train_fwd_bwd: join of the side stream failed");
       return PXO_ERR_HIP;
     }
     PXO_TRY(launch_mlp_bwd_weights(cfg, t.f.acts, t.f.enc, t.f.dz, t.f.d_raw_rgb, t.f.d_raw_sigma, t.f.dbias, t.f.M,
-                                   grads + n_mlp, t.wgrad_ws, t.wgrad_bytes, live_f, s, bias_flags));
+                                   grads + n_mlp, t.wgrad_ws, t.wgrad_bytes, live_f, s, plan.split_f, plan.x6_main,
+                                   plan.bias_from_wgrad));
   } else {
     PXO_TRY(launch_fill(grads + n_mlp, n_mlp, 0.f, s));
   }
@@ -696,15 +706,15 @@ int pxo_train_backward_work(const PxoCfg* cfg, int64_t B, void* ws, size_t ws_by
   const int64_t nc = (t.c.M + kLiveRows - 1) / kLiveRows, nf = cfg->num_fine_samples > 0 ? (t.f.M + kLiveRows - 1) / kLiveRows : 0;
   *total_chunks = nc + nf;
   // dense pass (also when the step fell back to it because a row range would not fit the live lists): every chunk is live.
-  // The mode is the one the last step on this workspace RECORDED, not one re-derived from today's tuning knobs.
-  bool skipped = false;
-  {
-    std::lock_guard<std::mutex> lk(g_step_mu);
-    auto it = g_step_skipped.find(ws);
-    if (it == g_step_skipped.end()) { set_error("pxo_train_backward_work: no pxo_train_fwd_bwd call has used this workspace"); return PXO_ERR_ARG; }
-    skipped = it->second;
+  // The mode is the one the last step on this workspace RECORDED in it, not one re-derived from today's tuning knobs.
+  unsigned int record = 0;
+  if (hipMemcpyAsync(&record, t.scalars + kStepWordsAt, sizeof(record), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    set_error("pxo_train_backward_work: copy back failed");
+    return PXO_ERR_HIP;
   }
-  if (!skipped) {
+  if ((record & ~1u) != kStepRecord) { set_error("pxo_train_backward_work: no pxo_train_fwd_bwd call has used this workspace"); return PXO_ERR_ARG; }
+  if (!(record & 1u)) {
     *live_chunks = nc + nf;
     return PXO_OK;
   }

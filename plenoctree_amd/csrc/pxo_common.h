@@ -180,35 +180,100 @@ int launch_mlp_fwd(const PxoCfg* cfg, const float* packed_fwd, const float* pts,
 // chunk_live (may be NULL = dense): one byte per kLiveRows rows, WRITTEN by the backward(data) kernel (1: some row of the
 // chunk has a non-zero upstream gradient) and READ by the weight-gradient kernels, which skip dead chunks
 __host__ __device__ inline int64_t live_flags(int64_t M) { return (M + kLiveRows - 1) / kLiveRows + kTM / kLiveRows; }
-// tile_counter (may be NULL = static tile stride): a device word; the persistent workgroups then TAKE tiles from it
-// instead of striding over them (skipped tiles do not leave workgroups idle; a late-starting workgroup is not the tail).
-// counter_is_zero: the caller zeroed it on the stream already (the train step's first launch does); otherwise a memset is
-// enqueued here.
+// tile_counter (may be NULL = static tile stride): a ZERO device word (the train step's first launch zeroes them); the
+// persistent workgroups then TAKE tiles from it instead of striding over them (skipped tiles do not leave workgroups idle; a
+// late-starting workgroup is not the tail).
+// bias_from_wgrad (bf16x6 with its own weight-gradient kernel only; the train step passes the same value to BOTH launches of a
+// pass): the bias gradients of Dense_1..7 are the column sums of dz_1..7 that wgrad_x6_kernel takes while it streams dz --
+// backward(data) then skips its per-layer lane reductions for those layers (6 % of its time) and the reduce reads the
+// per-range sums instead of the per-slot partials.
 int launch_mlp_bwd_data(const PxoCfg* cfg, const float* packed_bwd, const float* d_raw_rgb,
                         const float* d_raw_sigma, const uint32_t* mask, int64_t M, float* dz,
                         float* dbias_partial, uint8_t* chunk_live, unsigned int* tile_counter, hipStream_t s,
-                        bool counter_is_zero = false, int flags = 0);
-// flags of launch_mlp_bwd_data / launch_mlp_bwd_weights.  kBiasFromWgrad (bf16x6 with its own weight-gradient kernel only; the
-// train step sets it on BOTH launches of a pass): the bias gradients of Dense_1..7 are the column sums of dz_1..7 that
-// wgrad_x6_kernel takes while it streams dz -- backward(data) then skips its per-layer lane reductions for those layers
-// (6 % of its time) and the reduce reads the per-range sums instead of the per-slot partials.
-constexpr int kBiasFromWgrad = 1;
-// run-time choices between implementations of the same result (pxo_set_tuning; A/B sessions and equality tests)
-int tune_tile_sched();        // PXO_TUNE_TILE_SCHED: 0 static stride, 1 device counter (dense training kernels)
-int tune_wgrad_ranges();      // PXO_TUNE_WGRAD_RANGES: 0 = built-in choice, n > 0 = row ranges per layer of the 256x256 products
-int tune_wgrad_skinny_ranges();  // PXO_TUNE_WGRAD_SKINNY_RANGES: the same for the enc-based pair and the head product
-int tune_x6_wgrad();          // PXO_TUNE_X6_WGRAD: 1 (default) = in bf16x6 the 256x256 weight gradients run on the bf16 pipe too, 0 = float32 MFMA
-// can the weight-gradient kernels skip dead chunks for a pass of M rows (every row range fits a workgroup's live list)?
-// If not the whole reverse pass of the step runs dense (pxo_train_fwd_bwd decides up front).
-bool wgrad_skip_supported(int64_t M);
+                        bool bias_from_wgrad);
+
+// ---- run-time choices between implementations of the same result (pxo_set_tuning; A/B sessions and equality tests) ----
+// An entry point takes ONE snapshot of the knobs (pxo_api.hip tuning_snapshot) and passes what it decided from it down; no
+// function below the entry points reads a knob.
+struct Tuning {
+  int tile_sched;             // PXO_TUNE_TILE_SCHED: 0 static stride, 1 device counter (dense training kernels)
+  int wgrad_ranges;           // PXO_TUNE_WGRAD_RANGES: 0 = built-in choice, n > 0 = row ranges per layer of the 256x256 products
+  int wgrad_skinny_ranges;    // PXO_TUNE_WGRAD_SKINNY_RANGES: the same for the enc-based pair and the head product
+  int coarse_stream;          // PXO_TUNE_COARSE_REVERSE_STREAM: 1 = the coarse reverse pass on a side stream
+  int x6_wgrad;               // PXO_TUNE_X6_WGRAD: 1 = in bf16x6 the 256x256 weight gradients run on the bf16 pipe too, 0 = float32 MFMA
+};
+
+constexpr int kKC = 32;           // row granularity of the weight-gradient split (rows_per_wg is a multiple of it)
+// The split of a pass of M rows over `ncu` CUs: row ranges per layer of the 256x256 products / of the skinny products.
+//  * big passes (>= 1024 rows per CU): one range per CU and layer (NL whole waves of workgroups on the 2 ncu slots);
+//  * smaller ones: 4 ncu / NL ranges (4 waves) -- round 3, rays/s at 4096 / 1024 / 512 rays per step on 256 CUs:
+//    256 ranges 161.0 k / 141.6 k / 123.6 k, 146 ranges 156.5 k / 144.3 k / 127.9 k (one launch per layer: 159.7 k /
+//    139.9 k / 120.3 k): long ranges lose on big passes (the two column halves drift apart and the shared operand stops
+//    hitting L2), short ones pay 64 MB of slab traffic per layer;
+//  * the skinny products run two workgroups per CU: 2 ncu ranges, ncu below 512 rows per CU (round 3, ms per step
+//    at 512 / 1024 / 4096 rays: 512 ranges 3.732 / 6.686 / 24.19, 256 ranges 3.716 / 6.689 / 24.28, 384: 3.739 / 6.722 /
+//    24.41, 128: slower).
+// Tuning::wgrad_ranges / wgrad_skinny_ranges override either (A/B sessions).
+struct WgradSplit { int64_t rpw_main; int P_main; int64_t rpw_skinny; int P_skinny; };
+inline void split_rows(int64_t M, int64_t target, int64_t* rows_per_wg, int* P) {
+  int64_t rpw = (M + target - 1) / target;
+  rpw = (rpw + kKC - 1) / kKC * kKC;
+  if (rpw < kKC) rpw = kKC;
+  *rows_per_wg = rpw;
+  *P = (int)((M + rpw - 1) / rpw);
+}
+inline WgradSplit wgrad_split(int64_t M, int ncu, const Tuning& tu) {
+  constexpr int NL = kDepth - 1;
+  WgradSplit w;
+  int ranges = M >= (int64_t)1024 * ncu ? ncu : (4 * ncu / NL > 0 ? 4 * ncu / NL : 1);
+  if (tu.wgrad_ranges > 0) ranges = tu.wgrad_ranges;
+  if (ranges > ncu) ranges = ncu;
+  split_rows(M, ranges, &w.rpw_main, &w.P_main);
+  int skinny = M < (int64_t)512 * ncu ? ncu : 2 * ncu;
+  if (tu.wgrad_skinny_ranges > 0) skinny = tu.wgrad_skinny_ranges;
+  if (skinny > 2 * ncu) skinny = 2 * ncu;
+  split_rows(M, skinny, &w.rpw_skinny, &w.P_skinny);
+  return w;
+}
+// zero-row skipping needs every row range to fit a workgroup's live-chunk list
+inline bool wgrad_split_fits_live_list(const WgradSplit& w) {
+  return w.rpw_main <= (int64_t)kMaxLiveChunks * kLiveRows && w.rpw_skinny <= (int64_t)kMaxLiveChunks * kLiveRows;
+}
+
+// What a train step (or a standalone reverse launch) decides before its first launch, from one Tuning snapshot.
+struct StepPlan {
+  bool dyn;                   // the dense MLP launches take their tiles from the device counters
+  WgradSplit split_c, split_f;  // weight-gradient row ranges of the coarse / fine pass (split_f: M_f = 0 without a fine level)
+  bool skip;                  // skip_zero_rows, and every range of both passes fits the live lists: else the reverse pass runs
+                              // dense (> 32,768 rows per range, i.e. more than 8.4 M sample rows on 256 CUs: same bits, no saving)
+  bool x6_main;               // the 256x256 weight gradients on the bf16 pipe (bf16x6 with Tuning::x6_wgrad)
+  bool bias_from_wgrad;       // the train step takes the bias gradients of Dense_1..7 from that kernel (launch_mlp_bwd_data)
+  bool fork;                  // the coarse reverse pass on the side stream (needs a fine level)
+};
+inline StepPlan plan_step(const PxoCfg& cfg, int64_t M_c, int64_t M_f, int ncu, const Tuning& tu) {
+  StepPlan p;
+  p.dyn = tu.tile_sched != 0;
+  p.split_c = wgrad_split(M_c, ncu, tu);
+  p.split_f = wgrad_split(M_f, ncu, tu);
+  p.skip = cfg.skip_zero_rows != 0 && wgrad_split_fits_live_list(p.split_c) &&
+           (M_f == 0 || wgrad_split_fits_live_list(p.split_f));
+  p.x6_main = cfg.mlp_precision == PXO_MLP_BF16X6 && tu.x6_wgrad != 0;
+  p.bias_from_wgrad = p.x6_main;
+  p.fork = M_f > 0 && tu.coarse_stream != 0;
+  return p;
+}
+
 // wgrad_x6_kernels.hip: the 256x256 products of Dense_1..7 in bf16x6 (same grid, slabs and reduce as the float32 launch)
 void launch_wgrad_main_x6(const float* acts, const float* dz1, int64_t M, int64_t rpw, int P, float* slab, int n_layers,
                           int64_t layer_stride, const uint8_t* chunk_live, float* dz_colsum, hipStream_t s);
 size_t wgrad_workspace_bytes(const PxoCfg* cfg, int64_t M);
+// split: the caller's (wgrad_split of this M); chunk_live only with a split that fits the live lists (StepPlan::skip);
+// bias_from_wgrad only with x6_main (StepPlan)
 int launch_mlp_bwd_weights(const PxoCfg* cfg, const float* acts, const float* enc, const float* dz,
                            const float* d_raw_rgb, const float* d_raw_sigma,
                            const float* dbias_partial, int64_t M, float* grads, void* ws,
-                           size_t ws_bytes, const uint8_t* chunk_live, hipStream_t s, int flags = 0);
+                           size_t ws_bytes, const uint8_t* chunk_live, hipStream_t s, const WgradSplit& split,
+                           bool x6_main, bool bias_from_wgrad);
 int launch_count_live(const uint8_t* chunk_live, int64_t n, unsigned long long* out, hipStream_t s);
 int launch_posenc(const float* x, int64_t N, float* enc, hipStream_t s);
 // opt-in split-precision forward (mlp_x3_kernels.hip); pts == nullptr selects the dense-grid point source
@@ -261,9 +326,11 @@ struct UniformJob { uint64_t stream_id; int64_t n; float lo, hi; float* out; };
 // sq_x != NULL: the same launch also writes the kSumsqBlocks fixed-order partial sums of squares of sq_x[0 .. sq_n) (the
 // parameter norm of weight_l2, train.py:101-108: it depends on the parameters only, so it rides with the step's first launch)
 constexpr int kSumsqBlocks = 64;
-// zero_words != NULL: the same launch also zeroes n_zero (<= 256) device words (the tile counters of the step's MLP launches)
+// step_words != NULL: the same launch also writes n_words (<= 256) device words, step_words[0] = first_word and the rest zero
+// (the train step's record and the tile counters of its MLP launches)
 int launch_uniform_jobs(uint64_t seed, const UniformJob* jobs, int n_jobs, hipStream_t s, const float* sq_x = nullptr,
-                        int64_t sq_n = 0, float* sq_partial = nullptr, unsigned int* zero_words = nullptr, int n_zero = 0);
+                        int64_t sq_n = 0, float* sq_partial = nullptr, unsigned int* step_words = nullptr, int n_words = 0,
+                        unsigned int first_word = 0);
 int launch_finalize_stats(const float* sse_f, const float* sse_c, const float* sp_exp, const float* sumsq_partial,
                           int64_t B, int64_t n_sp, float sp_weight, int64_t n_params, float* stats, hipStream_t s);
 int launch_adam_pack(const PxoCfg* cfg, float* p, float* m, float* v, const float* g, float lr, int64_t step,

@@ -588,13 +588,14 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
   c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
 }
 
-struct UniformJobs { UniformJob job[3]; int n_jobs; const float* sq_x; int64_t sq_n; float* sq_partial; unsigned int* zero_words; int n_zero; };
+struct UniformJobs { UniformJob job[3]; int n_jobs; const float* sq_x; int64_t sq_n; float* sq_partial; unsigned int* step_words; int n_words; unsigned int first_word; };
 
 // blockIdx.y selects the job; element idx of a job is word idx % 4 of the Philox block with counter idx / 4 and the
 // job's stream id in the upper counter words
 __global__ __launch_bounds__(256) void uniform_kernel(uint64_t seed, UniformJobs J) {
-  // the tile counters of the step's persistent MLP launches (mlp_kernels.hip TileTicket) start from zero
-  if (blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < J.n_zero) J.zero_words[threadIdx.x] = 0u;
+  // the train step's record word, then the tile counters of its persistent MLP launches (mlp_kernels.hip TileTicket) from zero
+  if (blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < J.n_words)
+    J.step_words[threadIdx.x] = threadIdx.x == 0 ? J.first_word : 0u;
   if ((int)blockIdx.y == J.n_jobs) {
     if (J.sq_x == nullptr) return;
     // parameter-norm partials (weight_l2 = sum(p^2) / n, train.py:101-108): kSumsqBlocks blocks, strided loads, fixed-order
@@ -696,7 +697,7 @@ int launch_sample_batch(uint64_t seed, uint64_t stream_id, const float* c2w, int
 }
 
 int launch_uniform_jobs(uint64_t seed, const UniformJob* jobs, int n_jobs, hipStream_t s, const float* sq_x, int64_t sq_n,
-                        float* sq_partial, unsigned int* zero_words, int n_zero) {
+                        float* sq_partial, unsigned int* step_words, int n_words, unsigned int first_word) {
   UniformJobs J;
   int64_t qmax = 0;
   int nj = 0;
@@ -707,12 +708,12 @@ int launch_uniform_jobs(uint64_t seed, const UniformJob* jobs, int n_jobs, hipSt
     if (q > qmax) qmax = q;
   }
   const bool sq = sq_x != nullptr && sq_partial != nullptr;
-  if (zero_words == nullptr || n_zero < 0) n_zero = 0;
-  if (n_zero > 256) { set_error("uniform: at most 256 words can be zeroed by the launch (got %d)", n_zero); return PXO_ERR_ARG; }
-  if (nj == 0 && !sq && n_zero == 0) return PXO_OK;
+  if (step_words == nullptr || n_words < 0) n_words = 0;
+  if (n_words > 256) { set_error("uniform: at most 256 words can be written by the launch (got %d)", n_words); return PXO_ERR_ARG; }
+  if (nj == 0 && !sq && n_words == 0) return PXO_OK;
   for (int i = nj; i < 3; ++i) J.job[i] = UniformJob{0, 0, 0.f, 0.f, nullptr};
   J.n_jobs = nj; J.sq_x = sq ? sq_x : nullptr; J.sq_n = sq_n; J.sq_partial = sq_partial;
-  J.zero_words = zero_words; J.n_zero = n_zero;
+  J.step_words = step_words; J.n_words = n_words; J.first_word = first_word;
   int64_t bx = (qmax + 255) / 256;
   if (sq && bx < kSumsqBlocks) bx = kSumsqBlocks;
   if (bx < 1) bx = 1;

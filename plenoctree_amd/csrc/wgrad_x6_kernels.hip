@@ -11,7 +11,7 @@
 // x 16 bytes -- which is what both MFMA operands of a "TN" product want: a lane's A fragment is 8 rows of one input feature,
 // its B fragment 8 rows of one output column.  A thread owns (one column, one k-block) of X and of dZ: 8 + 8 dword loads with
 // the lanes along the row (256-byte wave loads), each group of 8 a whole fragment: one ds_write_b128 per part, conflict-free
-// both ways.  While it streams dZ the kernel also sums its columns per range: the bias gradients of Dense_1..7 (kBiasFromWgrad in
+// both ways.  While it streams dZ the kernel also sums its columns per range: the bias gradients of Dense_1..7 (bias_from_wgrad in
 // pxo_common.h; backward(data) then drops its lane reductions for those layers, 6 % of its time).  (A first version with two 4-wave workgroups per range -- column halves, X split twice -- gave the same bits
 // and was 7 % slower: 2.63 vs 2.44 ms per launch.)
 #include "pxo_common.h"

@@ -1275,6 +1275,47 @@ def test_wgrad_ranges_tuning_and_long_ranges_in_skipping_mode():
             ops.set_tuning(knob, bad)
 
 
+def test_backward_work_reports_the_record_in_its_workspace():
+    """pxo_train_backward_work reports the mode the step recorded in the workspace it ran on: a later pxo_set_tuning that would
+    make a step run dense does not change the report, and fresh memory at the same address -- the caching allocator handing
+    the freed workspace out again, poisoned with 0xFF -- holds no record at all."""
+    from plenoctree_amd import _lib
+    ops = _ops(); dev = _gpu()
+    cfg = O.Cfg(sparsity_npoints=777)
+    flat = make_params(cfg)
+    n = flat.numel() // 2
+    B = 600
+    rays = make_rays(B)
+    px = torch.rand(B, 3, generator=torch.Generator().manual_seed(2))
+    g = torch.Generator().manual_seed(3)
+    t_rand, u = torch.rand(B, 64, generator=g), torch.rand(B, 128, generator=g)
+    sp = (torch.rand(777, 3, generator=g) * 2 - 1) * 1.5
+    pcfg = pxo_cfg(ops, cfg)
+    pcfg.skip_zero_rows = 1
+    fd = flat.to(dev)
+    packed = [ops.pack_weights(pcfg, fd[i * n:(i + 1) * n].contiguous()) for i in range(2)]
+    grads = torch.zeros_like(fd); stats = torch.zeros(6, device=dev)
+    nbytes = ops.train_workspace_bytes(pcfg, B)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ops.train_fwd_bwd(pcfg, fd, packed, *[r.to(dev) for r in rays], px.to(dev), grads, stats, ws, randomized=True,
+                      t_rand=t_rand.to(dev), u=u.to(dev), sp_points=sp.to(dev))
+    live, total = ops.train_backward_work(pcfg, B, ws)
+    assert live < total, (live, total)                                      # the step skipped
+    try:
+        ops.set_tuning(ops.TUNE_WGRAD_RANGES, 2)                            # a step now would run dense (ranges too long)
+        assert ops.train_backward_work(pcfg, B, ws) == (live, total)
+    finally:
+        ops.set_tuning(ops.TUNE_WGRAD_RANGES, 0)
+    ptr = ws.data_ptr()
+    del ws
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if ws.data_ptr() != ptr:
+        pytest.skip("the caching allocator did not hand the freed workspace out again")
+    ws.fill_(0xFF)
+    with pytest.raises(_lib.PxoError, match="no pxo_train_fwd_bwd call"):
+        ops.train_backward_work(pcfg, B, ws)
+
+
 def test_per_host_image_shards_on_the_device():
     """datasets shard=(rank, world) through the fused launch (pxo_sample_batch's `first`): 8 x 512 rays = the 1 x 4096 batch,
     bit for bit, over several steps -- the reference's single-host sampler (datasets.py:159-166 + utils.shard)."""

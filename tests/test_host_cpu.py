@@ -311,6 +311,30 @@ def test_tile_schedule_properties(tmp_path):
     assert int(res.stdout.split("cases ")[1].split()[0]) > 100000
 
 
+def test_step_plan_properties(tmp_path):
+    """What a train step decides from one tuning snapshot before its first launch (pxo_common.h: wgrad_split, plan_step),
+    checked on the REAL header compiled as host code (tests/native/plan_check.cpp) for passes of 1 .. 9 M rows (around the
+    32,768-rows-per-range limit of the live-chunk lists included), 8 CU counts and every tuning value class: zero-row
+    skipping only where every row range of both passes fits a live list, the bf16x6 bias gradients from the weight-gradient
+    kernel exactly when that kernel runs, and the launchers handed the very split the skip decision was made on."""
+    import shutil
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("needs hipcc")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "plan_check")
+    cmd = [hipcc, "-O1", "-std=c++17", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+           "-I" + os.path.join(root, "plenoctree_amd", "csrc"), "-I" + os.path.join(root, "include"),
+           os.path.join(root, "tests", "native", "plan_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and " bad 0 " in res.stdout, res.stdout[-2000:]
+    fields = res.stdout.split()
+    count = {k: int(fields[fields.index(k) + 1]) for k in ("cases", "skipping", "dense_fallback")}
+    assert count["cases"] > 1000000 and count["skipping"] > 0 and count["dense_fallback"] > 0, count
+
+
 def test_device_helpers_on_the_host(tmp_path, golden_dir):
     """The kernels' own helper functions, compiled as host code and run on the CPU (tests/native/device_helpers_check.cpp):
     `sh_basis<0..4>` of pxo_sh.h - the code the shading kernels and the octree renderer execute - against the reference's
