@@ -43,6 +43,11 @@ extern "C" {
 #define PXO_ENC_DIM 63      /* 3*(1+2*10), nerf_sh/nerf/model_utils.py:145-173 */
 #define PXO_ENC_PAD 64
 #define PXO_NUM_LEAVES 20   /* per MLP: 10 x (kernel, bias) */
+/* the view-conditioned ("vanilla NeRF") MLP of the pxo_vd_* entry points (octree/nerf/model_utils.py:64-85 with
+ * net_depth_condition 1, net_width_condition 128, deg_view 4) */
+#define PXO_VD_NUM_LEAVES 24        /* per MLP: 12 x (kernel, bias) */
+#define PXO_VD_WIDTH_CONDITION 128
+#define PXO_VD_DIR_ENC 27           /* 3*(1+2*4), posenc(viewdirs, 0, deg_view), octree/nerf/models.py:243-248 */
 
 /* Hyper-parameters of the path: the flags of nerf_sh/nerf/utils.py:61-230 that reach the
  * model (NerfModel fields, nerf_sh/nerf/models.py:55-78) and the loss (train.py:77-85). */
@@ -99,10 +104,11 @@ typedef struct PxoLeaf {
 
 /* ABI version of this header: bumped whenever a struct gains a field or an entry point changes meaning (5: PxoCfg has
  * noise_std + skip_zero_rows, pxo_profile_enable takes a tag MASK, pxo_set_tuning / pxo_occupy_cus exist; 6: PXO_MLP_BF16X6,
- * pxo_adam_pack_step serves every precision, PXO_TUNE_COARSE_REVERSE_STREAM / PXO_TUNE_X6_WGRAD).  A binding checks
+ * pxo_adam_pack_step serves every precision, PXO_TUNE_COARSE_REVERSE_STREAM / PXO_TUNE_X6_WGRAD; 7: the pxo_vd_* entry points of
+ * the view-conditioned head and its SH projection).  A binding checks
  * pxo_version() == PXO_ABI_VERSION and pxo_cfg_bytes() == sizeof(PxoCfg) after dlopen (plenoctree_amd/_lib.py does): a
  * caller built against an older header would otherwise pass a short PxoCfg and have its tail read from past the end. */
-#define PXO_ABI_VERSION 6
+#define PXO_ABI_VERSION 7
 const char* pxo_last_error(void);
 int pxo_version(void);
 size_t pxo_cfg_bytes(void);
@@ -321,6 +327,42 @@ int pxo_eval_points(const PxoCfg* cfg, const float* packed_fwd, const float* poi
  * all y,z (ij meshgrid order, x slowest).  sigma_out [(x1-x0)*reso*reso]. */
 int pxo_grid_sigma(const PxoCfg* cfg, const float* packed_fwd, int reso, int x0, int x1,
                    const float offset[3], const float scale[3], float* sigma_out, void* stream);
+
+/* ---- view-conditioned NeRF (use_viewdirs = true): extraction by SH projection ---------------------------------------------
+ * The reference's second extraction workflow: a vanilla NeRF whose colour head takes the view direction is turned into a
+ * PlenOctree by projecting its radiance onto spherical harmonics (octree/extraction.py:217-241,362-375).  Forward only, float32
+ * only (mlp_precision: PXO_MLP_F32; the bf16 split precisions return PXO_ERR_UNSUPPORTED); PxoCfg, pxo_param_layout and
+ * PXO_NUM_LEAVES keep describing SH models.
+ *
+ * Parameter arena of ONE such MLP (flax key order, octree/nerf/models.py:91-102): Dense_0..7 trunk (as for an SH model),
+ * Dense_8 sigma 256 -> 1, Dense_9 bottleneck 256 -> 256, Dense_10 condition (256 + 27) -> 128, Dense_11 rgb 128 -> 3;
+ * kernels [in,out], each followed by its bias: 595,844 floats.  leaves: PXO_VD_NUM_LEAVES entries (may be NULL). */
+int pxo_vd_param_layout(PxoLeaf* leaves, int64_t* floats_per_mlp);
+/* The image the entry points below stream: the forward image of an SH model of degree 0 made of the trunk, Dense_8 and an empty
+ * colour head -- so pxo_grid_sigma / pxo_eval_points with a PxoCfg of sh_deg 0 evaluate this model's sigma from it
+ * (octree/extraction.py:250-274,290-320 need nothing else) -- followed by Dense_8..11 as they are in the arena. */
+int pxo_vd_packed_floats(int64_t* floats);
+int pxo_vd_pack_weights(const float* mlp_params, float* packed, void* stream);
+
+/* NerfModel.eval_points_raw(points, viewdirs, cross_broadcast) of the torch twin (octree/nerf/models.py:211-252 over
+ * octree/nerf/model_utils.py:126-157): raw (pre-sigmoid) colour and raw sigma [N].  cross_broadcast != 0: viewdirs [R,3],
+ * raw_rgb [N,R,3] (every point under every direction; this call materialises it -- the parity hook and the general-purpose
+ * form); else viewdirs [N,3] (R must equal N), raw_rgb [N,3].  raw_rgb may be NULL (sigma only; viewdirs then unused).
+ * ws: pxo_vd_eval_workspace_bytes(N, R, cross_broadcast). */
+int pxo_vd_eval_workspace_bytes(int64_t N, int64_t R, int cross_broadcast, size_t* bytes);
+int pxo_vd_eval_points_raw(int mlp_precision, const float* packed, const float* points, int64_t N, const float* viewdirs,
+                           int64_t R, int cross_broadcast, float* raw_rgb, float* raw_sigma, void* ws, size_t ws_bytes,
+                           void* stream);
+
+/* project_nerf_to_sh (octree/extraction.py:217-241) = ProjectFunctionNeRF (octree/nerf/sh_proj.py:278-306) over
+ * eval_points_raw(cross_broadcast=True), fused: coeffs[p, c*K + k] = 4 pi / R * sum_r raw_rgb[p,r,c] * Y_k(dirs[r]),
+ * K = (sh_deg+1)^2, sh_deg 0..4 -- channel-major like the raw_rgb of an SH model, so pxo_mean_over_samples and the tree take
+ * it unchanged -- and raw_sigma [N].  dirs [R,3]: unit vectors, given by the caller (the reference draws them inside,
+ * sh_proj.py:289-290).  No tensor of size N x R exists: the workspace grows with N and with R, not with their product.  The sum
+ * over r has a fixed order that depends on r alone, so a point's result does not depend on the batch it is evaluated in. */
+int pxo_vd_project_workspace_bytes(int64_t N, int64_t R, size_t* bytes);
+int pxo_vd_project_sh(int mlp_precision, const float* packed, const float* points, int64_t N, const float* dirs, int64_t R,
+                      int sh_deg, float* coeffs, float* raw_sigma, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- run-time choices between implementations of the same result ----------------------- */
 /* Process-wide, and not synchronised with steps in flight on other host threads: a call reads all knobs once, when it is

@@ -16,6 +16,9 @@ NET_WIDTH = 256
 ENC_DIM = 63
 ENC_PAD = 64
 NUM_LEAVES = 20
+VD_NUM_LEAVES = 24                  # PXO_VD_NUM_LEAVES: the view-conditioned MLP, 12 x (kernel, bias)
+VD_WIDTH_CONDITION = 128
+VD_DIR_ENC = 27
 MLP_F32, MLP_BF16X3, MLP_BF16X6 = 0, 1, 2
 
 
@@ -70,7 +73,7 @@ class PxoCamera(Structure):
 
 
 TREE_MAX_DEPTH = 10
-ABI_VERSION = 6                     # PXO_ABI_VERSION of include/plenoctree_hip.h
+ABI_VERSION = 7                     # PXO_ABI_VERSION of include/plenoctree_hip.h
 
 P = c_void_p
 CFG = POINTER(PxoCfg)
@@ -125,6 +128,13 @@ SIGNATURES = {
     "pxo_profile_enable": (c_int, [c_int]),
     "pxo_profile_read": (c_int, [c_int, POINTER(c_int64), POINTER(ctypes.c_double), POINTER(c_int64)]),
     "pxo_grid_sigma": (c_int, [CFG, P, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P]),
+    "pxo_vd_param_layout": (c_int, [POINTER(PxoLeaf), POINTER(c_int64)]),
+    "pxo_vd_packed_floats": (c_int, [POINTER(c_int64)]),
+    "pxo_vd_pack_weights": (c_int, [P, P, P]),
+    "pxo_vd_eval_workspace_bytes": (c_int, [c_int64, c_int64, c_int, POINTER(c_size_t)]),
+    "pxo_vd_eval_points_raw": (c_int, [c_int, P, P, c_int64, P, c_int64, c_int, P, P, P, c_size_t, P]),
+    "pxo_vd_project_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "pxo_vd_project_sh": (c_int, [c_int, P, P, c_int64, P, c_int64, c_int, P, P, P, c_size_t, P]),
     # include/plenoctree_octree.h
     "pxo_threshold_mask": (c_int, [P, c_int64, c_float, P, P]),
     "pxo_tree_workspace_bytes": (c_int, [c_int, POINTER(c_size_t)]),

@@ -211,3 +211,121 @@ def restore_torch_checkpoint(train_dir, state, trust_pickle=False):
     state.m.zero_(); state.v.zero_()
     state.repack()
     return path
+
+
+# ---- view-conditioned NeRF (use_viewdirs = true), read for extraction by SH projection --------------------------------------
+# Both formats the reference reads for such a model (octree/nerf/models.py:52-113): the torch twin's state dict (MLP_i.
+# input_layers.j, sigma_layer, bottleneck_layer, condition_layers.0, rgb_layer; Linear weights [out,in]) and the flax / JaxNeRF
+# msgpack tree (Dense_0..11, kernels [in,out]).
+_VD_TORCH_NAMES = ([f"input_layers.{i}" for i in range(8)] +
+                   ["sigma_layer", "bottleneck_layer", "condition_layers.0", "rgb_layer"])
+
+
+def _vd_leaves():
+    from ... import ops
+    return ops.vd_param_layout()
+
+
+def vd_arena_to_tree(flat):
+    """flat 2-MLP arena (numpy) of a view-conditioned model -> {"MLP_i": {"Dense_j": {"kernel": [in,out], "bias": [out]}}}."""
+    leaves, n = _vd_leaves()
+    tree = {}
+    for mi in range(2):
+        mlp = {}
+        for layer, is_bias, off, rows, cols in leaves:
+            d = mlp.setdefault(f"Dense_{layer}", {})
+            a = flat[mi * n + off: mi * n + off + rows * cols]
+            d["bias" if is_bias else "kernel"] = a.copy() if is_bias else a.reshape(rows, cols).copy()
+        tree[f"MLP_{mi}"] = mlp
+    return tree
+
+
+def vd_tree_to_arena(tree, where="checkpoint"):
+    """Inverse of vd_arena_to_tree.  A tree whose shapes are not those of the view-conditioned model raises a ValueError that names
+    the first leaf that does not fit (and says so when the shapes are an SH model's)."""
+    leaves, n = _vd_leaves()
+    flat = np.zeros(2 * n, np.float32)
+    for mi in range(2):
+        mlp = tree.get(f"MLP_{mi}")
+        if mlp is None:
+            raise ValueError(f"{where}: no MLP_{mi} in the parameter tree")
+        for layer, is_bias, off, rows, cols in leaves:
+            name = f"MLP_{mi}/Dense_{layer}/{'bias' if is_bias else 'kernel'}"
+            dense = mlp.get(f"Dense_{layer}")
+            if dense is None or ("bias" if is_bias else "kernel") not in dense:
+                hint = " (Dense_0..9 only: a use_viewdirs=false SH model; extract it without --use_viewdirs)" if layer >= 10 else ""
+                raise ValueError(f"{where}: leaf {name} is missing{hint}")
+            a = np.asarray(dense["bias" if is_bias else "kernel"], np.float32)
+            want = (rows,) if is_bias else (rows, cols)
+            if tuple(a.shape) != want:
+                raise ValueError(f"{where}: leaf {name} has shape {tuple(a.shape)}, the view-conditioned model "
+                                 f"(use_viewdirs=true, net_width_condition 128, deg_view 4) needs {want}")
+            flat[mi * n + off: mi * n + off + rows * cols] = a.reshape(-1)
+    return flat
+
+
+def vd_torch_state_dict_to_tree(sd, where="torch checkpoint"):
+    """The torch twin's state dict of a use_viewdirs=True model as the flax tree (the inverse of octree/nerf/models.py:79-102:
+    Dense_i -> input_layers.i, sigma_layer, bottleneck_layer, condition_layers.0, rgb_layer; kernel = weight.T)."""
+    for k in sd:
+        if "sg_lambda" in k or "sg_mu_spher" in k:
+            raise ValueError(f"{where}: key {k!r}: the SG basis is not built on the MI355X path")
+        if "condition_layers." in k and "condition_layers.0." not in k:
+            raise ValueError(f"{where}: key {k!r}: net_depth_condition must be 1")
+    tree = {}
+    for mi in range(2):
+        mlp = {}
+        for li, name in enumerate(_VD_TORCH_NAMES):
+            wk, bk = f"MLP_{mi}.{name}.weight", f"MLP_{mi}.{name}.bias"
+            if wk not in sd or bk not in sd:
+                hint = " (no view-conditioned head: a use_viewdirs=false SH model)" if li >= 9 else ""
+                raise ValueError(f"{where}: leaf {wk} / {bk} is missing{hint}")
+            w = sd[wk].detach().cpu().numpy() if hasattr(sd[wk], "detach") else np.asarray(sd[wk])
+            b = sd[bk].detach().cpu().numpy() if hasattr(sd[bk], "detach") else np.asarray(sd[bk])
+            mlp[f"Dense_{li}"] = {"kernel": np.ascontiguousarray(w.T.astype(np.float32)), "bias": b.astype(np.float32)}
+        tree[f"MLP_{mi}"] = mlp
+    return tree
+
+
+def vd_state_dict_from_arena(flat):
+    """The torch twin's state dict (weights [out,in]) of a flat view-conditioned arena: what its `*.ckpt` holds under "model"."""
+    tree = vd_arena_to_tree(np.asarray(flat, np.float32))
+    sd = {}
+    for mi in range(2):
+        for li, name in enumerate(_VD_TORCH_NAMES):
+            d = tree[f"MLP_{mi}"][f"Dense_{li}"]
+            sd[f"MLP_{mi}.{name}.weight"] = torch.from_numpy(np.ascontiguousarray(d["kernel"].T))
+            sd[f"MLP_{mi}.{name}.bias"] = torch.from_numpy(d["bias"].copy())
+    return sd
+
+
+def load_viewdirs_arena(train_dir, is_jaxnerf_ckpt=False, trust_pickle=False):
+    """(flat arena as numpy, path, format) of the newest checkpoint of a view-conditioned model in train_dir, chosen like
+    extraction.load_nerf_checkpoint chooses for SH models: `*.ckpt` torch state dict first unless is_jaxnerf_ckpt, else the flax
+    msgpack `checkpoint_<step>`."""
+    if not is_jaxnerf_ckpt:
+        path = train_dir if os.path.isfile(train_dir) and train_dir.endswith(".ckpt") else latest_torch_checkpoint(train_dir)
+        if path is not None:
+            try:
+                ckpt = torch.load(path, map_location="cpu", weights_only=True)
+            except Exception as e:
+                if not trust_pickle:
+                    raise ValueError(f"{path}: holds more than tensors ({type(e).__name__}); pass --trust_ckpt_pickle true for "
+                                     "files you trust") from e
+                ckpt = torch.load(path, map_location="cpu", weights_only=False)
+            if not isinstance(ckpt, dict) or "model" not in ckpt:
+                raise ValueError(f'{path}: not a checkpoint of the reference\'s torch twin (no "model" state dict)')
+            return vd_tree_to_arena(vd_torch_state_dict_to_tree(ckpt["model"], path), path), path, "torch state dict"
+    path = train_dir if os.path.isfile(train_dir) else latest_checkpoint(train_dir)
+    if path is None:
+        raise FileNotFoundError(f"no *.ckpt (torch state dict) and no checkpoint_<step> (flax msgpack) in {train_dir}")
+    with open(path, "rb") as f:
+        tree = msgpack_restore(f.read())
+    return vd_tree_to_arena(tree["optimizer"]["target"]["params"], path), path, "flax msgpack"
+
+
+def restore_viewdirs_checkpoint(train_dir, state, is_jaxnerf_ckpt=False, trust_pickle=False):
+    flat, path, fmt = load_viewdirs_arena(train_dir, is_jaxnerf_ckpt, trust_pickle)
+    state.params.copy_(torch.from_numpy(flat).to(state.params.device))
+    state.repack()
+    return f"* restore ckpt from {path} ({fmt}, view-conditioned head)"

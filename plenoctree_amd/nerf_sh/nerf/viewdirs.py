@@ -1,0 +1,141 @@
+"""The view-conditioned ("vanilla") NeRF of the reference, for extraction by SH projection only.
+
+Host-side mirror of the torch twin with use_viewdirs=True (octree/nerf/models.py:116-252 over octree/nerf/model_utils.py:64-158,
+net_depth_condition 1, net_width_condition 128, deg_view 4): per MLP twelve dense layers in flax key order -- Dense_0..7 trunk,
+Dense_8 sigma, Dense_9 bottleneck, Dense_10 condition, Dense_11 rgb -- in one flat float32 arena (MLP_0 then MLP_1).  All
+arithmetic is done by libplenoctree_hip.so (csrc/viewdirs_kernels.hip) through plenoctree_amd.ops.  Training and ray rendering
+with this head are not built: nerf_sh.train / eval keep rejecting use_viewdirs=true (utils.check_supported).
+"""
+import math
+
+import torch
+
+from ... import ops
+
+DIRECTION_STREAM = 16        # Philox stream id of the projection's direction draw (0..4: the train step's draws)
+
+
+class ViewdirsState:
+    """Parameters of the two MLPs and the images the kernels stream.  `packed[i][0]` starts with the forward image of an SH model
+    of degree 0 (trunk + Dense_8), so the sigma-only consumers of a TrainState (extraction.grid_sigma) take this state as it is."""
+
+    def __init__(self, params):
+        self.params = params
+        self.n_mlp = params.numel() // 2
+        self.packed = [None, None]
+        self._ws = None
+        self.repack()
+
+    def mlp_params(self, i):
+        return self.params[i * self.n_mlp:(i + 1) * self.n_mlp]
+
+    def repack(self):
+        for i in range(2):
+            img = self.packed[i][0] if self.packed[i] is not None else None
+            self.packed[i] = (ops.vd_pack_weights(self.mlp_params(i), img), None)
+
+    def workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.params.device)
+        return self._ws
+
+
+class ViewdirsModel:
+    def __init__(self, num_coarse_samples=64, num_fine_samples=128, mlp_precision=0):
+        # the SH model of degree 0 whose forward image opens the packed image: what pxo_grid_sigma is called with
+        self.cfg = ops.make_cfg(num_coarse_samples=num_coarse_samples, num_fine_samples=num_fine_samples, sh_deg=0)
+        self.num_coarse_samples = num_coarse_samples
+        self.num_fine_samples = num_fine_samples
+        self.mlp_precision = mlp_precision
+
+    def _which(self, coarse):
+        return 1 if (self.num_fine_samples > 0 and not coarse) else 0
+
+    def eval_points_raw(self, state, points, viewdirs=None, coarse=False, cross_broadcast=False):
+        """octree/nerf/models.py:211-252: raw_rgb [N,3] (viewdirs [N,3]) or [N,R,3] (cross_broadcast, viewdirs [R,3]), raw
+        sigma [N,1]."""
+        N = points.reshape(-1, 3).shape[0]
+        R = viewdirs.shape[0] if viewdirs is not None else 0
+        ws = state.workspace(ops.vd_eval_workspace_bytes(N, R, cross_broadcast))
+        rgb, sigma = ops.vd_eval_points_raw(state.packed[self._which(coarse)][0], points, viewdirs, cross_broadcast, ws=ws,
+                                            mlp_precision=self.mlp_precision)
+        return rgb, sigma.view(-1, 1)
+
+    def project_sh(self, state, points, dirs, sh_deg, coarse=False, coeffs=None, raw_sigma=None):
+        """project_nerf_to_sh (octree/extraction.py:217-241) for a given direction set: coeffs [N,3K], raw sigma [N]."""
+        N = points.reshape(-1, 3).shape[0]
+        ws = state.workspace(ops.vd_project_workspace_bytes(N, dirs.shape[0]))
+        return ops.vd_project_sh(state.packed[self._which(coarse)][0], points, dirs, sh_deg, ws=ws, coeffs=coeffs,
+                                 raw_sigma=raw_sigma, mlp_precision=self.mlp_precision)
+
+
+def init_params(seed=20200823):
+    """Glorot-uniform kernels, zero biases, host RNG (as nerf.models.init_params)."""
+    from .models import glorot_uniform_
+    leaves, n = ops.vd_param_layout()
+    flat = torch.zeros(2 * n, dtype=torch.float32)
+    gen = torch.Generator().manual_seed(seed)
+    for mi in range(2):
+        for layer, is_bias, off, rows, cols in leaves:
+            if not is_bias:
+                glorot_uniform_(flat[mi * n + off: mi * n + off + rows * cols].view(rows, cols), rows, cols, gen)
+    return flat
+
+
+def check_extraction_flags(args):
+    """What octree.extraction builds of a use_viewdirs=true model; everything else is rejected by name."""
+    bad = []
+    if not args.use_viewdirs:
+        bad.append("use_viewdirs=false (an SH model: the plain extraction path)")
+    if args.net_depth_condition != 1:
+        bad.append(f"net_depth_condition={args.net_depth_condition} (need 1)")
+    if args.net_width_condition != 128:
+        bad.append(f"net_width_condition={args.net_width_condition} (need 128)")
+    if args.deg_view != 4:
+        bad.append(f"deg_view={args.deg_view} (need 4)")
+    if args.sh_deg < 0 or args.sh_deg > 4:
+        bad.append(f"sh_deg={args.sh_deg} (the projection needs 0..4)")
+    if args.sg_dim > 0:
+        bad.append("sg_dim>0 (spherical gaussians)")
+    if args.legacy_posenc_order:
+        bad.append("legacy_posenc_order")
+    if (args.net_depth, args.net_width, args.skip_layer) != (8, 256, 4):
+        bad.append("net_depth/net_width/skip_layer != 8/256/4")
+    if (args.min_deg_point, args.max_deg_point) != (0, 10):
+        bad.append("min/max_deg_point != 0/10")
+    if args.num_rgb_channels != 3 or args.num_sigma_channels != 1:
+        bad.append("num_rgb_channels/num_sigma_channels != 3/1")
+    if getattr(args, "mlp_precision", "f32") != "f32":
+        bad.append(f"mlp_precision={args.mlp_precision} (the view-conditioned head is float32 only)")
+    if getattr(args, "projection_samples", 1) < 1:
+        bad.append(f"projection_samples={args.projection_samples} (need >= 1)")
+    if getattr(args, "render_path", False) or getattr(args, "spherify", False):
+        bad.append("render_path / spherify (LLFF scenes)")
+    if (args.net_activation.lower(), args.sigma_activation.lower()) != ("relu", "relu"):
+        bad.append("activations other than relu")
+    if bad:
+        raise NotImplementedError("SH projection of a view-dependent NeRF, not built on the MI355X path: " + "; ".join(bad))
+
+
+def get_model_state(args, device):
+    """Model + state with freshly initialised parameters (the caller restores a checkpoint)."""
+    check_extraction_flags(args)
+    model = ViewdirsModel(args.num_coarse_samples, args.num_fine_samples)
+    return model, ViewdirsState(init_params(args.seed).to(device))
+
+
+def sphere_directions(u, v):
+    """spherical_uniform_sampling + spher2cart (octree/nerf/sh_proj.py:241-245, 28-33) for given uniforms u, v in [0,1):
+    theta = acos(2u - 1), phi = 2 pi v -> unit vectors [R,3] (float64 arithmetic, rounded once to float32)."""
+    u, v = u.double(), v.double()
+    theta = torch.acos(2.0 * u - 1.0)
+    phi = 2.0 * math.pi * v
+    r = torch.sin(theta)
+    return torch.stack([r * torch.cos(phi), r * torch.sin(phi), torch.cos(theta)], dim=-1).float().contiguous()
+
+
+def draw_directions(seed, count, device):
+    """The run's ONE direction set: 2 * count uniforms of Philox stream (seed, DIRECTION_STREAM), u first, then v."""
+    uv = ops.uniform(seed, DIRECTION_STREAM, 2 * count, device=device)
+    return sphere_directions(uv[:count], uv[count:])

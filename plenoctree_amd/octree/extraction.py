@@ -164,6 +164,54 @@ def step2(args, tree, model, state, comm, seed=0):
     tree.max_depth_data().copy_(block[: total * 8])
 
 
+def projection_chunk_points(n_dirs, budget_bytes=1 << 30, samples_per_cell=8):
+    """Points per call of the fused projection: as many as fit `budget_bytes` of its workspace (the saved trunk activations,
+    about 9 KB per point; the directions' share does not grow with the points), in whole groups of 64 nodes' samples.  The
+    reference's `chunk // (S * R // 10)` (:363) bounds its [points x directions x 283] tensors, which do not exist here."""
+    base = ops.vd_project_workspace_bytes(0, n_dirs)
+    per_point = (ops.vd_project_workspace_bytes(4096, n_dirs) - base) / 4095.0
+    group = 64 * 8 * samples_per_cell
+    return max(int((budget_bytes - base) / per_point) // group, 1) * group
+
+
+SAMPLE_GROUP = 64
+
+
+def sample_cells_by_group(tree, S, n0, cnt, total, seed):
+    """The sample points of nodes [n0, n0 + cnt) drawn per aligned group of 64 nodes (N3Tree.sample_max_depth_cells seeds a
+    draw by its first node): a node's points then depend on the node alone, not on the chunk or the rank it is evaluated in."""
+    parts = []
+    for g0 in range(n0 // SAMPLE_GROUP * SAMPLE_GROUP, n0 + cnt, SAMPLE_GROUP):
+        pts = tree.sample_max_depth_cells(S, first=g0, count=min(SAMPLE_GROUP, total - g0), seed=seed)
+        lo, hi = max(n0, g0) - g0, min(n0 + cnt, g0 + SAMPLE_GROUP) - g0
+        parts.append(pts.view(-1, 8 * S, 3)[lo:hi])
+    return torch.cat(parts).reshape(-1, S, 3)
+
+
+def step2_projection(args, tree, model, state, comm, dirs, seed=0, record=None):
+    """Step 2 for a view-dependent NeRF (:362-375 with project_nerf_to_sh :217-241): the S samples of every deepest-level cell
+    go through the fused SH projection under ONE direction set `dirs` for the whole run (the reference draws one per chunk),
+    then the mean over the samples.  --chunk caps the points per call (above the workspace-derived size it has no effect); no
+    result depends on it.  record: a dict that receives the sample points per node range (tests)."""
+    S = args.samples_per_cell
+    _, total = tree.max_depth_nodes()
+    per = (total + comm.world - 1) // comm.world
+    a, b = min(comm.rank * per, total), min((comm.rank + 1) * per, total)
+    pts_per_call = min(projection_chunk_points(dirs.shape[0], samples_per_cell=S), max(args.chunk // (8 * S), 1) * 64 * 8 * S)
+    chunk_nodes = max(pts_per_call // (8 * S), 1)
+    block = torch.zeros(per * 8, tree.data_dim, dtype=torch.float32, device=tree.device)
+    for n0 in range(a, b, chunk_nodes):
+        cnt = min(chunk_nodes, b - n0)
+        pts = sample_cells_by_group(tree, S, n0, cnt, total, seed)
+        if record is not None:
+            record.setdefault("points", []).append((n0, cnt, pts.view(-1, 3).detach().cpu()))
+        coeffs, sigma = model.project_sh(state, pts.view(-1, 3), dirs, args.sh_deg)
+        ops.mean_over_samples(ops.make_cfg(sh_deg=args.sh_deg), coeffs, sigma, S, out=block[(n0 - a) * 8:(n0 - a + cnt) * 8])
+    if comm.is_dist:
+        block = comm.all_gather_cat(block)
+    tree.max_depth_data().copy_(block[: total * 8])
+
+
 def tree_center_radius(tree):
     radius = 0.5 / tree.invradius
     center = (1.0 - 2.0 * tree.offset) * radius
@@ -231,7 +279,7 @@ def define_flags():
     # not a reference flag: a `*.ckpt` holding more than tensors (argparse.Namespace, numpy scalars ...) is unpickled in full, like
     # the reference's plain torch.load, only when this says so (the default reads tensors only and explains itself otherwise)
     a("--trust_ckpt_pickle", type=utils._bool, nargs="?", const=True, default=False)
-    a("--projection_samples", type=int, default=10000)       # :133-137: SH projection of a view-dependent NeRF only
+    a("--projection_samples", type=int, default=10000)       # :133-137: directions of the SH projection (--use_viewdirs true)
     a("--renderer_step_size", type=float, default=1e-4)
     a("--no_early_stop", action="store_true")
     return p
@@ -260,19 +308,43 @@ def load_nerf_checkpoint(args, state):
     return f"* no *.ckpt in {args.train_dir}: restore ckpt from {path} (flax msgpack, as with --is_jaxnerf_ckpt)"
 
 
-def main(argv=None):
+def check_viewdirs_flags(args):
+    """Flag check of the --use_viewdirs true path: utils.check_flags' directory checks, then what the projection builds."""
+    from ..nerf_sh.nerf import viewdirs
+    if args.train_dir is None:
+        raise ValueError("train_dir must be set. None set now.")
+    if args.data_dir is None and args.dataset != "synthetic":
+        raise ValueError("data_dir must be set. None set now.")
+    viewdirs.check_extraction_flags(args)
+
+
+def main(argv=None, record_projection=False):
+    """record_projection: keep the run's direction set and step-2 sample points on the returned tree (`projection_record`)."""
     args = define_flags().parse_args(argv)
     utils.update_flags(args)
+    args._record_projection = bool(record_projection)
     if not torch.cuda.is_available():
         raise SystemExit("octree.extraction needs a ROCm GPU; the HIP path has no CPU fallback")
     comm = dist.init_from_env()
     torch.cuda.set_device(comm.local_rank)
     device = torch.device("cuda", comm.local_rank)
-    utils.check_flags(args, require_data=True, world_size=comm.world)
     say = print if comm.rank == 0 else (lambda *a, **k: None)
-    say("* Loading NeRF", flush=True)
-    model, state = models.get_model_state(args, device, restore=False)
-    say(load_nerf_checkpoint(args, state), flush=True)
+    dirs = None
+    if args.use_viewdirs:
+        # a view-dependent ("vanilla") NeRF: extraction opts in explicitly (training / rendering with this head are not built,
+        # so the generic check_flags keeps rejecting it) and projects its radiance onto SH of degree --sh_deg (:362-375)
+        from ..nerf_sh.nerf import checkpoints, viewdirs
+        check_viewdirs_flags(args)
+        say("* Loading NeRF (view-conditioned head)", flush=True)
+        model, state = viewdirs.get_model_state(args, device)
+        say(checkpoints.restore_viewdirs_checkpoint(args.train_dir, state, bool(args.is_jaxnerf_ckpt),
+                                                    bool(getattr(args, "trust_ckpt_pickle", False))), flush=True)
+        dirs = viewdirs.draw_directions(args.seed, args.projection_samples, device)
+    else:
+        utils.check_flags(args, require_data=True, world_size=comm.world)
+        say("* Loading NeRF", flush=True)
+        model, state = models.get_model_state(args, device, restore=False)
+        say(load_nerf_checkpoint(args, state), flush=True)
     dataset = datasets.get_dataset("train", args, device)
     if args.bbox_from_data:                                  # :447-451 (NSVF datasets carry bbox.txt)
         bbox = getattr(dataset, "bbox", None)
@@ -303,7 +375,13 @@ def main(argv=None):
     say(f"  {int(mask.sum())} / {reso ** 3} voxels kept ({args.masking_mode} mask); step 1 took {t1 - t0:.2f} s", flush=True)
     say(tree, flush=True)
     say("* Step 2: AA", args.samples_per_cell, flush=True)
-    step2(args, tree, model, state, comm, seed=args.seed)
+    if dirs is not None:
+        say(f"  SH projection: {dirs.shape[0]} directions, one set for the run", flush=True)
+        record = {"dirs": dirs.detach().cpu()} if getattr(args, "_record_projection", False) else None
+        step2_projection(args, tree, model, state, comm, dirs, seed=args.seed, record=record)
+        tree.projection_record = record
+    else:
+        step2(args, tree, model, state, comm, seed=args.seed)
     tree.relu_sigma_()
     tree.shrink_to_fit()
     torch.cuda.synchronize(); comm.barrier(); t2 = time.time()

@@ -455,3 +455,84 @@ def mean_over_samples(cfg, raw_rgb, raw_sigma, samples_per_cell, out=None):
     check(_lib.load().pxo_mean_over_samples(ctypes.byref(cfg), _f(raw_rgb), _f(raw_sigma.reshape(-1)), n,
                                             samples_per_cell, _f(out), _stream()), "pxo_mean_over_samples")
     return out
+
+
+# ---- view-conditioned NeRF (use_viewdirs = true): the pxo_vd_* entry points -------------------------------------------------
+def vd_param_layout():
+    """[(layer, is_bias, offset, rows, cols)] of ONE view-conditioned MLP's sub-arena (Dense_0..11) and its size in floats."""
+    leaves = (_lib.PxoLeaf * _lib.VD_NUM_LEAVES)()
+    n = ctypes.c_int64(0)
+    check(_lib.load().pxo_vd_param_layout(leaves, ctypes.byref(n)), "pxo_vd_param_layout")
+    return [(l.layer, l.is_bias, l.offset, l.rows, l.cols) for l in leaves], n.value
+
+
+def vd_packed_floats():
+    n = ctypes.c_int64(0)
+    check(_lib.load().pxo_vd_packed_floats(ctypes.byref(n)), "pxo_vd_packed_floats")
+    return n.value
+
+
+def vd_pack_weights(mlp_params, packed=None):
+    _require_gpu()
+    if packed is None:
+        packed = _new(vd_packed_floats(), device=mlp_params.device)
+    check(_lib.load().pxo_vd_pack_weights(_f(mlp_params), _f(packed), _stream()), "pxo_vd_pack_weights")
+    return packed
+
+
+def _ws(ws, nbytes, device):
+    if ws is None or ws.numel() < nbytes:
+        ws = _new(max(nbytes, 16), device=device, dtype=torch.uint8)
+    return ws
+
+
+def vd_eval_workspace_bytes(N, R, cross_broadcast):
+    n = ctypes.c_size_t(0)
+    check(_lib.load().pxo_vd_eval_workspace_bytes(N, R, int(bool(cross_broadcast)), ctypes.byref(n)), "pxo_vd_eval_workspace_bytes")
+    return n.value
+
+
+def vd_eval_points_raw(packed, points, viewdirs=None, cross_broadcast=False, ws=None, mlp_precision=0):
+    """eval_points_raw of the view-conditioned model: raw_rgb [N,R,3] (cross_broadcast) or [N,3] (or None without viewdirs),
+    raw_sigma [N]."""
+    _require_gpu()
+    points = points.reshape(-1, 3)
+    N, dev = points.shape[0], points.device
+    R = viewdirs.shape[0] if viewdirs is not None else 0
+    raw_rgb = None
+    if viewdirs is not None:
+        raw_rgb = _new(N, R, 3, device=dev) if cross_broadcast else _new(N, 3, device=dev)
+    raw_sigma = _new(N, device=dev)
+    nbytes = vd_eval_workspace_bytes(N, R, cross_broadcast)
+    ws = _ws(ws, nbytes, dev)
+    check(_lib.load().pxo_vd_eval_points_raw(int(mlp_precision), _f(packed), _f(points), N, _f(viewdirs), R,
+                                             int(bool(cross_broadcast)), _f(raw_rgb), _f(raw_sigma), _p(ws), ws.numel(),
+                                             _stream()), "pxo_vd_eval_points_raw")
+    return raw_rgb, raw_sigma
+
+
+def vd_project_workspace_bytes(N, R):
+    n = ctypes.c_size_t(0)
+    check(_lib.load().pxo_vd_project_workspace_bytes(N, R, ctypes.byref(n)), "pxo_vd_project_workspace_bytes")
+    return n.value
+
+
+def vd_project_sh(packed, points, dirs, sh_deg, ws=None, coeffs=None, raw_sigma=None, mlp_precision=0):
+    """Fused SH projection: coeffs [N, 3K] (channel-major) and raw_sigma [N] for unit directions dirs [R,3]."""
+    _require_gpu()
+    points = points.reshape(-1, 3)
+    N, dev = points.shape[0], points.device
+    R = dirs.shape[0]
+    K = (int(sh_deg) + 1) ** 2
+    if coeffs is None:
+        coeffs = _new(N, 3 * max(K, 1), device=dev)
+    if raw_sigma is None:
+        raw_sigma = _new(N, device=dev)
+    n = ctypes.c_size_t(0)
+    lib = _lib.load()
+    if lib.pxo_vd_project_workspace_bytes(N, R, ctypes.byref(n)) != 0:
+        n.value = 16                                       # the call below reports what is wrong with the arguments
+    ws = _ws(ws, n.value, dev)
+    check(lib.pxo_vd_project_sh(int(mlp_precision), _f(packed), _f(points), N, _f(dirs), R, int(sh_deg), _f(coeffs),
+                                _f(raw_sigma), _p(ws), ws.numel(), _stream()), "pxo_vd_project_sh")
+    return coeffs, raw_sigma
