@@ -105,10 +105,11 @@ typedef struct PxoLeaf {
 /* ABI version of this header: bumped whenever a struct gains a field or an entry point changes meaning (5: PxoCfg has
  * noise_std + skip_zero_rows, pxo_profile_enable takes a tag MASK, pxo_set_tuning / pxo_occupy_cus exist; 6: PXO_MLP_BF16X6,
  * pxo_adam_pack_step serves every precision, PXO_TUNE_COARSE_REVERSE_STREAM / PXO_TUNE_X6_WGRAD; 7: the pxo_vd_* entry points of
- * the view-conditioned head and its SH projection).  A binding checks
+ * the view-conditioned head and its SH projection; 8: ray rendering with that head -- pxo_vd_render_fwd, pxo_vd_composite_fwd,
+ * PXO_TUNE_VD_RAY_BLOCK).  A binding checks
  * pxo_version() == PXO_ABI_VERSION and pxo_cfg_bytes() == sizeof(PxoCfg) after dlopen (plenoctree_amd/_lib.py does): a
  * caller built against an older header would otherwise pass a short PxoCfg and have its tail read from past the end. */
-#define PXO_ABI_VERSION 7
+#define PXO_ABI_VERSION 8
 const char* pxo_last_error(void);
 int pxo_version(void);
 size_t pxo_cfg_bytes(void);
@@ -364,6 +365,32 @@ int pxo_vd_project_workspace_bytes(int64_t N, int64_t R, size_t* bytes);
 int pxo_vd_project_sh(int mlp_precision, const float* packed, const float* points, int64_t N, const float* dirs, int64_t R,
                       int sh_deg, float* coeffs, float* raw_sigma, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- view-conditioned NeRF: ray rendering ----------------------------------------------------------------------------------
+ * NerfModel.__call__ with use_viewdirs (nerf_sh/nerf/models.py:216-348: sample_along_rays :232-241, MLP_0 with the
+ * view-direction condition :242-264, sigmoid / relu / volumetric_rendering :269-292, sample_pdf :296-307, MLP_1 :308-348),
+ * forward only, float32 only.  Argument conventions of pxo_render_fwd: packed0/1 = the pxo_vd_pack_weights images of MLP_0 /
+ * MLP_1; t_rand [B,Nc] / u [B,Nf] or NULL (drawn from Philox streams 0 / 1 of `seed` when randomized); fine outputs and packed1
+ * may be NULL when num_fine_samples == 0.  Read from cfg: num_coarse_samples, num_fine_samples, near_, far_, lindisp,
+ * white_bkgd, noise_std (streams 3 / 4, as in pxo_render_fwd), mlp_precision; sh_deg is ignored.
+ * The B rays are walked in internal blocks of PXO_TUNE_VD_RAY_BLOCK rays (coarse, then fine, per block): the trunk runs in its
+ * saved-tensor form (its last saved activation is the head's input), about 9 KB per sample, so the workspace is that of ONE block
+ * (plus 4 (Nc + Nf) bytes per ray of the whole batch for the draws) and does not grow with B beyond a block.  Per block the
+ * direction term of Dense_10 is evaluated once per RAY, and one kernel per level computes Dense_9, Dense_10 and Dense_11 for
+ * 16 consecutive samples without writing the 128-wide intermediate to memory.  A sample's raw colour and sigma are bit for bit
+ * those of pxo_vd_eval_points_raw for that point and direction, and a ray's result does not depend on B or on the block size. */
+int pxo_vd_render_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes);
+int pxo_vd_render_fwd(const PxoCfg* cfg, const float* packed0, const float* packed1, const float* origins,
+                      const float* directions, const float* viewdirs, int64_t B, int randomized, const float* t_rand,
+                      const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f, float* disp_f,
+                      float* acc_f, void* ws, size_t ws_bytes, void* stream);
+/* The compositing step of the above on its own (sigmoid + relu + volumetric_rendering, nerf_sh/nerf/models.py:280-292 over
+ * nerf_sh/nerf/model_utils.py:176-222): raw_rgb [B*S,3] (pre-sigmoid), raw_sigma [B*S], z_vals [B,S], directions [B,3] (their
+ * norm scales the sample distances) -> comp_rgb [B,3], disp [B], acc [B], weights [B,S] (may be NULL).  Reads white_bkgd
+ * from cfg. */
+int pxo_vd_composite_fwd(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, const float* z_vals,
+                         const float* directions, int64_t B, int S, float* comp_rgb, float* disp, float* acc,
+                         float* weights, void* stream);
+
 /* ---- run-time choices between implementations of the same result ----------------------- */
 /* Process-wide, and not synchronised with steps in flight on other host threads: a call reads all knobs once, when it is
  * enqueued, and decides from that one snapshot; a train step records its zero-row mode in its workspace
@@ -390,6 +417,12 @@ int pxo_vd_project_sh(int mlp_precision, const float* packed, const float* point
 /*   PXO_TUNE_X6_WGRAD      with PXO_MLP_BF16X6 only.  1 (default): the 256x256 weight-gradient products of Dense_1..7 run in bf16x6
  *                          too (wgrad_x6_kernels.hip); 0: on the float32 MFMA pipe like the float32 path (A/B). */
 #define PXO_TUNE_X6_WGRAD 4
+/*   PXO_TUNE_VD_RAY_BLOCK  rays per internal block of pxo_vd_render_fwd, 1 .. PXO_VD_RAY_BLOCK_MAX (default
+ *                          PXO_VD_RAY_BLOCK_DEFAULT): sets the workspace (about 1.7 MB per ray at 64 + 128 samples) and the
+ *                          rows per launch.  Blocks are independent: bits unchanged. */
+#define PXO_TUNE_VD_RAY_BLOCK 5
+#define PXO_VD_RAY_BLOCK_DEFAULT 1024
+#define PXO_VD_RAY_BLOCK_MAX 4096
 int pxo_set_tuning(int knob, int value);
 int pxo_get_tuning(int knob, int* value);
 

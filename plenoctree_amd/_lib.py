@@ -73,7 +73,7 @@ class PxoCamera(Structure):
 
 
 TREE_MAX_DEPTH = 10
-ABI_VERSION = 7                     # PXO_ABI_VERSION of include/plenoctree_hip.h
+ABI_VERSION = 8                     # PXO_ABI_VERSION of include/plenoctree_hip.h
 
 P = c_void_p
 CFG = POINTER(PxoCfg)
@@ -135,6 +135,9 @@ SIGNATURES = {
     "pxo_vd_eval_points_raw": (c_int, [c_int, P, P, c_int64, P, c_int64, c_int, P, P, P, c_size_t, P]),
     "pxo_vd_project_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
     "pxo_vd_project_sh": (c_int, [c_int, P, P, c_int64, P, c_int64, c_int, P, P, P, c_size_t, P]),
+    "pxo_vd_render_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
+    "pxo_vd_render_fwd": (c_int, [CFG, P, P, P, P, P, c_int64, c_int, P, P, c_uint64, P, P, P, P, P, P, P, c_size_t, P]),
+    "pxo_vd_composite_fwd": (c_int, [CFG, P, P, P, P, c_int64, c_int, P, P, P, P, P]),
     # include/plenoctree_octree.h
     "pxo_threshold_mask": (c_int, [P, c_int64, c_float, P, P]),
     "pxo_tree_workspace_bytes": (c_int, [c_int, POINTER(c_size_t)]),

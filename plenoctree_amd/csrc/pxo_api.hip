@@ -60,9 +60,11 @@ static std::atomic<int> g_tune_x6_wgrad{1};
 // and per-kernel HIP-event times stop meaning anything (the fine forward shares the GPU with the coarse reverse: 4.83 ms
 // "per launch" instead of 3.95), so the measured default stays the single stream.
 static std::atomic<int> g_tune_coarse_stream{0};
-static Tuning tuning_snapshot() {
+// PXO_TUNE_VD_RAY_BLOCK: rays per internal block of pxo_vd_render_fwd (viewdirs_kernels.hip); bits unchanged
+static std::atomic<int> g_tune_vd_ray_block{PXO_VD_RAY_BLOCK_DEFAULT};
+Tuning tuning_snapshot() {
   return Tuning{g_tune_tile_sched.load(), g_tune_wgrad_ranges.load(), g_tune_wgrad_skinny_ranges.load(),
-                g_tune_coarse_stream.load(), g_tune_x6_wgrad.load()};
+                g_tune_coarse_stream.load(), g_tune_x6_wgrad.load(), g_tune_vd_ray_block.load()};
 }
 
 // The side stream of that mode and its fork / join events: one set per host thread and device, created on first use and kept
@@ -350,6 +352,11 @@ int pxo_set_tuning(int knob, int value) {
       PXO_REQUIRE(value == 0 || value == 1, "pxo_set_tuning: bf16x6 weight gradients must be 0 (float32 MFMA) or 1 (bf16x6), got %d", value);
       g_tune_x6_wgrad = value;
       return PXO_OK;
+    case PXO_TUNE_VD_RAY_BLOCK:
+      PXO_REQUIRE(value >= 1 && value <= PXO_VD_RAY_BLOCK_MAX, "pxo_set_tuning: rays per block of pxo_vd_render_fwd must be 1 .. %d, got %d",
+                  PXO_VD_RAY_BLOCK_MAX, value);
+      g_tune_vd_ray_block = value;
+      return PXO_OK;
     default:
       set_error("pxo_set_tuning: unknown knob %d", knob);
       return PXO_ERR_ARG;
@@ -363,6 +370,7 @@ int pxo_get_tuning(int knob, int* value) {
     case PXO_TUNE_WGRAD_SKINNY_RANGES: *value = g_tune_wgrad_skinny_ranges; return PXO_OK;
     case PXO_TUNE_COARSE_REVERSE_STREAM: *value = g_tune_coarse_stream; return PXO_OK;
     case PXO_TUNE_X6_WGRAD: *value = g_tune_x6_wgrad; return PXO_OK;
+    case PXO_TUNE_VD_RAY_BLOCK: *value = g_tune_vd_ray_block; return PXO_OK;
     default: set_error("pxo_get_tuning: unknown knob %d", knob); return PXO_ERR_ARG;
   }
 }

@@ -201,7 +201,9 @@ struct Tuning {
   int wgrad_skinny_ranges;    // PXO_TUNE_WGRAD_SKINNY_RANGES: the same for the enc-based pair and the head product
   int coarse_stream;          // PXO_TUNE_COARSE_REVERSE_STREAM: 1 = the coarse reverse pass on a side stream
   int x6_wgrad;               // PXO_TUNE_X6_WGRAD: 1 = in bf16x6 the 256x256 weight gradients run on the bf16 pipe too, 0 = float32 MFMA
+  int vd_ray_block;           // PXO_TUNE_VD_RAY_BLOCK: rays per internal block of pxo_vd_render_fwd
 };
+Tuning tuning_snapshot();     // pxo_api.hip: every knob, read once
 
 constexpr int kKC = 32;           // row granularity of the weight-gradient split (rows_per_wg is a multiple of it)
 // The split of a pass of M rows over `ncu` CUs: row ranges per layer of the 256x256 products / of the skinny products.
@@ -312,7 +314,12 @@ int launch_mean_samples(const float* raw_rgb, const float* raw_sigma, int64_t n_
                         hipStream_t s);
 int launch_uniform(uint64_t seed, uint64_t stream_id, int64_t n, float lo, float hi, float* out,
                    hipStream_t s);
-int launch_add_noise(float* raw, int64_t n, float noise_std, const float* noise, uint64_t seed, uint64_t stream_id, hipStream_t s);
+// first: raw[i] takes the draw of element first + i of the stream (a block of a larger batch)
+int launch_add_noise(float* raw, int64_t n, float noise_std, const float* noise, uint64_t seed, uint64_t stream_id, hipStream_t s,
+                     int64_t first = 0);
+// compositing of the view-conditioned head (render_kernels.hip vd_composite_fwd_kernel); weights may be NULL
+int launch_vd_composite_fwd(int white_bkgd, const float* raw_rgb, const float* raw_sigma, const float* z, const float* dirs,
+                            int64_t B, int S, float* comp_rgb, float* disp, float* acc, float* weights, hipStream_t s);
 int launch_adam(float* p, float* m, float* v, const float* g, int64_t n, float lr, int64_t step,
                 float grad_scale, hipStream_t s);
 // training form of the compositing: forward + pixel loss + reverse in one launch (see render_kernels.hip); serves the

@@ -94,6 +94,27 @@ struct SampleState {
   float raw_sigma;
 };
 
+// relu(sigma), the distance to the next sample and exp(-sigma dist) of one valid sample; returns 1 - alpha + eps, its factor of
+// the transmittance product (shared by the SH and the view-conditioned compositing kernels)
+__device__ __forceinline__ float sample_alpha(const float* __restrict__ raw_sigma, const float* __restrict__ z_vals, int64_t base,
+                                              int s0, int S, int lane, float norm_d, SampleState& st) {
+  st.raw_sigma = raw_sigma[base + lane];
+  const float sigma = fmaxf(st.raw_sigma, 0.f);  // relu, models.py:281
+  st.z = z_vals[base + lane];
+  const bool last = (s0 + lane == S - 1);
+  st.dist = (last ? 1e10f : z_vals[base + lane + 1] - st.z) * norm_d;
+  st.e = expf(-sigma * st.dist);
+  return (1.f - (1.f - st.e)) + 1e-10f;            // 1 - alpha + eps, model_utils.py:202
+}
+// transmittance before each sample of the chunk from the lanes' factors f; `carry` is the product over previous chunks
+__device__ __forceinline__ void chunk_transmittance(float f, int lane, float& carry, SampleState& st) {
+  const float incl = wave_scan_mul(f, lane);
+  float excl = __shfl_up(incl, 1);
+  if (lane == 0) excl = 1.f;
+  st.T = carry * excl;
+  carry = carry * __shfl(incl, 63);
+}
+
 // loads the chunk's raw SH coefficients through LDS (coalesced), evaluates sigmoid(eval_sh),
 // relu(sigma), alpha and the transmittance scan; `carry` is the product over previous chunks.
 template <int DEG>
@@ -123,19 +144,9 @@ __device__ __forceinline__ void shade_chunk(const float* __restrict__ raw_rgb, c
       for (int k = 0; k < K; ++k) pre += Y[k] * wl[lane * CS + c * K + k];
       st.rgb[c] = 1.f / (1.f + expf(-pre));        // sigmoid, models.py:280
     }
-    st.raw_sigma = raw_sigma[base + lane];
-    const float sigma = fmaxf(st.raw_sigma, 0.f);  // relu, models.py:281
-    st.z = z_vals[base + lane];
-    const bool last = (s0 + lane == S - 1);
-    st.dist = (last ? 1e10f : z_vals[base + lane + 1] - st.z) * norm_d;
-    st.e = expf(-sigma * st.dist);
-    f = (1.f - (1.f - st.e)) + 1e-10f;             // 1 - alpha + eps, model_utils.py:202
+    f = sample_alpha(raw_sigma, z_vals, base, s0, S, lane, norm_d, st);
   }
-  const float incl = wave_scan_mul(f, lane);
-  float excl = __shfl_up(incl, 1);
-  if (lane == 0) excl = 1.f;
-  st.T = carry * excl;
-  carry = carry * __shfl(incl, 63);
+  chunk_transmittance(f, lane, carry, st);
 }
 
 template <int DEG>
@@ -177,6 +188,63 @@ __global__ __launch_bounds__(kRayThreads) void shade_composite_fwd_kernel(
     disp[ray] = dsp;
     acc_out[ray] = s_acc;
   }
+}
+
+// The same compositing for the view-conditioned head (nerf_sh/nerf/models.py:269-284 with use_viewdirs: rgb =
+// sigmoid(raw_rgb), three channels per sample, no SH sum): one wave per ray, 64-sample chunks, the guarded arithmetic of
+// the kernel above.  The sample's 12 bytes are read straight from memory (no LDS staging).  weights may be NULL.
+__global__ __launch_bounds__(kRayThreads) void vd_composite_fwd_kernel(
+    const float* __restrict__ raw_rgb, const float* __restrict__ raw_sigma, const float* __restrict__ z_vals,
+    const float* __restrict__ dirs, int64_t B, int S, int white, float* __restrict__ comp_rgb, float* __restrict__ disp,
+    float* __restrict__ acc_out, float* __restrict__ weights) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t ray = blockIdx.x * (int64_t)kRaysPerBlock + wave;
+  const bool ray_ok = ray < B;
+  if (!ray_ok) ray = B - 1;
+  const float dx = dirs[ray * 3], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
+  const float norm_d = sqrtf(dx * dx + dy * dy + dz * dz);
+  float carry = 1.f, s_r = 0.f, s_g = 0.f, s_b = 0.f, s_depth = 0.f, s_acc = 0.f;
+  const int nch = (S + 63) / 64;
+  for (int ch = 0; ch < nch; ++ch) {
+    const int s0 = ch * 64;
+    const int64_t base = ray * S + s0;
+    SampleState st;
+    float f = 1.f;
+    st.e = 1.f; st.z = 0.f; st.dist = 0.f; st.raw_sigma = 0.f;
+    st.rgb[0] = st.rgb[1] = st.rgb[2] = 0.f;
+    if (s0 + lane < S) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) st.rgb[c] = 1.f / (1.f + expf(-raw_rgb[(base + lane) * 3 + c]));   // sigmoid, models.py:280
+      f = sample_alpha(raw_sigma, z_vals, base, s0, S, lane, norm_d, st);
+    }
+    chunk_transmittance(f, lane, carry, st);
+    const float w = (1.f - st.e) * st.T;
+    s_r += w * st.rgb[0]; s_g += w * st.rgb[1]; s_b += w * st.rgb[2];
+    s_depth += w * st.z; s_acc += w;
+    if (weights && ray_ok && s0 + lane < S) weights[base + lane] = w;
+  }
+  s_r = wave_sum(s_r); s_g = wave_sum(s_g); s_b = wave_sum(s_b);
+  s_depth = wave_sum(s_depth); s_acc = wave_sum(s_acc);
+  if (ray_ok && lane == 0) {
+    const float inv_eps = 1e10f;
+    float dsp = s_acc / s_depth;
+    dsp = (dsp > 0.f && dsp < inv_eps && s_acc > 1e-10f) ? dsp : inv_eps;  // model_utils.py:217-219
+    const float bg = white ? 1.f - s_acc : 0.f;
+    comp_rgb[ray * 3 + 0] = s_r + bg;
+    comp_rgb[ray * 3 + 1] = s_g + bg;
+    comp_rgb[ray * 3 + 2] = s_b + bg;
+    disp[ray] = dsp;
+    acc_out[ray] = s_acc;
+  }
+}
+
+int launch_vd_composite_fwd(int white_bkgd, const float* raw_rgb, const float* raw_sigma, const float* z, const float* dirs,
+                            int64_t B, int S, float* comp_rgb, float* disp, float* acc, float* weights, hipStream_t s) {
+  if (B == 0) return PXO_OK;
+  if (S > 64 * kMaxChunks || S < 1) { set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks); return PXO_ERR_ARG; }
+  hipLaunchKernelGGL(vd_composite_fwd_kernel, dim3((unsigned)((B + kRaysPerBlock - 1) / kRaysPerBlock)), dim3(kRayThreads), 0, s,
+                     raw_rgb, raw_sigma, z, dirs, B, S, white_bkgd, comp_rgb, disp, acc, weights);
+  return check_launch("vd_composite_fwd");
 }
 
 // reverse of the above for a loss on comp_rgb only; no gradient flows to z (stop_gradient,
@@ -724,14 +792,17 @@ int launch_uniform_jobs(uint64_t seed, const UniformJob* jobs, int n_jobs, hipSt
 
 // add_gaussian_noise (nerf_sh/nerf/model_utils.py:317-332): raw += noise_std * N(0,1).  Injected draws, or Box-Muller on the
 // Philox block of the element's quad (layout in include/plenoctree_hip.h).
+// raw[i] is element first + i of the stream (first = 0: the whole draw; a block of rays of a larger batch passes its offset, so
+// that the draw of an element does not depend on how the batch is cut into blocks).
 __global__ void add_noise_kernel(float* __restrict__ raw, int64_t n, float noise_std, const float* __restrict__ noise,
-                                 uint64_t seed, uint64_t stream_id) {
-  const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (q * 4 >= n) return;
+                                 uint64_t seed, uint64_t stream_id, int64_t first) {
+  const int64_t q = (first >> 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;      // quad of the stream
+  const int64_t end = first + n;
+  if (q * 4 >= end) return;
   float z[4];
   if (noise) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = q * 4 + i < n ? noise[q * 4 + i] : 0.0f;
+    for (int i = 0; i < 4; ++i) z[i] = (q * 4 + i >= first && q * 4 + i < end) ? noise[q * 4 + i - first] : 0.0f;
   } else {
     uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -754,14 +825,16 @@ __global__ void add_noise_kernel(float* __restrict__ raw, int64_t n, float noise
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int64_t idx = q * 4 + i;
-    if (idx < n) raw[idx] = raw[idx] + noise_std * z[i];
+    if (idx >= first && idx < end) raw[idx - first] = raw[idx - first] + noise_std * z[i];
   }
 }
 
-int launch_add_noise(float* raw, int64_t n, float noise_std, const float* noise, uint64_t seed, uint64_t stream_id, hipStream_t s) {
+int launch_add_noise(float* raw, int64_t n, float noise_std, const float* noise, uint64_t seed, uint64_t stream_id, hipStream_t s,
+                     int64_t first) {
   if (n == 0) return PXO_OK;
-  const int64_t q = (n + 3) / 4;
-  hipLaunchKernelGGL(add_noise_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, s, raw, n, noise_std, noise, seed, stream_id);
+  const int64_t q = (first + n + 3) / 4 - first / 4;
+  hipLaunchKernelGGL(add_noise_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, s, raw, n, noise_std, noise, seed, stream_id,
+                     first);
   return check_launch("add_gaussian_noise");
 }
 

@@ -94,68 +94,136 @@ __global__ __launch_bounds__(kVdWc) void vd_dir_kernel(const float* __restrict__
 }
 
 // A = (x7 . W9 + b9) . W10[:256] (sigma = Dense_8(x7) comes from the trunk launch's own head, like pxo_grid_sigma's).  16 points
-// per workgroup; every dot product runs as four interleaved chains (k mod 4) that are added pairwise at the end.
+// per workgroup; every dot product runs as four interleaved chains (k mod 4) that are added pairwise at the end.  The three
+// steps are __device__ functions shared by vd_head_kernel (A to memory: the projection and the per-point form) and
+// vd_ray_head_kernel (A stays in LDS: ray rendering), so that both produce the same bits.
 constexpr int kHeadPts = 16;
 constexpr int kHeadLd = 260;
-__global__ __launch_bounds__(256) void vd_head_kernel(const float* __restrict__ x7, const float* __restrict__ head, int64_t N,
-                                                      float* __restrict__ A) {
-  __shared__ __attribute__((aligned(16))) float xs[kHeadPts * kHeadLd];
-  __shared__ __attribute__((aligned(16))) float bs[kHeadPts * kHeadLd];
-  const int t = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * kHeadPts;
+// x7 rows [row0, row0 + 16) -> xs (rows past N: zeros)
+__device__ __forceinline__ void head_load_x7(const float* __restrict__ x7, int64_t row0, int64_t N, float* __restrict__ xs, int t) {
   for (int i = t; i < kHeadPts * 64; i += 256) {
     const int p = i >> 6, q = i & 63;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (row0 + p < N) v = *reinterpret_cast<const float4*>(x7 + (row0 + p) * kW + 4 * q);
     *reinterpret_cast<float4*>(&xs[p * kHeadLd + 4 * q]) = v;
   }
-  __syncthreads();
-  {  // bottleneck column t of the 16 points
-    float acc[kHeadPts][4];
+}
+// bottleneck (Dense_9) column t of the 16 points: xs -> bs
+__device__ __forceinline__ void head_bottleneck(const float* __restrict__ xs, float* __restrict__ bs, const float* __restrict__ head,
+                                                int t) {
+  float acc[kHeadPts][4];
 #pragma unroll
-    for (int p = 0; p < kHeadPts; ++p) acc[p][0] = acc[p][1] = acc[p][2] = acc[p][3] = 0.f;
-    for (int k = 0; k < kW; k += 4) {
-      const float w0 = head[kW9 + (int64_t)(k + 0) * kW + t], w1 = head[kW9 + (int64_t)(k + 1) * kW + t],
-                  w2 = head[kW9 + (int64_t)(k + 2) * kW + t], w3 = head[kW9 + (int64_t)(k + 3) * kW + t];
+  for (int p = 0; p < kHeadPts; ++p) acc[p][0] = acc[p][1] = acc[p][2] = acc[p][3] = 0.f;
+  for (int k = 0; k < kW; k += 4) {
+    const float w0 = head[kW9 + (int64_t)(k + 0) * kW + t], w1 = head[kW9 + (int64_t)(k + 1) * kW + t],
+                w2 = head[kW9 + (int64_t)(k + 2) * kW + t], w3 = head[kW9 + (int64_t)(k + 3) * kW + t];
 #pragma unroll
-      for (int p = 0; p < kHeadPts; ++p) {
-        const float4 x = *reinterpret_cast<const float4*>(&xs[p * kHeadLd + k]);
-        acc[p][0] = fmaf(x.x, w0, acc[p][0]);
-        acc[p][1] = fmaf(x.y, w1, acc[p][1]);
-        acc[p][2] = fmaf(x.z, w2, acc[p][2]);
-        acc[p][3] = fmaf(x.w, w3, acc[p][3]);
-      }
+    for (int p = 0; p < kHeadPts; ++p) {
+      const float4 x = *reinterpret_cast<const float4*>(&xs[p * kHeadLd + k]);
+      acc[p][0] = fmaf(x.x, w0, acc[p][0]);
+      acc[p][1] = fmaf(x.y, w1, acc[p][1]);
+      acc[p][2] = fmaf(x.z, w2, acc[p][2]);
+      acc[p][3] = fmaf(x.w, w3, acc[p][3]);
     }
-    const float b = head[kB9 + t];
-#pragma unroll
-    for (int p = 0; p < kHeadPts; ++p) bs[p * kHeadLd + t] = ((acc[p][0] + acc[p][1]) + (acc[p][2] + acc[p][3])) + b;
   }
-  __syncthreads();
-  {  // A column j of 8 points
-    const int j = t & (kVdWc - 1), ph = t >> 7;
-    float acc[8][4];
+  const float b = head[kB9 + t];
 #pragma unroll
-    for (int p = 0; p < 8; ++p) acc[p][0] = acc[p][1] = acc[p][2] = acc[p][3] = 0.f;
-    for (int k = 0; k < kW; k += 4) {
-      const float w0 = head[kW10 + (int64_t)(k + 0) * kVdWc + j], w1 = head[kW10 + (int64_t)(k + 1) * kVdWc + j],
-                  w2 = head[kW10 + (int64_t)(k + 2) * kVdWc + j], w3 = head[kW10 + (int64_t)(k + 3) * kVdWc + j];
+  for (int p = 0; p < kHeadPts; ++p) bs[p * kHeadLd + t] = ((acc[p][0] + acc[p][1]) + (acc[p][2] + acc[p][3])) + b;
+}
+// A column j = t & 127 of the 8 points (t >> 7) * 8 .. + 7: bs -> a
+__device__ __forceinline__ void head_condition(const float* __restrict__ bs, const float* __restrict__ head, int t, float (&a)[8]) {
+  const int j = t & (kVdWc - 1), ph = t >> 7;
+  float acc[8][4];
 #pragma unroll
-      for (int p = 0; p < 8; ++p) {
-        const float4 x = *reinterpret_cast<const float4*>(&bs[(ph * 8 + p) * kHeadLd + k]);
-        acc[p][0] = fmaf(x.x, w0, acc[p][0]);
-        acc[p][1] = fmaf(x.y, w1, acc[p][1]);
-        acc[p][2] = fmaf(x.z, w2, acc[p][2]);
-        acc[p][3] = fmaf(x.w, w3, acc[p][3]);
-      }
-    }
+  for (int p = 0; p < 8; ++p) acc[p][0] = acc[p][1] = acc[p][2] = acc[p][3] = 0.f;
+  for (int k = 0; k < kW; k += 4) {
+    const float w0 = head[kW10 + (int64_t)(k + 0) * kVdWc + j], w1 = head[kW10 + (int64_t)(k + 1) * kVdWc + j],
+                w2 = head[kW10 + (int64_t)(k + 2) * kVdWc + j], w3 = head[kW10 + (int64_t)(k + 3) * kVdWc + j];
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
-      const int64_t row = row0 + ph * 8 + p;
-      if (row < N) A[row * kVdWc + j] = (acc[p][0] + acc[p][1]) + (acc[p][2] + acc[p][3]);
+      const float4 x = *reinterpret_cast<const float4*>(&bs[(ph * 8 + p) * kHeadLd + k]);
+      acc[p][0] = fmaf(x.x, w0, acc[p][0]);
+      acc[p][1] = fmaf(x.y, w1, acc[p][1]);
+      acc[p][2] = fmaf(x.z, w2, acc[p][2]);
+      acc[p][3] = fmaf(x.w, w3, acc[p][3]);
     }
+  }
+#pragma unroll
+  for (int p = 0; p < 8; ++p) a[p] = (acc[p][0] + acc[p][1]) + (acc[p][2] + acc[p][3]);
+}
+
+__global__ __launch_bounds__(256) void vd_head_kernel(const float* __restrict__ x7, const float* __restrict__ head, int64_t N,
+                                                      float* __restrict__ A) {
+  __shared__ __attribute__((aligned(16))) float xs[kHeadPts * kHeadLd];
+  __shared__ __attribute__((aligned(16))) float bs[kHeadPts * kHeadLd];
+  const int t = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * kHeadPts;
+  head_load_x7(x7, row0, N, xs, t);
+  __syncthreads();
+  head_bottleneck(xs, bs, head, t);
+  __syncthreads();
+  float a[8];
+  head_condition(bs, head, t, a);
+  const int j = t & (kVdWc - 1), ph = t >> 7;
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    const int64_t row = row0 + ph * 8 + p;
+    if (row < N) A[row * kVdWc + j] = a[p];
   }
 }
 
+// channels [c0, c0 + NC) of one row's raw colour: relu(a + c) . W11 + b11, two chains (j parity) per channel
+template <int NC>
+__device__ __forceinline__ void row_rgb(const float* __restrict__ a, const float* __restrict__ c, const float* __restrict__ head,
+                                        int c0, float* __restrict__ out) {
+  float s0[NC], s1[NC];
+#pragma unroll
+  for (int ch = 0; ch < NC; ++ch) s0[ch] = s1[ch] = 0.f;
+  for (int j = 0; j < kVdWc; j += 2) {
+    const float h0 = fmaxf(a[j] + c[j], 0.f), h1 = fmaxf(a[j + 1] + c[j + 1], 0.f);
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) {
+      s0[ch] = fmaf(h0, head[kW11 + j * 3 + c0 + ch], s0[ch]);
+      s1[ch] = fmaf(h1, head[kW11 + (j + 1) * 3 + c0 + ch], s1[ch]);
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < NC; ++ch) out[ch] = (s0[ch] + s1[ch]) + head[kB11 + c0 + ch];
+}
+
+// Ray rendering: raw_rgb[row] = relu(A[row] + C[row / S]) . W11 + b11 for 16 consecutive sample rows, A = Dense_9(x7) . W10[:256]
+// computed in LDS by the functions above and never written to memory (the vd_head_kernel + vd_point_kernel pair moves 1 KB per
+// sample through it, and needs C per sample instead of per ray).  C [rays,128]: vd_dir_kernel on the block's view directions.
+// The ray of a row is looked up per row: a group of 16 straddles two rays whenever S is not a multiple of 16.
+__global__ __launch_bounds__(256) void vd_ray_head_kernel(const float* __restrict__ x7, const float* __restrict__ head,
+                                                          const float* __restrict__ C, int64_t M, int S,
+                                                          float* __restrict__ raw_rgb) {
+  __shared__ __attribute__((aligned(16))) float xs[kHeadPts * kHeadLd];
+  __shared__ __attribute__((aligned(16))) float bs[kHeadPts * kHeadLd];
+  const int t = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * kHeadPts;
+  head_load_x7(x7, row0, M, xs, t);
+  __syncthreads();
+  head_bottleneck(xs, bs, head, t);
+  __syncthreads();
+  float a[8];
+  head_condition(bs, head, t, a);
+  const int j = t & (kVdWc - 1), ph = t >> 7;
+#pragma unroll
+  for (int p = 0; p < 8; ++p) xs[(ph * 8 + p) * kHeadLd + j] = a[p];      // xs was last read before the second barrier
+  for (int i = t; i < kHeadPts * kVdWc; i += 256) {                        // C of each row's ray -> columns 128.. of xs
+    const int p = i >> 7, jj = i & (kVdWc - 1);
+    const int64_t row = row0 + p < M ? row0 + p : M - 1;
+    xs[p * kHeadLd + kVdWc + jj] = C[(row / S) * kVdWc + jj];
+  }
+  __syncthreads();
+  if (t < kHeadPts * 3) {
+    const int p = t / 3, ch = t - 3 * p;
+    float v;
+    row_rgb<1>(&xs[p * kHeadLd], &xs[p * kHeadLd + kVdWc], head, ch, &v);
+    if (row0 + p < M) raw_rgb[(row0 + p) * 3 + ch] = v;
+  }
+}
 
 // rgb of one (point, direction) pair: relu(a + c) . W11 + b11, two chains (j parity).  c, w and b are wave-uniform.
 __device__ __forceinline__ void pair_rgb(const float (&a)[kVdWc], const float* __restrict__ c, const float* __restrict__ w,
@@ -237,16 +305,7 @@ __global__ __launch_bounds__(kPairThreads) void vd_point_kernel(const float* __r
                                                                float* __restrict__ out) {
   const int64_t p = (int64_t)blockIdx.x * kPairThreads + threadIdx.x;
   if (p >= N) return;
-  float s0[3] = {0.f, 0.f, 0.f}, s1[3] = {0.f, 0.f, 0.f};
-  for (int j = 0; j < kVdWc; j += 2) {
-    const float h0 = fmaxf(A[p * kVdWc + j] + Cn[p * kVdWc + j], 0.f), h1 = fmaxf(A[p * kVdWc + j + 1] + Cn[p * kVdWc + j + 1], 0.f);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      s0[ch] = fmaf(h0, head[kW11 + j * 3 + ch], s0[ch]);
-      s1[ch] = fmaf(h1, head[kW11 + (j + 1) * 3 + ch], s1[ch]);
-    }
-  }
-  for (int ch = 0; ch < 3; ++ch) out[p * 3 + ch] = (s0[ch] + s1[ch]) + head[kB11 + ch];
+  row_rgb<3>(A + p * kVdWc, Cn + p * kVdWc, head, 0, out + p * 3);
 }
 
 namespace {
@@ -330,6 +389,62 @@ int launch_pair(int sh_deg, const float* A, const float* C, const float* Y, cons
 }
 
 constexpr int64_t kVdMaxRows = (int64_t)1 << 30;    // keeps every grid dimension and every index product in range
+
+// ---- ray rendering ------------------------------------------------------------------------------------------------------------
+// Workspace of pxo_vd_render_fwd: the buffers of ONE block of `rb` rays at S = Nc + Nf samples (the coarse level uses a prefix of
+// them: its points, raw values and saved tensors are dead once its weights exist), and the draws of the whole batch.
+struct VdRenderWs {
+  float *acts, *enc, *z_c, *w_c, *z_f, *pts, *raw_sigma, *raw_rgb, *C, *t_rand, *u;
+  uint32_t* mask;
+  int64_t rb;
+  size_t total;
+};
+
+void vd_render_carve(const PxoCfg* cfg, int64_t B, int block, void* ws, VdRenderWs& w) {
+  VdCarver c(ws);
+  const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples, S = Nc + Nf;
+  w.rb = B < block ? (B > 0 ? B : 1) : block;
+  const int64_t n = w.rb * S;
+  w.acts = c.take<float>(n * kW * kDepth);
+  w.enc = c.take<float>(n * kEncPad);
+  w.mask = c.take<uint32_t>(mask_words(n));
+  w.z_c = c.take<float>(w.rb * Nc);
+  w.w_c = c.take<float>(w.rb * Nc);
+  w.z_f = c.take<float>(n);
+  w.pts = c.take<float>(n * 3);
+  w.raw_sigma = c.take<float>(n);
+  w.raw_rgb = c.take<float>(n * 3);
+  w.C = c.take<float>((dir_blocks(w.rb) + 1) * kDirBlock * kVdWc);
+  w.t_rand = c.take<float>(B * Nc);
+  w.u = c.take<float>(B * (Nf > 0 ? Nf : 1));
+  w.total = (c.off + 255) & ~(size_t)255;
+}
+
+// one level of one block: trunk (raw sigma, x7), the direction term once per ray, the fused head (raw colour)
+int vd_render_level(const float* packed, int64_t nb, int S, const float* viewdirs, VdRenderWs& w, hipStream_t s) {
+  const PxoCfg tcfg = trunk_cfg();
+  const int64_t M = nb * S;
+  int rc = launch_mlp_fwd(&tcfg, packed, w.pts, M, nullptr, w.raw_sigma, w.acts, w.enc, w.mask, s);
+  if (rc != PXO_OK) return rc;
+  const float* x7 = w.acts + (int64_t)(kDepth - 1) * M * kW;
+  const float* head = packed + fwd_image_floats(0);
+  hipLaunchKernelGGL(vd_dir_kernel, dim3((unsigned)(dir_blocks(nb) * kDirBlock)), dim3(kVdWc), 0, s, viewdirs, head, nb, w.C,
+                     (float*)nullptr);
+  rc = check_launch("vd_dir");
+  if (rc != PXO_OK) return rc;
+  hipLaunchKernelGGL(vd_ray_head_kernel, dim3((unsigned)((M + kHeadPts - 1) / kHeadPts)), dim3(256), 0, s, x7, head, w.C, M, S,
+                     w.raw_rgb);
+  return check_launch("vd_ray_head");
+}
+
+// the cfg checks of the SH entry points, without sh_deg (this model has none: the reference's rendering presets say -1)
+int vd_render_cfg(const PxoCfg* cfg, const char* what) {
+  PXO_REQUIRE(cfg != nullptr, "%s: cfg is NULL", what);
+  PxoCfg c = *cfg;
+  c.sh_deg = 0;
+  const int rc = validate_cfg(&c);
+  return rc != PXO_OK ? rc : vd_precision(cfg->mlp_precision, what);
+}
 
 }  // namespace
 }  // namespace pxo
@@ -440,6 +555,82 @@ int pxo_vd_project_sh(int mlp_precision, const float* packed, const float* point
   if (rc != PXO_OK) return rc;
   const float weight = (float)(4.0 * 3.14159265358979323846 / (double)R);
   return launch_pair<true>(sh_deg, w.A, w.C, w.Y, head, N, (int)R, weight, coeffs, s);
+}
+
+int pxo_vd_render_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
+  int rc = vd_render_cfg(cfg, "pxo_vd_render_workspace_bytes");
+  if (rc != PXO_OK) return rc;
+  PXO_REQUIRE(bytes && B >= 0 && B <= kVdMaxRows, "pxo_vd_render_workspace_bytes: bad arguments");
+  VdRenderWs w;
+  vd_render_carve(cfg, B, tuning_snapshot().vd_ray_block, nullptr, w);
+  *bytes = w.total;
+  return PXO_OK;
+}
+
+int pxo_vd_render_fwd(const PxoCfg* cfg, const float* packed0, const float* packed1, const float* origins,
+                      const float* directions, const float* viewdirs, int64_t B, int randomized, const float* t_rand,
+                      const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f, float* disp_f,
+                      float* acc_f, void* ws, size_t ws_bytes, void* stream) {
+  int rc = vd_render_cfg(cfg, "pxo_vd_render_fwd");
+  if (rc != PXO_OK) return rc;
+  if (B == 0) return PXO_OK;                   // an empty batch has no buffers to check
+  PXO_REQUIRE(B > 0 && B <= kVdMaxRows && packed0 && origins && directions && viewdirs && rgb_c && disp_c && acc_c && ws,
+              "pxo_vd_render_fwd: bad arguments");
+  const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples, S = Nc + Nf;
+  if (Nf > 0) PXO_REQUIRE(packed1 && rgb_f && disp_f && acc_f, "pxo_vd_render_fwd: fine outputs/weights missing");
+  VdRenderWs w;
+  vd_render_carve(cfg, B, tuning_snapshot().vd_ray_block, ws, w);
+  if (ws_bytes < w.total) { set_error("pxo_vd_render_fwd: workspace %zu < %zu", ws_bytes, w.total); return PXO_ERR_WORKSPACE; }
+  hipStream_t s = (hipStream_t)stream;
+  // the draws of the whole batch (jax.random.uniform call sites model_utils.py:135,262), the streams of pxo_render_fwd
+  UniformJob jobs[2];
+  int nj = 0;
+  if (randomized && !t_rand) { jobs[nj++] = UniformJob{0, B * Nc, 0.f, 1.f, w.t_rand}; t_rand = w.t_rand; }
+  if (randomized && Nf > 0 && !u) { jobs[nj++] = UniformJob{1, B * Nf, 0.f, 1.f, w.u}; u = w.u; }
+  if (!randomized) { t_rand = nullptr; u = nullptr; }
+  rc = launch_uniform_jobs(seed, jobs, nj, s);
+  if (rc != PXO_OK) return rc;
+  const bool noisy = randomized != 0 && cfg->noise_std > 0.f;     // (noise_std is not None) and randomized, model_utils.py:329
+  for (int64_t r0 = 0; r0 < B; r0 += w.rb) {
+    const int64_t nb = B - r0 < w.rb ? B - r0 : w.rb;
+    const float *o = origins + r0 * 3, *d = directions + r0 * 3, *v = viewdirs + r0 * 3;
+    rc = launch_sample_along_rays(o, d, nb, Nc, cfg->near_, cfg->far_, cfg->lindisp, t_rand ? t_rand + r0 * Nc : nullptr, w.z_c,
+                                  w.pts, s);
+    if (rc != PXO_OK) return rc;
+    rc = vd_render_level(packed0, nb, Nc, v, w, s);
+    if (rc != PXO_OK) return rc;
+    if (noisy) {                                                   // models.py:258-264
+      rc = launch_add_noise(w.raw_sigma, nb * Nc, cfg->noise_std, nullptr, seed, 3, s, r0 * Nc);
+      if (rc != PXO_OK) return rc;
+    }
+    rc = launch_vd_composite_fwd(cfg->white_bkgd, w.raw_rgb, w.raw_sigma, w.z_c, d, nb, Nc, rgb_c + r0 * 3, disp_c + r0,
+                                 acc_c + r0, Nf > 0 ? w.w_c : nullptr, s);
+    if (rc != PXO_OK) return rc;
+    if (Nf == 0) continue;
+    rc = launch_sample_pdf(w.z_c, w.w_c, o, d, nb, Nc, Nf, u ? u + r0 * Nf : nullptr, w.z_f, w.pts, s);
+    if (rc != PXO_OK) return rc;
+    rc = vd_render_level(packed1, nb, S, v, w, s);
+    if (rc != PXO_OK) return rc;
+    if (noisy) {                                                   // models.py:318-324
+      rc = launch_add_noise(w.raw_sigma, nb * S, cfg->noise_std, nullptr, seed, 4, s, r0 * S);
+      if (rc != PXO_OK) return rc;
+    }
+    rc = launch_vd_composite_fwd(cfg->white_bkgd, w.raw_rgb, w.raw_sigma, w.z_f, d, nb, S, rgb_f + r0 * 3, disp_f + r0,
+                                 acc_f + r0, nullptr, s);
+    if (rc != PXO_OK) return rc;
+  }
+  return PXO_OK;
+}
+
+int pxo_vd_composite_fwd(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, const float* z_vals,
+                         const float* directions, int64_t B, int S, float* comp_rgb, float* disp, float* acc, float* weights,
+                         void* stream) {
+  PXO_REQUIRE(cfg != nullptr, "pxo_vd_composite_fwd: cfg is NULL");
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(B > 0 && raw_rgb && raw_sigma && z_vals && directions && comp_rgb && disp && acc,
+              "pxo_vd_composite_fwd: bad arguments");
+  return launch_vd_composite_fwd(cfg->white_bkgd, raw_rgb, raw_sigma, z_vals, directions, B, S, comp_rgb, disp, acc, weights,
+                                 (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from .. import dist
-from .nerf import datasets, models, utils
+from .nerf import datasets, models, utils, viewdirs
 
 
 def save_outputs(out_dir, idx, rgb, disp):
@@ -27,16 +27,24 @@ def save_summary(out_dir, step, psnrs, ssims):
 
 
 def main(argv=None):
-    args = utils.define_flags().parse_args(argv)
+    args = viewdirs.add_checkpoint_flags(utils.define_flags()).parse_args(argv)
     utils.update_flags(args)
     if not torch.cuda.is_available():
         raise SystemExit("nerf_sh.eval needs a ROCm GPU; the HIP path has no CPU fallback")
     comm = dist.init_from_env()
     torch.cuda.set_device(comm.local_rank)
     device = torch.device("cuda", comm.local_rank)
-    utils.check_flags(args, world_size=comm.world)
+    if args.use_viewdirs:
+        # a view-dependent ("vanilla") NeRF: rendering opts in explicitly, like octree.extraction (training with this head is not
+        # built, so the generic check_flags keeps rejecting it)
+        viewdirs.check_render_dirs(args)
+    else:
+        utils.check_flags(args, world_size=comm.world)
     dataset = datasets.get_dataset("test", args, device)
-    model, state = models.get_model_state(args, device, restore=True)
+    if args.use_viewdirs:
+        model, state = viewdirs.restore_for_render(args, device, say=print if comm.rank == 0 else (lambda *a, **k: None))
+    else:
+        model, state = models.get_model_state(args, device, restore=True)
     out_dir = os.path.join(args.train_dir, "test_preds")
     if args.save_output and comm.rank == 0:
         os.makedirs(out_dir, exist_ok=True)

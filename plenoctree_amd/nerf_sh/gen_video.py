@@ -11,12 +11,12 @@ import numpy as np
 import torch
 
 from .. import dist, ops
-from .nerf import models, utils
+from .nerf import models, utils, viewdirs
 
 
 def define_flags():
     """nerf_sh/gen_video.py:52-105."""
-    p = utils.define_flags()
+    p = viewdirs.add_checkpoint_flags(utils.define_flags())
     a = p.add_argument
     a("--elevation", type=float, default=-30.0)
     a("--num_views", type=int, default=40)
@@ -45,8 +45,11 @@ def main(argv=None):
     comm = dist.init_from_env()
     torch.cuda.set_device(comm.local_rank)
     device = torch.device("cuda", comm.local_rank)
-    utils.check_flags(args, require_data=False, world_size=comm.world)
     say = print if comm.rank == 0 else (lambda *a, **k: None)
+    if args.use_viewdirs:
+        viewdirs.check_render_dirs(args, require_data=False)
+    else:
+        utils.check_flags(args, require_data=False, world_size=comm.world)
     say("* Generating poses", flush=True)
     poses = render_poses(args)
     if args.write_poses and comm.rank == 0:
@@ -57,7 +60,10 @@ def main(argv=None):
         K = np.loadtxt(args.intrin)
         focal = (K[0, 0] + K[1, 1]) * 0.5
     say("* Creating model", flush=True)
-    model, state = models.get_model_state(args, device, restore=True)
+    if args.use_viewdirs:      # a view-dependent ("vanilla") NeRF: opts in explicitly, like octree.extraction
+        model, state = viewdirs.restore_for_render(args, device, say=say, require_data=False)
+    else:
+        model, state = models.get_model_state(args, device, restore=True)
     video_dir = os.path.join(args.train_dir, "video", "e{:03}".format(int(-args.elevation * 10)))
     frames_dir = os.path.join(video_dir, "frames")
     say(" Saving to", video_dir, flush=True)

@@ -1,10 +1,11 @@
-"""The view-conditioned ("vanilla") NeRF of the reference, for extraction by SH projection only.
+"""The view-conditioned ("vanilla") NeRF of the reference: extraction by SH projection, and ray rendering (eval, gen_video).
 
 Host-side mirror of the torch twin with use_viewdirs=True (octree/nerf/models.py:116-252 over octree/nerf/model_utils.py:64-158,
 net_depth_condition 1, net_width_condition 128, deg_view 4): per MLP twelve dense layers in flax key order -- Dense_0..7 trunk,
 Dense_8 sigma, Dense_9 bottleneck, Dense_10 condition, Dense_11 rgb -- in one flat float32 arena (MLP_0 then MLP_1).  All
-arithmetic is done by libplenoctree_hip.so (csrc/viewdirs_kernels.hip) through plenoctree_amd.ops.  Training and ray rendering
-with this head are not built: nerf_sh.train / eval keep rejecting use_viewdirs=true (utils.check_supported).
+arithmetic is done by libplenoctree_hip.so (csrc/viewdirs_kernels.hip) through plenoctree_amd.ops.  Training with this head is
+not built: nerf_sh.train keeps rejecting use_viewdirs=true (utils.check_supported); nerf_sh.eval and nerf_sh.gen_video opt in
+through check_render_flags.
 """
 import math
 
@@ -21,6 +22,7 @@ class ViewdirsState:
 
     def __init__(self, params):
         self.params = params
+        self.step = 0                # no optimiser state is restored: what eval names its per-step summary files with
         self.n_mlp = params.numel() // 2
         self.packed = [None, None]
         self._ws = None
@@ -42,15 +44,29 @@ class ViewdirsState:
 
 
 class ViewdirsModel:
-    def __init__(self, num_coarse_samples=64, num_fine_samples=128, mlp_precision=0):
-        # the SH model of degree 0 whose forward image opens the packed image: what pxo_grid_sigma is called with
-        self.cfg = ops.make_cfg(num_coarse_samples=num_coarse_samples, num_fine_samples=num_fine_samples, sh_deg=0)
+    def __init__(self, num_coarse_samples=64, num_fine_samples=128, mlp_precision=0, near=2.0, far=6.0, white_bkgd=True,
+                 lindisp=False, noise_std=None):
+        # the SH model of degree 0 whose forward image opens the packed image: what pxo_grid_sigma is called with; the ray
+        # renderer reads its sample counts, near / far, lindisp, white_bkgd and noise_std
+        self.cfg = ops.make_cfg(num_coarse_samples=num_coarse_samples, num_fine_samples=num_fine_samples, sh_deg=0, near_=near,
+                                far_=far, white_bkgd=int(bool(white_bkgd)), lindisp=int(bool(lindisp)),
+                                noise_std=0.0 if noise_std is None else noise_std, mlp_precision=mlp_precision)
         self.num_coarse_samples = num_coarse_samples
         self.num_fine_samples = num_fine_samples
         self.mlp_precision = mlp_precision
 
     def _which(self, coarse):
         return 1 if (self.num_fine_samples > 0 and not coarse) else 0
+
+    def apply(self, state, rays, randomized, t_rand=None, u=None, seed=0):
+        """model.apply(variables, key_0, key_1, rays, randomized) with use_viewdirs (nerf_sh/nerf/models.py:216-348): returns
+        [(rgb, disp, acc)_coarse, (rgb, disp, acc)_fine].  The jax keys are replaced by explicit uniforms (t_rand [B,Nc],
+        u [B,Nf]) or a Philox `seed`, as in NerfModel.apply."""
+        ws = state.workspace(ops.vd_render_workspace_bytes(self.cfg, rays.origins.shape[0]))
+        return ops.vd_render_fwd(self.cfg, state.packed[0][0], state.packed[1][0], rays.origins, rays.directions, rays.viewdirs,
+                                 randomized=randomized, t_rand=t_rand, u=u, seed=seed, ws=ws)
+
+    __call__ = apply
 
     def eval_points_raw(self, state, points, viewdirs=None, coarse=False, cross_broadcast=False):
         """octree/nerf/models.py:211-252: raw_rgb [N,3] (viewdirs [N,3]) or [N,R,3] (cross_broadcast, viewdirs [R,3]), raw
@@ -83,18 +99,19 @@ def init_params(seed=20200823):
     return flat
 
 
-def check_extraction_flags(args):
-    """What octree.extraction builds of a use_viewdirs=true model; everything else is rejected by name."""
+def _unbuilt_flags(args, projection):
+    """Names of the flags of a use_viewdirs=true model that the MI355X path does not build; `projection`: the clauses of the
+    SH projection (sh_deg, projection_samples) too."""
     bad = []
     if not args.use_viewdirs:
-        bad.append("use_viewdirs=false (an SH model: the plain extraction path)")
+        bad.append("use_viewdirs=false (an SH model: the plain path)")
     if args.net_depth_condition != 1:
         bad.append(f"net_depth_condition={args.net_depth_condition} (need 1)")
     if args.net_width_condition != 128:
         bad.append(f"net_width_condition={args.net_width_condition} (need 128)")
     if args.deg_view != 4:
         bad.append(f"deg_view={args.deg_view} (need 4)")
-    if args.sh_deg < 0 or args.sh_deg > 4:
+    if projection and (args.sh_deg < 0 or args.sh_deg > 4):
         bad.append(f"sh_deg={args.sh_deg} (the projection needs 0..4)")
     if args.sg_dim > 0:
         bad.append("sg_dim>0 (spherical gaussians)")
@@ -108,21 +125,71 @@ def check_extraction_flags(args):
         bad.append("num_rgb_channels/num_sigma_channels != 3/1")
     if getattr(args, "mlp_precision", "f32") != "f32":
         bad.append(f"mlp_precision={args.mlp_precision} (the view-conditioned head is float32 only)")
-    if getattr(args, "projection_samples", 1) < 1:
+    if projection and getattr(args, "projection_samples", 1) < 1:
         bad.append(f"projection_samples={args.projection_samples} (need >= 1)")
     if getattr(args, "render_path", False) or getattr(args, "spherify", False):
         bad.append("render_path / spherify (LLFF scenes)")
     if (args.net_activation.lower(), args.sigma_activation.lower()) != ("relu", "relu"):
         bad.append("activations other than relu")
+    return bad
+
+
+def check_extraction_flags(args):
+    """What octree.extraction builds of a use_viewdirs=true model; everything else is rejected by name."""
+    bad = _unbuilt_flags(args, projection=True)
     if bad:
         raise NotImplementedError("SH projection of a view-dependent NeRF, not built on the MI355X path: " + "; ".join(bad))
 
 
-def get_model_state(args, device):
-    """Model + state with freshly initialised parameters (the caller restores a checkpoint)."""
-    check_extraction_flags(args)
-    model = ViewdirsModel(args.num_coarse_samples, args.num_fine_samples)
+def check_render_flags(args):
+    """What nerf_sh.eval / gen_video build of a use_viewdirs=true model: check_extraction_flags without the projection's
+    clauses (the reference's rendering presets say sh_deg: -1), plus what the renderer itself reads."""
+    bad = _unbuilt_flags(args, projection=False)
+    if args.rgb_activation.lower() != "sigmoid":
+        bad.append("rgb_activation other than sigmoid")
+    if args.noise_std is not None and args.noise_std < 0:
+        bad.append("noise_std < 0")
+    if bad:
+        raise NotImplementedError("rendering a view-dependent NeRF, not built on the MI355X path: " + "; ".join(bad))
+
+
+def check_render_dirs(args, require_data=True):
+    """Flag check of the --use_viewdirs true branch of nerf_sh.eval / gen_video: utils.check_flags' directory checks, then
+    check_render_flags."""
+    if args.train_dir is None:
+        raise ValueError("train_dir must be set. None set now.")
+    if require_data and args.data_dir is None and args.dataset != "synthetic":
+        raise ValueError("data_dir must be set. None set now.")
+    check_render_flags(args)
+
+
+def get_model_state(args, device, render=False):
+    """Model + state with freshly initialised parameters (the caller restores a checkpoint).  render: the flag check of the ray
+    renderer instead of the projection's."""
+    (check_render_flags if render else check_extraction_flags)(args)
+    model = ViewdirsModel(args.num_coarse_samples, args.num_fine_samples, near=args.near, far=args.far,
+                          white_bkgd=args.white_bkgd, lindisp=args.lindisp, noise_std=args.noise_std)
     return model, ViewdirsState(init_params(args.seed).to(device))
+
+
+def restore_for_render(args, device, say=print, require_data=True):
+    """The --use_viewdirs true branch of nerf_sh.eval / gen_video, as octree.extraction's: flag checks, model + state, newest
+    checkpoint of train_dir (`*.ckpt` torch state dict, or flax msgpack with --is_jaxnerf_ckpt)."""
+    from . import checkpoints
+    check_render_dirs(args, require_data)
+    say("* Loading NeRF (view-conditioned head)", flush=True)
+    model, state = get_model_state(args, device, render=True)
+    say(checkpoints.restore_viewdirs_checkpoint(args.train_dir, state, bool(getattr(args, "is_jaxnerf_ckpt", False)),
+                                                bool(getattr(args, "trust_ckpt_pickle", False))), flush=True)
+    return model, state
+
+
+def add_checkpoint_flags(parser):
+    """The checkpoint flags of octree.extraction (same names) for the CLIs that render a view-conditioned model."""
+    from . import utils
+    parser.add_argument("--is_jaxnerf_ckpt", type=utils._bool, nargs="?", const=True, default=False)
+    parser.add_argument("--trust_ckpt_pickle", type=utils._bool, nargs="?", const=True, default=False)
+    return parser
 
 
 def sphere_directions(u, v):

@@ -355,6 +355,7 @@ PROF_MLP_FWD, PROF_MLP_BWD_DATA, PROF_WGRAD_MAIN, PROF_WGRAD_OTHER, PROF_NUM_TAG
 
 
 TUNE_TILE_SCHED, TUNE_WGRAD_RANGES, TUNE_WGRAD_SKINNY_RANGES, TUNE_COARSE_REVERSE_STREAM, TUNE_X6_WGRAD = 0, 1, 2, 3, 4        # PXO_TUNE_* of include/plenoctree_hip.h
+TUNE_VD_RAY_BLOCK = 5               # rays per internal block of vd_render_fwd (1 .. 4096, default 1024)
 
 
 def set_tuning(knob, value):
@@ -536,3 +537,39 @@ def vd_project_sh(packed, points, dirs, sh_deg, ws=None, coeffs=None, raw_sigma=
     check(lib.pxo_vd_project_sh(int(mlp_precision), _f(packed), _f(points), N, _f(dirs), R, int(sh_deg), _f(coeffs),
                                 _f(raw_sigma), _p(ws), ws.numel(), _stream()), "pxo_vd_project_sh")
     return coeffs, raw_sigma
+
+
+def vd_render_workspace_bytes(cfg, B):
+    n = ctypes.c_size_t(0)
+    check(_lib.load().pxo_vd_render_workspace_bytes(ctypes.byref(cfg), B, ctypes.byref(n)), "pxo_vd_render_workspace_bytes")
+    return n.value
+
+
+def vd_render_fwd(cfg, packed0, packed1, origins, directions, viewdirs, randomized=False, t_rand=None, u=None, seed=0, ws=None):
+    """NerfModel.__call__ of the view-conditioned model, forward: [(rgb,disp,acc)_coarse, (rgb,disp,acc)_fine] (the fine entry
+    only with num_fine_samples > 0).  packed0/1: the vd_pack_weights images of MLP_0 / MLP_1."""
+    _require_gpu()
+    B, dev = origins.shape[0], origins.device
+    ws = _ws(ws, vd_render_workspace_bytes(cfg, B), dev)
+    outs = [(_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev))]
+    fine = cfg.num_fine_samples > 0
+    if fine:
+        outs.append((_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev)))
+    f = outs[1] if fine else (None, None, None)
+    check(_lib.load().pxo_vd_render_fwd(ctypes.byref(cfg), _f(packed0), _f(packed1), _f(origins), _f(directions), _f(viewdirs), B,
+                                        int(randomized), _f(t_rand), _f(u), seed, _f(outs[0][0]), _f(outs[0][1]),
+                                        _f(outs[0][2]), _f(f[0]), _f(f[1]), _f(f[2]), _p(ws), ws.numel(), _stream()),
+          "pxo_vd_render_fwd")
+    return outs
+
+
+def vd_composite_fwd(cfg, raw_rgb, raw_sigma, z_vals, directions):
+    """sigmoid + relu + volumetric_rendering of the view-conditioned model: raw_rgb [B*S,3] -> (comp_rgb [B,3], disp [B], acc [B],
+    weights [B,S])."""
+    _require_gpu()
+    B, S = z_vals.shape
+    dev = z_vals.device
+    comp, disp, acc, w = _new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev), _new(B, S, device=dev)
+    check(_lib.load().pxo_vd_composite_fwd(ctypes.byref(cfg), _f(raw_rgb), _f(raw_sigma), _f(z_vals), _f(directions), B, S,
+                                           _f(comp), _f(disp), _f(acc), _f(w), _stream()), "pxo_vd_composite_fwd")
+    return comp, disp, acc, w
