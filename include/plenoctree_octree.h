@@ -147,6 +147,63 @@ int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float
                           const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* out_rgb,
                           const float* grad_out, float* grad_data, void* stream);
 
+/* ---- compressed trees rendered in place  (the palette form octree/compression.py:88-139 writes) ----
+ *
+ * File arrays (K = basis_dim, r = n_retained, Kq = K - r, C = n_internal * 8 cells, P = 2^bits palette entries):
+ *   quant_colors  float16 [Kq, P, 3]     quant_map  uint16 [Kq, C]     sigma  float16 or float32 [C]
+ *   data_retained float16 [r, C, 3]      (only with --retain r)
+ * Device layout made by pxo_octree_quant_pack, one buffer of four 256-byte aligned sections (PxoQuantLayout):
+ *   idx       uint16  [C, idx_stride]    idx_stride = Kq rounded up to a multiple of 4: a leaf's indices are contiguous
+ *                                        and every 8-byte group of four is 8-byte aligned whatever Kq is (odd for SH9,
+ *                                        SH25 or an odd remainder after `retain`); the padding holds index 0
+ *   palette   float16 [Kq, P, 4]         (r, g, b, 0): one 8-byte load per lookup
+ *   sigma     float32 [C]                widened (exactly) from the file's type
+ *   retained  float16 [C, r, 4]          (r, g, b, 0) per retained basis function; ret_stride = 4 r
+ * Bytes per leaf: 2 idx_stride + 4 + 8 r (SH16, retain 0: 36; float form 4 (3K+1) = 196), plus 8 Kq P for the palettes. */
+typedef struct PxoQuantLayout {
+  int64_t idx_offset, palette_offset, sigma_offset, retained_offset;   /* bytes into the packed buffer */
+  int64_t total_bytes;
+  int32_t idx_stride;           /* uint16 elements per leaf */
+  int32_t ret_stride;           /* float16 elements per leaf */
+} PxoQuantLayout;
+
+/* Read-only view of a packed compressed tree for pxo_octree_render_quant_fwd. */
+typedef struct PxoQuantTree {
+  const int32_t* child;
+  const uint16_t* idx;          /* packed indices [C, idx_stride], 8-byte aligned */
+  const void* palette;          /* float16 [Kq, 2^bits, 4], 8-byte aligned */
+  const float* sigma;           /* [C] */
+  const void* retained;         /* float16 [C, n_retained, 4], 8-byte aligned; ignored when n_retained == 0 */
+  int64_t n_internal;
+  int32_t basis_dim;            /* 1, 4, 9, 16 or 25 */
+  int32_t n_retained;           /* 0 .. basis_dim - 1 */
+  int32_t bits;                 /* 1 .. 16 */
+  int32_t idx_stride;
+  int32_t ret_stride;
+  float offset[3];
+  float invradius[3];
+} PxoQuantTree;
+
+/* Section offsets, strides and size of the packed form of a tree in the format of octree/compression.py:88-139
+ * (host only). */
+int pxo_octree_quant_pack_bytes(int64_t n_internal, int basis_dim, int n_retained, int bits, PxoQuantLayout* layout);
+/* Packs the arrays of a file written by octree/compression.py:88-139, uploaded as they are (device pointers), into
+ * `packed` (layout->total_bytes bytes, 256-byte aligned): transposes quant_map, pads the palette entries and the retained
+ * planes to 8 bytes and widens sigma (sigma_elem_bytes: 2 = float16, 4 = float32).  data_retained may be NULL when
+ * n_retained == 0.  Indices are NOT range-checked here: the caller validates them against 2^bits on the host (the
+ * renderer masks them to `bits` bits, so a bad index can give a wrong colour but never an out-of-range read). */
+int pxo_octree_quant_pack(const uint16_t* quant_map, const void* quant_colors, const void* sigma, int sigma_elem_bytes,
+                          const void* data_retained, int64_t n_internal, int basis_dim, int n_retained, int bits,
+                          void* packed, size_t packed_bytes, void* stream);
+/* pxo_octree_render_fwd on a tree in the palette form of octree/compression.py:88-139, read in place: same rays, same
+ * options, same sample sequence; per shaded sample and channel c, p_c = sum_b Y_b(viewdir) coef[c][b] with coef from
+ * `retained` for b < n_retained and from palette[b - n_retained][idx[leaf][b - n_retained]] otherwise, each float16
+ * widened to float32.  Lanes per ray: the forward value of pxo_octree_set_lanes_per_ray (4, 8, 16; default 4); the
+ * summation order over b is fixed by (lanes per ray, basis_dim, n_retained).  Forward only: a compressed tree is
+ * read-only. */
+int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb,
+                                void* stream);
 
 /* ---- work counters of the marchers (roofline pass: scripts/octree_bench.py states each kernel's algorithmic bytes from
  *      these; nothing on the product path calls them) ----

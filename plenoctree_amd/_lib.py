@@ -72,6 +72,17 @@ class PxoCamera(Structure):
     _fields_ = [("c2w", c_void_p), ("fx", c_float), ("fy", c_float), ("width", c_int32), ("height", c_int32)]
 
 
+class PxoQuantLayout(Structure):
+    _fields_ = [("idx_offset", c_int64), ("palette_offset", c_int64), ("sigma_offset", c_int64),
+                ("retained_offset", c_int64), ("total_bytes", c_int64), ("idx_stride", c_int32), ("ret_stride", c_int32)]
+
+
+class PxoQuantTree(Structure):
+    _fields_ = [("child", c_void_p), ("idx", c_void_p), ("palette", c_void_p), ("sigma", c_void_p), ("retained", c_void_p),
+                ("n_internal", c_int64), ("basis_dim", c_int32), ("n_retained", c_int32), ("bits", c_int32),
+                ("idx_stride", c_int32), ("ret_stride", c_int32), ("offset", c_float * 3), ("invradius", c_float * 3)]
+
+
 TREE_MAX_DEPTH = 10
 ABI_VERSION = 8                     # PXO_ABI_VERSION of include/plenoctree_hip.h
 
@@ -157,6 +168,10 @@ SIGNATURES = {
                                       POINTER(PxoRenderOpts), P, P]),
     "pxo_octree_render_bwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
                                       POINTER(PxoRenderOpts), P, P, P, P]),
+    "pxo_octree_quant_pack_bytes": (c_int, [c_int64, c_int, c_int, c_int, POINTER(PxoQuantLayout)]),
+    "pxo_octree_quant_pack": (c_int, [P, P, P, c_int, P, c_int64, c_int, c_int, c_int, P, c_size_t, P]),
+    "pxo_octree_render_quant_fwd": (c_int, [POINTER(PxoQuantTree), POINTER(PxoCamera), P, P, P, c_int64,
+                                            POINTER(PxoRenderOpts), P, P]),
     "pxo_octree_count_work": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), POINTER(PxoRenderOpts), P, P, P]),
     "pxo_grid_weight_count_work": (c_int, [P, c_int, P, c_int, c_float, c_float, c_int, c_int, POINTER(PxoRenderOpts),
                                            F3, F3, P, P, P]),

@@ -1,5 +1,6 @@
 // PlenOctree side of the path on gfx950: N3Tree build from the grid mask, leaf sampling, the
-// training-view weight mask over the dense grid, and the octree volume renderer (forward + gradient).
+// training-view weight mask over the dense grid, the octree volume renderer (forward + gradient), and the forward
+// renderer of compressed trees read through their palettes (octree_render_quant_kernel, at the end of the namespace).
 // C ABI: include/plenoctree_octree.h (reference call sites cited there).
 //
 // This translation unit is compiled with -ffp-contract=off: the marching arithmetic (sample positions,
@@ -1540,6 +1541,226 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
   p[i] = p[i] - lr * gi;
 }
 
+// ------------------------------------------------------------------------------------------
+// palette-form renderer: compressed trees (octree/compression.py:88-139) read in place, forward only.
+// Device layout: include/plenoctree_octree.h (PxoQuantLayout).
+// ------------------------------------------------------------------------------------------
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));        // a palette entry / a retained plane: (r, g, b, 0), 8 bytes
+typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));        // four consecutive palette indices of a leaf, 8 bytes
+
+static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+// one thread per (group of four planes, cell), cells fastest: the 2-byte reads of a wave are one contiguous run of a plane
+__global__ void quant_pack_idx_kernel(const uint16_t* __restrict__ qmap, int64_t cells, int Kq, int groups,
+                                      u16x4* __restrict__ idx) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= cells * groups) return;
+  const int64_t cell = i % cells;
+  const int g = (int)(i / cells);
+  u16x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int q = 4 * g + e;
+    v[e] = q < Kq ? qmap[(int64_t)q * cells + cell] : (uint16_t)0;
+  }
+  idx[cell * groups + g] = v;
+}
+
+// [m, 3] float16 -> [m, 4]: palette entries (m = Kq * 2^bits)
+__global__ void quant_pack_pad_kernel(const _Float16* __restrict__ src, int64_t m, f16x4* __restrict__ dst) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  f16x4 v;
+  v[0] = src[i * 3]; v[1] = src[i * 3 + 1]; v[2] = src[i * 3 + 2]; v[3] = (_Float16)0.0f;
+  dst[i] = v;
+}
+
+// data_retained [r, cells, 3] float16 -> [cells, r, 4]
+__global__ void quant_pack_retained_kernel(const _Float16* __restrict__ src, int64_t cells, int r, f16x4* __restrict__ dst) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;       // (plane, cell), cells fastest
+  if (i >= cells * r) return;
+  const int64_t cell = i % cells;
+  const int b = (int)(i / cells);
+  f16x4 v;
+  v[0] = src[i * 3]; v[1] = src[i * 3 + 1]; v[2] = src[i * 3 + 2]; v[3] = (_Float16)0.0f;
+  dst[cell * r + b] = v;
+}
+
+template <typename T>
+__global__ void quant_pack_sigma_kernel(const T* __restrict__ src, int64_t cells, float* __restrict__ dst) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < cells) dst[i] = (float)src[i];
+}
+
+struct QuantRenderArgs {
+  PxoQuantTree tree;
+  PxoCamera cam;
+  int has_cam;
+  const float* origins;
+  const float* dirs;
+  const float* viewdirs;
+  int64_t B;
+  PxoRenderOpts opt;
+};
+
+// octree_render_kernel<0, ROW>'s rays, march and compositing; a shaded sample's colour comes through the palettes.  Plane
+// ownership inside a ray's ROW lanes: lane l owns the retained planes l, l + ROW, .. and the groups l, l + ROW, .. of four
+// consecutive quantised planes (one 8-byte index load per group, one 8-byte palette load per plane, all three channels in
+// it).  A lane sums its retained planes, then its quantised planes, both ascending; row_sum adds the lanes: the order
+// depends on (ROW, K, r) only.
+template <int ROW>
+__global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(QuantRenderArgs A, float* __restrict__ out_rgb) {
+  using G = RowGeom<ROW>;
+  constexpr int kRow = ROW, kRaysPerBlock = G::kRaysPerBlock;
+  constexpr int kQM = (7 + ROW - 1) / ROW;         // index groups per lane: Kq <= 25 -> at most 7 groups of four
+  constexpr int kRM = (24 + ROW - 1) / ROW;        // retained planes per lane: r <= 24
+  __shared__ int s_stack[kRaysPerBlock][kMaxD + 2];
+  __shared__ float s_basis[kRaysPerBlock][25];
+  const int row = threadIdx.x / kRow, l = threadIdx.x % kRow;
+  int64_t ray;
+  float origin[3], dir[3], vdir[3];
+  bool active = true;
+  if (A.has_cam) {
+    const int W = A.cam.width, H = A.cam.height;
+    const int tiles_x = (W + 2 * G::kWTX - 1) / (2 * G::kWTX);
+    const int bx = (int)(blockIdx.x % tiles_x), by = (int)(blockIdx.x / tiles_x);
+    const int wv = row / G::kRaysPerWave, q = row % G::kRaysPerWave;
+    const int px = (bx * 2 + (wv & 1)) * G::kWTX + q % G::kWTX, py = (by * 2 + (wv >> 1)) * G::kWTY + q / G::kWTX;
+    active = px < W && py < H;
+    ray = (int64_t)py * W + px;
+    if (active) {
+      camera_ray(A.cam.c2w, A.cam.fx, A.cam.fy, W, H, px, py, origin, dir);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) vdir[a] = dir[a];
+    }
+  } else {
+    ray = blockIdx.x * (int64_t)kRaysPerBlock + row;
+    active = ray < A.B;
+    if (active) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        origin[a] = A.origins[ray * 3 + a];
+        dir[a] = A.dirs[ray * 3 + a];
+        vdir[a] = A.viewdirs[ray * 3 + a];
+      }
+    }
+  }
+  if (!active) return;                         // whole rows leave together; no block-level barrier below
+
+  const int K = A.tree.basis_dim, R = A.tree.n_retained, Kq = K - R, bits = A.tree.bits;
+  const int groups = A.tree.idx_stride >> 2;
+  const uint32_t id_mask = (1u << bits) - 1u;
+  const float bg = A.opt.background_brightness;
+  TreeRay r;
+  to_tree_ray(origin, dir, A.tree.offset, A.tree.invradius, r);
+  CellExit cell_exit;
+  cell_exit.init(r.invdir);
+  if (r.tmax < 0.0f || r.tmin > r.tmax) {
+    for (int c = l; c < 3; c += kRow) out_rgb[ray * 3 + c] = bg;
+    return;
+  }
+
+  if (l == 0) sh_basis_dyn(K, vdir[0], vdir[1], vdir[2], s_basis[row]);
+  __builtin_amdgcn_wave_barrier();
+  float yr[kRM], yq[4 * kQM];                  // basis values of the planes this lane owns (0 past the end)
+#pragma unroll
+  for (int m = 0; m < kRM; ++m) yr[m] = (l + kRow * m) < R ? s_basis[row][l + kRow * m] : 0.0f;
+#pragma unroll
+  for (int j = 0; j < 4 * kQM; ++j) {
+    const int q = 4 * (l + kRow * (j >> 2)) + (j & 3);
+    yq[j] = q < Kq ? s_basis[row][R + q] : 0.0f;
+  }
+  const int32_t* __restrict__ child = A.tree.child;
+  const float* __restrict__ sigma = A.tree.sigma;
+  const u16x4* __restrict__ idx = reinterpret_cast<const u16x4*>(A.tree.idx);
+  const f16x4* __restrict__ palette = reinterpret_cast<const f16x4*>(A.tree.palette);
+  const f16x4* __restrict__ retained = reinterpret_cast<const f16x4*>(A.tree.retained);
+
+  Marcher mk;
+  mk.init(s_stack[row]);
+  float t = r.tmin, light = 1.0f;
+  float out[3] = {0.f, 0.f, 0.f};
+  bool stopped = false;
+  // the float kernel's software pipeline: sigma requested, the next sample located, then the current one shaded
+  auto locate = [&](float tt, int64_t& leaf_o, float& delta_o) {
+    float pos[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + tt * r.d[a]);
+    int depth;
+    leaf_o = mk.find(child, pos, depth);
+    const float cube = (float)(2u << depth);
+    float local[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) local[a] = __builtin_amdgcn_fractf(pos[a] * cube);
+    delta_o = cell_exit(local) * inv_cells(depth) + A.opt.step_size;
+  };
+  int64_t leaf = 0;
+  float delta_t = 0.0f;
+  bool more = t < r.tmax;
+  if (more) locate(t, leaf, delta_t);
+  while (more) {
+    const float sg = sigma[leaf];
+    const float tn = t + delta_t;
+    more = tn > t && tn < r.tmax;              // !(tn > t): step below the resolution of t, stop rather than spin
+    const int64_t leaf_cur = leaf;
+    const float delta_cur = delta_t;
+    if (more) locate(tn, leaf, delta_t);
+    t = tn;
+    if (sg > A.opt.sigma_thresh) {
+      const float dtw = delta_cur * r.delta_scale;
+      const float att = expf(-dtw * sg);
+      const float weight = light * (1.0f - att);
+      float p0 = 0.f, p1 = 0.f, p2 = 0.f;
+#pragma unroll
+      for (int m = 0; m < kRM; ++m) {
+        const int b = l + kRow * m;
+        if (b < R) {
+          const f16x4 c = retained[leaf_cur * R + b];
+          p0 += (float)c[0] * yr[m];
+          p1 += (float)c[1] * yr[m];
+          p2 += (float)c[2] * yr[m];
+        }
+      }
+      const u16x4* __restrict__ ids = idx + leaf_cur * groups;
+#pragma unroll
+      for (int m = 0; m < kQM; ++m) {
+        const int g = l + kRow * m;
+        if (g < groups) {
+          const u16x4 id = ids[g];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int q = 4 * g + e;
+            if (q < Kq) {                      // the row's padding has no palette
+              const f16x4 c = palette[((int64_t)q << bits) + ((uint32_t)id[e] & id_mask)];
+              p0 += (float)c[0] * yq[4 * m + e];
+              p1 += (float)c[1] * yq[4 * m + e];
+              p2 += (float)c[2] * yq[4 * m + e];
+            }
+          }
+        }
+      }
+      p0 = row_sum<ROW>(p0);
+      p1 = row_sum<ROW>(p1);
+      p2 = row_sum<ROW>(p2);
+      const float c0 = 1.0f / (1.0f + expf(-p0)), c1 = 1.0f / (1.0f + expf(-p1)), c2 = 1.0f / (1.0f + expf(-p2));
+      out[0] += weight * c0;
+      out[1] += weight * c1;
+      out[2] += weight * c2;
+      light = light * att;
+      if (light <= A.opt.stop_thresh) {
+        const float scale = 1.0f / (1.0f - light);
+        out[0] *= scale; out[1] *= scale; out[2] *= scale;
+        stopped = true;
+        break;
+      }
+    }
+  }
+  if (!stopped) {
+    out[0] += light * bg; out[1] += light * bg; out[2] += light * bg;
+  }
+  for (int c = l; c < 3; c += kRow) out_rgb[ray * 3 + c] = c == 0 ? out[0] : (c == 1 ? out[1] : out[2]);
+}
+
 }  // namespace pxo
 
 // ==========================================================================================
@@ -1924,6 +2145,114 @@ int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float
     default: hipLaunchKernelGGL((octree_render_kernel<1, 16>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, (float*)nullptr, out_rgb, grad_out, grad_data); break;
   }
   return check_launch("octree_render_bwd");
+}
+
+// ---- compressed trees (octree/compression.py:88-139) ----
+static int quant_format_ok(int64_t n_internal, int basis_dim, int n_retained, int bits, const char* who) {
+  const int K = basis_dim;
+  PXO_REQUIRE(K == 1 || K == 4 || K == 9 || K == 16 || K == 25, "%s: basis_dim %d is not an SH format (1,4,9,16,25)", who, K);
+  PXO_REQUIRE(n_retained >= 0 && n_retained < K, "%s: n_retained %d must be in [0, basis_dim %d)", who, n_retained, K);
+  PXO_REQUIRE(bits >= 1 && bits <= 16, "%s: bits %d must be in 1..16 (the map is uint16)", who, bits);
+  PXO_REQUIRE(n_internal >= 1 && n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
+  return PXO_OK;
+}
+
+int pxo_octree_quant_pack_bytes(int64_t n_internal, int basis_dim, int n_retained, int bits, PxoQuantLayout* layout) {
+  if (int rc = quant_format_ok(n_internal, basis_dim, n_retained, bits, "pxo_octree_quant_pack_bytes")) return rc;
+  PXO_REQUIRE(layout, "pxo_octree_quant_pack_bytes: null layout");
+  const int64_t cells = n_internal * 8, Kq = basis_dim - n_retained;
+  PxoQuantLayout L{};
+  L.idx_stride = (int32_t)((Kq + 3) & ~(int64_t)3);
+  L.ret_stride = 4 * n_retained;
+  int64_t off = 0;
+  L.idx_offset = off;      off += align256(cells * L.idx_stride * 2);
+  L.palette_offset = off;  off += align256((Kq << bits) * 8);
+  L.sigma_offset = off;    off += align256(cells * 4);
+  L.retained_offset = off; off += align256(cells * L.ret_stride * 2);
+  L.total_bytes = off;
+  *layout = L;
+  return PXO_OK;
+}
+
+int pxo_octree_quant_pack(const uint16_t* quant_map, const void* quant_colors, const void* sigma, int sigma_elem_bytes,
+                          const void* data_retained, int64_t n_internal, int basis_dim, int n_retained, int bits,
+                          void* packed, size_t packed_bytes, void* stream) {
+  PxoQuantLayout L;
+  if (int rc = pxo_octree_quant_pack_bytes(n_internal, basis_dim, n_retained, bits, &L)) return rc;
+  PXO_REQUIRE(quant_map && quant_colors && sigma && packed, "pxo_octree_quant_pack: null pointer");
+  PXO_REQUIRE(n_retained == 0 || data_retained, "pxo_octree_quant_pack: n_retained %d but data_retained is null", n_retained);
+  PXO_REQUIRE(sigma_elem_bytes == 2 || sigma_elem_bytes == 4, "pxo_octree_quant_pack: sigma must be float16 (2) or float32 (4)");
+  PXO_REQUIRE(((uintptr_t)packed & 255) == 0, "pxo_octree_quant_pack: packed buffer must be 256-byte aligned");
+  if (packed_bytes < (size_t)L.total_bytes) {
+    set_error("pxo_octree_quant_pack: buffer %zu < %lld", packed_bytes, (long long)L.total_bytes);
+    return PXO_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* base = static_cast<char*>(packed);
+  const int64_t cells = n_internal * 8;
+  const int Kq = basis_dim - n_retained, groups = L.idx_stride / 4;
+  hipLaunchKernelGGL(quant_pack_idx_kernel, dim3((unsigned)blocks_for(cells * groups, 256)), dim3(256), 0, s, quant_map, cells, Kq,
+                     groups, reinterpret_cast<u16x4*>(base + L.idx_offset));
+  const int64_t entries = (int64_t)Kq << bits;
+  hipLaunchKernelGGL(quant_pack_pad_kernel, dim3((unsigned)blocks_for(entries, 256)), dim3(256), 0, s,
+                     static_cast<const _Float16*>(quant_colors), entries, reinterpret_cast<f16x4*>(base + L.palette_offset));
+  float* sig = reinterpret_cast<float*>(base + L.sigma_offset);
+  if (sigma_elem_bytes == 2)
+    hipLaunchKernelGGL(quant_pack_sigma_kernel<_Float16>, dim3((unsigned)blocks_for(cells, 256)), dim3(256), 0, s,
+                       static_cast<const _Float16*>(sigma), cells, sig);
+  else
+    hipLaunchKernelGGL(quant_pack_sigma_kernel<float>, dim3((unsigned)blocks_for(cells, 256)), dim3(256), 0, s,
+                       static_cast<const float*>(sigma), cells, sig);
+  if (n_retained)
+    hipLaunchKernelGGL(quant_pack_retained_kernel, dim3((unsigned)blocks_for(cells * n_retained, 256)), dim3(256), 0, s,
+                       static_cast<const _Float16*>(data_retained), cells, n_retained,
+                       reinterpret_cast<f16x4*>(base + L.retained_offset));
+  return check_launch("octree_quant_pack");
+}
+
+int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
+  const char* who = "pxo_octree_render_quant_fwd";
+  if (int rc = check_opts(opts, who)) return rc;
+  PXO_REQUIRE(tree && tree->child && tree->idx && tree->palette && tree->sigma, "%s: null tree", who);
+  if (int rc = quant_format_ok(tree->n_internal, tree->basis_dim, tree->n_retained, tree->bits, who)) return rc;
+  const int Kq = tree->basis_dim - tree->n_retained;
+  PXO_REQUIRE(tree->idx_stride == ((Kq + 3) & ~3) && tree->ret_stride == 4 * tree->n_retained,
+              "%s: strides (%d, %d) are not those of pxo_octree_quant_pack_bytes", who, tree->idx_stride, tree->ret_stride);
+  PXO_REQUIRE(tree->n_retained == 0 || tree->retained, "%s: n_retained %d but retained is null", who, tree->n_retained);
+  PXO_REQUIRE((((uintptr_t)tree->idx | (uintptr_t)tree->palette | (uintptr_t)tree->retained) & 7) == 0,
+              "%s: idx, palette and retained must be 8-byte aligned", who);
+  PXO_REQUIRE(B >= 0, "%s: B < 0", who);
+  QuantRenderArgs A;
+  A.tree = *tree;
+  A.opt = *opts;
+  A.B = B;
+  A.has_cam = cam != nullptr;
+  const int row = g_row_override[0] ? g_row_override[0] : 4;     // unmeasured against 8 / 16 (see DESIGN): the float kernel's default
+  int64_t blocks;
+  if (cam) {
+    PXO_REQUIRE(cam->c2w && cam->width >= 1 && cam->height >= 1 && cam->fx > 0.0f && cam->fy > 0.0f, "%s: bad camera", who);
+    PXO_REQUIRE(B == (int64_t)cam->width * cam->height, "%s: B must be width*height in camera mode", who);
+    A.cam = *cam;
+    A.origins = A.dirs = A.viewdirs = nullptr;
+    const int rpw = 64 / row, wtx = rpw <= 4 ? 2 : (rpw <= 16 ? 4 : 8), tx = 2 * wtx, ty = 2 * (rpw / wtx);
+    blocks = (int64_t)((cam->width + tx - 1) / tx) * ((cam->height + ty - 1) / ty);
+  } else {
+    PXO_REQUIRE(B == 0 || (origins && dirs && viewdirs), "%s: null ray arrays", who);
+    A.cam = PxoCamera{};
+    A.origins = origins; A.dirs = dirs; A.viewdirs = viewdirs;
+    blocks = blocks_for(B, kRenderThreads / row);
+  }
+  PXO_REQUIRE(blocks < ((int64_t)1 << 31), "%s: too many rays for one launch", who);
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(out_rgb, "%s: null output", who);
+  const dim3 grid((unsigned)blocks), block(kRenderThreads);
+  switch (row) {
+    case 4: hipLaunchKernelGGL(octree_render_quant_kernel<4>, grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
+    case 8: hipLaunchKernelGGL(octree_render_quant_kernel<8>, grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
+    default: hipLaunchKernelGGL(octree_render_quant_kernel<16>, grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
+  }
+  return check_launch("octree_render_quant_fwd");
 }
 
 int pxo_octree_count_work(const PxoTree* tree, const PxoCamera* cam, const PxoRenderOpts* opts, unsigned long long* counts,

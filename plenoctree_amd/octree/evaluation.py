@@ -2,6 +2,7 @@
 mean PSNR of its renders of the test split; test images are sharded over the GPUs.
 
     python -m plenoctree_amd.octree.evaluation --input tree_opt.npz --config blender --data_dir ... [--write_images DIR]
+        [--keep_compressed]     (a tree written by octree.compression is rendered from its palette form, in place)
 """
 import os
 import sys
@@ -23,6 +24,8 @@ def define_flags():
     a("--write_images", type=str, default=None)                  # :64-68
     a("--renderer_step_size", type=float, default=1e-4)          # octree/nerf/utils.py:211-215
     a("--no_early_stop", action="store_true")
+    a("--keep_compressed", action="store_true",
+      help="evaluate a compressed tree (octree.compression) in its palette form instead of re-inflating it to float32")
     return p
 
 
@@ -41,7 +44,10 @@ def main(argv=None):
     dataset = datasets.get_dataset("test", args, device)
     if comm.rank == 0:
         print("N3Tree load", args.input, flush=True)
-    tree = N3Tree.load(args.input, map_location=device)
+    tree = N3Tree.load(args.input, map_location=device, keep_quantized=args.keep_compressed)   # not compressed + flag: ValueError
+    if args.keep_compressed and comm.rank == 0:
+        print(f"compressed tree kept in place: {tree.nbytes / 2 ** 20:.1f} MB on the device "
+              f"(float form: {tree.float_nbytes / 2 ** 20:.1f} MB)", flush=True)
     want_frames = args.write_images is not None or args.write_vid is not None
     psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True)
     if comm.rank == 0:

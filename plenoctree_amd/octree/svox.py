@@ -378,40 +378,57 @@ class N3Tree:
         (np.savez_compressed if compress else np.savez)(path, **z)
 
     @classmethod
-    def load(cls, path, device="cpu", map_location=None):
+    def load(cls, path, device="cpu", map_location=None, keep_quantized=False):
+        """svox N3Tree.load.  A compressed file (octree/compression.py) is re-inflated to float32 `data`, unless
+        `keep_quantized`: then the palette form is kept as it is and a read-only QuantizedN3Tree comes back."""
         dev = torch.device(map_location if map_location is not None else device)
         z = np.load(path)
+        if keep_quantized:
+            if "quant_colors" not in z.files:
+                raise ValueError(f"{path}: keep_quantized=True needs a compressed tree (no quant_colors in the file)")
+            return QuantizedN3Tree(z, dev)
+        return cls._from_npz(z, dev)
+
+    @classmethod
+    def _from_npz(cls, z, dev):
         if "quant_colors" in z.files:
             z = _dequantized(z)
         t = object.__new__(cls)
-        t.N = 2
-        fmt = str(z["data_format"]) if "data_format" in z.files else "RGBA"
-        t.data_format = DataFormat(fmt, int(z["data_dim"]))
-        child = z["child"]
-        if child.shape[1:] != (2, 2, 2):
-            raise NotImplementedError("only octrees (N = 2) are supported")
-        n = int(z["n_internal"]) if "n_internal" in z.files else child.shape[0]
-        t.child = torch.from_numpy(child[:n].astype(np.int32)).to(dev)
+        n = _load_geometry(t, z, dev)
         t.data = torch.nn.Parameter(torch.from_numpy(z["data"][:n].astype(np.float32)).to(dev))
-        if "parent_depth" in z.files:
-            pd = z["parent_depth"][:n].astype(np.int32)
-        else:
-            pd = parent_depth_from_child(child[:n])
-        t.parent_depth = torch.from_numpy(pd).to(dev)
-        if "invradius3" in z.files:
-            invradius = z["invradius3"].astype(np.float32)
-        else:
-            invradius = np.repeat(np.float32(z["invradius"]), 3)
-        t._set_transform(invradius, z["offset"].astype(np.float32))
-        t.depth_limit = int(z["depth_limit"]) if "depth_limit" in z.files else int(pd[:, 1].max())
-        t.geom_resize_fact = float(z["geom_resize_fact"]) if "geom_resize_fact" in z.files else 1.0
-        counts = np.bincount(pd[:, 1])
-        t._reset_caches()
-        t._level_order = not bool((np.diff(pd[:, 1]) < 0).any())
-        t.level_nodes = [int(c) for c in counts]
-        if t.max_depth > TREE_MAX_DEPTH:
-            raise NotImplementedError(f"tree depth {t.max_depth} exceeds {TREE_MAX_DEPTH}")
         return t
+
+
+def _load_geometry(t, z, dev):
+    """The part of N3Tree.load that does not touch the leaf values: format, child, parent_depth, transform, levels.
+    Returns the node count."""
+    t.N = 2
+    fmt = str(z["data_format"]) if "data_format" in z.files else "RGBA"
+    t.data_format = DataFormat(fmt, int(z["data_dim"]))
+    child = z["child"]
+    if child.shape[1:] != (2, 2, 2):
+        raise NotImplementedError("only octrees (N = 2) are supported")
+    n = int(z["n_internal"]) if "n_internal" in z.files else child.shape[0]
+    t.child = torch.from_numpy(child[:n].astype(np.int32)).to(dev)
+    if "parent_depth" in z.files:
+        pd = z["parent_depth"][:n].astype(np.int32)
+    else:
+        pd = parent_depth_from_child(child[:n])
+    t.parent_depth = torch.from_numpy(pd).to(dev)
+    if "invradius3" in z.files:
+        invradius = z["invradius3"].astype(np.float32)
+    else:
+        invradius = np.repeat(np.float32(z["invradius"]), 3)
+    N3Tree._set_transform(t, invradius, z["offset"].astype(np.float32))
+    t.depth_limit = int(z["depth_limit"]) if "depth_limit" in z.files else int(pd[:, 1].max())
+    t.geom_resize_fact = float(z["geom_resize_fact"]) if "geom_resize_fact" in z.files else 1.0
+    counts = np.bincount(pd[:, 1])
+    N3Tree._reset_caches(t)
+    t._level_order = not bool((np.diff(pd[:, 1]) < 0).any())
+    t.level_nodes = [int(c) for c in counts]
+    if len(t.level_nodes) - 1 > TREE_MAX_DEPTH:
+        raise NotImplementedError(f"tree depth {len(t.level_nodes) - 1} exceeds {TREE_MAX_DEPTH}")
+    return n
 
 
 def _dequantized(z):
@@ -436,6 +453,133 @@ class _NpzDict(dict):
     @property
     def files(self):
         return list(self.keys())
+
+
+def _validated_quant(z, n):
+    """The palette arrays of a compressed npz (first n nodes), checked on the host before anything reaches the GPU:
+    (quant_map uint16 [Kq, n*8], quant_colors float16 [Kq, 2^bits, 3], sigma [n*8], data_retained float16 [r, n*8, 3] or
+    None, bits).  Every inconsistency is a ValueError naming the offending array."""
+    K = (int(z["data_dim"]) - 1) // 3
+    colors, qmap, sigma = np.asarray(z["quant_colors"]), np.asarray(z["quant_map"]), np.asarray(z["sigma"])
+    retained = np.asarray(z["data_retained"]) if "data_retained" in z.files else None
+    if colors.ndim != 3 or colors.shape[2] != 3:
+        raise ValueError(f"quant_colors: shape {colors.shape} is not [K', 2^bits, 3]")
+    Kq, P = colors.shape[0], colors.shape[1]
+    bits = P.bit_length() - 1
+    if P != 1 << bits or not 1 <= bits <= 16:
+        raise ValueError(f"quant_colors: {P} palette entries are not 2^bits with bits in 1..16")
+    if qmap.shape[0] != Kq:
+        raise ValueError(f"quant_map: {qmap.shape[0]} planes but quant_colors has {Kq} palettes")
+    r = 0 if retained is None else retained.shape[0]
+    if Kq < 1 or r + Kq != K:
+        which = "quant_colors" if retained is None else "data_retained"
+        raise ValueError(f"{which}: {r} retained + {Kq} quantised planes do not make basis_dim {K} of {z['data_format']}")
+    cells = (2, 2, 2)
+    if qmap.shape[1] < n or qmap.shape[2:] != cells:
+        raise ValueError(f"quant_map: shape {qmap.shape} does not hold [K', {n}, 2, 2, 2] leaves like child")
+    if sigma.shape[0] < n or sigma.shape[1:] != cells:
+        raise ValueError(f"sigma: shape {sigma.shape} does not hold [{n}, 2, 2, 2] leaves like child")
+    if retained is not None and (retained.ndim != 6 or retained.shape[1] < n or retained.shape[2:] != cells + (3,)):
+        raise ValueError(f"data_retained: shape {retained.shape} does not hold [r, {n}, 2, 2, 2, 3] leaves like child")
+    if not np.issubdtype(qmap.dtype, np.integer):
+        raise ValueError(f"quant_map: dtype {qmap.dtype} is not an integer type")
+    qmap = qmap[:, :n].reshape(Kq, n * 8)
+    if qmap.size and (int(qmap.min()) < 0 or int(qmap.max()) >= P):
+        raise ValueError(f"quant_map: index {int(qmap.max()) if int(qmap.min()) >= 0 else int(qmap.min())} is outside its "
+                         f"palette of {P} entries")
+    if sigma.dtype not in (np.float16, np.float32):
+        raise ValueError(f"sigma: dtype {sigma.dtype} is neither float16 nor float32")
+    if colors.dtype != np.float16 or (retained is not None and retained.dtype != np.float16):
+        raise ValueError("quant_colors / data_retained: expected float16, as octree.compression writes them")
+    return (np.ascontiguousarray(qmap.astype(np.uint16, copy=False)), np.ascontiguousarray(colors),
+            np.ascontiguousarray(sigma[:n].reshape(n * 8)),
+            None if retained is None else np.ascontiguousarray(retained[:, :n].reshape(r, n * 8, 3)), bits)
+
+
+class QuantizedN3Tree:
+    """A compressed tree (octree/compression.py) kept in its palette form: `N3Tree.load(path, keep_quantized=True)`.
+
+    Read-only.  It has the geometry of an N3Tree (child, parent_depth, offset, invradius, depth_limit, data_format,
+    n_internal, max_depth, device) and is rendered in place by VolumeRenderer; on a GPU device the file's arrays are
+    uploaded as they are and packed there (include/plenoctree_octree.h, PxoQuantLayout), with no gather over the leaves
+    on the host.  There is no `data`: everything that needs float leaf values goes through `dequantize()`."""
+
+    def __init__(self, z, dev):
+        self._z = _NpzDict({k: z[k] for k in z.files})           # the file's arrays, for dequantize()
+        n = _load_geometry(self, self._z, dev)
+        qmap, colors, sigma, retained, self.bits = _validated_quant(self._z, n)
+        self.n_retained = 0 if retained is None else retained.shape[0]
+        self._layout = oops.quant_layout(n, self.basis_dim, self.n_retained, self.bits)
+        self._packed = None
+        if dev.type == "cuda":
+            up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+            self._packed, _ = oops.quant_pack(up(qmap.view(np.int16)), up(colors), up(sigma), up(retained), n, self.basis_dim,
+                                              self.n_retained, self.bits)
+
+    basis_dim = N3Tree.basis_dim
+    data_dim = N3Tree.data_dim
+    n_internal = N3Tree.n_internal
+    n_leaves = N3Tree.n_leaves
+    max_depth = N3Tree.max_depth
+
+    @property
+    def device(self):
+        return self.child.device
+
+    @property
+    def nbytes(self):
+        """Device bytes of this form: the packed buffer (indices, palettes, sigma, retained planes) + child + parent_depth."""
+        return int(self._layout.total_bytes) + 4 * (self.child.numel() + self.parent_depth.numel())
+
+    @property
+    def float_nbytes(self):
+        """Device bytes the float form (`dequantize()`, what N3Tree.load makes of the same file) takes."""
+        return 4 * self.n_internal * 8 * self.data_dim + 4 * (self.child.numel() + self.parent_depth.numel())
+
+    def quant_view(self):
+        if self._packed is None:
+            raise PxoError("a QuantizedN3Tree renders on a ROCm device only (there is no CPU fallback): load it with map_location='cuda'")
+        return oops.quant_tree_view(self.child, self._packed, self._layout, self.basis_dim, self.n_retained, self.bits,
+                                    self.offset, self.invradius)
+
+    def dequantize(self):
+        """The float N3Tree that `N3Tree.load(path)` makes of the same file, on this tree's device."""
+        return N3Tree._from_npz(self._z, self.device)
+
+    def __repr__(self):
+        return (f"svox.QuantizedN3Tree(N=2, data_format:{self.data_format}, n_internal:{self.n_internal}, bits:{self.bits}, "
+                f"retained:{self.n_retained}, {self.nbytes / 2 ** 20:.1f} MB on the device, float form {self.float_nbytes / 2 ** 20:.1f} MB)")
+
+    def _read_only(self, what):
+        raise PxoError(f"{what}: a QuantizedN3Tree is read-only and has no float leaf data; call dequantize() for an N3Tree")
+
+    @property
+    def data(self):
+        self._read_only("tree.data")
+
+    def parameters(self):
+        self._read_only("tree.parameters()")
+
+    def __getitem__(self, key):
+        self._read_only("tree[...]")
+
+    def __setitem__(self, key, value):
+        self._read_only("tree[...] = value")
+
+    def refine(self, *args, **kwargs):
+        self._read_only("refine")
+
+    def refine_from_mask(self, mask):
+        self._read_only("refine_from_mask")
+
+    def relu_sigma_(self):
+        self._read_only("relu_sigma_")
+
+    def view(self):
+        self._read_only("view()")
+
+    def save(self, path, shrink=True, compress=True):
+        self._read_only("save")
 
 
 def parent_depth_from_child(child):
@@ -493,6 +637,9 @@ class VolumeRenderer:
         """[H,W,3] image.  With grad mode on and a tree whose `data` requires grad the exact render (fast=False, as in
         octree/optimization.py:216) is differentiable; the early-stopping preset (fast=True, evaluation) never is."""
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.tree.device)
+        if isinstance(self.tree, QuantizedN3Tree):
+            # nothing in a compressed tree requires grad: rendered directly, with grad mode on as well, `fast` both ways
+            return oops.octree_render_quant_persp(self.tree.quant_view(), c2w, width, height, fx, self._opts(fast), fy)
         data = self.tree.data
         if torch.is_grad_enabled() and data.requires_grad:
             if fast:
@@ -506,6 +653,8 @@ class VolumeRenderer:
 
     def forward(self, origins, dirs, viewdirs, fast=False):
         """Colours [B,3] of explicit world-space rays (unit `dirs`)."""
+        if isinstance(self.tree, QuantizedN3Tree):
+            return oops.octree_render_quant_rays(self.tree.quant_view(), origins, dirs, viewdirs, self._opts(fast))
         return oops.octree_render_rays(self.tree.view(), origins, dirs, viewdirs, self._opts(fast))
 
     __call__ = forward

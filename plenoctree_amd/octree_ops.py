@@ -226,6 +226,76 @@ def octree_render_rays(tree, origins, dirs, viewdirs, opts):
     return out
 
 
+# ---- compressed trees rendered in place (the palette form of octree/compression.py:88-139) ----
+def quant_layout(n_internal, basis_dim, n_retained, bits):
+    """PxoQuantLayout of the packed form (host only: no GPU needed)."""
+    lay = _lib.PxoQuantLayout()
+    check(_lib.load().pxo_octree_quant_pack_bytes(int(n_internal), int(basis_dim), int(n_retained), int(bits),
+                                                  ctypes.byref(lay)), "pxo_octree_quant_pack_bytes")
+    return lay
+
+
+def quant_pack(quant_map, quant_colors, sigma, data_retained, n_internal, basis_dim, n_retained, bits):
+    """The file's arrays, uploaded as they are (quant_map int16 holding the uint16 bits [Kq, n*8], quant_colors float16
+    [Kq, 2^bits, 3], sigma float16 / float32 [n*8], data_retained float16 [r, n*8, 3] or None) -> the packed uint8 buffer."""
+    _require_gpu()
+    if quant_map.dtype != torch.int16 or quant_colors.dtype != torch.float16 or sigma.dtype not in (torch.float16, torch.float32):
+        raise PxoError("quant_pack: quant_map must be int16 (uint16 bits), quant_colors float16, sigma float16 or float32")
+    if data_retained is not None and data_retained.dtype != torch.float16:
+        raise PxoError("quant_pack: data_retained must be float16")
+    Kq, cells = basis_dim - n_retained, n_internal * 8
+    if quant_map.numel() != Kq * cells or quant_colors.numel() != Kq * (3 << bits) or sigma.numel() != cells or \
+            (data_retained.numel() if data_retained is not None else 0) != n_retained * cells * 3:
+        raise PxoError("quant_pack: array sizes do not match (n_internal, basis_dim, n_retained, bits)")
+    lay = quant_layout(n_internal, basis_dim, n_retained, bits)
+    packed = torch.zeros(lay.total_bytes, dtype=torch.uint8, device=quant_map.device)
+    check(_lib.load().pxo_octree_quant_pack(_p(quant_map), _p(quant_colors), _p(sigma), sigma.element_size(),
+                                            _p(data_retained), n_internal, basis_dim, n_retained, bits, _p(packed),
+                                            lay.total_bytes, _stream()), "pxo_octree_quant_pack")
+    return packed, lay
+
+
+def quant_tree_view(child, packed, lay, basis_dim, n_retained, bits, offset, invradius):
+    """PxoQuantTree struct over torch storage (keeps no reference: the caller owns the tensors)."""
+    if child.dtype != torch.int32:
+        raise PxoError("child must be int32")
+    if packed.dtype != torch.uint8 or packed.numel() < lay.total_bytes:
+        raise PxoError("packed buffer is smaller than its layout")
+    base = _p(packed).value
+    t = _lib.PxoQuantTree()
+    t.child = _p(child).value
+    t.idx = base + lay.idx_offset
+    t.palette = base + lay.palette_offset
+    t.sigma = base + lay.sigma_offset
+    t.retained = base + lay.retained_offset
+    t.n_internal = child.shape[0]
+    t.basis_dim, t.n_retained, t.bits = int(basis_dim), int(n_retained), int(bits)
+    t.idx_stride, t.ret_stride = lay.idx_stride, lay.ret_stride
+    t.offset = _vec3(offset)
+    t.invradius = _vec3(invradius)
+    return t
+
+
+def octree_render_quant_persp(qtree, c2w, width, height, fx, opts, fy=None):
+    """octree_render_persp on a PxoQuantTree."""
+    _require_gpu()
+    cam, keep = _camera(c2w, width, height, fx, fy)
+    out = _new(height, width, 3, device=keep.device)
+    check(_lib.load().pxo_octree_render_quant_fwd(ctypes.byref(qtree), ctypes.byref(cam), None, None, None, width * height,
+                                                  ctypes.byref(opts), _f(out), _stream()), "pxo_octree_render_quant_fwd")
+    return out
+
+
+def octree_render_quant_rays(qtree, origins, dirs, viewdirs, opts):
+    """octree_render_rays on a PxoQuantTree."""
+    _require_gpu()
+    B = origins.shape[0]
+    out = _new(B, 3, device=origins.device)
+    check(_lib.load().pxo_octree_render_quant_fwd(ctypes.byref(qtree), None, _f(origins), _f(dirs), _f(viewdirs), B,
+                                                  ctypes.byref(opts), _f(out), _stream()), "pxo_octree_render_quant_fwd")
+    return out
+
+
 def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None):
     _require_gpu()
     check(_lib.load().pxo_octree_render_bwd(ctypes.byref(tree), None, _f(origins), _f(dirs), _f(viewdirs),

@@ -1,0 +1,218 @@
+"""Compressed trees rendered in place (pxo_octree_render_quant_fwd) against oracle/octree_oracle.py on the dequantised
+float32 data.
+
+Bar: the float renderer's own against the same oracle, atol 2e-5, rtol 0 (tests/test_gpu_octree.py): the march takes the
+same steps, the coefficients are the same float32 values (float16 widened exactly), only exp / sigmoid and the SH
+summation order differ.  The float kernel on `N3Tree.load(path)` is held to the same bar, so the two kernels are within
+4e-5 of each other; that is asserted, and the measured maximum is printed.
+
+Cases (tests/_quant_cases.py): every SH format with and without retained planes, palettes of 1, 8 and 16 bits, depth-3
+trees with leaves at every depth and sigma-0 leaves, a 13 x 9 camera (no multiple of any lane variant's patch, some pixels
+miss the volume), 37 explicit rays whose view directions differ from their directions, exact and early-stop options,
+4, 8 and 16 lanes per ray.  The oracle reference of a case is computed once and shared.
+"""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _quant_cases as Q
+from oracle import octree_oracle as T
+from _helpers import _gpu, close
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+W, H, FX, STEP = 13, 9, 12.0, 1e-3
+LANES = (4, 8, 16)
+# (theta, phi) of the camera per `fast`
+POSES = {False: (20.0, 30.0), True: (250.0, -5.0)}
+
+
+def _pose(theta, phi, radius=4.0):
+    from plenoctree_amd.nerf_sh.nerf.datasets import pose_spherical
+    return pose_spherical(theta, phi, radius)
+
+
+def _svox():
+    from plenoctree_amd.octree import svox
+    return svox
+
+
+def _oops():
+    from plenoctree_amd import octree_ops
+    return octree_ops
+
+
+@functools.lru_cache(maxsize=None)
+def _want_image(key, fast):
+    c = Q.case(*key)
+    return T.render_persp(c.tree, _pose(*POSES[fast]), W, H, FX, T.RenderOptions.for_renderer(STEP, fast))
+
+
+@functools.lru_cache(maxsize=None)
+def _rays():
+    """37 rays: from outside towards the volume, a few from inside, one that misses; view directions unrelated to them."""
+    rs = np.random.RandomState(37)
+    o = np.concatenate([rs.randn(31, 3) * 3.0, rs.rand(5, 3) * 0.5, [[9.0, 9.0, 9.0]]]).astype(f32)
+    d = (np.asarray(Q.CENTER) - o + rs.randn(37, 3) * 0.4).astype(f32)
+    d[-1] = [1.0, 0.0, 0.0]
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    v = rs.randn(37, 3).astype(f32)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    return o, d.astype(f32), v.astype(f32)
+
+
+@functools.lru_cache(maxsize=None)
+def _want_rays(key, fast):
+    c = Q.case(*key)
+    o, d, v = _rays()
+    opt = T.RenderOptions.for_renderer(STEP, fast)
+    return np.stack([T.render_ray(c.tree, oo, dd, vv, opt) for oo, dd, vv in zip(o, d, v)])
+
+
+def _load_both(tmp_path, key):
+    svox = _svox(); dev = _gpu()
+    path = Q.case(*key).save(os.path.join(str(tmp_path), "tree.npz"))
+    return svox.N3Tree.load(path, map_location=dev, keep_quantized=True), svox.N3Tree.load(path, map_location=dev)
+
+
+@pytest.mark.parametrize("key", Q.CASES, ids=lambda k: "SH%d-retain%d-bits%d" % k)
+def test_quant_render_matches_oracle_and_float_kernel(tmp_path, key):
+    svox = _svox(); oops = _oops(); dev = _gpu()
+    c = Q.case(*key)
+    q, f = _load_both(tmp_path, key)
+    assert (c.sigma == 0).any() and (c.sigma > 0).any()
+    assert len(set(c.tree.depths().tolist())) >= 3 and c.tree.depths().max() == 3       # leaves at mixed depths
+    rq, rf = svox.VolumeRenderer(q, step_size=STEP), svox.VolumeRenderer(f, step_size=STEP)
+    o, d, v = (torch.from_numpy(a).to(dev) for a in _rays())
+    worst = 0.0
+    try:
+        for fast in (False, True):
+            c2w = torch.from_numpy(_pose(*POSES[fast]))
+            want = _want_image(key, fast)
+            assert float(np.abs(want - 1.0).max()) > 0.2                    # the view sees the tree ...
+            assert (want == 1.0).all(-1).any()                              # ... and some pixels miss the volume
+            want_r = _want_rays(key, fast)
+            with torch.no_grad():
+                img_f = rf.render_persp(c2w, width=W, height=H, fx=FX, fast=fast)
+                ray_f = rf.forward(o, d, v, fast=fast)
+            close(f"float kernel image fast={fast}", img_f, torch.from_numpy(want), rtol=0, atol=2e-5)
+            close(f"float kernel rays fast={fast}", ray_f, torch.from_numpy(want_r), rtol=0, atol=2e-5)
+            for lanes in (0,) + LANES:                                      # 0: the default
+                oops.set_lanes_per_ray(lanes, 0)
+                img = rq.render_persp(c2w, width=W, height=H, fx=FX, fast=fast)          # grad mode on: nothing requires grad
+                rays = rq.forward(o, d, v, fast=fast)
+                assert img.shape == (H, W, 3) and not img.requires_grad
+                e_img = float((img.cpu() - torch.from_numpy(want)).abs().max())
+                e_ray = float((rays.cpu() - torch.from_numpy(want_r)).abs().max())
+                d_img = float((img - img_f).abs().max())
+                d_ray = float((rays - ray_f).abs().max())
+                worst = max(worst, d_img, d_ray)
+                print(f"SH{key[0]} retain {key[1]} bits {key[2]} fast={fast} lanes={lanes}: max |palette - oracle| image {e_img:.3g} "
+                      f"rays {e_ray:.3g}; max |palette - float kernel| image {d_img:.3g} rays {d_ray:.3g}")
+                close(f"palette image fast={fast} lanes={lanes}", img, torch.from_numpy(want), rtol=0, atol=2e-5)
+                close(f"palette rays fast={fast} lanes={lanes}", rays, torch.from_numpy(want_r), rtol=0, atol=2e-5)
+                close(f"palette vs float image fast={fast} lanes={lanes}", img, img_f, rtol=0, atol=4e-5)
+                close(f"palette vs float rays fast={fast} lanes={lanes}", rays, ray_f, rtol=0, atol=4e-5)
+            assert np.allclose(want_r[-1], 1.0) and torch.equal(rays[-1].cpu(), torch.ones(3))     # the ray that misses
+    finally:
+        oops.set_lanes_per_ray(0, 0)
+    print(f"SH{key[0]} retain {key[1]} bits {key[2]}: max |palette kernel - float kernel| {worst:.3g}")
+
+
+@pytest.mark.parametrize("key", [k for k in Q.CASES if k[2] == 16], ids=lambda k: "SH%d-retain%d-bits%d" % k)
+def test_high_indices_are_hit_by_a_ray(key):
+    """16-bit palettes: the exact-options camera of the test above shades leaves whose index is 65535 and leaves whose
+    index is >= 32768 (a signed or truncated index read would take another palette entry there; the entries are random,
+    so the images of that test would be off by far more than its bound)."""
+    c = Q.case(*key)
+    assert c.quant_colors.shape[1] == 65536
+    opt = T.RenderOptions.for_renderer(STEP, False)
+    c2w = _pose(*POSES[False])
+    sig = c.sigma.reshape(-1)
+    shaded = set()
+    for iy in range(H):
+        for ix in range(W):
+            o, d = T.cam2world_ray(ix, iy, c2w, W, H, FX, FX)
+            shaded.update(leaf for leaf, _ in (T.march_tree(c.tree, o, d, opt) or []) if sig[leaf] > 0)
+    shaded = np.array(sorted(shaded))
+    ids = c.quant_map.reshape(c.quant_map.shape[0], -1)[:, shaded]
+    assert (ids[0] == 65535).sum() >= 3
+    assert ((ids >= 32768) & (ids < 65535)).sum() >= 10
+    last = c.quant_colors[0, 65535].astype(f32)
+    assert np.abs(last - c.quant_colors[0, 32767].astype(f32)).max() > 1e-2      # 65535 & 0x7fff would show
+
+
+@pytest.mark.parametrize("key", [(4, 1, 8), (9, 0, 16), (16, 4, 16), (25, 1, 1), (1, 0, 8)], ids=lambda k: "SH%d-retain%d-bits%d" % k)
+def test_pack_kernel_writes_the_documented_layout(tmp_path, key):
+    """The packed buffer read back from the device equals a numpy restatement of include/plenoctree_octree.h
+    (PxoQuantLayout), byte for byte, padding included."""
+    K, r, bits = key
+    c = Q.case(*key)
+    q, _ = _load_both(tmp_path, key)
+    buf = q._packed.cpu().numpy()
+    n = c.tree.n_internal
+    cells, Kq, P = n * 8, K - r, 1 << bits
+    sections, stride = Q.layout_bytes(n, K, r, bits)
+    assert buf.size == sum(sections) == q._layout.total_bytes
+    idx = np.zeros((cells, stride), np.uint16)
+    idx[:, :Kq] = c.quant_map.reshape(Kq, cells).T
+    pal = np.zeros((Kq, P, 4), np.float16)
+    pal[..., :3] = c.quant_colors
+    sigma = c.sigma.reshape(cells).astype(f32)
+    ret = np.zeros((cells, r, 4), np.float16)
+    if r:
+        ret[..., :3] = c.data_retained.reshape(r, cells, 3).transpose(1, 0, 2)
+    want = np.zeros(buf.size, np.uint8)
+    off = 0
+    for arr, size in zip((idx, pal, sigma, ret), sections):
+        raw = arr.reshape(-1).view(np.uint8)
+        want[off:off + raw.size] = raw
+        off += size
+    assert np.array_equal(buf, want)
+    assert idx.max() >= 32768 or bits < 16
+
+
+def test_evaluation_keep_compressed(tmp_path, capsys, monkeypatch):
+    """octree.evaluation on 4 views of the synthetic scene, with and without --keep_compressed: the rendered images agree to
+    4e-5 (two kernels, each within 2e-5 of the oracle), hence so does the PSNR; the size line is printed; a file that is
+    not compressed is refused with the flag."""
+    svox = _svox(); _gpu()
+    from plenoctree_amd.octree import evaluation
+    key = (16, 4, 16)
+    c = Q.case(*key)
+    path = c.save(os.path.join(str(tmp_path), "tree_min.npz"))
+    cfg_path = os.path.join(str(tmp_path), "tiny.yaml")
+    with open(cfg_path, "w") as fh:
+        fh.write("dataset: synthetic\nfactor: 16\nnum_coarse_samples: 64\nnum_fine_samples: 128\nuse_viewdirs: false\n"
+                 "white_bkgd: true\nbatch_size: 1024\nsh_deg: 3\nrandomized: true\n")
+    common = ["--train_dir", str(tmp_path), "--config", cfg_path, "--synthetic_views", "4", "4", "--renderer_step_size", "1e-3",
+              "--input"]
+    images = []
+    plain = svox.VolumeRenderer.render_persp
+
+    def recording(self, *a, **k):
+        im = plain(self, *a, **k)
+        images.append((type(self.tree).__name__, im.detach().cpu()))
+        return im
+
+    monkeypatch.setattr(svox.VolumeRenderer, "render_persp", recording)
+    psnr_f = evaluation.main(common + [path])
+    out_f = capsys.readouterr().out
+    psnr_q = evaluation.main(common + [path, "--keep_compressed"])
+    out_q = capsys.readouterr().out
+    assert [t for t, _ in images] == ["N3Tree"] * 4 + ["QuantizedN3Tree"] * 4
+    for (_, a), (_, b) in zip(images[:4], images[4:]):
+        assert float(np.abs(a.numpy() - 1.0).max()) > 0.2
+        close("evaluation image", b, a, rtol=0, atol=4e-5)
+    print(f"PSNR float {psnr_f:.6f} dB, kept compressed {psnr_q:.6f} dB")
+    assert np.isfinite(psnr_f) and np.isfinite(psnr_q)
+    q = svox.N3Tree.load(path, keep_quantized=True)
+    line = f"compressed tree kept in place: {q.nbytes / 2 ** 20:.1f} MB on the device (float form: {q.float_nbytes / 2 ** 20:.1f} MB)"
+    assert line in out_q and "kept in place" not in out_f
+    flat = os.path.join(str(tmp_path), "tree_float.npz")
+    svox.N3Tree.load(path).save(flat)
+    with pytest.raises(ValueError, match="keep_quantized"):
+        evaluation.main(common + [flat, "--keep_compressed"])
