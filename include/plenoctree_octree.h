@@ -137,6 +137,24 @@ int pxo_octree_get_tuning(int knob, int* value);
 int pxo_octree_render_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                           const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb,
                           void* stream);
+/* pxo_octree_render_fwd with three more outputs per ray, taken from the same march (same rays, same options, same sample
+ * sequence; out_rgb is bit for bit that of pxo_octree_render_fwd).  The march visits samples i = 0, 1, .. at parameters t_i
+ * (tree units, t_0 = tmin) with steps delta_i.  A sample is shaded when sigma_i > sigma_thresh; then, with light = 1 before
+ * the first sample,
+ *   dtw_i = delta_i * delta_scale,  att_i = exp(-dtw_i * sigma_i),  w_i = light * (1 - att_i),  light *= att_i,
+ *   s_i   = (t_i + 0.5 * delta_i) * delta_scale
+ * s_i is the Euclidean world distance from the ray ORIGIN along the unit direction to the middle of the step (not from the
+ * point where the ray enters the volume, and not z-depth).  out_aux [B,3] (camera mode: [H,W,3]) holds per ray
+ *   [0] alpha    sum of w_i over the shaded samples (= 1 - final light up to round-off)
+ *   [1] depth    sum of w_i * s_i: the expected termination distance, NOT divided by alpha, no background term
+ *   [2] surface  s_i of the first shaded sample after which light <= surface_thresh; +inf if that never happens
+ * With stop_thresh > 0 a ray that stops early has rgb, alpha and depth multiplied by 1 / (1 - light); surface is never
+ * scaled.  A ray that misses the volume gets (0, 0, +inf) and the background as its rgb.  Requires
+ * stop_thresh < surface_thresh < 1 (PXO_ERR_ARG otherwise: an early stop could come before the crossing) and a non-null
+ * out_aux.  Not differentiable: there is no gradient entry point for these outputs. */
+int pxo_octree_render_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                              const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
+                              float* out_rgb, float* out_aux, void* stream);
 /* Gradient of sum(out_rgb * grad_out) w.r.t. tree->data, ACCUMULATED (atomic adds) into grad_data
  * [n_internal,2,2,2,D] -- zero it first (optimizer.zero_grad(), octree/optimization.py:221-224).
  * Training semantics: exact marching (stop_thresh is ignored: no early-stop rescale).
@@ -204,6 +222,13 @@ int pxo_octree_quant_pack(const uint16_t* quant_map, const void* quant_colors, c
 int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                                 const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb,
                                 void* stream);
+/* pxo_octree_render_aux_fwd on a tree in the palette form: out_rgb is that of pxo_octree_render_quant_fwd, out_aux as defined
+ * at pxo_octree_render_aux_fwd (it depends on sigma and the geometry only, so it equals the float tree's bit for bit when
+ * that tree carries the same float32 sigma).  Same argument checks as pxo_octree_render_quant_fwd, plus those on
+ * surface_thresh and out_aux. */
+int pxo_octree_render_quant_aux_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                    const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
+                                    float* out_rgb, float* out_aux, void* stream);
 
 /* ---- work counters of the marchers (roofline pass: scripts/octree_bench.py states each kernel's algorithmic bytes from
  *      these; nothing on the product path calls them) ----

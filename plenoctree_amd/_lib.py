@@ -166,12 +166,16 @@ SIGNATURES = {
     "pxo_octree_get_tuning": (c_int, [c_int, POINTER(c_int)]),
     "pxo_octree_render_fwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
                                       POINTER(PxoRenderOpts), P, P]),
+    "pxo_octree_render_aux_fwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
+                                          POINTER(PxoRenderOpts), c_float, P, P, P]),
     "pxo_octree_render_bwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
                                       POINTER(PxoRenderOpts), P, P, P, P]),
     "pxo_octree_quant_pack_bytes": (c_int, [c_int64, c_int, c_int, c_int, POINTER(PxoQuantLayout)]),
     "pxo_octree_quant_pack": (c_int, [P, P, P, c_int, P, c_int64, c_int, c_int, c_int, P, c_size_t, P]),
     "pxo_octree_render_quant_fwd": (c_int, [POINTER(PxoQuantTree), POINTER(PxoCamera), P, P, P, c_int64,
                                             POINTER(PxoRenderOpts), P, P]),
+    "pxo_octree_render_quant_aux_fwd": (c_int, [POINTER(PxoQuantTree), POINTER(PxoCamera), P, P, P, c_int64,
+                                                POINTER(PxoRenderOpts), c_float, P, P, P]),
     "pxo_octree_count_work": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), POINTER(PxoRenderOpts), P, P, P]),
     "pxo_grid_weight_count_work": (c_int, [P, c_int, P, c_int, c_float, c_float, c_int, c_int, POINTER(PxoRenderOpts),
                                            F3, F3, P, P, P]),

@@ -19,6 +19,8 @@
 // leaf, so a leaf's 3*K coefficients are fetched as coalesced 32/64-byte row loads and reduced with row-local
 // DPP shuffles.  The node path of the previous sample is kept in LDS; the descent for the next sample
 // resumes at the deepest node the two positions share instead of the root.
+#include <type_traits>
+
 #include "pxo_common.h"
 #include "pxo_sh.h"
 #include "../../include/plenoctree_octree.h"
@@ -779,6 +781,12 @@ struct RenderArgs {
   int64_t B;
   PxoRenderOpts opt;
 };
+// what an AUX instantiation of a forward renderer takes on top: the launches without AUX keep their argument block as it is
+struct AuxOut {
+  float* out;                                  // [B,3]: alpha, depth, surface (plenoctree_octree.h)
+  float surface_thresh;
+};
+struct RenderAuxArgs : RenderArgs, AuxOut {};
 
 // Per-row marching state + the leaf lookup with path reuse.
 struct Marcher {
@@ -836,8 +844,13 @@ struct Marcher {
 // the three channels: 4 ceil(K/4/ROW) + 1 registers instead of a selector-weighted triple per data element, and a third
 // of the FMAs.  KF = K (1, 4, 9, 16, 25) makes K a compile-time constant (SH16 at 4 lanes: one float4 per lane and channel,
 // 56 VGPRs - 8 waves per SIMD - against 112 for the index-ordered path); KF = -1 keeps it a run-time value.
-template <int MODE, int ROW, bool VEC = false, int KF = 0>
-__global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(RenderArgs A, float* __restrict__ out_rgb,
+// AUX (forward only): three more row-uniform accumulators per ray -- alpha = sum of the weights, depth = sum of weight x
+// sample distance, surface = distance of the sample at which the transmittance first falls to A.surface_thresh -- written to
+// A.out[ray*3 + c] by the lanes that write out_rgb.  A sample's distance is (t + delta / 2) delta_scale with the sample's OWN
+// t, kept in t_cur across the pipeline's advance of t.
+template <int MODE, int ROW, bool VEC = false, int KF = 0, bool AUX = false>
+__global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::conditional_t<AUX, RenderAuxArgs, RenderArgs> A,
+                                                                        float* __restrict__ out_rgb,
                                                                         const float* __restrict__ fwd_rgb,
                                                                         const float* __restrict__ grad_out,
                                                                         float* __restrict__ grad_data) {
@@ -884,8 +897,11 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(RenderArg
   CellExit cell_exit;
   cell_exit.init(r.invdir);
   const bool miss = r.tmax < 0.0f || r.tmin > r.tmax;
+  static_assert(!AUX || MODE == 0, "alpha / depth / surface: forward only");
   if (MODE == 0 && miss) {
     for (int c = l; c < 3; c += kRow) out_rgb[ray * 3 + c] = bg;
+    if constexpr (AUX)
+      for (int c = l; c < 3; c += kRow) A.out[ray * 3 + c] = c == 2 ? INFINITY : 0.0f;
     return;
   }
   if (MODE == 1 && miss) return;
@@ -943,6 +959,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(RenderArg
     mk.init(s_stack[row]);
     float t = r.tmin, light = 1.0f;
     float out[3] = {0.f, 0.f, 0.f};
+    float aux[3] = {0.f, 0.f, INFINITY};         // AUX: alpha, depth, surface
     bool stopped = false;
     // One sample = the leaf at parameter tt and the step to the next sample; neither depends on the leaf's DATA.  The march is
     // software-pipelined on that: a sample's sigma is requested, then the NEXT sample is located (its child-pointer loads
@@ -971,6 +988,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(RenderArg
       more = tn > t && tn < r.tmax;              // !(tn > t): step below the resolution of t, stop rather than spin
       const int64_t leaf_cur = leaf;
       const float delta_cur = delta_t;
+      const float t_cur = t;
       if (more) locate(tn, leaf, delta_t);       // the next sample, while sigma is on its way
       t = tn;
       if (sg > A.opt.sigma_thresh) {
@@ -1036,9 +1054,16 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(RenderArg
           out[1] += weight * c1;
           out[2] += weight * c2;
           light = light * att;
+          if constexpr (AUX) {
+            const float s = (t_cur + 0.5f * delta_cur) * r.delta_scale;
+            aux[0] += weight;
+            aux[1] += weight * s;
+            if (light <= A.surface_thresh && aux[2] == INFINITY) aux[2] = s;
+          }
           if (MODE == 0 && light <= A.opt.stop_thresh) {
             const float scale = 1.0f / (1.0f - light);
             out[0] *= scale; out[1] *= scale; out[2] *= scale;
+            if constexpr (AUX) { aux[0] *= scale; aux[1] *= scale; }
             stopped = true;
             break;
           }
@@ -1067,6 +1092,8 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(RenderArg
           out[0] += light * bg; out[1] += light * bg; out[2] += light * bg;
         }
         for (int c = l; c < 3; c += kRow) out_rgb[ray * 3 + c] = c == 0 ? out[0] : (c == 1 ? out[1] : out[2]);
+        if constexpr (AUX)
+          for (int c = l; c < 3; c += kRow) A.out[ray * 3 + c] = c == 0 ? aux[0] : (c == 1 ? aux[1] : aux[2]);
       } else {
         accum = (g[0] * (out[0] + light * bg) + g[1] * (out[1] + light * bg)) + g[2] * (out[2] + light * bg);
       }
@@ -1602,14 +1629,17 @@ struct QuantRenderArgs {
   int64_t B;
   PxoRenderOpts opt;
 };
+struct QuantRenderAuxArgs : QuantRenderArgs, AuxOut {};
 
 // octree_render_kernel<0, ROW>'s rays, march and compositing; a shaded sample's colour comes through the palettes.  Plane
 // ownership inside a ray's ROW lanes: lane l owns the retained planes l, l + ROW, .. and the groups l, l + ROW, .. of four
 // consecutive quantised planes (one 8-byte index load per group, one 8-byte palette load per plane, all three channels in
 // it).  A lane sums its retained planes, then its quantised planes, both ascending; row_sum adds the lanes: the order
-// depends on (ROW, K, r) only.
-template <int ROW>
-__global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(QuantRenderArgs A, float* __restrict__ out_rgb) {
+// depends on (ROW, K, r) only.  AUX: the float kernel's three extra outputs, the same way (they depend on sigma and the
+// geometry only, and sigma is the float tree's).
+template <int ROW, bool AUX = false>
+__global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(std::conditional_t<AUX, QuantRenderAuxArgs, QuantRenderArgs> A,
+                                                                              float* __restrict__ out_rgb) {
   using G = RowGeom<ROW>;
   constexpr int kRow = ROW, kRaysPerBlock = G::kRaysPerBlock;
   constexpr int kQM = (7 + ROW - 1) / ROW;         // index groups per lane: Kq <= 25 -> at most 7 groups of four
@@ -1657,6 +1687,8 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(Qua
   cell_exit.init(r.invdir);
   if (r.tmax < 0.0f || r.tmin > r.tmax) {
     for (int c = l; c < 3; c += kRow) out_rgb[ray * 3 + c] = bg;
+    if constexpr (AUX)
+      for (int c = l; c < 3; c += kRow) A.out[ray * 3 + c] = c == 2 ? INFINITY : 0.0f;
     return;
   }
 
@@ -1680,6 +1712,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(Qua
   mk.init(s_stack[row]);
   float t = r.tmin, light = 1.0f;
   float out[3] = {0.f, 0.f, 0.f};
+  float aux[3] = {0.f, 0.f, INFINITY};           // AUX: alpha, depth, surface
   bool stopped = false;
   // the float kernel's software pipeline: sigma requested, the next sample located, then the current one shaded
   auto locate = [&](float tt, int64_t& leaf_o, float& delta_o) {
@@ -1704,6 +1737,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(Qua
     more = tn > t && tn < r.tmax;              // !(tn > t): step below the resolution of t, stop rather than spin
     const int64_t leaf_cur = leaf;
     const float delta_cur = delta_t;
+    const float t_cur = t;
     if (more) locate(tn, leaf, delta_t);
     t = tn;
     if (sg > A.opt.sigma_thresh) {
@@ -1747,9 +1781,16 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(Qua
       out[1] += weight * c1;
       out[2] += weight * c2;
       light = light * att;
+      if constexpr (AUX) {
+        const float s = (t_cur + 0.5f * delta_cur) * r.delta_scale;
+        aux[0] += weight;
+        aux[1] += weight * s;
+        if (light <= A.surface_thresh && aux[2] == INFINITY) aux[2] = s;
+      }
       if (light <= A.opt.stop_thresh) {
         const float scale = 1.0f / (1.0f - light);
         out[0] *= scale; out[1] *= scale; out[2] *= scale;
+        if constexpr (AUX) { aux[0] *= scale; aux[1] *= scale; }
         stopped = true;
         break;
       }
@@ -1759,6 +1800,8 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(Qua
     out[0] += light * bg; out[1] += light * bg; out[2] += light * bg;
   }
   for (int c = l; c < 3; c += kRow) out_rgb[ray * 3 + c] = c == 0 ? out[0] : (c == 1 ? out[1] : out[2]);
+  if constexpr (AUX)
+    for (int c = l; c < 3; c += kRow) A.out[ray * 3 + c] = c == 0 ? aux[0] : (c == 1 ? aux[1] : aux[2]);
 }
 
 }  // namespace pxo
@@ -2099,6 +2142,46 @@ int pxo_octree_render_fwd(const PxoTree* tree, const PxoCamera* cam, const float
   return check_launch("octree_render_fwd");
 }
 
+// stop_thresh < surface_thresh < 1: an early stop (light <= stop_thresh) then never comes before the crossing
+static int check_surface_thresh(const PxoRenderOpts* o, float surface_thresh, const char* who) {
+  PXO_REQUIRE(o->stop_thresh < surface_thresh && surface_thresh < 1.0f,
+              "%s: surface_thresh %g must lie in (stop_thresh %g, 1)", who, (double)surface_thresh, (double)o->stop_thresh);
+  return PXO_OK;
+}
+
+int pxo_octree_render_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                              const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
+                              float* out_rgb, float* out_aux, void* stream) {
+  const char* who = "pxo_octree_render_aux_fwd";
+  RenderAuxArgs A;
+  unsigned grid;
+  int row;
+  if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, false, A, grid, row)) return rc;
+  if (int rc = check_surface_thresh(opts, surface_thresh, who)) return rc;
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(out_rgb && out_aux, "%s: null output", who);
+  A.out = out_aux;
+  A.surface_thresh = surface_thresh;
+  const float* none = nullptr;
+  switch (row) {
+    case 4:
+#define PXO_AUX4(KF_) hipLaunchKernelGGL((octree_render_kernel<0, 4, true, KF_, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr)
+      switch (tree->basis_dim) {
+        case 1: PXO_AUX4(1); break;
+        case 4: PXO_AUX4(4); break;
+        case 9: PXO_AUX4(9); break;
+        case 16: PXO_AUX4(16); break;
+        case 25: PXO_AUX4(25); break;
+        default: PXO_AUX4(-1); break;
+      }
+#undef PXO_AUX4
+      break;
+    case 8: hipLaunchKernelGGL((octree_render_kernel<0, 8, true, 0, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr); break;
+    default: hipLaunchKernelGGL((octree_render_kernel<0, 16, true, 0, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr); break;
+  }
+  return check_launch("octree_render_aux_fwd");
+}
+
 int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                           const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* out_rgb,
                           const float* grad_out, float* grad_data, void* stream) {
@@ -2210,9 +2293,10 @@ int pxo_octree_quant_pack(const uint16_t* quant_map, const void* quant_colors, c
   return check_launch("octree_quant_pack");
 }
 
-int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
-                                const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
-  const char* who = "pxo_octree_render_quant_fwd";
+// the argument checks and the launch shape of the palette renderers (with and without the extra outputs)
+static int quant_render_args(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                             const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const char* who, QuantRenderArgs& A,
+                             int64_t& blocks, int& row) {
   if (int rc = check_opts(opts, who)) return rc;
   PXO_REQUIRE(tree && tree->child && tree->idx && tree->palette && tree->sigma, "%s: null tree", who);
   if (int rc = quant_format_ok(tree->n_internal, tree->basis_dim, tree->n_retained, tree->bits, who)) return rc;
@@ -2223,13 +2307,11 @@ int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, 
   PXO_REQUIRE((((uintptr_t)tree->idx | (uintptr_t)tree->palette | (uintptr_t)tree->retained) & 7) == 0,
               "%s: idx, palette and retained must be 8-byte aligned", who);
   PXO_REQUIRE(B >= 0, "%s: B < 0", who);
-  QuantRenderArgs A;
   A.tree = *tree;
   A.opt = *opts;
   A.B = B;
   A.has_cam = cam != nullptr;
-  const int row = g_row_override[0] ? g_row_override[0] : 4;     // unmeasured against 8 / 16 (see DESIGN): the float kernel's default
-  int64_t blocks;
+  row = g_row_override[0] ? g_row_override[0] : 4;     // unmeasured against 8 / 16 (see DESIGN): the float kernel's default
   if (cam) {
     PXO_REQUIRE(cam->c2w && cam->width >= 1 && cam->height >= 1 && cam->fx > 0.0f && cam->fy > 0.0f, "%s: bad camera", who);
     PXO_REQUIRE(B == (int64_t)cam->width * cam->height, "%s: B must be width*height in camera mode", who);
@@ -2244,6 +2326,16 @@ int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, 
     blocks = blocks_for(B, kRenderThreads / row);
   }
   PXO_REQUIRE(blocks < ((int64_t)1 << 31), "%s: too many rays for one launch", who);
+  return PXO_OK;
+}
+
+int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
+  const char* who = "pxo_octree_render_quant_fwd";
+  QuantRenderArgs A;
+  int64_t blocks;
+  int row;
+  if (int rc = quant_render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, A, blocks, row)) return rc;
   if (B == 0) return PXO_OK;
   PXO_REQUIRE(out_rgb, "%s: null output", who);
   const dim3 grid((unsigned)blocks), block(kRenderThreads);
@@ -2253,6 +2345,28 @@ int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, 
     default: hipLaunchKernelGGL(octree_render_quant_kernel<16>, grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
   }
   return check_launch("octree_render_quant_fwd");
+}
+
+int pxo_octree_render_quant_aux_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                    const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
+                                    float* out_rgb, float* out_aux, void* stream) {
+  const char* who = "pxo_octree_render_quant_aux_fwd";
+  QuantRenderAuxArgs A;
+  int64_t blocks;
+  int row;
+  if (int rc = quant_render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, A, blocks, row)) return rc;
+  if (int rc = check_surface_thresh(opts, surface_thresh, who)) return rc;
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(out_rgb && out_aux, "%s: null output", who);
+  A.out = out_aux;
+  A.surface_thresh = surface_thresh;
+  const dim3 grid((unsigned)blocks), block(kRenderThreads);
+  switch (row) {
+    case 4: hipLaunchKernelGGL((octree_render_quant_kernel<4, true>), grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
+    case 8: hipLaunchKernelGGL((octree_render_quant_kernel<8, true>), grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
+    default: hipLaunchKernelGGL((octree_render_quant_kernel<16, true>), grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
+  }
+  return check_launch("octree_render_quant_aux_fwd");
 }
 
 int pxo_octree_count_work(const PxoTree* tree, const PxoCamera* cam, const PxoRenderOpts* opts, unsigned long long* counts,

@@ -3,6 +3,10 @@ mean PSNR of its renders of the test split; test images are sharded over the GPU
 
     python -m plenoctree_amd.octree.evaluation --input tree_opt.npz --config blender --data_dir ... [--write_images DIR]
         [--keep_compressed]     (a tree written by octree.compression is rendered from its palette form, in place)
+        [--write_aux DIR]       (per view NNN_rgba.png, the render with its opacity as the alpha channel, and NNN_depth.npz
+                                 with float32 depth / surface / alpha; distances are Euclidean, from the camera origin)
+        [--write_points F.ply]  (every --points_stride-th pixel of every view whose transmittance falls to --surface_thresh,
+                                 back-projected to its surface distance and coloured by the render)
 """
 import os
 import sys
@@ -12,7 +16,7 @@ import torch
 
 from .. import dist
 from ..nerf_sh.nerf import datasets, utils
-from . import extraction
+from . import aux_io, extraction
 from .svox import N3Tree
 
 
@@ -26,7 +30,41 @@ def define_flags():
     a("--no_early_stop", action="store_true")
     a("--keep_compressed", action="store_true",
       help="evaluate a compressed tree (octree.compression) in its palette form instead of re-inflating it to float32")
+    # not reference flags: the renderer's opacity / distance outputs (VolumeRenderer.render_persp_aux)
+    a("--write_aux", type=str, default=None, help="directory for NNN_rgba.png and NNN_depth.npz of every test view")
+    a("--write_points", type=str, default=None, help="binary PLY of the back-projected surface points of all test views")
+    a("--points_stride", type=int, default=4, help="--write_points takes every n-th pixel along both image axes")
+    a("--surface_thresh", type=float, default=0.5,
+      help="transmittance at which a ray is taken to have reached the surface (above the early-stop threshold, below 1)")
     return p
+
+
+class _AuxSink:
+    """Per-view consumer of eval_octree's aux_sink: writes the --write_aux files at once, collects the --write_points points."""
+
+    def __init__(self, args, dataset):
+        self.args, self.dataset = args, dataset
+        self.xyz, self.colors = [], []
+        if args.write_aux is not None:
+            os.makedirs(args.write_aux, exist_ok=True)
+
+    def __call__(self, idx, c2w, res):
+        rgb, alpha, depth, surface = (res[k].cpu().numpy() for k in ("rgb", "alpha", "depth", "surface"))
+        if self.args.write_aux is not None:
+            aux_io.write_rgba_png(os.path.join(self.args.write_aux, f"{idx:03d}_rgba.png"), rgb, alpha)
+            aux_io.write_depth_npz(os.path.join(self.args.write_aux, f"{idx:03d}_depth.npz"), depth, surface, alpha)
+        if self.args.write_points is not None:
+            xyz, col = aux_io.surface_points(c2w, self.dataset.focal, surface, rgb, self.args.points_stride)
+            self.xyz.append(xyz)
+            self.colors.append(col)
+
+    def write_points(self, comm):
+        path = self.args.write_points
+        if comm.world > 1:
+            path = os.path.splitext(path)[0] + f".rank{comm.rank}.ply"
+        print("Writing to", path, flush=True)
+        aux_io.write_ply(path, np.concatenate(self.xyz) if self.xyz else np.zeros((0, 3), np.float32),
+                         np.concatenate(self.colors) if self.colors else np.zeros((0, 3), np.uint8))
 
 
 def main(argv=None):
@@ -36,6 +74,9 @@ def main(argv=None):
         # checked BEFORE anything is rendered: imageio / ffmpeg are not installed, so only the animated GIF writer is built
         raise ValueError(f"--write_vid {args.write_vid}: only animated GIF output is built (no imageio/ffmpeg here); "
                          "give a .gif path")
+    want_aux = args.write_aux is not None or args.write_points is not None
+    if want_aux and args.points_stride < 1:
+        raise ValueError(f"--points_stride {args.points_stride}: must be >= 1")
     if not torch.cuda.is_available():
         raise SystemExit("octree.evaluation needs a ROCm GPU; the HIP path has no CPU fallback")
     comm = dist.init_from_env()
@@ -49,7 +90,14 @@ def main(argv=None):
         print(f"compressed tree kept in place: {tree.nbytes / 2 ** 20:.1f} MB on the device "
               f"(float form: {tree.float_nbytes / 2 ** 20:.1f} MB)", flush=True)
     want_frames = args.write_images is not None or args.write_vid is not None
-    psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True)
+    if want_aux:
+        sink = _AuxSink(args, dataset)
+        psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True,
+                                                    aux_sink=sink, surface_thresh=args.surface_thresh)
+        if args.write_points is not None:
+            sink.write_points(comm)
+    else:
+        psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True)
     if comm.rank == 0:
         print("Average PSNR", psnr, "SSIM", ssim, flush=True)
     if args.write_vid is not None and frames:

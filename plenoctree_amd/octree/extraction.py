@@ -219,17 +219,25 @@ def tree_center_radius(tree):
 
 
 @torch.no_grad()
-def eval_octree(tree, dataset, args, comm=None, want_frames=False, want_ssim=False):
+def eval_octree(tree, dataset, args, comm=None, want_frames=False, want_ssim=False, aux_sink=None, surface_thresh=0.5):
     """eval_octree (octree/nerf/utils.py:448-497): mean PSNR (and SSIM if asked) of the octree renders of a split;
-    images are sharded over the ranks.  LPIPS needs pretrained VGG weights, which cannot be fetched here."""
+    images are sharded over the ranks.  LPIPS needs pretrained VGG weights, which cannot be fetched here.
+    aux_sink (off by default): called as aux_sink(idx, c2w, res) for every view of this rank with the dict of
+    VolumeRenderer.render_persp_aux; the view is then rendered by that call (same rgb) instead of render_persp."""
     comm = comm or dist.Comm()
     r = VolumeRenderer(tree, step_size=args.renderer_step_size)
     acc = torch.zeros(3, dtype=torch.float64, device=tree.device)
     frames = []
     for idx in range(comm.rank, dataset.size, comm.world):
         gt = dataset.get_image(idx)["pixels"]
-        im = r.render_persp(torch.from_numpy(dataset.camtoworlds[idx]), width=dataset.w, height=dataset.h,
-                            fx=dataset.focal, fast=not args.no_early_stop)
+        if aux_sink is None:
+            im = r.render_persp(torch.from_numpy(dataset.camtoworlds[idx]), width=dataset.w, height=dataset.h,
+                                fx=dataset.focal, fast=not args.no_early_stop)
+        else:
+            res = r.render_persp_aux(torch.from_numpy(dataset.camtoworlds[idx]), width=dataset.w, height=dataset.h,
+                                     fx=dataset.focal, fast=not args.no_early_stop, surface_thresh=surface_thresh)
+            im = res["rgb"]
+            aux_sink(idx, dataset.camtoworlds[idx], res)
         sse, _ = oops.image_mse(im, gt.contiguous(), want_grad=False)
         acc[0] += utils.compute_psnr(float(sse) / im.numel())
         acc[1] += 1

@@ -659,6 +659,33 @@ class VolumeRenderer:
 
     __call__ = forward
 
+    # ---- additions (no svox counterpart): opacity, expected distance and surface distance from the same march ----
+    def _aux_view(self, what):
+        if isinstance(self.tree, QuantizedN3Tree):
+            return self.tree.quant_view()
+        if torch.is_grad_enabled() and self.tree.data.requires_grad:
+            raise oops.PxoError(f"{what} is not differentiable (alpha, depth and surface have no gradient kernel): call it "
+                                "under torch.no_grad()")
+        return self.tree.view()
+
+    @staticmethod
+    def _aux_dict(rgb, aux):
+        return {"rgb": rgb, "alpha": aux[..., 0], "depth": aux[..., 1], "surface": aux[..., 2]}
+
+    def render_persp_aux(self, c2w, width=800, height=800, fx=1111.111, fy=None, fast=False, surface_thresh=0.5):
+        """dict(rgb [H,W,3], alpha [H,W], depth [H,W], surface [H,W]): render_persp's image with, per pixel, the opacity (sum
+        of the compositing weights), the expected termination distance (sum of weight x sample distance, not divided by
+        alpha) and the distance at which the transmittance first falls to `surface_thresh` (+inf where it never does).
+        Distances are Euclidean, in world units, from the ray origin.  Not differentiable."""
+        view = self._aux_view("render_persp_aux")
+        c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.tree.device)
+        return self._aux_dict(*oops.octree_render_aux_persp(view, c2w, width, height, fx, self._opts(fast), fy, surface_thresh))
+
+    def forward_aux(self, origins, dirs, viewdirs, fast=False, surface_thresh=0.5):
+        """render_persp_aux for explicit world-space rays (unit `dirs`): rgb [B,3], alpha / depth / surface [B]."""
+        view = self._aux_view("forward_aux")
+        return self._aux_dict(*oops.octree_render_aux_rays(view, origins, dirs, viewdirs, self._opts(fast), surface_thresh))
+
 
 # ---- svox.helpers._get_c_extension(): the slice of svox's native module the reference touches ---------------------------
 class _RenderOptions:

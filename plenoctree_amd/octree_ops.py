@@ -296,6 +296,40 @@ def octree_render_quant_rays(qtree, origins, dirs, viewdirs, opts):
     return out
 
 
+def _aux_entry(tree):
+    """(entry point, its name) of the renderer with the extra outputs for a PxoTree or a PxoQuantTree."""
+    if isinstance(tree, _lib.PxoQuantTree):
+        return _lib.load().pxo_octree_render_quant_aux_fwd, "pxo_octree_render_quant_aux_fwd"
+    if isinstance(tree, _lib.PxoTree):
+        return _lib.load().pxo_octree_render_aux_fwd, "pxo_octree_render_aux_fwd"
+    raise PxoError(f"expected a PxoTree or a PxoQuantTree, got {type(tree).__name__}")
+
+
+def octree_render_aux_persp(tree, c2w, width, height, fx, opts, fy=None, surface_thresh=0.5):
+    """(rgb [H,W,3], aux [H,W,3]) of a pinhole camera from one march: rgb is octree_render_persp's (octree_render_quant_persp's
+    for a PxoQuantTree), aux = (alpha, depth, surface) as defined at pxo_octree_render_aux_fwd.  Not differentiable."""
+    _require_gpu()
+    fn, name = _aux_entry(tree)
+    cam, keep = _camera(c2w, width, height, fx, fy)
+    out = _new(height, width, 3, device=keep.device)
+    aux = _new(height, width, 3, device=keep.device)
+    check(fn(ctypes.byref(tree), ctypes.byref(cam), None, None, None, width * height, ctypes.byref(opts),
+             float(surface_thresh), _f(out), _f(aux), _stream()), name)
+    return out, aux
+
+
+def octree_render_aux_rays(tree, origins, dirs, viewdirs, opts, surface_thresh=0.5):
+    """(rgb [B,3], aux [B,3]) of explicit world-space rays with unit dirs; see octree_render_aux_persp."""
+    _require_gpu()
+    fn, name = _aux_entry(tree)
+    B = origins.shape[0]
+    out = _new(B, 3, device=origins.device)
+    aux = _new(B, 3, device=origins.device)
+    check(fn(ctypes.byref(tree), None, _f(origins), _f(dirs), _f(viewdirs), B, ctypes.byref(opts), float(surface_thresh),
+             _f(out), _f(aux), _stream()), name)
+    return out, aux
+
+
 def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None):
     _require_gpu()
     check(_lib.load().pxo_octree_render_bwd(ctypes.byref(tree), None, _f(origins), _f(dirs), _f(viewdirs),

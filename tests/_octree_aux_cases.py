@@ -1,0 +1,83 @@
+"""The cases of tests/test_octree_aux_cpu.py and tests/test_gpu_octree_aux.py: the shapes of
+tests/test_gpu_octree.py::test_octree_render_matches_oracle (depth-3 trees with a third of their leaves empty, a 14 x 10
+camera at radius 4, 25 explicit rays with origins inside the volume and one ray that misses), with the references of
+tests/_octree_aux_oracle.py computed once per case and shared."""
+import functools
+
+import numpy as np
+
+import _octree_aux_oracle as A
+from oracle import octree_oracle as T
+
+f32 = np.float32
+KS = (1, 4, 9, 16, 25)
+W, H, FX = 14, 10, 13.0
+SURFACE_THRESH = 0.5
+# name -> (camera (theta, phi) or None for the explicit rays, step, background, fast)
+CONFIGS = {"exact": ((20.0, 30.0), 1e-3, 1.0, False), "fast": ((250.0, -5.0), 1e-3, 1.0, True), "rays": (None, 2e-3, 0.5, False)}
+
+
+def pose(theta, phi, radius=4.0):
+    from plenoctree_amd.nerf_sh.nerf.datasets import pose_spherical
+    return pose_spherical(theta, phi, radius)
+
+
+@functools.lru_cache(maxsize=None)
+def random_tree(depth, seed, K, p=0.15, center=(0.1, 0.0, -0.2), radius=(1.4, 1.5, 1.3)):
+    """Local copy of tests/test_gpu_octree.py `_random_tree`: oracle tree with random SH data, about a third of the leaves
+    empty (sigma <= 0)."""
+    reso = 2 ** (depth + 1)
+    mask = np.random.RandomState(seed).rand(reso, reso, reso) < p
+    t = T.build_from_mask(mask, depth, 3 * K + 1, center, radius)
+    rs = np.random.RandomState(seed + 100)
+    t.data[:] = (rs.randn(*t.data.shape) * 0.7).astype(f32)
+    t.data[..., -1] = ((rs.rand(*t.data.shape[:-1]) - 0.35) * 12.0).astype(f32)
+    return t
+
+
+def tree(K):
+    return random_tree(3, 10 + K, K)
+
+
+def options(config):
+    _, step, bg, fast = CONFIGS[config]
+    thr = 1e-2 if fast else 0.0
+    return T.RenderOptions(step, bg, thr, thr)
+
+
+@functools.lru_cache(maxsize=None)
+def explicit_rays(K):
+    """25 rays: 20 from outside, 4 from inside the volume, the last one misses it."""
+    rs = np.random.RandomState(K)
+    o = np.concatenate([rs.randn(20, 3) * 3.0, rs.rand(4, 3) * 0.5, [[9.0, 9.0, 9.0]]]).astype(f32)
+    d = (-o + rs.randn(25, 3) * 0.4).astype(f32)
+    d[-1] = [1.0, 0.0, 0.0]
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return o, d
+
+
+@functools.lru_cache(maxsize=None)
+def reference(K, config):
+    """(float32 Batch, float64 Batch) of the case; treat as read-only."""
+    cam = CONFIGS[config][0]
+    if cam is None:
+        o, d = explicit_rays(K)
+        return A.render_rays_aux(tree(K), o, d, d, options(config), SURFACE_THRESH)
+    return A.render_persp_aux(tree(K), pose(*cam), W, H, FX, options(config), SURFACE_THRESH)
+
+
+def read_ply(path):
+    """(xyz [n,3] float32, colours [n,3] uint8) of a file written by octree.aux_io.write_ply."""
+    from plenoctree_amd.octree.aux_io import PLY_VERTEX
+    with open(path, "rb") as f:
+        n = None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: no end_header")
+            if line.startswith(b"element vertex"):
+                n = int(line.split()[2])
+            if line.strip() == b"end_header":
+                break
+        v = np.frombuffer(f.read(), PLY_VERTEX, count=n)
+    return np.stack([v["x"], v["y"], v["z"]], -1), np.stack([v["red"], v["green"], v["blue"]], -1)
