@@ -106,10 +106,11 @@ typedef struct PxoLeaf {
  * noise_std + skip_zero_rows, pxo_profile_enable takes a tag MASK, pxo_set_tuning / pxo_occupy_cus exist; 6: PXO_MLP_BF16X6,
  * pxo_adam_pack_step serves every precision, PXO_TUNE_COARSE_REVERSE_STREAM / PXO_TUNE_X6_WGRAD; 7: the pxo_vd_* entry points of
  * the view-conditioned head and its SH projection; 8: ray rendering with that head -- pxo_vd_render_fwd, pxo_vd_composite_fwd,
- * PXO_TUNE_VD_RAY_BLOCK).  A binding checks
+ * PXO_TUNE_VD_RAY_BLOCK; 9: spherical-Gaussian models -- pxo_sg_render_fwd here, pxo_octree_render_sg_fwd /
+ * pxo_octree_render_sg_bwd in plenoctree_octree.h).  A binding checks
  * pxo_version() == PXO_ABI_VERSION and pxo_cfg_bytes() == sizeof(PxoCfg) after dlopen (plenoctree_amd/_lib.py does): a
  * caller built against an older header would otherwise pass a short PxoCfg and have its tail read from past the end. */
-#define PXO_ABI_VERSION 8
+#define PXO_ABI_VERSION 9
 const char* pxo_last_error(void);
 int pxo_version(void);
 size_t pxo_cfg_bytes(void);
@@ -273,6 +274,19 @@ int pxo_render_fwd(const PxoCfg* cfg, const float* packed_fwd0, const float* pac
                    int64_t B, int randomized, const float* t_rand, const float* u, uint64_t seed,
                    float* rgb_c, float* disp_c, float* acc_c, float* rgb_f, float* disp_f,
                    float* acc_f, void* ws, size_t ws_bytes, void* stream);
+
+/* NerfModel.__call__ of a NeRF-SG (sg_dim > 0: nerf_sh/nerf/models.py:204-210 reads the lobes, :273-292 and :331-348 shade
+ * with eval_sg, nerf_sh/nerf/sg.py:35-66), forward only.  pxo_render_fwd with one more argument: lobes, device float32
+ * [K,4] with K = (cfg->sh_deg+1)^2 = sg_dim, row i = (lambda_i, mu_i.x, mu_i.y, mu_i.z), lambda_i = softplus(sg_lambda_i),
+ * mu_i = spher2cart(sg_mu_spher_i) (the caller applies both).  The MLPs have the 3K+1 outputs of the SH model of that
+ * sh_deg, so packing, the MLP kernels of every mlp_precision and the workspace (pxo_render_workspace_bytes) are shared: a
+ * sample's raw colour and sigma are bit for bit those of pxo_eval_points.  Only the shading differs: per ray
+ * basis_i = exp(lambda_i * (dot(mu_i, viewdir) - 1)) / K in float32, evaluated as written, then rgb_c = sigmoid(sum_i
+ * raw[c*K+i] * basis_i) and the compositing of pxo_render_fwd.  PXO_ERR_ARG if lobes is NULL. */
+int pxo_sg_render_fwd(const PxoCfg* cfg, const float* lobes, const float* packed_fwd0, const float* packed_fwd1,
+                      const float* origins, const float* directions, const float* viewdirs, int64_t B, int randomized,
+                      const float* t_rand, const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c,
+                      float* rgb_f, float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream);
 
 /* loss_fn + value_and_grad of train_step (nerf_sh/train.py:66-116) on this device's shard.
  * params: the 2-MLP arena; packed_*: its images (pxo_pack_weights).  grads: 2-MLP arena,

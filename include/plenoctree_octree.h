@@ -165,6 +165,24 @@ int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float
                           const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* out_rgb,
                           const float* grad_out, float* grad_data, void* stream);
 
+/* ---- spherical-Gaussian trees  (svox data_format "SG<K>" with extra_data; octree/extraction.py:436-442, :481-499;
+ *      rendered at octree/nerf/utils.py:456-474, fine-tuned at octree/optimization.py:174-216) ----
+ * lobes: device float32 [tree->basis_dim, 4], row i = (lambda_i, mu_i.x, mu_i.y, mu_i.z) with lambda_i > 0 and mu_i a unit
+ * vector (the tree's extra_data).  The per-ray basis is
+ *   basis_i(d) = exp(lambda_i * (dot(mu_i, d) - 1)) / K      (eval_sg, nerf_sh/nerf/sg.py:35-66)
+ * in float32, evaluated as written (dot, minus 1, times lambda, expf, times 1/K), in place of the SH basis.  Everything
+ * else -- rays, march, sample sequence, early stop and its rescale, the out_rgb contract of the backward, the accumulation
+ * into grad_data, pxo_octree_set_lanes_per_ray and the tuning knobs -- is that of pxo_octree_render_fwd /
+ * pxo_octree_render_bwd; tree->data is laid out as for SH (channel-major, sigma last).  There is no gradient with respect
+ * to the lobes (svox does not optimise extra_data).  PXO_ERR_ARG if basis_dim is not 1, 4, 9, 16 or 25, data_dim != 3
+ * basis_dim + 1 or lobes is NULL. */
+int pxo_octree_render_sg_fwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                             const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb,
+                             void* stream);
+int pxo_octree_render_sg_bwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                             const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts,
+                             const float* out_rgb, const float* grad_out, float* grad_data, void* stream);
+
 /* ---- compressed trees rendered in place  (the palette form octree/compression.py:88-139 writes) ----
  *
  * File arrays (K = basis_dim, r = n_retained, Kq = K - r, C = n_internal * 8 cells, P = 2^bits palette entries):

@@ -84,7 +84,7 @@ class PxoQuantTree(Structure):
 
 
 TREE_MAX_DEPTH = 10
-ABI_VERSION = 8                     # PXO_ABI_VERSION of include/plenoctree_hip.h
+ABI_VERSION = 9                     # PXO_ABI_VERSION of include/plenoctree_hip.h
 
 P = c_void_p
 CFG = POINTER(PxoCfg)
@@ -126,6 +126,8 @@ SIGNATURES = {
     "pxo_render_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
     "pxo_render_fwd": (c_int, [CFG, P, P, P, P, P, c_int64, c_int, P, P, c_uint64, P, P, P, P, P, P, P,
                                c_size_t, P]),
+    "pxo_sg_render_fwd": (c_int, [CFG, P, P, P, P, P, P, c_int64, c_int, P, P, c_uint64, P, P, P, P, P, P, P,
+                                  c_size_t, P]),
     "pxo_train_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
     "pxo_train_fwd_bwd": (c_int, [CFG, P, P, P, P, P, P, P, P, P, c_int64, c_int, P, P, P, c_uint64, P, P,
                                   P, c_size_t, P]),
@@ -170,6 +172,10 @@ SIGNATURES = {
                                           POINTER(PxoRenderOpts), c_float, P, P, P]),
     "pxo_octree_render_bwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
                                       POINTER(PxoRenderOpts), P, P, P, P]),
+    "pxo_octree_render_sg_fwd": (c_int, [POINTER(PxoTree), P, POINTER(PxoCamera), P, P, P, c_int64,
+                                         POINTER(PxoRenderOpts), P, P]),
+    "pxo_octree_render_sg_bwd": (c_int, [POINTER(PxoTree), P, POINTER(PxoCamera), P, P, P, c_int64,
+                                         POINTER(PxoRenderOpts), P, P, P, P]),
     "pxo_octree_quant_pack_bytes": (c_int, [c_int64, c_int, c_int, c_int, POINTER(PxoQuantLayout)]),
     "pxo_octree_quant_pack": (c_int, [P, P, P, c_int, P, c_int64, c_int, c_int, c_int, P, c_size_t, P]),
     "pxo_octree_render_quant_fwd": (c_int, [POINTER(PxoQuantTree), POINTER(PxoCamera), P, P, P, c_int64,

@@ -771,6 +771,16 @@ __device__ __forceinline__ void sh_basis_dyn(int basis_dim, float x, float y, fl
     if (i < basis_dim) Y[i] = tmp[i];
 }
 
+// spherical-Gaussian basis of an SG<K> tree (nerf_sh/nerf/sg.py:35-66, svox data_format SG<K>): lobes [K,4] rows
+// (lambda, mu.x, mu.y, mu.z), basis_i = exp(lambda_i (mu_i . d - 1)) / K -- float32, evaluated in exactly that order
+__device__ __forceinline__ void sg_basis_dyn(int basis_dim, const float* __restrict__ lobes, float x, float y, float z, float* Y) {
+  const float inv_k = 1.0f / (float)basis_dim;
+  for (int i = 0; i < basis_dim; ++i) {
+    const float lam = lobes[4 * i], dot = lobes[4 * i + 1] * x + lobes[4 * i + 2] * y + lobes[4 * i + 3] * z;
+    Y[i] = expf(lam * (dot - 1.0f)) * inv_k;
+  }
+}
+
 struct RenderArgs {
   PxoTree tree;
   PxoCamera cam;
@@ -780,7 +790,13 @@ struct RenderArgs {
   const float* viewdirs;
   int64_t B;
   PxoRenderOpts opt;
+  const float* lobes;                          // NULL: SH tree; else the [basis_dim,4] lobes of an SG tree (kernel-uniform)
 };
+// the per-ray basis of either tree format; everything after it sees only basis[k]
+__device__ __forceinline__ void ray_basis(const RenderArgs& A, int basis_dim, const float (&vdir)[3], float* Y) {
+  if (A.lobes) sg_basis_dyn(basis_dim, A.lobes, vdir[0], vdir[1], vdir[2], Y);
+  else sh_basis_dyn(basis_dim, vdir[0], vdir[1], vdir[2], Y);
+}
 // what an AUX instantiation of a forward renderer takes on top: the launches without AUX keep their argument block as it is
 struct AuxOut {
   float* out;                                  // [B,3]: alpha, depth, surface (plenoctree_octree.h)
@@ -907,7 +923,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
   if (MODE == 1 && miss) return;
 
   // per-lane channel ownership: data index l + ROW j -> (channel, SH component)
-  if (l == 0) sh_basis_dyn(K, vdir[0], vdir[1], vdir[2], s_basis[row]);
+  if (l == 0) ray_basis(A, K, vdir, s_basis[row]);
   __builtin_amdgcn_wave_barrier();
   static_assert(!VEC || MODE == 0, "vector loads: forward only (the gradient scatter wants contiguous dword rows)");
   static_assert(KF == 0 || (VEC && MODE == 0), "channel-aligned paths: forward, vector loads");
@@ -1173,7 +1189,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_bwd4_kernel(Rend
   const bool alive = active && !(r.tmax < 0.0f || r.tmin > r.tmax);
 
   if (l == 0) {
-    if (alive) sh_basis_dyn(K, vdir[0], vdir[1], vdir[2], s_basis[row]);
+    if (alive) ray_basis(A, K, vdir, s_basis[row]);
     else
       for (int i = 0; i < 25; ++i) s_basis[row][i] = 0.0f;
   }
@@ -2051,6 +2067,7 @@ static int render_args(const PxoTree* tree, const PxoCamera* cam, const float* o
   A.opt = *opts;
   A.B = B;
   A.has_cam = cam != nullptr;
+  A.lobes = nullptr;                            // the SG entry points set it after their own checks
   int64_t blocks;
   if (cam) {
     PXO_REQUIRE(cam->c2w && cam->width >= 1 && cam->height >= 1 && cam->fx > 0.0f && cam->fy > 0.0f, "%s: bad camera", who);
@@ -2114,14 +2131,27 @@ int pxo_octree_get_tuning(int knob, int* value) {
   }
 }
 
-int pxo_octree_render_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
-                          const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
+// SG trees: the same launches with RenderArgs::lobes set.  The format is checked before render_args so that the message
+// names SG, not SH.
+static int check_sg(const PxoTree* tree, const float* lobes, const char* who) {
+  PXO_REQUIRE(tree, "%s: null tree", who);
+  const int K = tree->basis_dim;
+  PXO_REQUIRE(K == 1 || K == 4 || K == 9 || K == 16 || K == 25, "%s: basis_dim %d is not a supported SG format (sg_dim 1,4,9,16,25)", who, K);
+  PXO_REQUIRE(tree->data_dim == 3 * K + 1, "%s: data_dim %d != 3*basis_dim+1", who, tree->data_dim);
+  PXO_REQUIRE(lobes, "%s: null lobes (an SG tree needs its [basis_dim,4] extra_data)", who);
+  return PXO_OK;
+}
+
+static int octree_render_fwd_impl(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                  const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* lobes,
+                                  float* out_rgb, void* stream, const char* who) {
   RenderArgs A;
   unsigned grid;
   int row;
-  if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, "pxo_octree_render_fwd", false, A, grid, row)) return rc;
+  if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, false, A, grid, row)) return rc;
+  A.lobes = lobes;
   if (B == 0) return PXO_OK;
-  PXO_REQUIRE(out_rgb, "pxo_octree_render_fwd: null output");
+  PXO_REQUIRE(out_rgb, "%s: null output", who);
   const float* none = nullptr;
   switch (row) {
     case 4:
@@ -2139,7 +2169,19 @@ int pxo_octree_render_fwd(const PxoTree* tree, const PxoCamera* cam, const float
     case 8: hipLaunchKernelGGL((octree_render_kernel<0, 8, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr); break;
     default: hipLaunchKernelGGL((octree_render_kernel<0, 16, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr); break;
   }
-  return check_launch("octree_render_fwd");
+  return check_launch(who);
+}
+
+int pxo_octree_render_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                          const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
+  return octree_render_fwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, nullptr, out_rgb, stream, "pxo_octree_render_fwd");
+}
+
+int pxo_octree_render_sg_fwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                             const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb,
+                             void* stream) {
+  if (int rc = check_sg(tree, lobes, "pxo_octree_render_sg_fwd")) return rc;
+  return octree_render_fwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, lobes, out_rgb, stream, "pxo_octree_render_sg_fwd");
 }
 
 // stop_thresh < surface_thresh < 1: an early stop (light <= stop_thresh) then never comes before the crossing
@@ -2182,19 +2224,21 @@ int pxo_octree_render_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const f
   return check_launch("octree_render_aux_fwd");
 }
 
-int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
-                          const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* out_rgb,
-                          const float* grad_out, float* grad_data, void* stream) {
+static int octree_render_bwd_impl(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                  const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* lobes,
+                                  const float* out_rgb, const float* grad_out, float* grad_data, void* stream,
+                                  const char* who) {
   RenderArgs A;
   unsigned grid;
   int row;
-  if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, "pxo_octree_render_bwd", true, A, grid, row)) return rc;
+  if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, true, A, grid, row)) return rc;
+  A.lobes = lobes;
   if (B == 0) return PXO_OK;
-  PXO_REQUIRE(grad_out && grad_data, "pxo_octree_render_bwd: null pointer");
+  PXO_REQUIRE(grad_out && grad_data, "%s: null pointer", who);
   // the gradient pass marches exactly (no early stop, no 1/(1-T) rescale): a forward image made with
   // stop_thresh > 0 is not the image whose gradient this is
   PXO_REQUIRE(out_rgb == nullptr || opts->stop_thresh == 0.0f,
-              "pxo_octree_render_bwd: out_rgb must come from an exact march (stop_thresh == 0), got stop_thresh %g",
+              "%s: out_rgb must come from an exact march (stop_thresh == 0), got stop_thresh %g", who,
               (double)opts->stop_thresh);
   switch (row) {
     case 4:
@@ -2227,7 +2271,22 @@ int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float
     case 8: hipLaunchKernelGGL((octree_render_kernel<1, 8>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, (float*)nullptr, out_rgb, grad_out, grad_data); break;
     default: hipLaunchKernelGGL((octree_render_kernel<1, 16>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, (float*)nullptr, out_rgb, grad_out, grad_data); break;
   }
-  return check_launch("octree_render_bwd");
+  return check_launch(who);
+}
+
+int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                          const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* out_rgb,
+                          const float* grad_out, float* grad_data, void* stream) {
+  return octree_render_bwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, nullptr, out_rgb, grad_out, grad_data, stream,
+                                "pxo_octree_render_bwd");
+}
+
+int pxo_octree_render_sg_bwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                             const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts,
+                             const float* out_rgb, const float* grad_out, float* grad_data, void* stream) {
+  if (int rc = check_sg(tree, lobes, "pxo_octree_render_sg_bwd")) return rc;
+  return octree_render_bwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, lobes, out_rgb, grad_out, grad_data, stream,
+                                "pxo_octree_render_sg_bwd");
 }
 
 // ---- compressed trees (octree/compression.py:88-139) ----

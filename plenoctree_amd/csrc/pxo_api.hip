@@ -284,7 +284,7 @@ static int prepare_draws(const PxoCfg* cfg, TrainWs& t, int64_t B, int randomize
 
 static int forward_coarse(const PxoCfg* cfg, TrainWs& t, const float* pk0, const float* o, const float* d, const float* v,
                           int64_t B, const Draws& dr, const float* pixels, float* rgb_c, float* disp_c, float* acc_c,
-                          hipStream_t s, unsigned int* tile_counter = nullptr) {
+                          hipStream_t s, unsigned int* tile_counter = nullptr, const float* lobes = nullptr) {
   const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
   PXO_TRY(launch_sample_along_rays(o, d, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, t.c.z, t.c.pts, s));
   PXO_TRY(launch_mlp_fwd(cfg, pk0, t.c.pts, t.c.M, t.c.raw_rgb, t.c.raw_sigma, t.c.acts, t.c.enc, t.c.mask, s, tile_counter));
@@ -294,12 +294,12 @@ static int forward_coarse(const PxoCfg* cfg, TrainWs& t, const float* pk0, const
                                         Nf > 0 ? t.c.weights : nullptr, t.c.ray_sse, t.c.d_raw_rgb, t.c.d_raw_sigma,
                                         Nf > 0 ? 0 : t.n_sp, t.sp_exp, s);
   return launch_shade_composite_fwd(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, d, v, B, Nc, rgb_c, disp_c, acc_c,
-                                    t.c.weights, s);
+                                    t.c.weights, s, lobes);
 }
 
 static int forward_fine(const PxoCfg* cfg, TrainWs& t, const float* pk1, const float* o, const float* d, const float* v,
                         int64_t B, const Draws& dr, const float* pixels, float* rgb_f, float* disp_f, float* acc_f,
-                        hipStream_t s, unsigned int* tile_counter = nullptr) {
+                        hipStream_t s, unsigned int* tile_counter = nullptr, const float* lobes = nullptr) {
   const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
   PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, o, d, B, Nc, Nf, dr.u, t.f.z, t.f.pts, s));
   PXO_TRY(launch_mlp_fwd(cfg, pk1, t.f.pts, t.f.M, t.f.raw_rgb, t.f.raw_sigma, t.f.acts, t.f.enc, t.f.mask, s, tile_counter));
@@ -308,7 +308,7 @@ static int forward_fine(const PxoCfg* cfg, TrainWs& t, const float* pk1, const f
     return launch_shade_composite_train(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, pixels, B, Nc + Nf, nullptr,
                                         nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp, s);
   return launch_shade_composite_fwd(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, B, Nc + Nf, rgb_f, disp_f, acc_f,
-                                    t.f.weights, s);
+                                    t.f.weights, s, lobes);
 }
 
 // diagnostic: `blocks` workgroups of `threads` threads that do nothing for `micros` microseconds of the device's
@@ -575,29 +575,50 @@ int pxo_render_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
   return PXO_OK;
 }
 
-int pxo_render_fwd(const PxoCfg* cfg, const float* packed_fwd0, const float* packed_fwd1, const float* origins,
-                   const float* directions, const float* viewdirs, int64_t B, int randomized, const float* t_rand,
-                   const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f,
-                   float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream) {
+// lobes != NULL: the NeRF-SG form (pxo_sg_render_fwd); only the shade/composite launches differ
+static int render_fwd_impl(const PxoCfg* cfg, const float* packed_fwd0, const float* packed_fwd1, const float* origins,
+                           const float* directions, const float* viewdirs, int64_t B, int randomized, const float* t_rand,
+                           const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f,
+                           float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream, const float* lobes,
+                           const char* who) {
   PXO_TRY(validate_cfg(cfg));
   if (B == 0) return PXO_OK;                   // an empty batch has no buffers to check
   PXO_REQUIRE(B >= 0 && packed_fwd0 && origins && directions && viewdirs && rgb_c && disp_c && acc_c && ws,
-              "pxo_render_fwd: bad arguments");
+              "%s: bad arguments", who);
   if (cfg->num_fine_samples > 0)
-    PXO_REQUIRE(packed_fwd1 && rgb_f && disp_f && acc_f, "pxo_render_fwd: fine outputs/weights missing");
+    PXO_REQUIRE(packed_fwd1 && rgb_f && disp_f && acc_f, "%s: fine outputs/weights missing", who);
   TrainWs t;
   carve_train(cfg, B, ws, false, t);
   if (ws_bytes < t.total) {
-    set_error("pxo_render_fwd: workspace %zu < %zu", ws_bytes, t.total);
+    set_error("%s: workspace %zu < %zu", who, ws_bytes, t.total);
     return PXO_ERR_WORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
   Draws dr;
   PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, nullptr, seed, s, dr));
-  PXO_TRY(forward_coarse(cfg, t, packed_fwd0, origins, directions, viewdirs, B, dr, nullptr, rgb_c, disp_c, acc_c, s));
+  PXO_TRY(forward_coarse(cfg, t, packed_fwd0, origins, directions, viewdirs, B, dr, nullptr, rgb_c, disp_c, acc_c, s, nullptr, lobes));
   if (cfg->num_fine_samples > 0)
-    PXO_TRY(forward_fine(cfg, t, packed_fwd1, origins, directions, viewdirs, B, dr, nullptr, rgb_f, disp_f, acc_f, s));
+    PXO_TRY(forward_fine(cfg, t, packed_fwd1, origins, directions, viewdirs, B, dr, nullptr, rgb_f, disp_f, acc_f, s, nullptr, lobes));
   return PXO_OK;
+}
+
+int pxo_render_fwd(const PxoCfg* cfg, const float* packed_fwd0, const float* packed_fwd1, const float* origins,
+                   const float* directions, const float* viewdirs, int64_t B, int randomized, const float* t_rand,
+                   const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f,
+                   float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream) {
+  return render_fwd_impl(cfg, packed_fwd0, packed_fwd1, origins, directions, viewdirs, B, randomized, t_rand, u, seed, rgb_c,
+                         disp_c, acc_c, rgb_f, disp_f, acc_f, ws, ws_bytes, stream, nullptr, "pxo_render_fwd");
+}
+
+int pxo_sg_render_fwd(const PxoCfg* cfg, const float* lobes, const float* packed_fwd0, const float* packed_fwd1,
+                      const float* origins, const float* directions, const float* viewdirs, int64_t B, int randomized,
+                      const float* t_rand, const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c,
+                      float* rgb_f, float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream) {
+  PXO_TRY(validate_cfg(cfg));
+  PXO_REQUIRE(lobes, "pxo_sg_render_fwd: null lobes ([sg_dim,4] with sg_dim = (sh_deg+1)^2 = %d)",
+              (cfg->sh_deg + 1) * (cfg->sh_deg + 1));
+  return render_fwd_impl(cfg, packed_fwd0, packed_fwd1, origins, directions, viewdirs, B, randomized, t_rand, u, seed, rgb_c,
+                         disp_c, acc_c, rgb_f, disp_f, acc_f, ws, ws_bytes, stream, lobes, "pxo_sg_render_fwd");
 }
 
 int pxo_train_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {

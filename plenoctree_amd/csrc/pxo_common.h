@@ -298,7 +298,7 @@ int launch_sample_along_rays(const float* o, const float* d, int64_t B, int S, f
 int launch_shade_composite_fwd(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma,
                                const float* z, const float* dirs, const float* viewdirs, int64_t B,
                                int S, float* comp_rgb, float* disp, float* acc, float* weights,
-                               hipStream_t s);
+                               hipStream_t s, const float* lobes = nullptr);   // lobes [K,4]: the NeRF-SG basis instead of SH
 int launch_shade_composite_bwd(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma,
                                const float* z, const float* dirs, const float* viewdirs,
                                const float* d_comp_rgb, int64_t B, int S, float* d_raw_rgb,

@@ -149,12 +149,15 @@ __device__ __forceinline__ void shade_chunk(const float* __restrict__ raw_rgb, c
   chunk_transmittance(f, lane, carry, st);
 }
 
-template <int DEG>
+// SG (NeRF-SG, nerf_sh/nerf/models.py:204-210, :273-292 with sg_dim > 0): the head has K = (DEG+1)^2 lobes and the basis is
+// eval_sg's (nerf_sh/nerf/sg.py:35-66), Y_i = exp(lambda_i (mu_i . viewdir - 1)) / K from lobes [K,4] = (lambda, mu), in
+// place of the SH basis; the sum, the sigmoid and the compositing are the same code.
+template <int DEG, bool SG = false>
 __global__ __launch_bounds__(kRayThreads) void shade_composite_fwd_kernel(
     const float* __restrict__ raw_rgb, const float* __restrict__ raw_sigma, const float* __restrict__ z_vals,
     const float* __restrict__ dirs, const float* __restrict__ viewdirs, int64_t B, int S, int white,
     float* __restrict__ comp_rgb, float* __restrict__ disp, float* __restrict__ acc_out,
-    float* __restrict__ weights) {
+    float* __restrict__ weights, const float* __restrict__ lobes) {
   constexpr int K = (DEG + 1) * (DEG + 1), C = 3 * K, CS = C | 1;
   __shared__ float lds[kRaysPerBlock][64 * CS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -162,7 +165,16 @@ __global__ __launch_bounds__(kRayThreads) void shade_composite_fwd_kernel(
   const bool ray_ok = ray < B;
   if (!ray_ok) ray = B - 1;
   float Y[K];
-  sh_basis<DEG>(viewdirs[ray * 3], viewdirs[ray * 3 + 1], viewdirs[ray * 3 + 2], Y);
+  if constexpr (SG) {
+    const float vx = viewdirs[ray * 3], vy = viewdirs[ray * 3 + 1], vz = viewdirs[ray * 3 + 2];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      const float dot = __fadd_rn(__fadd_rn(__fmul_rn(lobes[4 * i + 1], vx), __fmul_rn(lobes[4 * i + 2], vy)), __fmul_rn(lobes[4 * i + 3], vz));
+      Y[i] = __fmul_rn(expf(__fmul_rn(lobes[4 * i], __fsub_rn(dot, 1.0f))), 1.0f / (float)K);
+    }
+  } else {
+    sh_basis<DEG>(viewdirs[ray * 3], viewdirs[ray * 3 + 1], viewdirs[ray * 3 + 2], Y);
+  }
   const float dx = dirs[ray * 3], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
   const float norm_d = sqrtf(dx * dx + dy * dy + dz * dz);
   float carry = 1.f, s_r = 0.f, s_g = 0.f, s_b = 0.f, s_depth = 0.f, s_acc = 0.f;
@@ -423,12 +435,19 @@ __global__ __launch_bounds__(kRayThreads) void shade_composite_train_kernel(
 
 int launch_shade_composite_fwd(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, const float* z,
                                const float* dirs, const float* viewdirs, int64_t B, int S, float* comp_rgb,
-                               float* disp, float* acc, float* weights, hipStream_t s) {
+                               float* disp, float* acc, float* weights, hipStream_t s, const float* lobes) {
   if (B == 0) return PXO_OK;
   if (S > 64 * kMaxChunks || S < 1) { set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks); return PXO_ERR_ARG; }
   dim3 grid((unsigned)((B + kRaysPerBlock - 1) / kRaysPerBlock)), block(kRayThreads);
+  if (lobes) {       // NeRF-SG: sg_dim = (sh_deg+1)^2 lobes
+#define CALL(D) hipLaunchKernelGGL((shade_composite_fwd_kernel<D, true>), grid, block, 0, s, raw_rgb, raw_sigma, z, dirs, \
+                                   viewdirs, B, S, cfg->white_bkgd, comp_rgb, disp, acc, weights, lobes)
+    PXO_DEG_SWITCH(cfg->sh_deg, CALL)
+#undef CALL
+    return check_launch("shade_composite_fwd (SG)");
+  }
 #define CALL(D) hipLaunchKernelGGL((shade_composite_fwd_kernel<D>), grid, block, 0, s, raw_rgb, raw_sigma, z, dirs, \
-                                   viewdirs, B, S, cfg->white_bkgd, comp_rgb, disp, acc, weights)
+                                   viewdirs, B, S, cfg->white_bkgd, comp_rgb, disp, acc, weights, (const float*)nullptr)
   PXO_DEG_SWITCH(cfg->sh_deg, CALL)
 #undef CALL
   return check_launch("shade_composite_fwd");

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from .. import dist, ops
-from .nerf import models, utils, viewdirs
+from .nerf import models, sg, utils, viewdirs
 
 
 def define_flags():
@@ -40,6 +40,7 @@ def render_poses(args):
 def main(argv=None):
     args = define_flags().parse_args(argv)
     utils.update_flags(args)
+    sg.apply_cli(args, argv)                     # --sg_dim K --sh_deg -1 on the command line win over the preset's sh_deg
     if not torch.cuda.is_available():
         raise SystemExit("nerf_sh.gen_video needs a ROCm GPU; the HIP path has no CPU fallback")
     comm = dist.init_from_env()
@@ -48,6 +49,8 @@ def main(argv=None):
     say = print if comm.rank == 0 else (lambda *a, **k: None)
     if args.use_viewdirs:
         viewdirs.check_render_dirs(args, require_data=False)
+    elif args.sg_dim > 0:
+        sg.check_dirs(args, require_data=False)
     else:
         utils.check_flags(args, require_data=False, world_size=comm.world)
     say("* Generating poses", flush=True)
@@ -62,6 +65,8 @@ def main(argv=None):
     say("* Creating model", flush=True)
     if args.use_viewdirs:      # a view-dependent ("vanilla") NeRF: opts in explicitly, like octree.extraction
         model, state = viewdirs.restore_for_render(args, device, say=say, require_data=False)
+    elif args.sg_dim > 0:      # a NeRF-SG (--sg_dim K --sh_deg -1)
+        model, state = sg.restore(args, device, say=say, require_data=False)
     else:
         model, state = models.get_model_state(args, device, restore=True)
     video_dir = os.path.join(args.train_dir, "video", "e{:03}".format(int(-args.elevation * 10)))

@@ -15,6 +15,10 @@ name, C-order bytes))).  State dict of TrainState(optimizer=flax.optim.Optimizer
                            "param_states": {"params": <same tree>{"grad_ema", "grad_sq_ema"}}}}}
 Unverified against a live flax (none available); tests/test_checkpoint_cpu.py drives the
 reference's own consumer code with these files instead.
+
+A NeRF-SG (sg_dim > 0) carries two more leaves beside MLP_0 / MLP_1, `sg_lambda` [K] and `sg_mu_spher` [K,2]
+(nerf_sh/nerf/models.py:107-117; top-level keys of the torch twin's state dict, octree/nerf/models.py:104-107).  They are
+read and written for the states of nerf.sg only; any other model refuses a file that holds them, by the key's name.
 """
 import glob
 import os
@@ -101,14 +105,48 @@ def state_to_tree(state):
     mt, vt = arena_to_tree(m, state.cfg), arena_to_tree(v, state.cfg)
     pstates = {mk: {dk: {lk: {"grad_ema": mt[mk][dk][lk], "grad_sq_ema": vt[mk][dk][lk]} for lk in dv}
                     for dk, dv in mv.items()} for mk, mv in params.items()}
+    if _is_sg(state):
+        # the two model-level parameters of a NeRF-SG (nerf_sh/nerf/models.py:107-117), beside MLP_0 / MLP_1; no moments are
+        # kept for them here (nothing on this path optimises them), so their Adam slots are written as zeros
+        for k in _SG_KEYS:
+            a = getattr(state, k).detach().cpu().numpy().astype(np.float32)
+            params[k] = a
+            pstates[k] = {"grad_ema": np.zeros_like(a), "grad_sq_ema": np.zeros_like(a)}
     return {"optimizer": {"target": {"params": params},
                           "state": {"step": np.asarray(state.step, np.int32), "param_states": {"params": pstates}}}}
+
+
+_SG_KEYS = ("sg_lambda", "sg_mu_spher")
+
+
+def _is_sg(state):
+    """A state of nerf.sg (sg_dim > 0): it carries sg_lambda / sg_mu_spher and takes them through set_lobe_params."""
+    return hasattr(state, "set_lobe_params")
+
+
+def _load_sg_keys(get, has, state, where):
+    """The SG keys of a checkpoint into an SG state; a non-SG state refuses them and an SG state requires them, by name."""
+    present = [k for k in _SG_KEYS if has(k)]
+    if not _is_sg(state):
+        if present:
+            raise ValueError(f"{where}: key {present[0]!r}: a spherical-Gaussian model; this model has sg_dim <= 0 "
+                             "(pass --sg_dim K --sh_deg -1)")
+        return
+    if len(present) != len(_SG_KEYS):
+        missing = [k for k in _SG_KEYS if k not in present]
+        raise ValueError(f"{where}: no {missing[0]!r}: not a NeRF-SG checkpoint (the model has sg_dim={state.sg_dim})")
+    lam, mu = (np.asarray(get(k).detach().cpu() if torch.is_tensor(get(k)) else get(k), np.float32) for k in _SG_KEYS)
+    K = state.sg_dim
+    if lam.shape != (K,) or mu.shape != (K, 2):
+        raise ValueError(f"{where}: sg_lambda {lam.shape} / sg_mu_spher {mu.shape}, the model (sg_dim={K}) needs ({K},) / ({K}, 2)")
+    state.set_lobe_params(torch.from_numpy(lam), torch.from_numpy(mu))
 
 
 def load_tree_into_state(tree, state):
     opt = tree["optimizer"]
     params = opt["target"]["params"]
     dev = state.params.device
+    _load_sg_keys(params.__getitem__, params.__contains__, state, "flax checkpoint")
     state.params.copy_(torch.from_numpy(tree_to_arena(params, state.cfg)).to(dev))
     ps = opt.get("state", {}).get("param_states", {}).get("params")
     if ps is not None:
@@ -158,13 +196,15 @@ def restore_checkpoint(train_dir, state=None):
 
 
 # ---- the reference's OTHER checkpoint format: a torch state dict of its torch twin ------------------------------------------
-def torch_state_dict_to_tree(sd, depth=8):
+def torch_state_dict_to_tree(sd, depth=8, sg=False):
     """`ckpt["model"]` of octree/nerf/models.py:52-63 (restore_model_state: `*.ckpt` files holding the state dict of the torch
     NerfModel, whose Linear weights are [out, in]) as the flax params tree: the inverse of the key map the reference applies to
     a flax checkpoint (octree/nerf/models.py:79-102: Dense_i -> input_layers.i for i < net_depth, then sigma_layer, then --
     without view directions -- rgb_layer; kernel = weight.T)."""
     names = [f"input_layers.{i}" for i in range(depth)] + ["sigma_layer", "rgb_layer"]
     for k in sd:
+        if sg and k in _SG_KEYS:           # a NeRF-SG state (octree/nerf/models.py:104-107): read by restore_torch_checkpoint
+            continue
         if any(t in k for t in ("bottleneck_layer", "condition_layers", "sg_lambda", "sg_mu_spher")):
             raise ValueError(f"torch checkpoint key {k!r}: the view-conditioned head / SG basis is not built on the MI355X path "
                              "(use_viewdirs=false SH models only)")
@@ -180,6 +220,24 @@ def torch_state_dict_to_tree(sd, depth=8):
             mlp[f"Dense_{li}"] = {"kernel": np.ascontiguousarray(w.T.astype(np.float32)), "bias": b.astype(np.float32)}
         tree[f"MLP_{mi}"] = mlp
     return tree
+
+
+def torch_state_dict_from_state(state):
+    """The torch twin's state dict (Linear weights [out,in]; plus sg_lambda / sg_mu_spher for a NeRF-SG, octree/nerf/models.py:
+    198-210) of a TrainState: what a `*.ckpt` of the reference holds under "model"."""
+    tree = arena_to_tree(state.params.detach().cpu().numpy(), state.cfg)
+    depth = len(tree["MLP_0"]) - 2
+    names = [f"input_layers.{i}" for i in range(depth)] + ["sigma_layer", "rgb_layer"]
+    sd = {}
+    for mi in range(2):
+        for li, name in enumerate(names):
+            d = tree[f"MLP_{mi}"][f"Dense_{li}"]
+            sd[f"MLP_{mi}.{name}.weight"] = torch.from_numpy(np.ascontiguousarray(d["kernel"].T))
+            sd[f"MLP_{mi}.{name}.bias"] = torch.from_numpy(d["bias"].copy())
+    if _is_sg(state):
+        for k in _SG_KEYS:
+            sd[k] = getattr(state, k).detach().cpu().clone()
+    return sd
 
 
 def latest_torch_checkpoint(train_dir):
@@ -206,7 +264,9 @@ def restore_torch_checkpoint(train_dir, state, trust_pickle=False):
     if not isinstance(ckpt, dict) or "model" not in ckpt:
         raise ValueError(f'{path}: not a checkpoint of the reference\'s torch twin (no "model" state dict)')
     from ... import _lib
-    params = torch_state_dict_to_tree(ckpt["model"], depth=_lib.NET_DEPTH)      # the depth the kernels (and state.cfg's arena) are built for
+    params = torch_state_dict_to_tree(ckpt["model"], depth=_lib.NET_DEPTH, sg=_is_sg(state))   # the depth the kernels (and state.cfg's arena) are built for
+    if _is_sg(state):
+        _load_sg_keys(ckpt["model"].__getitem__, ckpt["model"].__contains__, state, path)
     state.params.copy_(torch.from_numpy(tree_to_arena(params, state.cfg)).to(state.params.device))
     state.m.zero_(); state.v.zero_()
     state.repack()

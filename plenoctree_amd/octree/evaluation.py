@@ -39,6 +39,20 @@ def define_flags():
     return p
 
 
+def check_sg_flags(args):
+    """An SG tree (data_format SG<K>) renders and is scored like an SH tree; its palette form and the extra outputs are not
+    built, so the flags that need them are refused by name before anything is loaded onto the GPU."""
+    with np.load(args.input) as z:
+        fmt = str(z["data_format"]) if "data_format" in z.files else ""
+    if not fmt.startswith("SG"):
+        return
+    bad = [f for f, on in (("--keep_compressed", args.keep_compressed), ("--write_aux", args.write_aux is not None),
+                           ("--write_points", args.write_points is not None)) if on]
+    if bad:
+        raise NotImplementedError(f"{args.input} is an SG tree ({fmt}): {', '.join(bad)} not built for SG trees (palette-form "
+                                  "rendering and the alpha / depth / surface outputs are SH only)")
+
+
 class _AuxSink:
     """Per-view consumer of eval_octree's aux_sink: writes the --write_aux files at once, collects the --write_points points."""
 
@@ -85,6 +99,7 @@ def main(argv=None):
     dataset = datasets.get_dataset("test", args, device)
     if comm.rank == 0:
         print("N3Tree load", args.input, flush=True)
+    check_sg_flags(args)
     tree = N3Tree.load(args.input, map_location=device, keep_quantized=args.keep_compressed)   # not compressed + flag: ValueError
     if args.keep_compressed and comm.rank == 0:
         print(f"compressed tree kept in place: {tree.nbytes / 2 ** 20:.1f} MB on the device "

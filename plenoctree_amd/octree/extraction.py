@@ -8,6 +8,8 @@
   step 2  3-D antialiasing (:355-394)      S samples per deepest-level cell -> MLP_1 -> mean -> tree data,
                                            nodes sharded over the GPUs
   finish  relu on sigma, save npz, evaluate (:503-516)
+  --sg_dim K --sh_deg -1 (a NeRF-SG, :436-442, :481-499): the same steps with the MLP head of K lobes; the tree is `SG<K>` and
+  carries the lobes (softplus(sg_lambda), spher2cart(sg_mu_spher)) as extra_data
 
     python -m plenoctree_amd.octree.extraction --train_dir D --config blender --data_dir ... --output tree.npz
     python -m torch.distributed.run --nproc-per-node 8 -m plenoctree_amd.octree.extraction ...
@@ -330,6 +332,8 @@ def main(argv=None, record_projection=False):
     """record_projection: keep the run's direction set and step-2 sample points on the returned tree (`projection_record`)."""
     args = define_flags().parse_args(argv)
     utils.update_flags(args)
+    from ..nerf_sh.nerf import sg
+    sg.apply_cli(args, argv)                 # --sg_dim K --sh_deg -1 on the command line win over the preset's sh_deg
     args._record_projection = bool(record_projection)
     if not torch.cuda.is_available():
         raise SystemExit("octree.extraction needs a ROCm GPU; the HIP path has no CPU fallback")
@@ -348,6 +352,9 @@ def main(argv=None, record_projection=False):
         say(checkpoints.restore_viewdirs_checkpoint(args.train_dir, state, bool(args.is_jaxnerf_ckpt),
                                                     bool(getattr(args, "trust_ckpt_pickle", False))), flush=True)
         dirs = viewdirs.draw_directions(args.seed, args.projection_samples, device)
+    elif args.sg_dim > 0:
+        # a NeRF-SG (:436-442, :481-499): the SH steps with the head width of sg_dim, the tree takes the lobes as extra_data
+        model, state = sg.restore(args, device, say=say, extraction=True)
     else:
         utils.check_flags(args, require_data=True, world_size=comm.world)
         say("* Loading NeRF", flush=True)
@@ -371,10 +378,15 @@ def main(argv=None, record_projection=False):
     radius = [r * args.bbox_scale for r in radius]
     if args.bbox_cube:
         radius = [max(radius)] * 3
-    data_dim = 1 + args.num_rgb_channels * (args.sh_deg + 1) ** 2
+    basis_dim = args.sg_dim if args.sg_dim > 0 else (args.sh_deg + 1) ** 2
+    data_dim = 1 + args.num_rgb_channels * basis_dim
     say("data dim is", data_dim, flush=True)
+    if args.sg_dim > 0:
+        data_format, extra_data = f"SG{args.sg_dim}", state.lobes            # :437-442
+    else:
+        data_format, extra_data = f"SH{basis_dim}", None
     tree = N3Tree(N=args.tree_branch_n, data_dim=data_dim, init_refine=0, depth_limit=args.init_grid_depth,
-                  radius=radius, center=center, data_format=f"SH{(args.sh_deg + 1) ** 2}", map_location=device)
+                  radius=radius, center=center, data_format=data_format, extra_data=extra_data, map_location=device)
     reso = 2 ** (args.init_grid_depth + 1)
     say("* Step 1: Grid eval", reso, flush=True)
     torch.cuda.synchronize(); comm.barrier(); t0 = time.time()

@@ -26,7 +26,14 @@ levels refined per call both produce the same arrays (tests/test_gpu_octree.py).
 
 Storage and node order are svox's (include/plenoctree_octree.h).  Rendering, sampling, leaf lookup, the weight mask
 and the tree build run in libplenoctree_hip.so through plenoctree_amd.octree_ops; torch holds the device arrays.  Only
-N = 2 and the SH data formats (`SH1/4/9/16/25`) are supported -- anything else raises, there is no fallback.
+N = 2 and the SH data formats (`SH1/4/9/16/25`) and the spherical-Gaussian ones (`SG1/4/9/16/25` with `extra_data`, the [K,4]
+lobes (lambda, mu) of octree/extraction.py:436-442) are supported -- anything else raises, there is no fallback.
+
+SG rule (restated from the published svox, like the rest of this file; anchored to the reference's own eval_sg by
+tests/golden/sg_reference.npz): basis_i(d) = exp(lambda_i (mu_i . d - 1)) / K, colour_c = sigmoid(sum_i data[c*K+i] basis_i).
+extra_data is a buffer, not a parameter: it is saved, loaded, cloned and moved with the tree and never optimised.  An SG tree
+renders (render_persp, forward) and back-propagates; the extra outputs (render_persp_aux) and the palette form
+(keep_quantized) are not built for it.
 """
 import re
 import types
@@ -52,20 +59,24 @@ class DataFormat:
     RGBA, SH, SG, ASG = 0, 1, 2, 3
 
     def __init__(self, txt, data_dim=None):
-        m = re.fullmatch(r"SH(\d+)", str(txt))
+        m = re.fullmatch(r"(SH|SG)(\d+)", str(txt))
         if not m:
-            raise NotImplementedError(f"data_format {txt!r}: only the spherical-harmonics formats SH1/4/9/16/25 are supported")
-        k = int(m.group(1))
+            raise NotImplementedError(f"data_format {txt!r}: only the spherical-harmonics formats SH1/4/9/16/25 and the "
+                                      "spherical-Gaussian formats SG1/4/9/16/25 are supported")
+        k = int(m.group(2))
         if k not in (1, 4, 9, 16, 25):
+            if m.group(1) == "SG":
+                raise NotImplementedError(f"data_format {txt}: SG is built for sg_dim 1, 4, 9, 16 and 25 only (the widths of the "
+                                          "MLP head and of the renderers)")
             raise ValueError(f"data_format {txt}: basis_dim must be a square <= 25")
         if data_dim is not None and data_dim != 3 * k + 1:
             raise ValueError(f"data_dim {data_dim} does not match data_format {txt} (expected {3 * k + 1})")
-        self.format = DataFormat.SH
+        self.format = DataFormat.SH if m.group(1) == "SH" else DataFormat.SG
         self.basis_dim = k
         self.data_dim = 3 * k + 1
 
     def __repr__(self):
-        return f"SH{self.basis_dim}"
+        return f"{'SG' if self.format == DataFormat.SG else 'SH'}{self.basis_dim}"
 
     __str__ = __repr__
 
@@ -163,8 +174,6 @@ class N3Tree:
             raise NotImplementedError("only octrees (tree_branch_n = 2) are supported")
         if init_refine != 0:
             raise NotImplementedError("init_refine must be 0 (octree/extraction.py:491)")
-        if extra_data is not None:
-            raise NotImplementedError("extra_data (spherical-gaussian formats) is not supported")
         if not 1 <= depth_limit <= TREE_MAX_DEPTH:
             raise ValueError(f"depth_limit must be in [1, {TREE_MAX_DEPTH}]")
         self.N = 2
@@ -172,6 +181,7 @@ class N3Tree:
         self.depth_limit = int(depth_limit)
         self.geom_resize_fact = float(geom_resize_fact)
         dev = torch.device(map_location if map_location is not None else device)
+        self.extra_data = _checked_extra_data(extra_data, self.data_format, dev)
         radius, center = _vec3(radius, "radius"), _vec3(center, "center")
         self._set_transform((np.float32(0.5) / radius).astype(np.float32),
                             (np.float32(0.5) * (np.float32(1.0) - center / radius)).astype(np.float32))
@@ -349,6 +359,14 @@ class N3Tree:
     def view(self):
         return oops.tree_view(self.child, self.data.data, self.offset, self.invradius)
 
+    def basis_kwargs(self):
+        """What selects the renderer of this tree's basis in octree_ops: the lobes of an SG tree, nothing for an SH tree."""
+        return {} if self.extra_data is None else {"lobes": self.extra_data}
+
+    def to(self, device):
+        """The tree on another device (a new object; nn.Module.to of svox's N3Tree)."""
+        return self.clone(device=device)
+
     def clone(self, device=None):
         t = object.__new__(N3Tree)
         t.__dict__.update(self.__dict__)
@@ -356,6 +374,7 @@ class N3Tree:
         t.child, t.parent_depth = (x.detach().clone().to(dev) for x in (self.child, self.parent_depth))
         t.data = torch.nn.Parameter(self.data.data.detach().clone().to(dev), requires_grad=self.data.requires_grad)
         t.invradius, t.offset = self.invradius.clone(), self.offset.clone()
+        t.extra_data = None if self.extra_data is None else self.extra_data.detach().clone().to(dev)
         t.level_nodes = list(self.level_nodes)
         t._leaves = None
         return t
@@ -375,6 +394,8 @@ class N3Tree:
             "data": self.data.data.detach().half().cpu().numpy(),       # svox stores float16
             "data_format": str(self.data_format),
         }
+        if self.extra_data is not None:
+            z["extra_data"] = self.extra_data.detach().cpu().numpy()      # the SG lobes, float32 [K,4]
         (np.savez_compressed if compress else np.savez)(path, **z)
 
     @classmethod
@@ -386,6 +407,9 @@ class N3Tree:
         if keep_quantized:
             if "quant_colors" not in z.files:
                 raise ValueError(f"{path}: keep_quantized=True needs a compressed tree (no quant_colors in the file)")
+            if "data_format" in z.files and str(z["data_format"]).startswith("SG"):
+                raise NotImplementedError(f"{path}: keep_quantized=True on an SG tree ({z['data_format']}): palette-form rendering "
+                                          "is built for SH trees only; load it without keep_quantized")
             return QuantizedN3Tree(z, dev)
         return cls._from_npz(z, dev)
 
@@ -399,12 +423,30 @@ class N3Tree:
         return t
 
 
+def _checked_extra_data(extra_data, data_format, dev):
+    """The [K,4] float32 lobes of an SG tree on `dev`, or None for an SH tree; every mismatch with the format is named."""
+    if data_format.format != DataFormat.SG:
+        if extra_data is not None:
+            raise ValueError(f"extra_data given with data_format {data_format}: only the SG formats carry extra_data")
+        return None
+    if extra_data is None:
+        raise NotImplementedError(f"data_format {data_format} without extra_data: an SG tree needs its [{data_format.basis_dim}, 4] "
+                                  "lobes (lambda, mu.x, mu.y, mu.z), octree/extraction.py:436-442")
+    e = torch.as_tensor(np.asarray(extra_data.detach().cpu() if torch.is_tensor(extra_data) else extra_data), dtype=torch.float32)
+    if tuple(e.shape) != (data_format.basis_dim, 4):
+        raise ValueError(f"extra_data has shape {tuple(e.shape)}, data_format {data_format} needs ({data_format.basis_dim}, 4)")
+    if not bool(torch.isfinite(e).all()) or not bool((e[:, 0] > 0).all()):
+        raise ValueError("extra_data: the lobes must be finite with lambda (column 0) > 0")
+    return e.contiguous().to(dev)
+
+
 def _load_geometry(t, z, dev):
     """The part of N3Tree.load that does not touch the leaf values: format, child, parent_depth, transform, levels.
     Returns the node count."""
     t.N = 2
     fmt = str(z["data_format"]) if "data_format" in z.files else "RGBA"
     t.data_format = DataFormat(fmt, int(z["data_dim"]))
+    t.extra_data = _checked_extra_data(z["extra_data"] if "extra_data" in z.files else None, t.data_format, dev)
     child = z["child"]
     if child.shape[1:] != (2, 2, 2):
         raise NotImplementedError("only octrees (N = 2) are supported")
@@ -605,7 +647,7 @@ class _RenderPersp(torch.autograd.Function):
         tree = renderer.tree
         ctx.args = (renderer, c2w, width, height, fx, fy, opts)
         out = oops.octree_render_persp(oops.tree_view(tree.child, data.detach(), tree.offset, tree.invradius), c2w, width,
-                                       height, fx, opts, fy)
+                                       height, fx, opts, fy, **tree.basis_kwargs())
         ctx.save_for_backward(out)
         return out
 
@@ -615,7 +657,8 @@ class _RenderPersp(torch.autograd.Function):
         tree = renderer.tree
         grad = torch.zeros_like(tree.data.data)
         out, = ctx.saved_tensors
-        oops.octree_render_persp_bwd(tree.view(), c2w, width, height, fx, opts, grad_out.contiguous(), grad, fy, out_rgb=out)
+        oops.octree_render_persp_bwd(tree.view(), c2w, width, height, fx, opts, grad_out.contiguous(), grad, fy, out_rgb=out,
+                                     **tree.basis_kwargs())
         return grad, None, None, None, None, None, None, None
 
 
@@ -649,18 +692,21 @@ class VolumeRenderer:
                 raise oops.PxoError("render_persp(fast=True) is not differentiable: call it under torch.no_grad(), "
                                     "or use fast=False to optimise the tree")
             return _RenderPersp.apply(data, self, c2w, width, height, fx, fy, self._opts(False))
-        return oops.octree_render_persp(self.tree.view(), c2w, width, height, fx, self._opts(fast), fy)
+        return oops.octree_render_persp(self.tree.view(), c2w, width, height, fx, self._opts(fast), fy, **self.tree.basis_kwargs())
 
     def forward(self, origins, dirs, viewdirs, fast=False):
         """Colours [B,3] of explicit world-space rays (unit `dirs`)."""
         if isinstance(self.tree, QuantizedN3Tree):
             return oops.octree_render_quant_rays(self.tree.quant_view(), origins, dirs, viewdirs, self._opts(fast))
-        return oops.octree_render_rays(self.tree.view(), origins, dirs, viewdirs, self._opts(fast))
+        return oops.octree_render_rays(self.tree.view(), origins, dirs, viewdirs, self._opts(fast), **self.tree.basis_kwargs())
 
     __call__ = forward
 
     # ---- additions (no svox counterpart): opacity, expected distance and surface distance from the same march ----
     def _aux_view(self, what):
+        if getattr(self.tree, "extra_data", None) is not None:
+            raise NotImplementedError(f"{what} on an SG tree ({self.tree.data_format}): alpha / depth / surface are built for SH "
+                                      "trees only")
         if isinstance(self.tree, QuantizedN3Tree):
             return self.tree.quant_view()
         if torch.is_grad_enabled() and self.tree.data.requires_grad:

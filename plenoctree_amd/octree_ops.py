@@ -141,6 +141,37 @@ def tree_view(child, data, offset, invradius):
     return t
 
 
+def _lobes(lobes, tree):
+    """Device pointer of an SG tree's lobes [basis_dim, 4] (float32, contiguous, on the tree's device), checked on the host."""
+    if not torch.is_tensor(lobes) or lobes.dtype != torch.float32 or tuple(lobes.shape) != (tree.basis_dim, 4) or \
+            not lobes.is_contiguous() or not lobes.is_cuda:
+        raise PxoError(f"SG lobes must be a contiguous float32 [{tree.basis_dim}, 4] tensor on the GPU")
+    return _f(lobes)
+
+
+def _render_fwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out):
+    """pxo_octree_render_fwd, or pxo_octree_render_sg_fwd when the tree's SG lobes are given."""
+    if lobes is None:
+        check(_lib.load().pxo_octree_render_fwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts), _f(out),
+                                                _stream()), "pxo_octree_render_fwd")
+    else:
+        check(_lib.load().pxo_octree_render_sg_fwd(ctypes.byref(tree), _lobes(lobes, tree), cam, origins, dirs, viewdirs, B,
+                                                   ctypes.byref(opts), _f(out), _stream()), "pxo_octree_render_sg_fwd")
+    return out
+
+
+def _render_bwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out_rgb, grad_out, grad_data):
+    """pxo_octree_render_bwd, or pxo_octree_render_sg_bwd when the tree's SG lobes are given."""
+    if lobes is None:
+        check(_lib.load().pxo_octree_render_bwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts),
+                                                _f(out_rgb), _f(grad_out), _f(grad_data), _stream()), "pxo_octree_render_bwd")
+    else:
+        check(_lib.load().pxo_octree_render_sg_bwd(ctypes.byref(tree), _lobes(lobes, tree), cam, origins, dirs, viewdirs, B,
+                                                   ctypes.byref(opts), _f(out_rgb), _f(grad_out), _f(grad_data), _stream()),
+              "pxo_octree_render_sg_bwd")
+    return grad_data
+
+
 def _camera(c2w, width, height, fx, fy):
     c2w = c2w[:3, :4].contiguous().float()
     cam = _lib.PxoCamera(_f(c2w).value, float(fx), float(fx if fy is None else fy), int(width), int(height))
@@ -166,25 +197,21 @@ def set_tuning(knob, value):
     check(_lib.load().pxo_octree_set_tuning(int(knob), int(value)), "pxo_octree_set_tuning")
 
 
-def octree_render_persp(tree, c2w, width, height, fx, opts, fy=None):
-    """[H,W,3] image of a pinhole camera (VolumeRenderer.render_persp)."""
+def octree_render_persp(tree, c2w, width, height, fx, opts, fy=None, lobes=None):
+    """[H,W,3] image of a pinhole camera (VolumeRenderer.render_persp).  lobes: the [K,4] extra_data of an SG tree (the
+    spherical-Gaussian basis instead of SH), None for an SH tree."""
     _require_gpu()
     cam, keep = _camera(c2w, width, height, fx, fy)
     out = _new(height, width, 3, device=keep.device)
-    check(_lib.load().pxo_octree_render_fwd(ctypes.byref(tree), ctypes.byref(cam), None, None, None, width * height,
-                                            ctypes.byref(opts), _f(out), _stream()), "pxo_octree_render_fwd")
-    return out
+    return _render_fwd(tree, lobes, ctypes.byref(cam), None, None, None, width * height, opts, out)
 
 
-def octree_render_persp_bwd(tree, c2w, width, height, fx, opts, grad_out, grad_data, fy=None, out_rgb=None):
+def octree_render_persp_bwd(tree, c2w, width, height, fx, opts, grad_out, grad_data, fy=None, out_rgb=None, lobes=None):
     """Accumulates d sum(image * grad_out) / d data into grad_data; `out_rgb` = the exact forward image of the same
-    camera (saves one of the two marches) or None."""
+    camera (saves one of the two marches) or None.  lobes: as in octree_render_persp."""
     _require_gpu()
     cam, keep = _camera(c2w, width, height, fx, fy)
-    check(_lib.load().pxo_octree_render_bwd(ctypes.byref(tree), ctypes.byref(cam), None, None, None, width * height,
-                                            ctypes.byref(opts), _f(out_rgb), _f(grad_out), _f(grad_data), _stream()),
-          "pxo_octree_render_bwd")
-    return grad_data
+    return _render_bwd(tree, lobes, ctypes.byref(cam), None, None, None, width * height, opts, out_rgb, grad_out, grad_data)
 
 
 def octree_count_work(tree, c2w, width, height, fx, opts, fy=None, count_leaves=True):
@@ -216,14 +243,12 @@ def grid_weight_count_work(sigma_grid, reso, c2w_all, fx, fy, width, height, opt
             "distinct_voxels": int(seen.sum(dtype=torch.int64)) if count_voxels else None}
 
 
-def octree_render_rays(tree, origins, dirs, viewdirs, opts):
-    """[B,3] colours of explicit world-space rays with unit dirs (VolumeRenderer.forward)."""
+def octree_render_rays(tree, origins, dirs, viewdirs, opts, lobes=None):
+    """[B,3] colours of explicit world-space rays with unit dirs (VolumeRenderer.forward).  lobes: as in octree_render_persp."""
     _require_gpu()
     B = origins.shape[0]
     out = _new(B, 3, device=origins.device)
-    check(_lib.load().pxo_octree_render_fwd(ctypes.byref(tree), None, _f(origins), _f(dirs), _f(viewdirs), B,
-                                            ctypes.byref(opts), _f(out), _stream()), "pxo_octree_render_fwd")
-    return out
+    return _render_fwd(tree, lobes, None, _f(origins), _f(dirs), _f(viewdirs), B, opts, out)
 
 
 # ---- compressed trees rendered in place (the palette form of octree/compression.py:88-139) ----
@@ -330,12 +355,10 @@ def octree_render_aux_rays(tree, origins, dirs, viewdirs, opts, surface_thresh=0
     return out, aux
 
 
-def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None):
+def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None, lobes=None):
     _require_gpu()
-    check(_lib.load().pxo_octree_render_bwd(ctypes.byref(tree), None, _f(origins), _f(dirs), _f(viewdirs),
-                                            origins.shape[0], ctypes.byref(opts), _f(out_rgb), _f(grad_out), _f(grad_data),
-                                            _stream()), "pxo_octree_render_bwd")
-    return grad_data
+    return _render_bwd(tree, lobes, None, _f(origins), _f(dirs), _f(viewdirs), origins.shape[0], opts, out_rgb, grad_out,
+                       grad_data)
 
 
 def image_mse(im, gt, want_grad=True):

@@ -255,9 +255,14 @@ def train_workspace_bytes(cfg, B):
 
 
 def render_fwd(cfg, packed_fwd0, packed_fwd1, origins, directions, viewdirs, randomized=False, t_rand=None, u=None,
-               seed=0, ws=None):
-    """NerfModel.__call__ forward: [(rgb,disp,acc)_coarse, (rgb,disp,acc)_fine]."""
+               seed=0, ws=None, lobes=None):
+    """NerfModel.__call__ forward: [(rgb,disp,acc)_coarse, (rgb,disp,acc)_fine].  lobes [K,4] with K = (cfg.sh_deg+1)^2: the
+    model is a NeRF-SG with sg_dim = K (pxo_sg_render_fwd) and is shaded with that basis instead of SH."""
     _require_gpu()
+    if lobes is not None:
+        K = (cfg.sh_deg + 1) ** 2
+        if lobes.dtype != torch.float32 or tuple(lobes.shape) != (K, 4) or not lobes.is_contiguous() or not lobes.is_cuda:
+            raise PxoError(f"SG lobes must be a contiguous float32 [{K}, 4] tensor on the GPU")
     lib = _lib.load()
     B = origins.shape[0]
     dev = origins.device
@@ -269,10 +274,12 @@ def render_fwd(cfg, packed_fwd0, packed_fwd1, origins, directions, viewdirs, ran
     if fine:
         outs.append((_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev)))
     f = outs[1] if fine else (None, None, None)
-    check(lib.pxo_render_fwd(ctypes.byref(cfg), _f(packed_fwd0), _f(packed_fwd1), _f(origins), _f(directions),
-                             _f(viewdirs), B, int(randomized), _f(t_rand), _f(u), seed, _f(outs[0][0]),
-                             _f(outs[0][1]), _f(outs[0][2]), _f(f[0]), _f(f[1]), _f(f[2]), _p(ws), ws.numel(),
-                             _stream()), "pxo_render_fwd")
+    tail = (_f(packed_fwd0), _f(packed_fwd1), _f(origins), _f(directions), _f(viewdirs), B, int(randomized), _f(t_rand), _f(u),
+            seed, _f(outs[0][0]), _f(outs[0][1]), _f(outs[0][2]), _f(f[0]), _f(f[1]), _f(f[2]), _p(ws), ws.numel(), _stream())
+    if lobes is None:
+        check(lib.pxo_render_fwd(ctypes.byref(cfg), *tail), "pxo_render_fwd")
+    else:
+        check(lib.pxo_sg_render_fwd(ctypes.byref(cfg), _f(lobes), *tail), "pxo_sg_render_fwd")
     return outs
 
 

@@ -108,7 +108,8 @@ def main():
     p.add_argument("--size", type=int, default=800)
     p.add_argument("--step", type=float, default=1e-4)
     p.add_argument("--cams", type=int, default=8)
-    p.add_argument("--basis", type=int, default=16, help="SH basis_dim of the tree data (16 or 25)")
+    p.add_argument("--basis", type=int, default=16, help="basis_dim of the tree data (16 or 25)")
+    p.add_argument("--format", default="SH", choices=["SH", "SG"], help="SG: the same tree as SG<basis> with fixed lobes (renderer timings only differ)")
     p.add_argument("--gw-only", action="store_true", help="stop after grid_weight_render (A/B of that kernel)")
     p.add_argument("--hard", action="store_true", help="exact zeros outside the spheres (as a trained, relu'd density has) instead of fuzzy tails")
     p.add_argument("--no-roofline", action="store_true", help="skip the counting passes")
@@ -130,7 +131,7 @@ def main():
 
 def defaults(**over):
     """The argument namespace of `measure` for callers that are not this CLI (bench.py's `octree` record)."""
-    a = argparse.Namespace(depth=8, size=800, step=1e-4, cams=8, basis=16, gw_only=False, hard=False, no_roofline=False, reps=2, tune="")
+    a = argparse.Namespace(depth=8, size=800, step=1e-4, cams=8, basis=16, gw_only=False, hard=False, no_roofline=False, reps=2, tune="", format="SH")
     for k, v in over.items():
         setattr(a, k, v)
     return a
@@ -144,7 +145,16 @@ def measure(a):
     dev = torch.device("cuda", torch.cuda.current_device())      # the caller's device (bench.py: one rank per GPU)
     depth, reso = a.depth, 2 ** (a.depth + 1)
     K = a.basis
-    tree = N3Tree(N=2, data_dim=3 * K + 1, depth_limit=depth, radius=1.5, center=[0, 0, 0], data_format=f"SH{K}", map_location=dev)
+    fmt = getattr(a, "format", "SH")
+    lobes = None
+    if fmt == "SG":
+        # K lobes on a Fibonacci sphere, sharpness 0.5 .. 8: fixed, so that runs compare
+        i = np.arange(K) + 0.5
+        th, ph = np.arccos(1.0 - 2.0 * i / K), np.pi * (1.0 + 5.0 ** 0.5) * i
+        lobes = torch.from_numpy(np.stack([np.linspace(0.5, 8.0, K), np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)],
+                                          -1).astype(np.float32))
+    tree = N3Tree(N=2, data_dim=3 * K + 1, depth_limit=depth, radius=1.5, center=[0, 0, 0], data_format=f"{fmt}{K}",
+                  extra_data=lobes, map_location=dev)
     # density of three fuzzy spheres on the grid (world coords in [-1.5, 1.5]^3)
     ax = ((torch.arange(reso, device=dev, dtype=torch.float32) + 0.5) / reso - 0.5) * 3.0
     sig = torch.zeros(reso, reso, reso, device=dev)
@@ -159,7 +169,7 @@ def measure(a):
     focal = 0.5 * W / np.tan(0.5 * 0.6911112)
     rs = np.random.RandomState(7)
     cams = torch.from_numpy(np.stack([pose_spherical(rs.uniform(0, 360), rs.uniform(-10, 60), 4.0311) for _ in range(a.cams)])).to(dev)
-    out = {"sigma_positive_fraction": out_occ, "basis_dim": K, "depth": depth, "reso": reso, "image": [H, W], "step_size": a.step, "cams": a.cams}
+    out = {"sigma_positive_fraction": out_occ, "basis_dim": K, "format": fmt, "depth": depth, "reso": reso, "image": [H, W], "step_size": a.step, "cams": a.cams}
     SCENE.clear()
     SCENE.update(basis_dim=K, reso=reso, image=[H, W], cams=a.cams, step_size=float(a.step), hard=bool(a.hard))
 
@@ -234,7 +244,8 @@ def measure(a):
     def bwd(reuse):
         for c, imc in zip(cams, ims):
             _, g = oops.image_mse(imc, gt)
-            oops.octree_render_persp_bwd(tree.view(), c, W, H, focal, r._opts(False), g, grad, out_rgb=imc if reuse else None)
+            oops.octree_render_persp_bwd(tree.view(), c, W, H, focal, r._opts(False), g, grad, out_rgb=imc if reuse else None,
+                                         **tree.basis_kwargs())
     for reuse in (False, True):
         ms = timed(lambda: bwd(reuse), reps=a.reps) / a.cams
         key = "render_bwd_reusing_fwd" if reuse else "render_bwd"
