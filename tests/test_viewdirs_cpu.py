@@ -12,7 +12,8 @@ from plenoctree_amd import _lib, build, ops
 from plenoctree_amd.nerf_sh.nerf import checkpoints, utils, viewdirs
 from plenoctree_amd.octree import extraction
 
-from _viewdirs_helpers import fixture, host_model_f64, host_project_f64, seeded_state_dict
+from _viewdirs_helpers import (EDGE_CROSS_N, EDGE_CROSS_R, EDGE_DIR_N, EDGE_DIR_R, EDGE_PER_POINT_N, EDGE_POINT_N, EDGE_POINT_R,
+                               EdgeReference, edge_check, fixture, host_model_f64, host_project_f64, seeded_state_dict)
 
 
 @pytest.fixture(scope="module")
@@ -165,3 +166,39 @@ def test_fixture_agrees_with_the_float64_restatement():
         assert 0 < float(fx[f"floor_coeffs_{d}"]) < 1e-5
     assert 0 < float(fx["floor_rgb_cross"]) < 1e-5 and 0 < float(fx["floor_sigma"]) < 1e-5
     assert os.path.getsize(os.path.join(os.path.dirname(__file__), "golden", "viewdirs_projection.npz")) < 1 << 20
+
+
+def test_reference_arithmetic_stays_inside_the_edge_bounds():
+    """The bound of tests/test_gpu_viewdirs_edges.py, 4 x floor x max(1, range of the case / range of the fixture), leaves room
+    for the reference arithmetic itself: the float32 host restatement of every (N, R, degree) case of that file stays within it
+    of the float64 one.  What is left of the factor 4 is the kernels' allowance for their different summation order."""
+    ref = EdgeReference()
+    f32 = torch.float32
+    pts = ref.inp["points"]
+    worst = {}
+
+    def projection(N, R):
+        dirs = ref.dirs(R)
+        rgb, sigma = host_model_f64(ref.sd, pts[:N], dirs, cross=True, dtype=f32)
+        assert rgb.dtype == f32 and sigma.dtype == f32
+        for deg in range(5) if R != "special" else (4,):
+            want = ref.coeffs(N, R, deg)
+            got = host_project_f64(rgb, dirs, deg, dtype=f32)
+            assert got.dtype == f32
+            edge_check(f"coeffs_{deg} N={N} R={R}", got, want, ref.bound(f"coeffs_{deg}", want), worst)
+        edge_check(f"sigma N={N} R={R}", sigma, ref.sigma[:N], ref.bound("sigma", ref.sigma[:N]), worst)
+
+    for N in EDGE_POINT_N:
+        projection(N, EDGE_POINT_R)
+    for R in EDGE_DIR_R + ("special",):
+        projection(EDGE_DIR_N, R)
+    for N in EDGE_CROSS_N:
+        for R in EDGE_CROSS_R:
+            rgb, _ = host_model_f64(ref.sd, pts[:N], ref.dirs(R), cross=True, dtype=f32)
+            want = ref.cross(N, R)
+            edge_check(f"rgb_cross N={N} R={R}", rgb, want, ref.bound("rgb_cross", want), worst)
+    for N in EDGE_PER_POINT_N:
+        rgb, _ = host_model_f64(ref.sd, pts[:N], ref.dirs(N), dtype=f32)
+        want = ref.rgb_per_point[:N]
+        edge_check(f"rgb_point N={N}", rgb, want, ref.bound("rgb_point", want), worst)
+    print("worst float32-restatement multiple of the scaled floor:", {k: round(v, 2) for k, v in sorted(worst.items())})
