@@ -288,6 +288,54 @@ int pxo_sg_render_fwd(const PxoCfg* cfg, const float* lobes, const float* packed
                       const float* t_rand, const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c,
                       float* rgb_f, float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- training a NeRF-SG (entry points added without a change of PXO_ABI_VERSION: no struct and no existing call changes) ----
+ * The raw model-level parameters of a NeRF-SG (nerf_sh/nerf/models.py:107-117) travel as one device array
+ * sg_params [3K] = sg_lambda [K] followed by sg_mu_spher [K,2] row-major (theta_0, phi_0, theta_1, ...), K = (cfg->sh_deg+1)^2.
+ *
+ * pxo_sg_lobes: sg_params -> lobes [K,4], row i = (softplus(sg_lambda_i), sin theta_i cos phi_i, sin theta_i sin phi_i,
+ * cos theta_i) (eval_sg, nerf_sh/nerf/sg.py:54-58) in float32 on the device: the softplus as max(x, 0) + log1p(exp(-|x|)),
+ * sinf / cosf.  K in [1, 25].  PXO_ERR_ARG if sg_params or lobes is NULL. */
+int pxo_sg_lobes(const float* sg_params, int K, float* lobes, void* stream);
+
+/* pxo_shade_composite_train for a NeRF-SG: the basis of a ray is basis_i = exp(lambda_i * (dot(mu_i, viewdir) - 1)) / K from
+ * lobes [K,4], evaluated as pxo_sg_render_fwd evaluates it (comp_rgb / weights agree with its composite to float32 round-off);
+ * ray_sse, d_raw_rgb, d_raw_sigma, the sparsity rows and sp_exp are those of pxo_shade_composite_train with that basis.  One
+ * more output: d_lobes [K,4] = d(pixel loss of this launch)/d(lambda_i, mu_i.x, mu_i.y, mu_i.z), i.e. with dL/dbasis_i = sum
+ * over samples and channels of dL/dpre[c,s] * raw[s, c*K+i]: dL/dlambda_i = sum_rays dL/dbasis_i basis_i (dot(mu_i, v) - 1),
+ * dL/dmu_i = sum_rays dL/dbasis_i basis_i lambda_i v.  The sum over rays is taken without atomics: every workgroup of
+ * PXO_SG_RAYS_PER_BLOCK rays writes its partial to lobe_partials, a caller-provided scratch of
+ * ((B + PXO_SG_RAYS_PER_BLOCK - 1) / PXO_SG_RAYS_PER_BLOCK) * K * 4 floats, and a second launch adds the partials in a fixed
+ * order: two identical calls give bitwise-identical d_lobes.  PXO_ERR_ARG if lobes, d_lobes or lobe_partials is NULL. */
+#define PXO_SG_RAYS_PER_BLOCK 4
+int pxo_sg_shade_composite_train(const PxoCfg* cfg, const float* lobes, const float* raw_rgb, const float* raw_sigma,
+                                 const float* z_vals, const float* directions, const float* viewdirs,
+                                 const float* pixels, int64_t B, int S, float* comp_rgb, float* weights,
+                                 float* ray_sse, float* d_raw_rgb, float* d_raw_sigma, int64_t n_sp,
+                                 float* sp_exp, float* d_lobes, float* lobe_partials, void* stream);
+
+/* pxo_train_fwd_bwd_bucketed / pxo_train_fwd_bwd for a NeRF-SG (loss_fn + value_and_grad with sg_lambda and sg_mu_spher in
+ * optimizer.target, nerf_sh/train.py:66-116).  sg_params [3K] in: the lobes are derived from it on the device at the start of
+ * the call (as pxo_sg_lobes does; no host round trip).  sg_grads [3K] out: d(total loss)/d(sg_params), coarse plus fine level,
+ * through the softplus and spher2cart, with the weight-decay term 2 weight_decay_mult p / n included; n = 2 n_mlp + 3K is the
+ * element count of weight_l2 here (train.py:101-108 counts the SG leaves), for the MLP halves of `grads` too, and stats[5] =
+ * (sum(params^2) + sum(sg_params^2)) / n.  Everything else -- params, images, draws, grads, stats[0..4], the meaning of
+ * grads0_ready, the precisions (bf16x3: PXO_ERR_UNSUPPORTED) -- is as in pxo_train_fwd_bwd_bucketed.  The workspace is
+ * pxo_train_workspace_bytes plus the lobes and the per-workgroup partials of both levels: pxo_sg_train_workspace_bytes.
+ * PXO_ERR_ARG if sg_params or sg_grads is NULL. */
+int pxo_sg_train_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes);
+int pxo_sg_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const float* sg_params, const float* packed_fwd0,
+                                  const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1,
+                                  const float* origins, const float* directions, const float* viewdirs,
+                                  const float* pixels, int64_t B, int randomized, const float* t_rand, const float* u,
+                                  const float* sp_points, uint64_t seed, float* grads, float* sg_grads, float* stats,
+                                  void* ws, size_t ws_bytes, void* grads0_ready, void* stream);
+int pxo_sg_train_fwd_bwd(const PxoCfg* cfg, const float* params, const float* sg_params, const float* packed_fwd0,
+                         const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1,
+                         const float* origins, const float* directions, const float* viewdirs, const float* pixels,
+                         int64_t B, int randomized, const float* t_rand, const float* u, const float* sp_points,
+                         uint64_t seed, float* grads, float* sg_grads, float* stats, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* loss_fn + value_and_grad of train_step (nerf_sh/train.py:66-116) on this device's shard.
  * params: the 2-MLP arena; packed_*: its images (pxo_pack_weights).  grads: 2-MLP arena,
  * overwritten with d(total loss)/d(params).  stats[6] (device) = loss, psnr, loss_c,

@@ -85,6 +85,7 @@ class PxoQuantTree(Structure):
 
 TREE_MAX_DEPTH = 10
 ABI_VERSION = 9                     # PXO_ABI_VERSION of include/plenoctree_hip.h
+SG_RAYS_PER_BLOCK = 4               # PXO_SG_RAYS_PER_BLOCK: rays per partial of pxo_sg_shade_composite_train's lobe_partials
 
 P = c_void_p
 CFG = POINTER(PxoCfg)
@@ -133,6 +134,13 @@ SIGNATURES = {
                                   P, c_size_t, P]),
     "pxo_train_fwd_bwd_bucketed": (c_int, [CFG, P, P, P, P, P, P, P, P, P, c_int64, c_int, P, P, P, c_uint64, P, P,
                                            P, c_size_t, P, P]),
+    "pxo_sg_lobes": (c_int, [P, c_int, P, P]),
+    "pxo_sg_shade_composite_train": (c_int, [CFG, P, P, P, P, P, P, P, c_int64, c_int, P, P, P, P, P, c_int64, P, P, P, P]),
+    "pxo_sg_train_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
+    "pxo_sg_train_fwd_bwd": (c_int, [CFG, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, P, P, P, c_uint64, P, P, P,
+                                     P, c_size_t, P]),
+    "pxo_sg_train_fwd_bwd_bucketed": (c_int, [CFG, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, P, P, P, c_uint64, P, P, P,
+                                              P, c_size_t, P, P]),
     "pxo_train_backward_work": (c_int, [CFG, c_int64, P, c_size_t, POINTER(c_int64), POINTER(c_int64), P]),
     "pxo_event_create": (c_int, [POINTER(c_void_p)]),
     "pxo_event_destroy": (c_int, [P]),

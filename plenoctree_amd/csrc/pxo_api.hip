@@ -241,6 +241,20 @@ static void carve_train(const PxoCfg* cfg, int64_t B, void* ws, bool train, Trai
   t.total = (c.off + 255) & ~(size_t)255;
 }
 
+// What a NeRF-SG train step keeps behind the TrainWs block (whose layout and size stay those of the SH step): the lobes
+// derived from sg_params and the per-workgroup partials of the lobe gradient of both levels
+struct SgWs { float *lobes, *part_c, *part_f; int64_t ray_blocks; size_t total; };
+static void carve_sg(const PxoCfg* cfg, int64_t B, void* ws, size_t train_total, SgWs& g) {
+  Carver c(ws);
+  c.off = train_total;
+  const int K = sh_dim(cfg->sh_deg);
+  g.ray_blocks = sg_ray_blocks(B);
+  g.lobes = c.take<float>(4 * K);
+  g.part_c = c.take<float>(g.ray_blocks * 4 * K);
+  g.part_f = c.take<float>(g.ray_blocks * 4 * K);
+  g.total = (c.off + 255) & ~(size_t)255;
+}
+
 #define PXO_TRY(expr)            \
   do {                           \
     int _rc = (expr);            \
@@ -284,11 +298,16 @@ static int prepare_draws(const PxoCfg* cfg, TrainWs& t, int64_t B, int randomize
 
 static int forward_coarse(const PxoCfg* cfg, TrainWs& t, const float* pk0, const float* o, const float* d, const float* v,
                           int64_t B, const Draws& dr, const float* pixels, float* rgb_c, float* disp_c, float* acc_c,
-                          hipStream_t s, unsigned int* tile_counter = nullptr, const float* lobes = nullptr) {
+                          hipStream_t s, unsigned int* tile_counter = nullptr, const float* lobes = nullptr,
+                          float* lobe_partials = nullptr) {
   const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
   PXO_TRY(launch_sample_along_rays(o, d, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, t.c.z, t.c.pts, s));
   PXO_TRY(launch_mlp_fwd(cfg, pk0, t.c.pts, t.c.M, t.c.raw_rgb, t.c.raw_sigma, t.c.acts, t.c.enc, t.c.mask, s, tile_counter));
   if (dr.noisy) PXO_TRY(launch_add_noise(t.c.raw_sigma, B * Nc, cfg->noise_std, nullptr, dr.seed, 3, s));   // models.py:258-264
+  if (pixels && lobes)      // NeRF-SG: the same launch with the lobe basis and the partials of the lobe gradient
+    return launch_sg_shade_composite_train(cfg, lobes, t.c.raw_rgb, t.c.raw_sigma, t.c.z, d, v, pixels, B, Nc, nullptr,
+                                           Nf > 0 ? t.c.weights : nullptr, t.c.ray_sse, t.c.d_raw_rgb, t.c.d_raw_sigma,
+                                           Nf > 0 ? 0 : t.n_sp, t.sp_exp, lobe_partials, s);
   if (pixels)
     return launch_shade_composite_train(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, d, v, pixels, B, Nc, nullptr,
                                         Nf > 0 ? t.c.weights : nullptr, t.c.ray_sse, t.c.d_raw_rgb, t.c.d_raw_sigma,
@@ -299,11 +318,16 @@ static int forward_coarse(const PxoCfg* cfg, TrainWs& t, const float* pk0, const
 
 static int forward_fine(const PxoCfg* cfg, TrainWs& t, const float* pk1, const float* o, const float* d, const float* v,
                         int64_t B, const Draws& dr, const float* pixels, float* rgb_f, float* disp_f, float* acc_f,
-                        hipStream_t s, unsigned int* tile_counter = nullptr, const float* lobes = nullptr) {
+                        hipStream_t s, unsigned int* tile_counter = nullptr, const float* lobes = nullptr,
+                        float* lobe_partials = nullptr) {
   const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
   PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, o, d, B, Nc, Nf, dr.u, t.f.z, t.f.pts, s));
   PXO_TRY(launch_mlp_fwd(cfg, pk1, t.f.pts, t.f.M, t.f.raw_rgb, t.f.raw_sigma, t.f.acts, t.f.enc, t.f.mask, s, tile_counter));
   if (dr.noisy) PXO_TRY(launch_add_noise(t.f.raw_sigma, B * (Nc + Nf), cfg->noise_std, nullptr, dr.seed, 4, s));   // :318-324
+  if (pixels && lobes)
+    return launch_sg_shade_composite_train(cfg, lobes, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, pixels, B, Nc + Nf, nullptr,
+                                           nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp,
+                                           lobe_partials, s);
   if (pixels)
     return launch_shade_composite_train(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, pixels, B, Nc + Nf, nullptr,
                                         nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp, s);
@@ -630,30 +654,39 @@ int pxo_train_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
   return PXO_OK;
 }
 
-int pxo_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const float* packed_fwd0, const float* packed_bwd0,
-                               const float* packed_fwd1, const float* packed_bwd1, const float* origins,
-                               const float* directions, const float* viewdirs, const float* pixels, int64_t B,
-                               int randomized, const float* t_rand, const float* u, const float* sp_points, uint64_t seed,
-                               float* grads, float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream) {
+// sg_params != nullptr: the NeRF-SG step (pxo_sg_train_fwd_bwd_bucketed) -- the shade launches take the lobe basis and leave the
+// partials of the lobe gradient, sg_grads is filled at the end, and weight_l2 counts the 3K SG entries; `who` names the entry
+// point in messages
+static int train_fwd_bwd_impl(const PxoCfg* cfg, const float* params, const float* packed_fwd0, const float* packed_bwd0,
+                              const float* packed_fwd1, const float* packed_bwd1, const float* origins,
+                              const float* directions, const float* viewdirs, const float* pixels, int64_t B,
+                              int randomized, const float* t_rand, const float* u, const float* sp_points, uint64_t seed,
+                              float* grads, float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream,
+                              const float* sg_params, float* sg_grads, const char* who) {
   PXO_TRY(validate_cfg(cfg));
   PXO_REQUIRE(B >= 1 && params && packed_fwd0 && packed_bwd0 && origins && directions && viewdirs && pixels && grads &&
                   stats && ws,
-              "pxo_train_fwd_bwd: bad arguments");
+              "%s: bad arguments", who);
   if (cfg->mlp_precision != PXO_MLP_F32 && cfg->mlp_precision != PXO_MLP_BF16X6) {
-    set_error("pxo_train_fwd_bwd: training runs in float32 or its float32-accurate bf16x6 emulation only (mlp_precision bf16x3 is an inference option)");
+    set_error("%s: training runs in float32 or its float32-accurate bf16x6 emulation only (mlp_precision bf16x3 is an inference option)", who);
     return PXO_ERR_UNSUPPORTED;
   }
-  if (cfg->num_fine_samples > 0) PXO_REQUIRE(packed_fwd1 && packed_bwd1, "pxo_train_fwd_bwd: MLP_1 images missing");
+  if (cfg->num_fine_samples > 0) PXO_REQUIRE(packed_fwd1 && packed_bwd1, "%s: MLP_1 images missing", who);
   hipStream_t s = (hipStream_t)stream;
   TrainWs t;
   carve_train(cfg, B, ws, true, t);
-  if (ws_bytes < t.total) {
-    set_error("pxo_train_fwd_bwd: workspace %zu < %zu", ws_bytes, t.total);
+  const bool sg = sg_params != nullptr;
+  SgWs g{nullptr, nullptr, nullptr, 0, t.total};
+  if (sg) carve_sg(cfg, B, ws, t.total, g);
+  if (ws_bytes < g.total) {
+    set_error("%s: workspace %zu < %zu", who, ws_bytes, g.total);
     return PXO_ERR_WORKSPACE;
   }
   const int deg = cfg->sh_deg;
   const int64_t n_mlp = mlp_param_count(deg);
-  const float wd_coef = 2.f * cfg->weight_decay_mult / (float)(2 * n_mlp);   // d/dp of weight_decay_mult * sum(p^2)/n (train.py:101-114)
+  const int sgK = sh_dim(deg);
+  const int64_t n_all = 2 * n_mlp + (sg ? 3 * sgK : 0);                     // the SG leaves are counted (train.py:101-108)
+  const float wd_coef = 2.f * cfg->weight_decay_mult / (float)n_all;   // d/dp of weight_decay_mult * sum(p^2)/n (train.py:101-114)
   const int Nf = cfg->num_fine_samples;
   // everything the step decides, from one snapshot of the tuning knobs, before its first launch
   const StepPlan plan = plan_step(*cfg, t.c.M, Nf > 0 ? t.f.M : 0, num_cus(), tuning_snapshot());
@@ -671,11 +704,12 @@ int pxo_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const flo
   Draws dr;
   PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, sp_points, seed, s, dr, params, 2 * n_mlp, sumsq_partial, step_words,
                         kStepWords, kStepRecord | (plan.skip ? 1u : 0u)));
+  if (sg) PXO_TRY(launch_sg_lobes(sg_params, sgK, g.lobes, s));
   // coarse level: forward, losses (train.py:77-98), reverse of the compositing, reverse through MLP_0.  Nothing of the fine
   // level feeds MLP_0's gradient (the fine sample positions carry no gradient, model_utils.py:286), so it is complete here
   // -- a quarter into the step -- and its all-reduce can ride under the fine level.
   PXO_TRY(forward_coarse(cfg, t, packed_fwd0, origins, directions, viewdirs, B, dr, pixels, nullptr, nullptr, nullptr, s,
-                         cnt_fwd_c));
+                         cnt_fwd_c, g.lobes, g.part_c));
   // skip_zero_rows: rows with an exactly zero upstream gradient are left out of the reverse pass (bit-identical gradients)
   uint8_t* const live_c = plan.skip ? t.c.live : nullptr;
   uint8_t* const live_f = plan.skip ? t.f.live : nullptr;
@@ -690,16 +724,16 @@ int pxo_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const flo
                                  plan.bias_from_wgrad));
   if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads, params, n_mlp, wd_coef, fk.sc));
   if (grads0_ready && hipEventRecord((hipEvent_t)grads0_ready, fk.sc) != hipSuccess) {
-    set_error("pxo_train_fwd_bwd: hipEventRecord(grads0_ready) failed");
+    set_error("%s: hipEventRecord(grads0_ready) failed", who);
     return PXO_ERR_HIP;
   }
   if (Nf > 0) {
     PXO_TRY(forward_fine(cfg, t, packed_fwd1, origins, directions, viewdirs, B, dr, pixels, nullptr, nullptr, nullptr, s,
-                         cnt_fwd_f));
+                         cnt_fwd_f, g.lobes, g.part_f));
     PXO_TRY(launch_mlp_bwd_data(cfg, packed_bwd1, t.f.d_raw_rgb, t.f.d_raw_sigma, t.f.mask, t.f.M, t.f.dz, t.f.dbias, live_f,
                                 cnt_bwd_f, s, plan.bias_from_wgrad));
     if (!fk.join()) {                                         // the slabs are the coarse pass's until here
-      set_error("pxo_train_fwd_bwd: join of the side stream failed");
+      set_error("%s: join of the side stream failed", who);
       return PXO_ERR_HIP;
     }
     PXO_TRY(launch_mlp_bwd_weights(cfg, t.f.acts, t.f.enc, t.f.dz, t.f.d_raw_rgb, t.f.d_raw_sigma, t.f.dbias, t.f.M,
@@ -709,9 +743,87 @@ int pxo_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const flo
     PXO_TRY(launch_fill(grads + n_mlp, n_mlp, 0.f, s));
   }
   if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads + n_mlp, params + n_mlp, n_mlp, wd_coef, s));
+  // the lobe gradient: both levels' partials in a fixed order, back through softplus / spher2cart, plus its weight-decay term;
+  // the same launch adds sum(sg_params^2) to the first parameter-norm partial
+  if (sg)
+    PXO_TRY(launch_sg_lobe_grad(g.part_c, g.ray_blocks, Nf > 0 ? g.part_f : nullptr, g.ray_blocks, sgK, sg_params, wd_coef,
+                                nullptr, sg_grads, sumsq_partial, s));
   PXO_TRY(launch_finalize_stats(Nf > 0 ? t.f.ray_sse : nullptr, t.c.ray_sse, t.n_sp > 0 ? t.sp_exp : nullptr, sumsq_partial,
-                                B, t.n_sp, cfg->sparsity_weight, 2 * n_mlp, stats, s));
+                                B, t.n_sp, cfg->sparsity_weight, n_all, stats, s));
   return PXO_OK;
+}
+
+int pxo_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const float* packed_fwd0, const float* packed_bwd0,
+                               const float* packed_fwd1, const float* packed_bwd1, const float* origins,
+                               const float* directions, const float* viewdirs, const float* pixels, int64_t B,
+                               int randomized, const float* t_rand, const float* u, const float* sp_points, uint64_t seed,
+                               float* grads, float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream) {
+  return train_fwd_bwd_impl(cfg, params, packed_fwd0, packed_bwd0, packed_fwd1, packed_bwd1, origins, directions, viewdirs,
+                            pixels, B, randomized, t_rand, u, sp_points, seed, grads, stats, ws, ws_bytes, grads0_ready, stream,
+                            nullptr, nullptr, "pxo_train_fwd_bwd");
+}
+
+int pxo_sg_lobes(const float* sg_params, int K, float* lobes, void* stream) {
+  PXO_REQUIRE(sg_params != nullptr, "pxo_sg_lobes: null sg_params ([3K]: sg_lambda [K], then sg_mu_spher [K,2])");
+  PXO_REQUIRE(lobes != nullptr, "pxo_sg_lobes: null lobes ([K,4])");
+  PXO_REQUIRE(K >= 1 && K <= 25, "pxo_sg_lobes: K %d not in [1,25]", K);
+  return launch_sg_lobes(sg_params, K, lobes, (hipStream_t)stream);
+}
+
+int pxo_sg_shade_composite_train(const PxoCfg* cfg, const float* lobes, const float* raw_rgb, const float* raw_sigma,
+                                 const float* z_vals, const float* directions, const float* viewdirs, const float* pixels,
+                                 int64_t B, int S, float* comp_rgb, float* weights, float* ray_sse, float* d_raw_rgb,
+                                 float* d_raw_sigma, int64_t n_sp, float* sp_exp, float* d_lobes, float* lobe_partials,
+                                 void* stream) {
+  PXO_TRY(validate_cfg(cfg));
+  const int K = sh_dim(cfg->sh_deg);
+  PXO_REQUIRE(lobes != nullptr, "pxo_sg_shade_composite_train: null lobes ([sg_dim,4] with sg_dim = (sh_deg+1)^2 = %d)", K);
+  PXO_REQUIRE(d_lobes != nullptr && lobe_partials != nullptr,
+              "pxo_sg_shade_composite_train: null d_lobes ([%d,4]) or lobe_partials (%d floats per %d rays)", K, 4 * K,
+              PXO_SG_RAYS_PER_BLOCK);
+  PXO_REQUIRE(B >= 0 && n_sp >= 0, "pxo_sg_shade_composite_train: bad sizes B=%lld n_sp=%lld", (long long)B, (long long)n_sp);
+  hipStream_t s = (hipStream_t)stream;
+  if (B == 0) return launch_fill(d_lobes, 4 * K, 0.f, s);
+  PXO_REQUIRE(raw_rgb && raw_sigma && z_vals && directions && viewdirs && pixels && ray_sse && d_raw_rgb && d_raw_sigma &&
+                  (n_sp == 0 || sp_exp),
+              "pxo_sg_shade_composite_train: bad arguments");
+  PXO_TRY(launch_sg_shade_composite_train(cfg, lobes, raw_rgb, raw_sigma, z_vals, directions, viewdirs, pixels, B, S, comp_rgb,
+                                          weights, ray_sse, d_raw_rgb, d_raw_sigma, n_sp, sp_exp, lobe_partials, s));
+  return launch_sg_lobe_grad(lobe_partials, sg_ray_blocks(B), nullptr, 0, K, nullptr, 0.f, d_lobes, nullptr, nullptr, s);
+}
+
+int pxo_sg_train_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
+  PXO_TRY(validate_cfg(cfg));
+  PXO_REQUIRE(bytes && B >= 1, "pxo_sg_train_workspace_bytes: bad arguments");
+  TrainWs t;
+  carve_train(cfg, B, nullptr, true, t);
+  SgWs g;
+  carve_sg(cfg, B, nullptr, t.total, g);
+  *bytes = g.total;
+  return PXO_OK;
+}
+
+int pxo_sg_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const float* sg_params, const float* packed_fwd0,
+                                  const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1,
+                                  const float* origins, const float* directions, const float* viewdirs, const float* pixels,
+                                  int64_t B, int randomized, const float* t_rand, const float* u, const float* sp_points,
+                                  uint64_t seed, float* grads, float* sg_grads, float* stats, void* ws, size_t ws_bytes,
+                                  void* grads0_ready, void* stream) {
+  PXO_REQUIRE(sg_params != nullptr, "pxo_sg_train_fwd_bwd: null sg_params ([3K]: sg_lambda [K], then sg_mu_spher [K,2])");
+  PXO_REQUIRE(sg_grads != nullptr, "pxo_sg_train_fwd_bwd: null sg_grads ([3K])");
+  return train_fwd_bwd_impl(cfg, params, packed_fwd0, packed_bwd0, packed_fwd1, packed_bwd1, origins, directions, viewdirs,
+                            pixels, B, randomized, t_rand, u, sp_points, seed, grads, stats, ws, ws_bytes, grads0_ready, stream,
+                            sg_params, sg_grads, "pxo_sg_train_fwd_bwd");
+}
+
+int pxo_sg_train_fwd_bwd(const PxoCfg* cfg, const float* params, const float* sg_params, const float* packed_fwd0,
+                         const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1, const float* origins,
+                         const float* directions, const float* viewdirs, const float* pixels, int64_t B, int randomized,
+                         const float* t_rand, const float* u, const float* sp_points, uint64_t seed, float* grads,
+                         float* sg_grads, float* stats, void* ws, size_t ws_bytes, void* stream) {
+  return pxo_sg_train_fwd_bwd_bucketed(cfg, params, sg_params, packed_fwd0, packed_bwd0, packed_fwd1, packed_bwd1, origins,
+                                       directions, viewdirs, pixels, B, randomized, t_rand, u, sp_points, seed, grads, sg_grads,
+                                       stats, ws, ws_bytes, nullptr, stream);
 }
 
 int pxo_train_fwd_bwd(const PxoCfg* cfg, const float* params, const float* packed_fwd0, const float* packed_bwd0,

@@ -328,6 +328,18 @@ int launch_shade_composite_train(const PxoCfg* cfg, const float* raw_rgb, const 
                                  const float* dirs, const float* viewdirs, const float* pixels, int64_t B, int S,
                                  float* comp_rgb, float* weights, float* ray_sse, float* d_raw_rgb, float* d_raw_sigma,
                                  int64_t n_sp, float* sp_exp, hipStream_t s);
+// NeRF-SG training form of the same launch (render_kernels.hip sg_shade_composite_train_kernel): the basis from lobes [K,4], and
+// the per-workgroup partials of the lobe gradient in lobe_partials [sg_ray_blocks(B)][K][4]
+__host__ __device__ inline int64_t sg_ray_blocks(int64_t B) { return (B + PXO_SG_RAYS_PER_BLOCK - 1) / PXO_SG_RAYS_PER_BLOCK; }
+int launch_sg_shade_composite_train(const PxoCfg* cfg, const float* lobes, const float* raw_rgb, const float* raw_sigma,
+                                    const float* z, const float* dirs, const float* viewdirs, const float* pixels, int64_t B,
+                                    int S, float* comp_rgb, float* weights, float* ray_sse, float* d_raw_rgb,
+                                    float* d_raw_sigma, int64_t n_sp, float* sp_exp, float* lobe_partials, hipStream_t s);
+// sg_params [3K] -> lobes [K,4], and the fixed-order second stage of the lobe gradient (partials of up to two passes; see the
+// kernels' comments for d_lobes / sg_grads / sumsq_slot, each of which may be NULL)
+int launch_sg_lobes(const float* sg_params, int K, float* lobes, hipStream_t s);
+int launch_sg_lobe_grad(const float* part_a, int64_t nb_a, const float* part_b, int64_t nb_b, int K, const float* sg_params,
+                        float wd_coef, float* d_lobes, float* sg_grads, float* sumsq_slot, hipStream_t s);
 // up to 3 uniform draws (Philox streams of one seed) in one launch
 struct UniformJob { uint64_t stream_id; int64_t n; float lo, hi; float* out; };
 // sq_x != NULL: the same launch also writes the kSumsqBlocks fixed-order partial sums of squares of sq_x[0 .. sq_n) (the

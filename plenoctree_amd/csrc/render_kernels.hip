@@ -424,6 +424,223 @@ __global__ __launch_bounds__(kRayThreads) void shade_composite_train_kernel(
   }
 }
 
+// NeRF-SG training form (nerf_sh/nerf/models.py:273-292, :331-348 with sg_dim > 0, differentiated by train.py:116): the kernel
+// above with the basis of the forward SG kernel (the same expression, so the forward values agree to float32 round-off), plus
+// the gradient with respect to the lobes.  dL/dY_k = sum_s sum_c dp[c,s] raw[s, c K + k] with dp[c,s] = g_c w_s rgb_cs (1 -
+// rgb_cs); g_c is known only after the forward sweep, by when the reverse loop has reused the LDS tile, so the per-lane sums
+// A[c K + k] = sum_s w_s rgb_cs (1 - rgb_cs) raw[s, c K + k] are taken during the forward sweep, while a chunk's coefficients
+// still sit in LDS, and scaled by g_c afterwards (3K registers per lane; the LDS tile, not the registers, bounds the occupancy).
+// Then dL/dlambda_k = dL/dY_k Y_k (mu_k . v - 1) and dL/dmu_k = dL/dY_k Y_k lambda_k v per ray; the four rays of a workgroup
+// are added in a fixed order and written to lobe_partials [ray block][K][4] (sg_lobe_grad_kernel adds the blocks: no atomics).
+static_assert(kRaysPerBlock == PXO_SG_RAYS_PER_BLOCK, "lobe_partials is sized by PXO_SG_RAYS_PER_BLOCK");
+template <int K>
+__device__ __forceinline__ void sg_basis(const float* __restrict__ lobes, float vx, float vy, float vz, float (&Y)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(lobes[4 * i + 1], vx), __fmul_rn(lobes[4 * i + 2], vy)), __fmul_rn(lobes[4 * i + 3], vz));
+    Y[i] = __fmul_rn(expf(__fmul_rn(lobes[4 * i], __fsub_rn(dot, 1.0f))), 1.0f / (float)K);
+  }
+}
+
+template <int DEG>
+__global__ __launch_bounds__(kRayThreads) void sg_shade_composite_train_kernel(
+    const float* __restrict__ raw_rgb, const float* __restrict__ raw_sigma, const float* __restrict__ z_vals,
+    const float* __restrict__ dirs, const float* __restrict__ viewdirs, const float* __restrict__ pixels, int64_t B,
+    int S, int white, float* __restrict__ comp_rgb, float* __restrict__ weights, float* __restrict__ ray_sse,
+    float* __restrict__ d_raw_rgb, float* __restrict__ d_raw_sigma, int64_t n_sp, float sp_weight, float sp_length,
+    float* __restrict__ sp_exp, const float* __restrict__ lobes, float* __restrict__ lobe_partials) {
+  constexpr int K = (DEG + 1) * (DEG + 1), C = 3 * K, CS = C | 1;
+  __shared__ float lds[kRaysPerBlock][64 * CS];
+  const int64_t ray_blocks = (B + kRaysPerBlock - 1) / kRaysPerBlock;
+  if ((int64_t)blockIdx.x >= ray_blocks) {       // sparsity rows [B*S, B*S + n_sp)
+    const int64_t r0 = ((int64_t)blockIdx.x - ray_blocks) * kRayThreads;
+    const int64_t row = r0 + threadIdx.x;
+    const int64_t base = B * S;
+    if (row < n_sp) {
+      const float raw = raw_sigma[base + row];
+      const float e = expf(-sp_length * fmaxf(raw, 0.f));
+      sp_exp[row] = e;
+      d_raw_sigma[base + row] = raw > 0.f ? (sp_weight * sp_length / (float)n_sp) * e : 0.f;
+    }
+    const int64_t nrow = n_sp - r0 < kRayThreads ? n_sp - r0 : kRayThreads;
+    float* __restrict__ z0 = d_raw_rgb + (base + r0) * C;
+    for (int64_t i = threadIdx.x; i < nrow * C; i += kRayThreads) z0[i] = 0.f;
+    return;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t ray = blockIdx.x * (int64_t)kRaysPerBlock + wave;
+  const bool ray_ok = ray < B;
+  if (!ray_ok) ray = B - 1;
+  const float vx = viewdirs[ray * 3], vy = viewdirs[ray * 3 + 1], vz = viewdirs[ray * 3 + 2];
+  float Y[K];
+  sg_basis<K>(lobes, vx, vy, vz, Y);
+  const float dx = dirs[ray * 3], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
+  const float norm_d = sqrtf(dx * dx + dy * dy + dz * dz);
+  const float bgc = white ? 1.f : 0.f;
+  const int nch = (S + 63) / 64;
+  SampleState st[kMaxChunks];
+  float A[C];
+#pragma unroll
+  for (int j = 0; j < C; ++j) A[j] = 0.f;
+  float carry = 1.f, s_r = 0.f, s_g = 0.f, s_b = 0.f, s_acc = 0.f;
+#pragma unroll
+  for (int ch = 0; ch < kMaxChunks; ++ch)
+    if (ch < nch) {
+      shade_chunk<DEG>(raw_rgb, raw_sigma, z_vals, lds[wave], Y, ray, S, ch, lane, norm_d, carry, st[ch]);
+      const float w = (1.f - st[ch].e) * st[ch].T;
+      s_r += w * st[ch].rgb[0]; s_g += w * st[ch].rgb[1]; s_b += w * st[ch].rgb[2]; s_acc += w;
+      if (weights && ray_ok && ch * 64 + lane < S) weights[ray * S + ch * 64 + lane] = w;
+      if (ch * 64 + lane < S) {                  // the chunk's coefficients are still in the tile (rows past S hold stale data)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float q = w * st[ch].rgb[c] * (1.f - st[ch].rgb[c]);
+#pragma unroll
+          for (int k = 0; k < K; ++k) A[c * K + k] += q * lds[wave][lane * CS + c * K + k];
+        }
+      }
+    }
+  s_r = wave_sum(s_r); s_g = wave_sum(s_g); s_b = wave_sum(s_b); s_acc = wave_sum(s_acc);
+  const float bg = white ? 1.f - s_acc : 0.f;
+  const float c0 = s_r + bg, c1 = s_g + bg, c2 = s_b + bg;
+  const float e0 = c0 - pixels[ray * 3], e1 = c1 - pixels[ray * 3 + 1], e2 = c2 - pixels[ray * 3 + 2];
+  const float scale = 2.f / (float)(B * 3);
+  const float g0 = e0 * scale, g1 = e1 * scale, g2 = e2 * scale;
+  if (ray_ok && lane == 0) {
+    ray_sse[ray] = (e0 * e0 + e1 * e1) + e2 * e2;
+    if (comp_rgb) { comp_rgb[ray * 3] = c0; comp_rgb[ray * 3 + 1] = c1; comp_rgb[ray * 3 + 2] = c2; }
+  }
+  // dL/dY_k of this ray, left in lane k
+  float dY = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float t = wave_sum((g0 * A[k] + g1 * A[K + k]) + g2 * A[2 * K + k]);
+    if (lane == k) dY = t;
+  }
+  float suffix = 0.f;  // sum over later samples of dL/dw_j * w_j
+#pragma unroll
+  for (int ch = kMaxChunks - 1; ch >= 0; --ch) {
+    if (ch >= nch) continue;
+    const SampleState& q = st[ch];
+    const bool valid = ch * 64 + lane < S;
+    const float alpha = 1.f - q.e;
+    const float w = alpha * q.T;
+    const float dw = g0 * (q.rgb[0] - bgc) + g1 * (q.rgb[1] - bgc) + g2 * (q.rgb[2] - bgc);
+    const float G = valid ? dw * w : 0.f;
+    const float incl = wave_rscan_add(G, lane);
+    float excl = __shfl_down(incl, 1);
+    if (lane == 63) excl = 0.f;
+    const float R = suffix + excl;
+    suffix += __shfl(incl, 0);
+    const float fct = (1.f - alpha) + 1e-10f;
+    const float dalpha = dw * q.T - R / fct;
+    const float dsigma = dalpha * q.dist * q.e;
+    const int64_t base = ray * S + ch * 64;
+    if (ray_ok && valid) d_raw_sigma[base + lane] = q.raw_sigma > 0.f ? dsigma : 0.f;
+    __syncthreads();
+    if (valid) {
+      const float dp[3] = {g0 * w * q.rgb[0] * (1.f - q.rgb[0]), g1 * w * q.rgb[1] * (1.f - q.rgb[1]),
+                           g2 * w * q.rgb[2] * (1.f - q.rgb[2])};
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < K; ++k) lds[wave][lane * CS + c * K + k] = dp[c] * Y[k];
+    }
+    __syncthreads();
+    const int nvalid = S - ch * 64 < 64 ? S - ch * 64 : 64;
+    if (ray_ok)
+      for (int idx = lane; idx < nvalid * C; idx += 64) {
+        const int s = idx / C, j = idx - s * C;
+        d_raw_rgb[base * C + idx] = lds[wave][s * CS + j];
+      }
+  }
+  // the ray's gradient with respect to (lambda_k, mu_k) from lane k, then the workgroup's rays in wave order
+  __syncthreads();
+  if (lane < K) {
+    const float lam = lobes[4 * lane];
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(lobes[4 * lane + 1], vx), __fmul_rn(lobes[4 * lane + 2], vy)), __fmul_rn(lobes[4 * lane + 3], vz));
+    const float Yk = __fmul_rn(expf(__fmul_rn(lam, __fsub_rn(dot, 1.0f))), 1.0f / (float)K);
+    const float t = ray_ok ? dY * Yk : 0.f;
+    const float tl = t * lam;
+    lds[wave][4 * lane + 0] = t * (dot - 1.f);
+    lds[wave][4 * lane + 1] = tl * vx;
+    lds[wave][4 * lane + 2] = tl * vy;
+    lds[wave][4 * lane + 3] = tl * vz;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 4 * K) {
+    float sum = lds[0][threadIdx.x];
+#pragma unroll
+    for (int wv = 1; wv < kRaysPerBlock; ++wv) sum += lds[wv][threadIdx.x];
+    lobe_partials[(int64_t)blockIdx.x * (4 * K) + threadIdx.x] = sum;
+  }
+}
+
+// Second stage of the lobe gradient: workgroup k adds lobe k's rows of the per-block partials of up to two passes (coarse, then
+// fine) in a fixed order -- 64 strided slices per component, then a tree -- into d(loss)/d(lambda_k, mu_k); d_lobes [K,4]
+// receives them when not NULL.  With sg_params [3K] = (sg_lambda [K], sg_mu_spher [K,2]) the map of sg_lobes_kernel is reversed
+// as well: sg_grads[k] = dlambda sigmoid(sg_lambda_k), sg_grads[K + 2k .. +1] = dmu . d spher2cart / d(theta, phi), each plus
+// wd_coef times its parameter (the weight-decay term); workgroup 0 also adds sum(sg_params^2) to *sumsq_slot (weight_l2).
+__global__ __launch_bounds__(256) void sg_lobe_grad_kernel(const float* __restrict__ part_a, int64_t nb_a,
+                                                           const float* __restrict__ part_b, int64_t nb_b, int K,
+                                                           const float* __restrict__ sg_params, float wd_coef,
+                                                           float* __restrict__ d_lobes, float* __restrict__ sg_grads,
+                                                           float* __restrict__ sumsq_slot) {
+  __shared__ float red[256];
+  const int k = blockIdx.x, comp = threadIdx.x & 3;
+  float acc = 0.f;
+  for (int64_t b = threadIdx.x >> 2; b < nb_a; b += 64) acc += part_a[(b * K + k) * 4 + comp];
+  if (part_b)
+    for (int64_t b = threadIdx.x >> 2; b < nb_b; b += 64) acc += part_b[(b * K + k) * 4 + comp];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int st = 128; st >= 4; st >>= 1) {
+    if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const float dl = red[0], dmx = red[1], dmy = red[2], dmz = red[3];
+  if (d_lobes) { d_lobes[4 * k] = dl; d_lobes[4 * k + 1] = dmx; d_lobes[4 * k + 2] = dmy; d_lobes[4 * k + 3] = dmz; }
+  if (sg_params && sg_grads) {
+    const float x = sg_params[k], theta = sg_params[K + 2 * k], phi = sg_params[K + 2 * k + 1];
+    const float ex = expf(-fabsf(x));
+    const float sig = x >= 0.f ? 1.f / (1.f + ex) : ex / (1.f + ex);       // d softplus
+    const float st = sinf(theta), ct = cosf(theta), sp = sinf(phi), cp = cosf(phi);
+    sg_grads[k] = dl * sig + wd_coef * x;
+    sg_grads[K + 2 * k] = ((dmx * ct * cp + dmy * ct * sp) - dmz * st) + wd_coef * theta;
+    sg_grads[K + 2 * k + 1] = (dmy * st * cp - dmx * st * sp) + wd_coef * phi;
+    if (k == 0 && sumsq_slot) {
+      float sq = 0.f;
+      for (int i = 0; i < 3 * K; ++i) sq += sg_params[i] * sg_params[i];
+      *sumsq_slot += sq;
+    }
+  }
+}
+
+// sg_params [3K] = (sg_lambda [K], sg_mu_spher [K,2] row-major) -> lobes [K,4] = (softplus(sg_lambda), spher2cart(theta, phi))
+// (nerf_sh/nerf/sg.py:54-58): the softplus in its overflow-free form, float32 sinf / cosf
+__global__ void sg_lobes_kernel(const float* __restrict__ sg_params, int K, float* __restrict__ lobes) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  const float x = sg_params[k], theta = sg_params[K + 2 * k], phi = sg_params[K + 2 * k + 1];
+  const float st = sinf(theta);
+  lobes[4 * k] = fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
+  lobes[4 * k + 1] = st * cosf(phi);
+  lobes[4 * k + 2] = st * sinf(phi);
+  lobes[4 * k + 3] = cosf(theta);
+}
+
+int launch_sg_lobes(const float* sg_params, int K, float* lobes, hipStream_t s) {
+  hipLaunchKernelGGL(sg_lobes_kernel, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, s, sg_params, K, lobes);
+  return check_launch("sg_lobes");
+}
+
+int launch_sg_lobe_grad(const float* part_a, int64_t nb_a, const float* part_b, int64_t nb_b, int K, const float* sg_params,
+                        float wd_coef, float* d_lobes, float* sg_grads, float* sumsq_slot, hipStream_t s) {
+  hipLaunchKernelGGL(sg_lobe_grad_kernel, dim3((unsigned)K), dim3(256), 0, s, part_a, nb_a, part_b, nb_b, K, sg_params, wd_coef,
+                     d_lobes, sg_grads, sumsq_slot);
+  return check_launch("sg_lobe_grad");
+}
+
 #define PXO_DEG_SWITCH(deg, CALL) \
   switch (deg) {                  \
     case 0: CALL(0); break;       \
@@ -480,6 +697,22 @@ int launch_shade_composite_train(const PxoCfg* cfg, const float* raw_rgb, const 
   PXO_DEG_SWITCH(cfg->sh_deg, CALL)
 #undef CALL
   return check_launch("shade_composite_train");
+}
+
+int launch_sg_shade_composite_train(const PxoCfg* cfg, const float* lobes, const float* raw_rgb, const float* raw_sigma,
+                                    const float* z, const float* dirs, const float* viewdirs, const float* pixels, int64_t B,
+                                    int S, float* comp_rgb, float* weights, float* ray_sse, float* d_raw_rgb,
+                                    float* d_raw_sigma, int64_t n_sp, float* sp_exp, float* lobe_partials, hipStream_t s) {
+  if (B == 0) return PXO_OK;
+  if (S > 64 * kMaxChunks || S < 1) { set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks); return PXO_ERR_ARG; }
+  const int64_t blocks = sg_ray_blocks(B) + (n_sp + kRayThreads - 1) / kRayThreads;
+  dim3 grid((unsigned)blocks), block(kRayThreads);
+#define CALL(D) hipLaunchKernelGGL((sg_shade_composite_train_kernel<D>), grid, block, 0, s, raw_rgb, raw_sigma, z, dirs, \
+                                   viewdirs, pixels, B, S, cfg->white_bkgd, comp_rgb, weights, ray_sse, d_raw_rgb,          \
+                                   d_raw_sigma, n_sp, cfg->sparsity_weight, cfg->sparsity_length, sp_exp, lobes, lobe_partials)
+  PXO_DEG_SWITCH(cfg->sh_deg, CALL)
+#undef CALL
+  return check_launch("shade_composite_train (SG)");
 }
 
 // ------------------------------------------------------------------------------------------

@@ -18,7 +18,10 @@ reference's own consumer code with these files instead.
 
 A NeRF-SG (sg_dim > 0) carries two more leaves beside MLP_0 / MLP_1, `sg_lambda` [K] and `sg_mu_spher` [K,2]
 (nerf_sh/nerf/models.py:107-117; top-level keys of the torch twin's state dict, octree/nerf/models.py:104-107).  They are
-read and written for the states of nerf.sg only; any other model refuses a file that holds them, by the key's name.
+read and written for the states of nerf.sg only; any other model refuses a file that holds them, by the key's name.  In the
+flax format their Adam moments travel like the MLPs': param_states/params/sg_lambda|sg_mu_spher/{grad_ema, grad_sq_ema}, the
+shape of the leaf (nerf_sh.train optimises them, so a resumed NeRF-SG run continues its trajectory); a file without them --
+one written before NeRF-SG training existed, or a foreign one -- loads with zero moments, and a torch state dict carries none.
 """
 import glob
 import os
@@ -106,12 +109,14 @@ def state_to_tree(state):
     pstates = {mk: {dk: {lk: {"grad_ema": mt[mk][dk][lk], "grad_sq_ema": vt[mk][dk][lk]} for lk in dv}
                     for dk, dv in mv.items()} for mk, mv in params.items()}
     if _is_sg(state):
-        # the two model-level parameters of a NeRF-SG (nerf_sh/nerf/models.py:107-117), beside MLP_0 / MLP_1; no moments are
-        # kept for them here (nothing on this path optimises them), so their Adam slots are written as zeros
-        for k in _SG_KEYS:
+        # the two model-level parameters of a NeRF-SG (nerf_sh/nerf/models.py:107-117), beside MLP_0 / MLP_1, with their Adam
+        # moments in the same tree shape
+        ms, vs = state.sg_moments()
+        for i, k in enumerate(_SG_KEYS):
             a = getattr(state, k).detach().cpu().numpy().astype(np.float32)
             params[k] = a
-            pstates[k] = {"grad_ema": np.zeros_like(a), "grad_sq_ema": np.zeros_like(a)}
+            pstates[k] = {"grad_ema": ms[i].numpy().astype(np.float32).reshape(a.shape),
+                          "grad_sq_ema": vs[i].numpy().astype(np.float32).reshape(a.shape)}
     return {"optimizer": {"target": {"params": params},
                           "state": {"step": np.asarray(state.step, np.int32), "param_states": {"params": pstates}}}}
 
@@ -124,8 +129,9 @@ def _is_sg(state):
     return hasattr(state, "set_lobe_params")
 
 
-def _load_sg_keys(get, has, state, where):
-    """The SG keys of a checkpoint into an SG state; a non-SG state refuses them and an SG state requires them, by name."""
+def _load_sg_keys(get, has, state, where, moments=None):
+    """The SG keys of a checkpoint into an SG state; a non-SG state refuses them and an SG state requires them, by name.
+    `moments`: the param_states tree of a flax checkpoint; SG leaves without moments there load with zeros."""
     present = [k for k in _SG_KEYS if has(k)]
     if not _is_sg(state):
         if present:
@@ -139,16 +145,26 @@ def _load_sg_keys(get, has, state, where):
     K = state.sg_dim
     if lam.shape != (K,) or mu.shape != (K, 2):
         raise ValueError(f"{where}: sg_lambda {lam.shape} / sg_mu_spher {mu.shape}, the model (sg_dim={K}) needs ({K},) / ({K}, 2)")
-    state.set_lobe_params(torch.from_numpy(lam), torch.from_numpy(mu))
+    mv = [None, None]
+    if moments is not None and all(isinstance(moments.get(k), dict) for k in _SG_KEYS):
+        for i, leaf in enumerate(("grad_ema", "grad_sq_ema")):
+            parts = [moments[k].get(leaf) for k in _SG_KEYS]
+            if all(p is not None for p in parts):
+                parts = [np.asarray(p, np.float32) for p in parts]
+                if parts[0].shape != (K,) or parts[1].shape != (K, 2):
+                    raise ValueError(f"{where}: {leaf} of sg_lambda {parts[0].shape} / sg_mu_spher {parts[1].shape}, the model "
+                                     f"(sg_dim={K}) needs ({K},) / ({K}, 2)")
+                mv[i] = torch.from_numpy(np.concatenate([parts[0], parts[1].reshape(-1)]))
+    state.set_lobe_params(torch.from_numpy(lam), torch.from_numpy(mu), *mv)
 
 
 def load_tree_into_state(tree, state):
     opt = tree["optimizer"]
     params = opt["target"]["params"]
     dev = state.params.device
-    _load_sg_keys(params.__getitem__, params.__contains__, state, "flax checkpoint")
-    state.params.copy_(torch.from_numpy(tree_to_arena(params, state.cfg)).to(dev))
     ps = opt.get("state", {}).get("param_states", {}).get("params")
+    _load_sg_keys(params.__getitem__, params.__contains__, state, "flax checkpoint", ps)
+    state.params.copy_(torch.from_numpy(tree_to_arena(params, state.cfg)).to(dev))
     if ps is not None:
         state.m.copy_(torch.from_numpy(tree_to_arena(ps, state.cfg, "grad_ema")).to(dev))
         state.v.copy_(torch.from_numpy(tree_to_arena(ps, state.cfg, "grad_sq_ema")).to(dev))

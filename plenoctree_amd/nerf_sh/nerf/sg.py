@@ -1,5 +1,5 @@
-"""NeRF-SG: the reference's spherical-Gaussian output basis (nerf_sh/config/misc/sg.yaml, sg_dim: 25), read, ray-rendered and
-baked into an SG PlenOctree.
+"""NeRF-SG: the reference's spherical-Gaussian output basis (nerf_sh/config/misc/sg.yaml, sg_dim: 25), trained, read,
+ray-rendered and baked into an SG PlenOctree.
 
 Host-side mirror of the sg_dim > 0 branches of nerf_sh/nerf/models.py (:107-117 the two model-level parameters sg_lambda [K]
 and sg_mu_spher [K,2]; :204-210, :273-292, :331-348 the shading through eval_sg, nerf_sh/nerf/sg.py:35-66) and of
@@ -8,9 +8,18 @@ octree/extraction.py:436-442 (the lobes handed to the tree as extra_data).
 A NeRF-SG is the SH network with 3 * sg_dim + 1 outputs.  For sg_dim in {1, 4, 9, 16, 25} that is the MLP shape the kernels
 run for sh_deg = sqrt(sg_dim) - 1, so the model keeps a PxoCfg of that degree and shares packing, pxo_eval_points,
 pxo_grid_sigma and pxo_mean_over_samples with the SH path; only the shading differs (pxo_sg_render_fwd).  Lobes are one
-global set per model (the reference asserts a flag `sg_global` that it defines nowhere).  Training a NeRF-SG is not built:
-nerf_sh.train keeps rejecting sg_dim > 0 (utils.check_supported); nerf_sh.eval, nerf_sh.gen_video and octree.extraction opt
-in through check_render_flags / check_extraction_flags.
+global set per model (the reference asserts a flag `sg_global` that it defines nowhere).  utils.check_supported keeps
+rejecting sg_dim > 0; nerf_sh.train, nerf_sh.eval, nerf_sh.gen_video and octree.extraction opt in through check_train_flags /
+check_render_flags / check_extraction_flags.
+
+Training (train_step below; nerf_sh/nerf/models.py:107-117 puts sg_lambda and sg_mu_spher into the "params" collection, so
+train.py:101-119 differentiates, averages, decays and Adam-updates them like any other leaf): the raw parameters live on the
+device as one array sg_params [3K] = (sg_lambda [K], sg_mu_spher [K,2]) with their Adam moments; their gradient sits behind
+the two MLPs' in the state's reduce buffer, inside bucket 1, so the gradient exchange needs no collective of its own.
+pxo_sg_train_fwd_bwd derives the lobes from sg_params on the device, the update is pxo_adam_step on the 3K tail and pxo_sg_lobes
+refreshes state.lobes: nothing in a step waits for the host.  state.sg_lambda / state.sg_mu_spher are host copies, read back
+from the device when they are asked for after a step.  A state restored from a checkpoint takes its lobes from the host
+expression (lobes_from_params), which can differ from the device kernel's in the last float32 bit; training never reads them.
 """
 import math
 
@@ -54,25 +63,65 @@ def init_lobe_params(sg_dim, seed=20200823):
 
 
 class SgState(models.TrainState):
-    """TrainState of the two MLPs plus the model-level SG parameters (host) and the lobes the kernels read (device)."""
+    """TrainState of the two MLPs plus the model-level SG parameters: raw parameters, Adam moments and gradient on the device
+    of `params` (sg_params / sg_m / sg_v / sg_grads, [3K] each), host copies behind sg_lambda / sg_mu_spher, and the lobes the
+    kernels read."""
 
     def __init__(self, cfg, params, sg_lambda, sg_mu_spher, step=0):
         super().__init__(cfg, params, step)
+        # gradient arena [MLP_0 | MLP_1 | SG (3K) | 6 stats | pad]: bucket 0 is unchanged, the SG gradient rides in bucket 1
+        n, k3 = params.numel(), 3 * self.sg_dim
+        self.reduce_buf = torch.zeros(n + k3 + 8, dtype=torch.float32, device=params.device)
+        self.grads = self.reduce_buf[:n]
+        self.sg_grads = self.reduce_buf[n:n + k3]
+        self.stats = self.reduce_buf[n + k3:n + k3 + 6]
+        self.bucket0 = self.reduce_buf[:self.n_mlp]
+        self.bucket1 = self.reduce_buf[self.n_mlp:]
         self.set_lobe_params(sg_lambda, sg_mu_spher)
 
     @property
     def sg_dim(self):
         return (self.cfg.sh_deg + 1) ** 2
 
-    def set_lobe_params(self, sg_lambda, sg_mu_spher):
+    def _sync_host(self):
+        """The host copies follow the device parameters when a train step has moved them (one copy, when somebody asks)."""
+        if getattr(self, "_sg_stale", False):
+            K = self.sg_dim
+            p = self.sg_params.detach().cpu()
+            self._sg_lambda, self._sg_mu_spher = p[:K].clone(), p[K:].reshape(K, 2).clone()
+            self._sg_stale = False
+
+    @property
+    def sg_lambda(self):
+        self._sync_host()
+        return self._sg_lambda
+
+    @property
+    def sg_mu_spher(self):
+        self._sync_host()
+        return self._sg_mu_spher
+
+    def set_lobe_params(self, sg_lambda, sg_mu_spher, m=None, v=None):
+        """Raw parameters (and, from a checkpoint, their Adam moments as flat [3K] arrays; zeros otherwise) into the state."""
         sg_lambda = torch.as_tensor(sg_lambda, dtype=torch.float32).detach().cpu().reshape(-1).clone()
         sg_mu_spher = torch.as_tensor(sg_mu_spher, dtype=torch.float32).detach().cpu().clone()
         K = self.sg_dim
         if tuple(sg_lambda.shape) != (K,) or tuple(sg_mu_spher.shape) != (K, 2):
             raise ValueError(f"sg_lambda {tuple(sg_lambda.shape)} / sg_mu_spher {tuple(sg_mu_spher.shape)}: a model with "
                              f"sg_dim={K} needs ({K},) and ({K}, 2)")
-        self.sg_lambda, self.sg_mu_spher = sg_lambda, sg_mu_spher
-        self.lobes = lobes_from_params(sg_lambda, sg_mu_spher).to(self.params.device)
+        dev = self.params.device
+        self._sg_lambda, self._sg_mu_spher, self._sg_stale = sg_lambda, sg_mu_spher, False
+        self.sg_params = torch.cat([sg_lambda, sg_mu_spher.reshape(-1)]).to(dev)
+        self.sg_m, self.sg_v = (torch.zeros(3 * K, dtype=torch.float32, device=dev) if a is None else
+                                torch.as_tensor(a, dtype=torch.float32).reshape(3 * K).clone().to(dev) for a in (m, v))
+        self.lobes = lobes_from_params(sg_lambda, sg_mu_spher).to(dev)
+
+    def sg_moments(self):
+        """((m of sg_lambda [K], m of sg_mu_spher [K,2]), (v ...)) on the host, for a checkpoint."""
+        K = self.sg_dim
+        zero = torch.zeros(3 * K)
+        return tuple((a[:K].clone(), a[K:].reshape(K, 2).clone())
+                     for a in (getattr(self, n, zero).detach().cpu() for n in ("sg_m", "sg_v")))
 
 
 class SgModel(models.NerfModel):
@@ -138,6 +187,13 @@ def _unbuilt_flags(args):
     return bad
 
 
+def check_train_flags(args):
+    """What nerf_sh.train builds of an sg_dim > 0 model; everything else is rejected by name."""
+    bad = _unbuilt_flags(args)
+    if bad:
+        raise NotImplementedError("training a NeRF-SG, not built on the MI355X path: " + "; ".join(bad))
+
+
 def check_render_flags(args):
     """What nerf_sh.eval / gen_video build of an sg_dim > 0 model; everything else is rejected by name."""
     bad = _unbuilt_flags(args)
@@ -152,13 +208,15 @@ def check_extraction_flags(args):
         raise NotImplementedError("extraction of an SG PlenOctree, not built on the MI355X path: " + "; ".join(bad))
 
 
-def check_dirs(args, require_data=True, extraction=False):
-    """utils.check_flags' directory checks, then the SG flag check."""
+def check_dirs(args, require_data=True, extraction=False, train=False, world_size=1):
+    """utils.check_flags' directory (and, for training, batch-size) checks, then the SG flag check."""
     if args.train_dir is None:
         raise ValueError("train_dir must be set. None set now.")
     if require_data and args.data_dir is None and args.dataset != "synthetic":
         raise ValueError("data_dir must be set. None set now.")
-    (check_extraction_flags if extraction else check_render_flags)(args)
+    if train and args.batch_size % world_size != 0:
+        raise ValueError("Batch size must be divisible by the number of devices.")
+    (check_train_flags if train else check_extraction_flags if extraction else check_render_flags)(args)
 
 
 def make_cfg(args):
@@ -169,9 +227,9 @@ def make_cfg(args):
     return models.make_cfg(a)
 
 
-def get_model_state(args, device, extraction=False):
+def get_model_state(args, device, extraction=False, train=False):
     """Model + state with freshly initialised parameters (the caller restores a checkpoint)."""
-    (check_extraction_flags if extraction else check_render_flags)(args)
+    (check_train_flags if train else check_extraction_flags if extraction else check_render_flags)(args)
     cfg = make_cfg(args)
     params = models.init_params(cfg, args.seed).to(device)
     lam, mu = init_lobe_params(args.sg_dim, args.seed)
@@ -187,3 +245,41 @@ def restore(args, device, say=print, require_data=True, extraction=False):
     model, state = get_model_state(args, device, extraction)
     say(load_nerf_checkpoint(args, state), flush=True)
     return model, state
+
+
+def get_train_state(args, device):
+    """models.get_model_state for nerf_sh.train with sg_dim > 0: fresh parameters, then the newest flax checkpoint of train_dir
+    if there is one (resume: parameters, SG leaves and all Adam moments)."""
+    from . import checkpoints
+    model, state = get_model_state(args, device, train=True)
+    if args.train_dir:
+        checkpoints.restore_checkpoint(args.train_dir, state)
+    return model, state
+
+
+def train_step(model, state, batch, lr, randomized=True, t_rand=None, u=None, sp_points=None, seed=0, world_size=1,
+               reducer=None):
+    """models.train_step for a NeRF-SG: pxo_sg_train_fwd_bwd_bucketed leaves the SG gradient behind the MLPs' in the reduce
+    buffer (inside bucket 1, so `reducer` averages it with the rest), then Adam over the two MLPs with the re-pack, Adam over
+    the 3K SG tail at the same learning rate and step (train.py:119) and the refresh of state.lobes -- all on the stream."""
+    from ... import ops
+    cfg = model.cfg
+    rays = batch["rays"]
+    B = rays.origins.shape[0]
+    ws = state.workspace(ops.sg_train_workspace_bytes(cfg, B))
+    ev = reducer.ready_event() if reducer is not None else None
+    ops.sg_train_fwd_bwd(cfg, state.params, state.sg_params, state.packed, rays.origins, rays.directions, rays.viewdirs,
+                         batch["pixels"], state.grads, state.sg_grads, state.stats, ws, randomized=randomized, t_rand=t_rand, u=u,
+                         sp_points=sp_points, seed=seed, grads0_ready=ev)
+    scale = 1.0
+    if reducer is not None:
+        reducer.reduce(state.bucket0, state.bucket1)
+    if world_size > 1:
+        state.stats.mul_(1.0 / world_size)
+        scale = 1.0 / world_size
+    ops.adam_pack_step(cfg, state.params, state.m, state.v, state.grads, lr, state.step, state.packed, grad_scale=scale)
+    ops.adam_step(state.sg_params, state.sg_m, state.sg_v, state.sg_grads, lr, state.step, grad_scale=scale)
+    ops.sg_lobes(state.sg_params, state.sg_dim, state.lobes)
+    state._sg_stale = True
+    state.step += 1
+    return state.stats

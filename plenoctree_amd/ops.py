@@ -299,6 +299,63 @@ def train_fwd_bwd(cfg, params, packed, origins, directions, viewdirs, pixels, gr
           "pxo_train_fwd_bwd_bucketed")
 
 
+# ---- training a NeRF-SG: the pxo_sg_* entry points beside the three above -----------------------------------------------------
+def sg_lobes(sg_params, K, lobes=None):
+    """pxo_sg_lobes: raw sg_params [3K] (sg_lambda [K], then sg_mu_spher [K,2]) -> lobes [K,4] on the device, on the stream."""
+    _require_gpu()
+    if sg_params.numel() != 3 * K:
+        raise PxoError(f"sg_params has {sg_params.numel()} floats, sg_dim={K} needs {3 * K}")
+    if lobes is None:
+        lobes = _new(K, 4, device=sg_params.device)
+    check(_lib.load().pxo_sg_lobes(_f(sg_params), int(K), _f(lobes), _stream()), "pxo_sg_lobes")
+    return lobes
+
+
+def sg_shade_composite_train(cfg, lobes, raw_rgb, raw_sigma, z_vals, directions, viewdirs, pixels, n_sp=0, want_rgb=True,
+                             want_weights=True):
+    """shade_composite_train with the SG basis of `lobes` [K,4]; the dict gains d_lobes [K,4], the gradient of the launch's pixel
+    loss with respect to (lambda, mu)."""
+    _require_gpu()
+    lib = _lib.load()
+    B, S = z_vals.shape
+    C = raw_rgb.shape[-1]
+    K = sh_dim(cfg)
+    dev = raw_rgb.device
+    out = {"comp_rgb": _new(B, 3, device=dev) if want_rgb else None,
+           "weights": _new(B, S, device=dev) if want_weights else None,
+           "ray_sse": _new(B, device=dev), "d_raw_rgb": _new(B * S + n_sp, C, device=dev),
+           "d_raw_sigma": _new(B * S + n_sp, device=dev), "sp_exp": _new(max(n_sp, 1), device=dev),
+           "d_lobes": _new(K, 4, device=dev)}
+    partials = _new(max(-(-B // _lib.SG_RAYS_PER_BLOCK), 1) * K * 4, device=dev)
+    check(lib.pxo_sg_shade_composite_train(ctypes.byref(cfg), _f(lobes), _f(raw_rgb), _f(raw_sigma), _f(z_vals), _f(directions),
+                                           _f(viewdirs), _f(pixels), B, S, _f(out["comp_rgb"]), _f(out["weights"]),
+                                           _f(out["ray_sse"]), _f(out["d_raw_rgb"]), _f(out["d_raw_sigma"]), n_sp,
+                                           _f(out["sp_exp"]), _f(out["d_lobes"]), _f(partials), _stream()),
+          "pxo_sg_shade_composite_train")
+    return out
+
+
+def sg_train_workspace_bytes(cfg, B):
+    n = ctypes.c_size_t(0)
+    check(_lib.load().pxo_sg_train_workspace_bytes(ctypes.byref(cfg), B, ctypes.byref(n)), "pxo_sg_train_workspace_bytes")
+    return n.value
+
+
+def sg_train_fwd_bwd(cfg, params, sg_params, packed, origins, directions, viewdirs, pixels, grads, sg_grads, stats, ws,
+                     randomized=True, t_rand=None, u=None, sp_points=None, seed=0, grads0_ready=None):
+    """train_fwd_bwd of a NeRF-SG: sg_params [3K] in, sg_grads [3K] out (d total loss / d raw SG parameters, weight decay
+    included); stats[5] counts the SG leaves."""
+    _require_gpu()
+    lib = _lib.load()
+    (f0, b0), (f1, b1) = packed
+    B = origins.shape[0]
+    check(lib.pxo_sg_train_fwd_bwd_bucketed(ctypes.byref(cfg), _f(params), _f(sg_params), _f(f0), _f(b0), _f(f1), _f(b1),
+                                            _f(origins), _f(directions), _f(viewdirs), _f(pixels), B, int(randomized), _f(t_rand),
+                                            _f(u), _f(sp_points), seed, _f(grads), _f(sg_grads), _f(stats), _p(ws), ws.numel(),
+                                            grads0_ready.handle if grads0_ready is not None else None, _stream()),
+          "pxo_sg_train_fwd_bwd_bucketed")
+
+
 def train_backward_work(cfg, B, ws):
     """(live, total) 16-row chunks of the reverse pass of the last train_fwd_bwd call on workspace `ws` (synchronises)."""
     _require_gpu()
