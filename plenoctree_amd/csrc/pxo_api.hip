@@ -304,14 +304,10 @@ static int forward_coarse(const PxoCfg* cfg, TrainWs& t, const float* pk0, const
   PXO_TRY(launch_sample_along_rays(o, d, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, t.c.z, t.c.pts, s));
   PXO_TRY(launch_mlp_fwd(cfg, pk0, t.c.pts, t.c.M, t.c.raw_rgb, t.c.raw_sigma, t.c.acts, t.c.enc, t.c.mask, s, tile_counter));
   if (dr.noisy) PXO_TRY(launch_add_noise(t.c.raw_sigma, B * Nc, cfg->noise_std, nullptr, dr.seed, 3, s));   // models.py:258-264
-  if (pixels && lobes)      // NeRF-SG: the same launch with the lobe basis and the partials of the lobe gradient
-    return launch_sg_shade_composite_train(cfg, lobes, t.c.raw_rgb, t.c.raw_sigma, t.c.z, d, v, pixels, B, Nc, nullptr,
-                                           Nf > 0 ? t.c.weights : nullptr, t.c.ray_sse, t.c.d_raw_rgb, t.c.d_raw_sigma,
-                                           Nf > 0 ? 0 : t.n_sp, t.sp_exp, lobe_partials, s);
-  if (pixels)
+  if (pixels)               // with lobes (NeRF-SG): the lobe basis, and the partials of the lobe gradient
     return launch_shade_composite_train(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, d, v, pixels, B, Nc, nullptr,
                                         Nf > 0 ? t.c.weights : nullptr, t.c.ray_sse, t.c.d_raw_rgb, t.c.d_raw_sigma,
-                                        Nf > 0 ? 0 : t.n_sp, t.sp_exp, s);
+                                        Nf > 0 ? 0 : t.n_sp, t.sp_exp, lobes, lobe_partials, s);
   return launch_shade_composite_fwd(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, d, v, B, Nc, rgb_c, disp_c, acc_c,
                                     t.c.weights, s, lobes);
 }
@@ -324,13 +320,10 @@ static int forward_fine(const PxoCfg* cfg, TrainWs& t, const float* pk1, const f
   PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, o, d, B, Nc, Nf, dr.u, t.f.z, t.f.pts, s));
   PXO_TRY(launch_mlp_fwd(cfg, pk1, t.f.pts, t.f.M, t.f.raw_rgb, t.f.raw_sigma, t.f.acts, t.f.enc, t.f.mask, s, tile_counter));
   if (dr.noisy) PXO_TRY(launch_add_noise(t.f.raw_sigma, B * (Nc + Nf), cfg->noise_std, nullptr, dr.seed, 4, s));   // :318-324
-  if (pixels && lobes)
-    return launch_sg_shade_composite_train(cfg, lobes, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, pixels, B, Nc + Nf, nullptr,
-                                           nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp,
-                                           lobe_partials, s);
   if (pixels)
     return launch_shade_composite_train(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, pixels, B, Nc + Nf, nullptr,
-                                        nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp, s);
+                                        nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp, lobes,
+                                        lobe_partials, s);
   return launch_shade_composite_fwd(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, B, Nc + Nf, rgb_f, disp_f, acc_f,
                                     t.f.weights, s, lobes);
 }
@@ -517,7 +510,8 @@ int pxo_shade_composite_train(const PxoCfg* cfg, const float* raw_rgb, const flo
                   d_raw_rgb && d_raw_sigma && (n_sp == 0 || sp_exp),
               "pxo_shade_composite_train: bad arguments");
   return launch_shade_composite_train(cfg, raw_rgb, raw_sigma, z_vals, directions, viewdirs, pixels, B, S, comp_rgb,
-                                      weights, ray_sse, d_raw_rgb, d_raw_sigma, n_sp, sp_exp, (hipStream_t)stream);
+                                      weights, ray_sse, d_raw_rgb, d_raw_sigma, n_sp, sp_exp, nullptr, nullptr,
+                                      (hipStream_t)stream);
 }
 
 int pxo_sample_pdf(const float* z_coarse, const float* w_coarse, const float* origins, const float* directions,
@@ -787,8 +781,8 @@ int pxo_sg_shade_composite_train(const PxoCfg* cfg, const float* lobes, const fl
   PXO_REQUIRE(raw_rgb && raw_sigma && z_vals && directions && viewdirs && pixels && ray_sse && d_raw_rgb && d_raw_sigma &&
                   (n_sp == 0 || sp_exp),
               "pxo_sg_shade_composite_train: bad arguments");
-  PXO_TRY(launch_sg_shade_composite_train(cfg, lobes, raw_rgb, raw_sigma, z_vals, directions, viewdirs, pixels, B, S, comp_rgb,
-                                          weights, ray_sse, d_raw_rgb, d_raw_sigma, n_sp, sp_exp, lobe_partials, s));
+  PXO_TRY(launch_shade_composite_train(cfg, raw_rgb, raw_sigma, z_vals, directions, viewdirs, pixels, B, S, comp_rgb, weights,
+                                       ray_sse, d_raw_rgb, d_raw_sigma, n_sp, sp_exp, lobes, lobe_partials, s));
   return launch_sg_lobe_grad(lobe_partials, sg_ray_blocks(B), nullptr, 0, K, nullptr, 0.f, d_lobes, nullptr, nullptr, s);
 }
 

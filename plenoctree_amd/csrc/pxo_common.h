@@ -323,18 +323,13 @@ int launch_vd_composite_fwd(int white_bkgd, const float* raw_rgb, const float* r
 int launch_adam(float* p, float* m, float* v, const float* g, int64_t n, float lr, int64_t step,
                 float grad_scale, hipStream_t s);
 // training form of the compositing: forward + pixel loss + reverse in one launch (see render_kernels.hip); serves the
-// n_sp sparsity rows appended to the pass as well
+// n_sp sparsity rows appended to the pass as well.  With lobes [K,4] and lobe_partials [sg_ray_blocks(B)][K][4] it is the NeRF-SG
+// form: the basis from the lobes, and the per-workgroup partials of the lobe gradient; both NULL is the SH form
+__host__ __device__ inline int64_t sg_ray_blocks(int64_t B) { return (B + PXO_SG_RAYS_PER_BLOCK - 1) / PXO_SG_RAYS_PER_BLOCK; }
 int launch_shade_composite_train(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, const float* z,
                                  const float* dirs, const float* viewdirs, const float* pixels, int64_t B, int S,
                                  float* comp_rgb, float* weights, float* ray_sse, float* d_raw_rgb, float* d_raw_sigma,
-                                 int64_t n_sp, float* sp_exp, hipStream_t s);
-// NeRF-SG training form of the same launch (render_kernels.hip sg_shade_composite_train_kernel): the basis from lobes [K,4], and
-// the per-workgroup partials of the lobe gradient in lobe_partials [sg_ray_blocks(B)][K][4]
-__host__ __device__ inline int64_t sg_ray_blocks(int64_t B) { return (B + PXO_SG_RAYS_PER_BLOCK - 1) / PXO_SG_RAYS_PER_BLOCK; }
-int launch_sg_shade_composite_train(const PxoCfg* cfg, const float* lobes, const float* raw_rgb, const float* raw_sigma,
-                                    const float* z, const float* dirs, const float* viewdirs, const float* pixels, int64_t B,
-                                    int S, float* comp_rgb, float* weights, float* ray_sse, float* d_raw_rgb,
-                                    float* d_raw_sigma, int64_t n_sp, float* sp_exp, float* lobe_partials, hipStream_t s);
+                                 int64_t n_sp, float* sp_exp, const float* lobes, float* lobe_partials, hipStream_t s);
 // sg_params [3K] -> lobes [K,4], and the fixed-order second stage of the lobe gradient (partials of up to two passes; see the
 // kernels' comments for d_lobes / sg_grads / sumsq_slot, each of which may be NULL)
 int launch_sg_lobes(const float* sg_params, int K, float* lobes, hipStream_t s);

@@ -4,6 +4,8 @@
 //
 // Reference semantics: nerf_sh/nerf/model_utils.py:97-314, nerf_sh/nerf/sh.py:54-109,
 // nerf_sh/nerf/models.py:269-307.
+#include <type_traits>
+
 #include "pxo_common.h"
 #include "pxo_sh.h"
 
@@ -114,6 +116,26 @@ __device__ __forceinline__ void chunk_transmittance(float f, int lane, float& ca
   st.T = carry * excl;
   carry = carry * __shfl(incl, 63);
 }
+// end of the forward compositing of one ray: the wave's sums, disp with the guard of model_utils.py:217-219, the background and
+// the stores (lane 0)
+__device__ __forceinline__ void composite_store(float s_r, float s_g, float s_b, float s_depth, float s_acc, int64_t ray, bool ray_ok,
+                                                int lane, int white, float* __restrict__ comp_rgb, float* __restrict__ disp,
+                                                float* __restrict__ acc_out) {
+  s_r = wave_sum(s_r); s_g = wave_sum(s_g); s_b = wave_sum(s_b);
+  s_depth = wave_sum(s_depth); s_acc = wave_sum(s_acc);
+  if (ray_ok && lane == 0) {
+    const float inv_eps = 1e10f;
+    float dsp = s_acc / s_depth;
+    dsp = (dsp > 0.f && dsp < inv_eps && s_acc > 1e-10f) ? dsp : inv_eps;  // model_utils.py:217-219
+    const float bg = white ? 1.f - s_acc : 0.f;
+    comp_rgb[ray * 3 + 0] = s_r + bg;
+    comp_rgb[ray * 3 + 1] = s_g + bg;
+    comp_rgb[ray * 3 + 2] = s_b + bg;
+    disp[ray] = dsp;
+    acc_out[ray] = s_acc;
+  }
+}
+
 
 // loads the chunk's raw SH coefficients through LDS (coalesced), evaluates sigmoid(eval_sh),
 // relu(sigma), alpha and the transmittance scan; `carry` is the product over previous chunks.
@@ -151,7 +173,22 @@ __device__ __forceinline__ void shade_chunk(const float* __restrict__ raw_rgb, c
 
 // SG (NeRF-SG, nerf_sh/nerf/models.py:204-210, :273-292 with sg_dim > 0): the head has K = (DEG+1)^2 lobes and the basis is
 // eval_sg's (nerf_sh/nerf/sg.py:35-66), Y_i = exp(lambda_i (mu_i . viewdir - 1)) / K from lobes [K,4] = (lambda, mu), in
-// place of the SH basis; the sum, the sigmoid and the compositing are the same code.
+// place of the SH basis; the sum, the sigmoid and the compositing are the same code.  sg_lobe is the one copy of that
+// expression (explicitly rounded, so that forward, training and the lobe gradient see the same bits); it also hands back mu_i . v.
+template <int K>
+__device__ __forceinline__ float sg_lobe(const float* __restrict__ lobes, int i, float vx, float vy, float vz, float& dot) {
+  dot = __fadd_rn(__fadd_rn(__fmul_rn(lobes[4 * i + 1], vx), __fmul_rn(lobes[4 * i + 2], vy)), __fmul_rn(lobes[4 * i + 3], vz));
+  return __fmul_rn(expf(__fmul_rn(lobes[4 * i], __fsub_rn(dot, 1.0f))), 1.0f / (float)K);
+}
+template <int K>
+__device__ __forceinline__ void sg_basis(const float* __restrict__ lobes, float vx, float vy, float vz, float (&Y)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    float dot;
+    Y[i] = sg_lobe<K>(lobes, i, vx, vy, vz, dot);
+  }
+}
+
 template <int DEG, bool SG = false>
 __global__ __launch_bounds__(kRayThreads) void shade_composite_fwd_kernel(
     const float* __restrict__ raw_rgb, const float* __restrict__ raw_sigma, const float* __restrict__ z_vals,
@@ -166,12 +203,7 @@ __global__ __launch_bounds__(kRayThreads) void shade_composite_fwd_kernel(
   if (!ray_ok) ray = B - 1;
   float Y[K];
   if constexpr (SG) {
-    const float vx = viewdirs[ray * 3], vy = viewdirs[ray * 3 + 1], vz = viewdirs[ray * 3 + 2];
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-      const float dot = __fadd_rn(__fadd_rn(__fmul_rn(lobes[4 * i + 1], vx), __fmul_rn(lobes[4 * i + 2], vy)), __fmul_rn(lobes[4 * i + 3], vz));
-      Y[i] = __fmul_rn(expf(__fmul_rn(lobes[4 * i], __fsub_rn(dot, 1.0f))), 1.0f / (float)K);
-    }
+    sg_basis<K>(lobes, viewdirs[ray * 3], viewdirs[ray * 3 + 1], viewdirs[ray * 3 + 2], Y);
   } else {
     sh_basis<DEG>(viewdirs[ray * 3], viewdirs[ray * 3 + 1], viewdirs[ray * 3 + 2], Y);
   }
@@ -187,19 +219,7 @@ __global__ __launch_bounds__(kRayThreads) void shade_composite_fwd_kernel(
     s_depth += w * st.z; s_acc += w;
     if (ray_ok && ch * 64 + lane < S) weights[ray * S + ch * 64 + lane] = w;
   }
-  s_r = wave_sum(s_r); s_g = wave_sum(s_g); s_b = wave_sum(s_b);
-  s_depth = wave_sum(s_depth); s_acc = wave_sum(s_acc);
-  if (ray_ok && lane == 0) {
-    const float inv_eps = 1e10f;
-    float dsp = s_acc / s_depth;
-    dsp = (dsp > 0.f && dsp < inv_eps && s_acc > 1e-10f) ? dsp : inv_eps;  // model_utils.py:217-219
-    const float bg = white ? 1.f - s_acc : 0.f;
-    comp_rgb[ray * 3 + 0] = s_r + bg;
-    comp_rgb[ray * 3 + 1] = s_g + bg;
-    comp_rgb[ray * 3 + 2] = s_b + bg;
-    disp[ray] = dsp;
-    acc_out[ray] = s_acc;
-  }
+  composite_store(s_r, s_g, s_b, s_depth, s_acc, ray, ray_ok, lane, white, comp_rgb, disp, acc_out);
 }
 
 // The same compositing for the view-conditioned head (nerf_sh/nerf/models.py:269-284 with use_viewdirs: rgb =
@@ -235,28 +255,52 @@ __global__ __launch_bounds__(kRayThreads) void vd_composite_fwd_kernel(
     s_depth += w * st.z; s_acc += w;
     if (weights && ray_ok && s0 + lane < S) weights[base + lane] = w;
   }
-  s_r = wave_sum(s_r); s_g = wave_sum(s_g); s_b = wave_sum(s_b);
-  s_depth = wave_sum(s_depth); s_acc = wave_sum(s_acc);
-  if (ray_ok && lane == 0) {
-    const float inv_eps = 1e10f;
-    float dsp = s_acc / s_depth;
-    dsp = (dsp > 0.f && dsp < inv_eps && s_acc > 1e-10f) ? dsp : inv_eps;  // model_utils.py:217-219
-    const float bg = white ? 1.f - s_acc : 0.f;
-    comp_rgb[ray * 3 + 0] = s_r + bg;
-    comp_rgb[ray * 3 + 1] = s_g + bg;
-    comp_rgb[ray * 3 + 2] = s_b + bg;
-    disp[ray] = dsp;
-    acc_out[ray] = s_acc;
-  }
+  composite_store(s_r, s_g, s_b, s_depth, s_acc, ray, ray_ok, lane, white, comp_rgb, disp, acc_out);
 }
 
-int launch_vd_composite_fwd(int white_bkgd, const float* raw_rgb, const float* raw_sigma, const float* z, const float* dirs,
-                            int64_t B, int S, float* comp_rgb, float* disp, float* acc, float* weights, hipStream_t s) {
-  if (B == 0) return PXO_OK;
-  if (S > 64 * kMaxChunks || S < 1) { set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks); return PXO_ERR_ARG; }
-  hipLaunchKernelGGL(vd_composite_fwd_kernel, dim3((unsigned)((B + kRaysPerBlock - 1) / kRaysPerBlock)), dim3(kRayThreads), 0, s,
-                     raw_rgb, raw_sigma, z, dirs, B, S, white_bkgd, comp_rgb, disp, acc, weights);
-  return check_launch("vd_composite_fwd");
+// Reverse of the compositing for one 64-sample chunk of a ray, given the loss gradient (g0, g1, g2) on comp_rgb and the state q the
+// forward sweep left for the chunk.  The callers walk the chunks last to first; `suffix`, the sum over later samples of dL/dw_j w_j,
+// is carried across them (0 before the last chunk).  wl is the wave's LDS tile, through which d_raw_rgb leaves coalesced.  This is
+// the one copy of the reverse arithmetic: the backward kernel and both training forms call it.  (The chunk loop stays with the
+// callers: with the loop inside this function the compiler allocates more registers, see profiles/EXPERIMENTS.md.)
+template <int DEG>
+__device__ __forceinline__ void composite_reverse_chunk(const SampleState& q, int ch, int S, int lane, float* __restrict__ wl,
+                                                        const float (&Y)[(DEG + 1) * (DEG + 1)], int64_t ray, bool ray_ok,
+                                                        float g0, float g1, float g2, float bgc, float& suffix,
+                                                        float* __restrict__ d_raw_rgb, float* __restrict__ d_raw_sigma) {
+  constexpr int K = (DEG + 1) * (DEG + 1), C = 3 * K, CS = C | 1;
+  const bool valid = ch * 64 + lane < S;
+  const float alpha = 1.f - q.e;
+  const float w = alpha * q.T;
+  // comp = sum_s w_s c_s + bg*(1 - sum_s w_s)
+  const float dw = g0 * (q.rgb[0] - bgc) + g1 * (q.rgb[1] - bgc) + g2 * (q.rgb[2] - bgc);
+  const float G = valid ? dw * w : 0.f;
+  const float incl = wave_rscan_add(G, lane);
+  float excl = __shfl_down(incl, 1);
+  if (lane == 63) excl = 0.f;
+  const float R = suffix + excl;
+  suffix += __shfl(incl, 0);
+  const float fct = (1.f - alpha) + 1e-10f;
+  const float dalpha = dw * q.T - R / fct;
+  const float dsigma = dalpha * q.dist * q.e;     // d(1-exp(-s*dist))/ds
+  const int64_t base = ray * S + ch * 64;
+  if (ray_ok && valid) d_raw_sigma[base + lane] = q.raw_sigma > 0.f ? dsigma : 0.f;
+  __syncthreads();
+  if (valid) {
+    const float dp[3] = {g0 * w * q.rgb[0] * (1.f - q.rgb[0]), g1 * w * q.rgb[1] * (1.f - q.rgb[1]),
+                         g2 * w * q.rgb[2] * (1.f - q.rgb[2])};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < K; ++k) wl[lane * CS + c * K + k] = dp[c] * Y[k];
+  }
+  __syncthreads();
+  const int nvalid = S - ch * 64 < 64 ? S - ch * 64 : 64;
+  if (ray_ok)
+    for (int idx = lane; idx < nvalid * C; idx += 64) {
+      const int s = idx / C, j = idx - s * C;
+      d_raw_rgb[base * C + idx] = wl[s * CS + j];
+    }
 }
 
 // reverse of the above for a loss on comp_rgb only; no gradient flows to z (stop_gradient,
@@ -286,164 +330,46 @@ __global__ __launch_bounds__(kRayThreads) void shade_composite_bwd_kernel(
     if (ch < nch) shade_chunk<DEG>(raw_rgb, raw_sigma, z_vals, lds[wave], Y, ray, S, ch, lane, norm_d, carry, st[ch]);
   float suffix = 0.f;  // sum over later samples of dL/dw_j * w_j
 #pragma unroll
-  for (int ch = kMaxChunks - 1; ch >= 0; --ch) {
-    if (ch >= nch) continue;
-    const SampleState& q = st[ch];
-    const bool valid = ch * 64 + lane < S;
-    const float alpha = 1.f - q.e;
-    const float w = alpha * q.T;
-    // comp = sum_s w_s c_s + bg*(1 - sum_s w_s)
-    const float dw = g0 * (q.rgb[0] - bgc) + g1 * (q.rgb[1] - bgc) + g2 * (q.rgb[2] - bgc);
-    const float G = valid ? dw * w : 0.f;
-    const float incl = wave_rscan_add(G, lane);
-    float excl = __shfl_down(incl, 1);
-    if (lane == 63) excl = 0.f;
-    const float R = suffix + excl;
-    suffix += __shfl(incl, 0);
-    const float fct = (1.f - alpha) + 1e-10f;
-    const float dalpha = dw * q.T - R / fct;
-    const float dsigma = dalpha * q.dist * q.e;     // d(1-exp(-s*dist))/ds
-    const int64_t base = ray * S + ch * 64;
-    if (ray_ok && valid) d_raw_sigma[base + lane] = q.raw_sigma > 0.f ? dsigma : 0.f;
-    __syncthreads();
-    if (valid) {
-      const float dp[3] = {g0 * w * q.rgb[0] * (1.f - q.rgb[0]), g1 * w * q.rgb[1] * (1.f - q.rgb[1]),
-                           g2 * w * q.rgb[2] * (1.f - q.rgb[2])};
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int k = 0; k < K; ++k) lds[wave][lane * CS + c * K + k] = dp[c] * Y[k];
-    }
-    __syncthreads();
-    const int nvalid = S - ch * 64 < 64 ? S - ch * 64 : 64;
-    if (ray_ok)
-      for (int idx = lane; idx < nvalid * C; idx += 64) {
-        const int s = idx / C, j = idx - s * C;
-        d_raw_rgb[base * C + idx] = lds[wave][s * CS + j];
-      }
+  for (int ch = kMaxChunks - 1; ch >= 0; --ch)
+    if (ch < nch)
+      composite_reverse_chunk<DEG>(st[ch], ch, S, lane, lds[wave], Y, ray, ray_ok, g0, g1, g2, bgc, suffix, d_raw_rgb, d_raw_sigma);
+}
+
+// The sparsity rows appended to a training pass (train.py:77-85), rows [B*S, B*S + n_sp), kRayThreads of them per workgroup
+// starting at r0: e = exp(-len relu(s)), d_raw_sigma = w len e / n for s > 0, and a zero gradient on their raw_rgb [.., C].
+__device__ __forceinline__ void sparsity_rows(const float* __restrict__ raw_sigma, int64_t base, int64_t r0, int64_t n_sp, int C,
+                                              float sp_weight, float sp_length, float* __restrict__ sp_exp,
+                                              float* __restrict__ d_raw_rgb, float* __restrict__ d_raw_sigma) {
+  const int64_t row = r0 + threadIdx.x;
+  if (row < n_sp) {
+    const float raw = raw_sigma[base + row];
+    const float e = expf(-sp_length * fmaxf(raw, 0.f));
+    sp_exp[row] = e;
+    d_raw_sigma[base + row] = raw > 0.f ? (sp_weight * sp_length / (float)n_sp) * e : 0.f;
   }
+  const int64_t nrow = n_sp - r0 < kRayThreads ? n_sp - r0 : kRayThreads;
+  float* __restrict__ z0 = d_raw_rgb + (base + r0) * C;
+  for (int64_t i = threadIdx.x; i < nrow * C; i += kRayThreads) z0[i] = 0.f;
 }
 
 // Training form: forward compositing, the pixel loss of nerf_sh/train.py:89-98 and the reverse pass in ONE launch (the
 // backward kernel above already re-derives the whole forward state in registers; the loss gradient of a ray depends on
 // that ray's colour only).  Per ray: comp_rgb (+weights for sample_pdf), sse[ray] = sum_c (comp_c - px_c)^2 (summed
 // in a fixed order by finalize_stats), d_comp = 2 (comp - px) / (3 B), then d_raw_rgb / d_raw_sigma as above.
-// Blocks past the rays serve the sparsity rows appended to the pass (train.py:77-85): e = exp(-len relu(s)),
-// d_raw_sigma = w len e / n for s > 0, and a zero gradient on their raw_rgb.
-template <int DEG>
-__global__ __launch_bounds__(kRayThreads) void shade_composite_train_kernel(
-    const float* __restrict__ raw_rgb, const float* __restrict__ raw_sigma, const float* __restrict__ z_vals,
-    const float* __restrict__ dirs, const float* __restrict__ viewdirs, const float* __restrict__ pixels, int64_t B,
-    int S, int white, float* __restrict__ comp_rgb, float* __restrict__ weights, float* __restrict__ ray_sse,
-    float* __restrict__ d_raw_rgb, float* __restrict__ d_raw_sigma, int64_t n_sp, float sp_weight, float sp_length,
-    float* __restrict__ sp_exp) {
-  constexpr int K = (DEG + 1) * (DEG + 1), C = 3 * K, CS = C | 1;
-  __shared__ float lds[kRaysPerBlock][64 * CS];
-  const int64_t ray_blocks = (B + kRaysPerBlock - 1) / kRaysPerBlock;
-  if ((int64_t)blockIdx.x >= ray_blocks) {       // sparsity rows [B*S, B*S + n_sp)
-    const int64_t r0 = ((int64_t)blockIdx.x - ray_blocks) * kRayThreads;
-    const int64_t row = r0 + threadIdx.x;
-    const int64_t base = B * S;
-    if (row < n_sp) {
-      const float raw = raw_sigma[base + row];
-      const float e = expf(-sp_length * fmaxf(raw, 0.f));
-      sp_exp[row] = e;
-      d_raw_sigma[base + row] = raw > 0.f ? (sp_weight * sp_length / (float)n_sp) * e : 0.f;
-    }
-    const int64_t nrow = n_sp - r0 < kRayThreads ? n_sp - r0 : kRayThreads;
-    float* __restrict__ z0 = d_raw_rgb + (base + r0) * C;
-    for (int64_t i = threadIdx.x; i < nrow * C; i += kRayThreads) z0[i] = 0.f;
-    return;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t ray = blockIdx.x * (int64_t)kRaysPerBlock + wave;
-  const bool ray_ok = ray < B;
-  if (!ray_ok) ray = B - 1;
-  float Y[K];
-  sh_basis<DEG>(viewdirs[ray * 3], viewdirs[ray * 3 + 1], viewdirs[ray * 3 + 2], Y);
-  const float dx = dirs[ray * 3], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
-  const float norm_d = sqrtf(dx * dx + dy * dy + dz * dz);
-  const float bgc = white ? 1.f : 0.f;
-  const int nch = (S + 63) / 64;
-  SampleState st[kMaxChunks];
-  float carry = 1.f, s_r = 0.f, s_g = 0.f, s_b = 0.f, s_acc = 0.f;
-#pragma unroll
-  for (int ch = 0; ch < kMaxChunks; ++ch)
-    if (ch < nch) {
-      shade_chunk<DEG>(raw_rgb, raw_sigma, z_vals, lds[wave], Y, ray, S, ch, lane, norm_d, carry, st[ch]);
-      const float w = (1.f - st[ch].e) * st[ch].T;
-      s_r += w * st[ch].rgb[0]; s_g += w * st[ch].rgb[1]; s_b += w * st[ch].rgb[2]; s_acc += w;
-      if (weights && ray_ok && ch * 64 + lane < S) weights[ray * S + ch * 64 + lane] = w;
-    }
-  s_r = wave_sum(s_r); s_g = wave_sum(s_g); s_b = wave_sum(s_b); s_acc = wave_sum(s_acc);
-  const float bg = white ? 1.f - s_acc : 0.f;
-  const float c0 = s_r + bg, c1 = s_g + bg, c2 = s_b + bg;
-  const float e0 = c0 - pixels[ray * 3], e1 = c1 - pixels[ray * 3 + 1], e2 = c2 - pixels[ray * 3 + 2];
-  const float scale = 2.f / (float)(B * 3);
-  const float g0 = e0 * scale, g1 = e1 * scale, g2 = e2 * scale;
-  if (ray_ok && lane == 0) {
-    ray_sse[ray] = (e0 * e0 + e1 * e1) + e2 * e2;
-    if (comp_rgb) { comp_rgb[ray * 3] = c0; comp_rgb[ray * 3 + 1] = c1; comp_rgb[ray * 3 + 2] = c2; }
-  }
-  float suffix = 0.f;  // sum over later samples of dL/dw_j * w_j
-#pragma unroll
-  for (int ch = kMaxChunks - 1; ch >= 0; --ch) {
-    if (ch >= nch) continue;
-    const SampleState& q = st[ch];
-    const bool valid = ch * 64 + lane < S;
-    const float alpha = 1.f - q.e;
-    const float w = alpha * q.T;
-    const float dw = g0 * (q.rgb[0] - bgc) + g1 * (q.rgb[1] - bgc) + g2 * (q.rgb[2] - bgc);
-    const float G = valid ? dw * w : 0.f;
-    const float incl = wave_rscan_add(G, lane);
-    float excl = __shfl_down(incl, 1);
-    if (lane == 63) excl = 0.f;
-    const float R = suffix + excl;
-    suffix += __shfl(incl, 0);
-    const float fct = (1.f - alpha) + 1e-10f;
-    const float dalpha = dw * q.T - R / fct;
-    const float dsigma = dalpha * q.dist * q.e;
-    const int64_t base = ray * S + ch * 64;
-    if (ray_ok && valid) d_raw_sigma[base + lane] = q.raw_sigma > 0.f ? dsigma : 0.f;
-    __syncthreads();
-    if (valid) {
-      const float dp[3] = {g0 * w * q.rgb[0] * (1.f - q.rgb[0]), g1 * w * q.rgb[1] * (1.f - q.rgb[1]),
-                           g2 * w * q.rgb[2] * (1.f - q.rgb[2])};
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int k = 0; k < K; ++k) lds[wave][lane * CS + c * K + k] = dp[c] * Y[k];
-    }
-    __syncthreads();
-    const int nvalid = S - ch * 64 < 64 ? S - ch * 64 : 64;
-    if (ray_ok)
-      for (int idx = lane; idx < nvalid * C; idx += 64) {
-        const int s = idx / C, j = idx - s * C;
-        d_raw_rgb[base * C + idx] = lds[wave][s * CS + j];
-      }
-  }
-}
-
-// NeRF-SG training form (nerf_sh/nerf/models.py:273-292, :331-348 with sg_dim > 0, differentiated by train.py:116): the kernel
-// above with the basis of the forward SG kernel (the same expression, so the forward values agree to float32 round-off), plus
-// the gradient with respect to the lobes.  dL/dY_k = sum_s sum_c dp[c,s] raw[s, c K + k] with dp[c,s] = g_c w_s rgb_cs (1 -
+// Blocks past the rays serve the sparsity rows appended to the pass.
+//
+// SG selects the NeRF-SG form (nerf_sh/nerf/models.py:273-292, :331-348 with sg_dim > 0, differentiated by train.py:116): the
+// basis of the forward SG kernel (the same sg_lobe expression, so the forward values agree to float32 round-off), plus the
+// gradient with respect to the lobes.  dL/dY_k = sum_s sum_c dp[c,s] raw[s, c K + k] with dp[c,s] = g_c w_s rgb_cs (1 -
 // rgb_cs); g_c is known only after the forward sweep, by when the reverse loop has reused the LDS tile, so the per-lane sums
 // A[c K + k] = sum_s w_s rgb_cs (1 - rgb_cs) raw[s, c K + k] are taken during the forward sweep, while a chunk's coefficients
 // still sit in LDS, and scaled by g_c afterwards (3K registers per lane; the LDS tile, not the registers, bounds the occupancy).
 // Then dL/dlambda_k = dL/dY_k Y_k (mu_k . v - 1) and dL/dmu_k = dL/dY_k Y_k lambda_k v per ray; the four rays of a workgroup
 // are added in a fixed order and written to lobe_partials [ray block][K][4] (sg_lobe_grad_kernel adds the blocks: no atomics).
+// Without SG, lobes and lobe_partials are not read and nothing of this is compiled in.
 static_assert(kRaysPerBlock == PXO_SG_RAYS_PER_BLOCK, "lobe_partials is sized by PXO_SG_RAYS_PER_BLOCK");
-template <int K>
-__device__ __forceinline__ void sg_basis(const float* __restrict__ lobes, float vx, float vy, float vz, float (&Y)[K]) {
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(lobes[4 * i + 1], vx), __fmul_rn(lobes[4 * i + 2], vy)), __fmul_rn(lobes[4 * i + 3], vz));
-    Y[i] = __fmul_rn(expf(__fmul_rn(lobes[4 * i], __fsub_rn(dot, 1.0f))), 1.0f / (float)K);
-  }
-}
-
-template <int DEG>
-__global__ __launch_bounds__(kRayThreads) void sg_shade_composite_train_kernel(
+template <int DEG, bool SG>
+__global__ __launch_bounds__(kRayThreads) void shade_composite_train_kernel(
     const float* __restrict__ raw_rgb, const float* __restrict__ raw_sigma, const float* __restrict__ z_vals,
     const float* __restrict__ dirs, const float* __restrict__ viewdirs, const float* __restrict__ pixels, int64_t B,
     int S, int white, float* __restrict__ comp_rgb, float* __restrict__ weights, float* __restrict__ ray_sse,
@@ -452,19 +378,9 @@ __global__ __launch_bounds__(kRayThreads) void sg_shade_composite_train_kernel(
   constexpr int K = (DEG + 1) * (DEG + 1), C = 3 * K, CS = C | 1;
   __shared__ float lds[kRaysPerBlock][64 * CS];
   const int64_t ray_blocks = (B + kRaysPerBlock - 1) / kRaysPerBlock;
-  if ((int64_t)blockIdx.x >= ray_blocks) {       // sparsity rows [B*S, B*S + n_sp)
-    const int64_t r0 = ((int64_t)blockIdx.x - ray_blocks) * kRayThreads;
-    const int64_t row = r0 + threadIdx.x;
-    const int64_t base = B * S;
-    if (row < n_sp) {
-      const float raw = raw_sigma[base + row];
-      const float e = expf(-sp_length * fmaxf(raw, 0.f));
-      sp_exp[row] = e;
-      d_raw_sigma[base + row] = raw > 0.f ? (sp_weight * sp_length / (float)n_sp) * e : 0.f;
-    }
-    const int64_t nrow = n_sp - r0 < kRayThreads ? n_sp - r0 : kRayThreads;
-    float* __restrict__ z0 = d_raw_rgb + (base + r0) * C;
-    for (int64_t i = threadIdx.x; i < nrow * C; i += kRayThreads) z0[i] = 0.f;
+  if ((int64_t)blockIdx.x >= ray_blocks) {
+    sparsity_rows(raw_sigma, B * S, ((int64_t)blockIdx.x - ray_blocks) * kRayThreads, n_sp, C, sp_weight, sp_length, sp_exp,
+                  d_raw_rgb, d_raw_sigma);
     return;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -473,15 +389,21 @@ __global__ __launch_bounds__(kRayThreads) void sg_shade_composite_train_kernel(
   if (!ray_ok) ray = B - 1;
   const float vx = viewdirs[ray * 3], vy = viewdirs[ray * 3 + 1], vz = viewdirs[ray * 3 + 2];
   float Y[K];
-  sg_basis<K>(lobes, vx, vy, vz, Y);
+  if constexpr (SG) {
+    sg_basis<K>(lobes, vx, vy, vz, Y);
+  } else {
+    sh_basis<DEG>(vx, vy, vz, Y);
+  }
   const float dx = dirs[ray * 3], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
   const float norm_d = sqrtf(dx * dx + dy * dy + dz * dz);
   const float bgc = white ? 1.f : 0.f;
   const int nch = (S + 63) / 64;
   SampleState st[kMaxChunks];
-  float A[C];
+  [[maybe_unused]] float A[SG ? C : 1];
+  if constexpr (SG) {
 #pragma unroll
-  for (int j = 0; j < C; ++j) A[j] = 0.f;
+    for (int j = 0; j < C; ++j) A[j] = 0.f;
+  }
   float carry = 1.f, s_r = 0.f, s_g = 0.f, s_b = 0.f, s_acc = 0.f;
 #pragma unroll
   for (int ch = 0; ch < kMaxChunks; ++ch)
@@ -490,12 +412,14 @@ __global__ __launch_bounds__(kRayThreads) void sg_shade_composite_train_kernel(
       const float w = (1.f - st[ch].e) * st[ch].T;
       s_r += w * st[ch].rgb[0]; s_g += w * st[ch].rgb[1]; s_b += w * st[ch].rgb[2]; s_acc += w;
       if (weights && ray_ok && ch * 64 + lane < S) weights[ray * S + ch * 64 + lane] = w;
-      if (ch * 64 + lane < S) {                  // the chunk's coefficients are still in the tile (rows past S hold stale data)
+      if constexpr (SG) {
+        if (ch * 64 + lane < S) {                // the chunk's coefficients are still in the tile (rows past S hold stale data)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float q = w * st[ch].rgb[c] * (1.f - st[ch].rgb[c]);
+          for (int c = 0; c < 3; ++c) {
+            const float q = w * st[ch].rgb[c] * (1.f - st[ch].rgb[c]);
 #pragma unroll
-          for (int k = 0; k < K; ++k) A[c * K + k] += q * lds[wave][lane * CS + c * K + k];
+            for (int k = 0; k < K; ++k) A[c * K + k] += q * lds[wave][lane * CS + c * K + k];
+          }
         }
       }
     }
@@ -509,69 +433,40 @@ __global__ __launch_bounds__(kRayThreads) void sg_shade_composite_train_kernel(
     ray_sse[ray] = (e0 * e0 + e1 * e1) + e2 * e2;
     if (comp_rgb) { comp_rgb[ray * 3] = c0; comp_rgb[ray * 3 + 1] = c1; comp_rgb[ray * 3 + 2] = c2; }
   }
-  // dL/dY_k of this ray, left in lane k
-  float dY = 0.f;
+  [[maybe_unused]] float dY = 0.f;               // dL/dY_k of this ray, left in lane k
+  if constexpr (SG) {
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const float t = wave_sum((g0 * A[k] + g1 * A[K + k]) + g2 * A[2 * K + k]);
-    if (lane == k) dY = t;
+    for (int k = 0; k < K; ++k) {
+      const float t = wave_sum((g0 * A[k] + g1 * A[K + k]) + g2 * A[2 * K + k]);
+      if (lane == k) dY = t;
+    }
   }
   float suffix = 0.f;  // sum over later samples of dL/dw_j * w_j
 #pragma unroll
-  for (int ch = kMaxChunks - 1; ch >= 0; --ch) {
-    if (ch >= nch) continue;
-    const SampleState& q = st[ch];
-    const bool valid = ch * 64 + lane < S;
-    const float alpha = 1.f - q.e;
-    const float w = alpha * q.T;
-    const float dw = g0 * (q.rgb[0] - bgc) + g1 * (q.rgb[1] - bgc) + g2 * (q.rgb[2] - bgc);
-    const float G = valid ? dw * w : 0.f;
-    const float incl = wave_rscan_add(G, lane);
-    float excl = __shfl_down(incl, 1);
-    if (lane == 63) excl = 0.f;
-    const float R = suffix + excl;
-    suffix += __shfl(incl, 0);
-    const float fct = (1.f - alpha) + 1e-10f;
-    const float dalpha = dw * q.T - R / fct;
-    const float dsigma = dalpha * q.dist * q.e;
-    const int64_t base = ray * S + ch * 64;
-    if (ray_ok && valid) d_raw_sigma[base + lane] = q.raw_sigma > 0.f ? dsigma : 0.f;
+  for (int ch = kMaxChunks - 1; ch >= 0; --ch)
+    if (ch < nch)
+      composite_reverse_chunk<DEG>(st[ch], ch, S, lane, lds[wave], Y, ray, ray_ok, g0, g1, g2, bgc, suffix, d_raw_rgb, d_raw_sigma);
+  if constexpr (SG) {
+    // the ray's gradient with respect to (lambda_k, mu_k) from lane k, then the workgroup's rays in wave order
     __syncthreads();
-    if (valid) {
-      const float dp[3] = {g0 * w * q.rgb[0] * (1.f - q.rgb[0]), g1 * w * q.rgb[1] * (1.f - q.rgb[1]),
-                           g2 * w * q.rgb[2] * (1.f - q.rgb[2])};
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int k = 0; k < K; ++k) lds[wave][lane * CS + c * K + k] = dp[c] * Y[k];
+    if (lane < K) {
+      const float lam = lobes[4 * lane];
+      float dot;
+      const float Yk = sg_lobe<K>(lobes, lane, vx, vy, vz, dot);
+      const float t = ray_ok ? dY * Yk : 0.f;
+      const float tl = t * lam;
+      lds[wave][4 * lane + 0] = t * (dot - 1.f);
+      lds[wave][4 * lane + 1] = tl * vx;
+      lds[wave][4 * lane + 2] = tl * vy;
+      lds[wave][4 * lane + 3] = tl * vz;
     }
     __syncthreads();
-    const int nvalid = S - ch * 64 < 64 ? S - ch * 64 : 64;
-    if (ray_ok)
-      for (int idx = lane; idx < nvalid * C; idx += 64) {
-        const int s = idx / C, j = idx - s * C;
-        d_raw_rgb[base * C + idx] = lds[wave][s * CS + j];
-      }
-  }
-  // the ray's gradient with respect to (lambda_k, mu_k) from lane k, then the workgroup's rays in wave order
-  __syncthreads();
-  if (lane < K) {
-    const float lam = lobes[4 * lane];
-    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(lobes[4 * lane + 1], vx), __fmul_rn(lobes[4 * lane + 2], vy)), __fmul_rn(lobes[4 * lane + 3], vz));
-    const float Yk = __fmul_rn(expf(__fmul_rn(lam, __fsub_rn(dot, 1.0f))), 1.0f / (float)K);
-    const float t = ray_ok ? dY * Yk : 0.f;
-    const float tl = t * lam;
-    lds[wave][4 * lane + 0] = t * (dot - 1.f);
-    lds[wave][4 * lane + 1] = tl * vx;
-    lds[wave][4 * lane + 2] = tl * vy;
-    lds[wave][4 * lane + 3] = tl * vz;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < 4 * K) {
-    float sum = lds[0][threadIdx.x];
+    if ((int)threadIdx.x < 4 * K) {
+      float sum = lds[0][threadIdx.x];
 #pragma unroll
-    for (int wv = 1; wv < kRaysPerBlock; ++wv) sum += lds[wv][threadIdx.x];
-    lobe_partials[(int64_t)blockIdx.x * (4 * K) + threadIdx.x] = sum;
+      for (int wv = 1; wv < kRaysPerBlock; ++wv) sum += lds[wv][threadIdx.x];
+      lobe_partials[(int64_t)blockIdx.x * (4 * K) + threadIdx.x] = sum;
+    }
   }
 }
 
@@ -641,78 +536,90 @@ int launch_sg_lobe_grad(const float* part_a, int64_t nb_a, const float* part_b, 
   return check_launch("sg_lobe_grad");
 }
 
-#define PXO_DEG_SWITCH(deg, CALL) \
-  switch (deg) {                  \
-    case 0: CALL(0); break;       \
-    case 1: CALL(1); break;       \
-    case 2: CALL(2); break;       \
-    case 3: CALL(3); break;       \
-    default: CALL(4); break;      \
+// ---- launchers of the compositing kernels: one wave per ray, kRaysPerBlock rays per workgroup ----
+// The grid for B rays of S samples plus extra_blocks workgroups; false when there is nothing to launch, with the status in rc
+// (PXO_OK for an empty batch, PXO_ERR_ARG for an S the kernels' chunk arrays cannot hold).
+static bool ray_grid(int64_t B, int S, int64_t extra_blocks, dim3& grid, int& rc) {
+  rc = PXO_OK;
+  if (B == 0) return false;
+  if (S > 64 * kMaxChunks || S < 1) {
+    set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks);
+    rc = PXO_ERR_ARG;
+    return false;
   }
+  grid = dim3((unsigned)((B + kRaysPerBlock - 1) / kRaysPerBlock + extra_blocks));
+  return true;
+}
+
+// f(std::integral_constant<int, deg>) for the SH degree (sg_dim = (deg+1)^2 lobes) of the configuration
+template <typename F>
+static void deg_switch(int deg, F&& f) {
+  switch (deg) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+int launch_vd_composite_fwd(int white_bkgd, const float* raw_rgb, const float* raw_sigma, const float* z, const float* dirs,
+                            int64_t B, int S, float* comp_rgb, float* disp, float* acc, float* weights, hipStream_t s) {
+  dim3 grid;
+  int rc;
+  if (!ray_grid(B, S, 0, grid, rc)) return rc;
+  hipLaunchKernelGGL(vd_composite_fwd_kernel, grid, dim3(kRayThreads), 0, s, raw_rgb, raw_sigma, z, dirs, B, S, white_bkgd,
+                     comp_rgb, disp, acc, weights);
+  return check_launch("vd_composite_fwd");
+}
 
 int launch_shade_composite_fwd(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, const float* z,
                                const float* dirs, const float* viewdirs, int64_t B, int S, float* comp_rgb,
                                float* disp, float* acc, float* weights, hipStream_t s, const float* lobes) {
-  if (B == 0) return PXO_OK;
-  if (S > 64 * kMaxChunks || S < 1) { set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks); return PXO_ERR_ARG; }
-  dim3 grid((unsigned)((B + kRaysPerBlock - 1) / kRaysPerBlock)), block(kRayThreads);
-  if (lobes) {       // NeRF-SG: sg_dim = (sh_deg+1)^2 lobes
-#define CALL(D) hipLaunchKernelGGL((shade_composite_fwd_kernel<D, true>), grid, block, 0, s, raw_rgb, raw_sigma, z, dirs, \
-                                   viewdirs, B, S, cfg->white_bkgd, comp_rgb, disp, acc, weights, lobes)
-    PXO_DEG_SWITCH(cfg->sh_deg, CALL)
-#undef CALL
-    return check_launch("shade_composite_fwd (SG)");
-  }
-#define CALL(D) hipLaunchKernelGGL((shade_composite_fwd_kernel<D>), grid, block, 0, s, raw_rgb, raw_sigma, z, dirs, \
-                                   viewdirs, B, S, cfg->white_bkgd, comp_rgb, disp, acc, weights, (const float*)nullptr)
-  PXO_DEG_SWITCH(cfg->sh_deg, CALL)
-#undef CALL
-  return check_launch("shade_composite_fwd");
+  dim3 grid;
+  int rc;
+  if (!ray_grid(B, S, 0, grid, rc)) return rc;
+  deg_switch(cfg->sh_deg, [&](auto deg) {
+    constexpr int D = decltype(deg)::value;
+    const auto kernel = lobes ? shade_composite_fwd_kernel<D, true> : shade_composite_fwd_kernel<D, false>;   // NeRF-SG : SH
+    hipLaunchKernelGGL(kernel, grid, dim3(kRayThreads), 0, s, raw_rgb, raw_sigma, z, dirs, viewdirs, B, S, cfg->white_bkgd,
+                       comp_rgb, disp, acc, weights, lobes);
+  });
+  return check_launch(lobes ? "shade_composite_fwd (SG)" : "shade_composite_fwd");
 }
 
 int launch_shade_composite_bwd(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, const float* z,
                                const float* dirs, const float* viewdirs, const float* d_comp_rgb, int64_t B, int S,
                                float* d_raw_rgb, float* d_raw_sigma, hipStream_t s) {
-  if (B == 0) return PXO_OK;
-  if (S > 64 * kMaxChunks || S < 1) { set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks); return PXO_ERR_ARG; }
-  dim3 grid((unsigned)((B + kRaysPerBlock - 1) / kRaysPerBlock)), block(kRayThreads);
-#define CALL(D) hipLaunchKernelGGL((shade_composite_bwd_kernel<D>), grid, block, 0, s, raw_rgb, raw_sigma, z, dirs, \
-                                   viewdirs, d_comp_rgb, B, S, cfg->white_bkgd, d_raw_rgb, d_raw_sigma)
-  PXO_DEG_SWITCH(cfg->sh_deg, CALL)
-#undef CALL
+  dim3 grid;
+  int rc;
+  if (!ray_grid(B, S, 0, grid, rc)) return rc;
+  deg_switch(cfg->sh_deg, [&](auto deg) {
+    hipLaunchKernelGGL(shade_composite_bwd_kernel<decltype(deg)::value>, grid, dim3(kRayThreads), 0, s, raw_rgb, raw_sigma, z,
+                       dirs, viewdirs, d_comp_rgb, B, S, cfg->white_bkgd, d_raw_rgb, d_raw_sigma);
+  });
   return check_launch("shade_composite_bwd");
 }
 
 int launch_shade_composite_train(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, const float* z,
                                  const float* dirs, const float* viewdirs, const float* pixels, int64_t B, int S,
                                  float* comp_rgb, float* weights, float* ray_sse, float* d_raw_rgb, float* d_raw_sigma,
-                                 int64_t n_sp, float* sp_exp, hipStream_t s) {
-  if (B == 0) return PXO_OK;
-  if (S > 64 * kMaxChunks || S < 1) { set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks); return PXO_ERR_ARG; }
-  const int64_t blocks = (B + kRaysPerBlock - 1) / kRaysPerBlock + (n_sp + kRayThreads - 1) / kRayThreads;
-  dim3 grid((unsigned)blocks), block(kRayThreads);
-#define CALL(D) hipLaunchKernelGGL((shade_composite_train_kernel<D>), grid, block, 0, s, raw_rgb, raw_sigma, z, dirs, \
-                                   viewdirs, pixels, B, S, cfg->white_bkgd, comp_rgb, weights, ray_sse, d_raw_rgb,       \
-                                   d_raw_sigma, n_sp, cfg->sparsity_weight, cfg->sparsity_length, sp_exp)
-  PXO_DEG_SWITCH(cfg->sh_deg, CALL)
-#undef CALL
-  return check_launch("shade_composite_train");
-}
-
-int launch_sg_shade_composite_train(const PxoCfg* cfg, const float* lobes, const float* raw_rgb, const float* raw_sigma,
-                                    const float* z, const float* dirs, const float* viewdirs, const float* pixels, int64_t B,
-                                    int S, float* comp_rgb, float* weights, float* ray_sse, float* d_raw_rgb,
-                                    float* d_raw_sigma, int64_t n_sp, float* sp_exp, float* lobe_partials, hipStream_t s) {
-  if (B == 0) return PXO_OK;
-  if (S > 64 * kMaxChunks || S < 1) { set_error("samples per ray %d not in [1,%d]", S, 64 * kMaxChunks); return PXO_ERR_ARG; }
-  const int64_t blocks = sg_ray_blocks(B) + (n_sp + kRayThreads - 1) / kRayThreads;
-  dim3 grid((unsigned)blocks), block(kRayThreads);
-#define CALL(D) hipLaunchKernelGGL((sg_shade_composite_train_kernel<D>), grid, block, 0, s, raw_rgb, raw_sigma, z, dirs, \
-                                   viewdirs, pixels, B, S, cfg->white_bkgd, comp_rgb, weights, ray_sse, d_raw_rgb,          \
-                                   d_raw_sigma, n_sp, cfg->sparsity_weight, cfg->sparsity_length, sp_exp, lobes, lobe_partials)
-  PXO_DEG_SWITCH(cfg->sh_deg, CALL)
-#undef CALL
-  return check_launch("shade_composite_train (SG)");
+                                 int64_t n_sp, float* sp_exp, const float* lobes, float* lobe_partials, hipStream_t s) {
+  if ((lobes == nullptr) != (lobe_partials == nullptr)) {
+    set_error("shade_composite_train: lobes and lobe_partials go together (both for NeRF-SG, neither for SH)");
+    return PXO_ERR_ARG;
+  }
+  dim3 grid;
+  int rc;
+  if (!ray_grid(B, S, (n_sp + kRayThreads - 1) / kRayThreads, grid, rc)) return rc;
+  deg_switch(cfg->sh_deg, [&](auto deg) {
+    constexpr int D = decltype(deg)::value;
+    const auto kernel = lobes ? shade_composite_train_kernel<D, true> : shade_composite_train_kernel<D, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kRayThreads), 0, s, raw_rgb, raw_sigma, z, dirs, viewdirs, pixels, B, S,
+                       cfg->white_bkgd, comp_rgb, weights, ray_sse, d_raw_rgb, d_raw_sigma, n_sp, cfg->sparsity_weight,
+                       cfg->sparsity_length, sp_exp, lobes, lobe_partials);
+  });
+  return check_launch(lobes ? "shade_composite_train (SG)" : "shade_composite_train");
 }
 
 // ------------------------------------------------------------------------------------------

@@ -222,6 +222,16 @@ def adam_pack_step(cfg, params, m, v, grads, lr, step, packed, grad_scale=1.0):
                                  float(grad_scale), _f(f0), _f(b0), _f(f1), _f(b1), _stream()), "pxo_adam_pack_step")
 
 
+def _train_outputs(raw_rgb, B, S, n_sp, want_rgb, want_weights):
+    """The output dict of the *_shade_composite_train wrappers for raw_rgb [B*S + n_sp, 3K]."""
+    C = raw_rgb.shape[-1]
+    dev = raw_rgb.device
+    return {"comp_rgb": _new(B, 3, device=dev) if want_rgb else None,
+            "weights": _new(B, S, device=dev) if want_weights else None,
+            "ray_sse": _new(B, device=dev), "d_raw_rgb": _new(B * S + n_sp, C, device=dev),
+            "d_raw_sigma": _new(B * S + n_sp, device=dev), "sp_exp": _new(max(n_sp, 1), device=dev)}
+
+
 def shade_composite_train(cfg, raw_rgb, raw_sigma, z_vals, directions, viewdirs, pixels, n_sp=0, want_rgb=True,
                           want_weights=True):
     """Forward compositing + pixel loss + reverse in one launch: returns dict(comp_rgb, weights, ray_sse, d_raw_rgb,
@@ -229,12 +239,7 @@ def shade_composite_train(cfg, raw_rgb, raw_sigma, z_vals, directions, viewdirs,
     _require_gpu()
     lib = _lib.load()
     B, S = z_vals.shape
-    C = raw_rgb.shape[-1]
-    dev = raw_rgb.device
-    out = {"comp_rgb": _new(B, 3, device=dev) if want_rgb else None,
-           "weights": _new(B, S, device=dev) if want_weights else None,
-           "ray_sse": _new(B, device=dev), "d_raw_rgb": _new(B * S + n_sp, C, device=dev),
-           "d_raw_sigma": _new(B * S + n_sp, device=dev), "sp_exp": _new(max(n_sp, 1), device=dev)}
+    out = _train_outputs(raw_rgb, B, S, n_sp, want_rgb, want_weights)
     check(lib.pxo_shade_composite_train(ctypes.byref(cfg), _f(raw_rgb), _f(raw_sigma), _f(z_vals), _f(directions),
                                         _f(viewdirs), _f(pixels), B, S, _f(out["comp_rgb"]), _f(out["weights"]),
                                         _f(out["ray_sse"]), _f(out["d_raw_rgb"]), _f(out["d_raw_sigma"]), n_sp,
@@ -318,14 +323,10 @@ def sg_shade_composite_train(cfg, lobes, raw_rgb, raw_sigma, z_vals, directions,
     _require_gpu()
     lib = _lib.load()
     B, S = z_vals.shape
-    C = raw_rgb.shape[-1]
     K = sh_dim(cfg)
     dev = raw_rgb.device
-    out = {"comp_rgb": _new(B, 3, device=dev) if want_rgb else None,
-           "weights": _new(B, S, device=dev) if want_weights else None,
-           "ray_sse": _new(B, device=dev), "d_raw_rgb": _new(B * S + n_sp, C, device=dev),
-           "d_raw_sigma": _new(B * S + n_sp, device=dev), "sp_exp": _new(max(n_sp, 1), device=dev),
-           "d_lobes": _new(K, 4, device=dev)}
+    out = _train_outputs(raw_rgb, B, S, n_sp, want_rgb, want_weights)
+    out["d_lobes"] = _new(K, 4, device=dev)
     partials = _new(max(-(-B // _lib.SG_RAYS_PER_BLOCK), 1) * K * 4, device=dev)
     check(lib.pxo_sg_shade_composite_train(ctypes.byref(cfg), _f(lobes), _f(raw_rgb), _f(raw_sigma), _f(z_vals), _f(directions),
                                            _f(viewdirs), _f(pixels), B, S, _f(out["comp_rgb"]), _f(out["weights"]),

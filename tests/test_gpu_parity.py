@@ -265,14 +265,22 @@ def _oracle_composite(cfg, rays, raw_rgb, raw_sigma, z):
     return O.volumetric_rendering(rgb, torch.relu(raw_sigma), z, rays.directions, cfg.white_bkgd)
 
 
-@pytest.mark.parametrize("deg,S,white,opaque", [(3, 64, True, False), (3, 192, True, False), (4, 192, True, True),
-                                                  (1, 40, False, False), (0, 7, True, False), (2, 130, True, True),
-                                                  (3, 256, True, False), (4, 255, False, False)])
-def test_shade_composite_fwd_bwd(deg, S, white, opaque):
+def _ray_cases(B, cases, edge_cases):
+    """`cases` at B rays, under the ids they had before B was a parameter, then `edge_cases`, each with its own B in front: a
+    partial ray block, exactly one block and one ray in the second block, at S = 1 (the 1e10 distance alone), 63 / 65 (the
+    lane-63 carry, one sample in the second chunk) and 256 (all four chunks)."""
+    return ([pytest.param(B, *c, id="-".join(str(v) for v in c)) for c in cases] +
+            [pytest.param(*c, id="B" + "-".join(str(v) for v in c)) for c in edge_cases])
+
+
+@pytest.mark.parametrize("B,deg,S,white,opaque", _ray_cases(
+    37, [(3, 64, True, False), (3, 192, True, False), (4, 192, True, True), (1, 40, False, False), (0, 7, True, False),
+         (2, 130, True, True), (3, 256, True, False), (4, 255, False, False)],
+    [(1, 0, 1, True, False), (4, 2, 63, False, False), (5, 4, 65, True, True), (5, 2, 256, True, False)]))
+def test_shade_composite_fwd_bwd(B, deg, S, white, opaque):
     ops = _ops(); dev = _gpu()
     cfg = O.Cfg(sh_deg=deg, white_bkgd=white)
     pcfg = pxo_cfg(ops, cfg)
-    B = 37
     rays, raw_rgb, raw_sigma, z = _composite_inputs(B, S, cfg.num_rgb_channels, 17 + S, opaque)
     args = (raw_rgb.reshape(B * S, -1).to(dev), raw_sigma.reshape(-1).to(dev), z.to(dev), rays.directions.to(dev),
             rays.viewdirs.to(dev))
@@ -291,15 +299,15 @@ def test_shade_composite_fwd_bwd(deg, S, white, opaque):
     close("d_raw_sigma", d_sigma, rs.grad.reshape(-1), rtol=2e-4, atol=1e-6 * max(1.0, float(rs.grad.abs().max())))
 
 
-@pytest.mark.parametrize("deg,S,white,n_sp", [(3, 64, True, 0), (3, 192, True, 1000), (4, 192, True, 257), (1, 40, False, 3),
-                                              (3, 256, True, 100), (4, 255, False, 0)])
-def test_shade_composite_train_fused(deg, S, white, n_sp):
+@pytest.mark.parametrize("B,deg,S,white,n_sp", _ray_cases(
+    41, [(3, 64, True, 0), (3, 192, True, 1000), (4, 192, True, 257), (1, 40, False, 3), (3, 256, True, 100), (4, 255, False, 0)],
+    [(1, 0, 1, True, 1), (4, 2, 63, False, 256), (5, 4, 65, True, 1), (5, 2, 256, True, 256)]))
+def test_shade_composite_train_fused(B, deg, S, white, n_sp):
     """The one-launch training form (compositing + pixel loss + reverse + sparsity rows) against the loss of
     nerf_sh/train.py:77-98 differentiated by autograd on the oracle, and against the separate fwd / bwd kernels."""
     ops = _ops(); dev = _gpu()
     cfg = O.Cfg(sh_deg=deg, white_bkgd=white, sparsity_length=0.07, sparsity_weight=2e-3)
     pcfg = pxo_cfg(ops, cfg)
-    B = 41
     C = cfg.num_rgb_channels
     rays, raw_rgb, raw_sigma, z = _composite_inputs(B, S, C, 29 + S, False)
     gen = torch.Generator().manual_seed(5)
