@@ -191,35 +191,44 @@ def _sg_shade_f64(raw_rgb, raw_sigma, lobes, viewdirs, z, dirs, white):
     return O.volumetric_rendering(torch.sigmoid(pre), torch.relu(raw_sigma.double().reshape(B, Sn, 1)), z.double(), dirs.double(), white)
 
 
-@pytest.mark.parametrize("K,precision", [(25, 0), (4, 0), (25, 2)], ids=["sg25-f32", "sg4-f32", "sg25-bf16x6"])
-def test_sg_render_fwd_against_eval_sg_over_the_kernels_own_samples(K, precision):
-    """24 rays, 64 + 128 samples, t_rand / u supplied.  The raw outputs of pxo_eval_points at the kernel's own sample points
-    (pxo_sample_along_rays, then pxo_sample_pdf on the host-composited coarse weights) go through eval_sg and the oracle's
-    volumetric rendering in float64."""
+# (K, precision, Nc, Nf, B); the fine level of the added sample counts has 63, 65 and 256 samples
+_SG_FWD_EDGES = [(K, 0, Nc, Nf, 5) for K in (9, 16) for Nc, Nf in ((20, 43), (20, 45), (128, 128))]
+_SG_FWD_CASES = [(25, 0, 64, 128, 24), (4, 0, 64, 128, 24), (25, 2, 64, 128, 24), (1, 0, 64, 128, 24), (9, 0, 64, 128, 24),
+                 (16, 0, 64, 128, 24)] + _SG_FWD_EDGES
+_SG_FWD_IDS = ["sg25-f32", "sg4-f32", "sg25-bf16x6", "sg1-f32", "sg9-f32", "sg16-f32"] + [f"sg{c[0]}-f32-{c[2]}+{c[3]}-B{c[4]}"
+                                                                                          for c in _SG_FWD_EDGES]
+
+
+@pytest.mark.parametrize("K,precision,Nc,Nf,B", _SG_FWD_CASES, ids=_SG_FWD_IDS)
+def test_sg_render_fwd_against_eval_sg_over_the_kernels_own_samples(K, precision, Nc, Nf, B):
+    """24 rays, 64 + 128 samples, t_rand / u supplied, every lobe count (shade_composite_fwd_kernel<DEG, true> for DEG 0..4);
+    K = 9 and 16 also on 5 rays (a partial ray block) whose fine level has 63 samples (the lane-63 carry without a second
+    chunk), 65 (one live row in the second chunk) and 256 (all four chunks).  The raw outputs of pxo_eval_points at the kernel's
+    own sample points (pxo_sample_along_rays, then pxo_sample_pdf on the host-composited coarse weights) go through eval_sg and
+    the oracle's volumetric rendering in float64."""
     from plenoctree_amd import ops
     dev = _gpu()
     deg = int(round(np.sqrt(K))) - 1
     ocfg = O.Cfg(sh_deg=deg)
-    cfg = ops.make_cfg(sh_deg=deg, mlp_precision=precision)
+    cfg = ops.make_cfg(sh_deg=deg, mlp_precision=precision, num_coarse_samples=Nc, num_fine_samples=Nf)
     flat = make_params(ocfg, seed=20 + K, bias_scale=0.2).to(dev)
     n = flat.numel() // 2
     pk = [ops.pack_weights(cfg, flat[i * n:(i + 1) * n].contiguous(), need_bwd=False)[0] for i in range(2)]
     lobes = torch.from_numpy(G.lobes(K)).to(dev)
     gen = torch.Generator().manual_seed(K)
-    B = 24
     cam = torch.randn(B, 3, generator=gen); cam = 4.0 * cam / cam.norm(dim=-1, keepdim=True)
     dirs = 0.5 * (torch.rand(B, 3, generator=gen) - 0.5) - cam
     dirs = dirs / dirs.norm(dim=-1, keepdim=True) * (1.0 + 0.1 * torch.rand(B, 1, generator=gen))
     vdirs = dirs / dirs.norm(dim=-1, keepdim=True)
-    t_rand, u = torch.rand(B, 64, generator=gen), torch.rand(B, 128, generator=gen)
+    t_rand, u = torch.rand(B, Nc, generator=gen), torch.rand(B, Nf, generator=gen)
     o, d, v, t_rand_d, u_d = (x.to(dev).contiguous() for x in (cam, dirs, vdirs, t_rand, u))
     out = ops.render_fwd(cfg, pk[0], pk[1], o, d, v, randomized=True, t_rand=t_rand_d, u=u_d, lobes=lobes)
     sh = ops.render_fwd(cfg, pk[0], pk[1], o, d, v, randomized=True, t_rand=t_rand_d, u=u_d)
     assert float((out[1][0] - sh[1][0]).abs().max()) > 1e-2                     # not the SH shading of the same weights
-    z_c, pts = ops.sample_along_rays(o, d, 64, 2.0, 6.0, t_rand_d)
+    z_c, pts = ops.sample_along_rays(o, d, Nc, 2.0, 6.0, t_rand_d)
     raw_rgb, raw_sigma = ops.eval_points(cfg, pk[0], pts.reshape(-1, 3), want_rgb=True)
     rgb_c, disp_c, acc_c, w = _sg_shade_f64(raw_rgb.cpu(), raw_sigma.cpu(), G.lobes(K), vdirs, z_c.cpu(), dirs, True)
-    z_f, pts_f = ops.sample_pdf(z_c, w.float().to(dev).contiguous(), o, d, 128, u_d)
+    z_f, pts_f = ops.sample_pdf(z_c, w.float().to(dev).contiguous(), o, d, Nf, u_d)
     raw_rgb, raw_sigma = ops.eval_points(cfg, pk[1], pts_f.reshape(-1, 3), want_rgb=True)
     rgb_f, disp_f, acc_f, _ = _sg_shade_f64(raw_rgb.cpu(), raw_sigma.cpu(), G.lobes(K), vdirs, z_f.cpu(), dirs, True)
     assert 0.05 < float(acc_f.mean()) and float(acc_f.min()) < 0.999            # the rays see translucent and empty space

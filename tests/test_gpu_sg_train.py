@@ -18,6 +18,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import _octree_sg_cases as G                                          # noqa: E402
+import _sg_train_cases as C                                           # noqa: E402
 import _sg_train_oracle as T                                          # noqa: E402
 from _helpers import _gpu, _ops, close, make_params, make_rays, pxo_cfg   # noqa: E402
 from oracle import nerf_oracle as O                                   # noqa: E402
@@ -25,19 +26,7 @@ from oracle import nerf_oracle as O                                   # noqa: E4
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 PRECISIONS = [("f32", 0), ("bf16x6", 2)]
-_worst = {"ratio": 0.0}
-
-
-def _stage_inputs(K, B, S, n_sp, seed):
-    gen = torch.Generator().manual_seed(seed)
-    rays = make_rays(B, seed)
-    raw_rgb = torch.randn(B, S, 3 * K, generator=gen)
-    raw_sigma = torch.randn(B, S, 1, generator=gen) * 3.0
-    z, _ = O.sample_along_rays(rays.origins, rays.directions, S, 2.0, 6.0, torch.rand(B, S, generator=gen))
-    px = torch.rand(B, 3, generator=gen)
-    sp_sigma = torch.randn(n_sp, generator=gen) * 20
-    sp_rgb = torch.randn(n_sp, 3 * K, generator=gen)
-    return rays, raw_rgb, raw_sigma, z, px, sp_sigma, sp_rgb
+_worst = {"ratio": 0.0, "edges": 0.0, "partition": 0.0, "step_sg": 0.0, "step_mlp": 0.0}
 
 
 # ---- 1. the stage kernel --------------------------------------------------------------------------------------------
@@ -56,7 +45,7 @@ def test_sg_shade_composite_train_against_the_float64_twin(K, B, S, white, n_sp)
     deg = int(round(np.sqrt(K))) - 1
     cfg = O.Cfg(sh_deg=deg, white_bkgd=white, sparsity_length=0.07, sparsity_weight=2e-3)
     pcfg = pxo_cfg(ops, cfg)
-    rays, raw_rgb, raw_sigma, z, px, sp_sigma, sp_rgb = _stage_inputs(K, B, S, n_sp, 31 + S + K)
+    rays, raw_rgb, raw_sigma, z, px, sp_sigma, sp_rgb = C.stage_inputs(K, B, S, n_sp, C.stage_seed(K, S))
     lobes = torch.from_numpy(G.lobes(K))
     all_rgb = torch.cat([raw_rgb.reshape(B * S, 3 * K), sp_rgb]).to(dev)
     all_sigma = torch.cat([raw_sigma.reshape(-1), sp_sigma]).to(dev)
@@ -85,6 +74,79 @@ def test_sg_shade_composite_train_against_the_float64_twin(K, B, S, white, n_sp)
     assert rel <= 4 * floor, (rel, floor)
     for k in ("d_lobes", "comp_rgb", "d_raw_rgb", "d_raw_sigma", "ray_sse"):
         assert torch.equal(out[k], again[k]), k
+
+
+def _run_stage(ops, dev, cfg, inputs, lobes, n_sp, **kw):
+    rays, raw_rgb, raw_sigma, z, px, sp_sigma, sp_rgb = inputs
+    B, S = z.shape
+    all_rgb = torch.cat([raw_rgb.reshape(B * S, -1), sp_rgb]).to(dev)
+    all_sigma = torch.cat([raw_sigma.reshape(-1), sp_sigma]).to(dev)
+    return ops.sg_shade_composite_train(pxo_cfg(ops, cfg), lobes.to(dev), all_rgb, all_sigma, z.to(dev).contiguous(),
+                                        rays.directions.to(dev).contiguous(), rays.viewdirs.to(dev).contiguous(),
+                                        px.to(dev).contiguous(), n_sp=n_sp, **kw)
+
+
+@pytest.mark.parametrize("case", C.STAGE_CASES, ids=C.stage_id)
+def test_sg_shade_composite_train_at_lobe_count_chunk_and_stride_edges(case):
+    """The edges the product above leaves out (tests/_sg_train_cases.py): K = 9 and 16 (shade_composite_train_kernel<2,true> and
+    <3,true>), S = 1, 63, 65 and 256, and 64, 65 and 129 ray blocks (the second stage of the lobe gradient adds the per-block
+    partials 64 blocks at a time).  The checks of the test above, unchanged, except that the floor of d_lobes is max(float32
+    twin, 1.5e-7): 4 x floor was measured at floors of 1.5e-7 .. 4.1e-7, and a floor estimated from a six-term sum (S = 1 gives
+    8e-8 .. 1e-7) is noisier than that.  tests/test_sg_train_cpu.py holds every case to a gradient norm > 1e-4, no all-zero lobe
+    row, a float32-twin error < 1e-6, and shows that leaving out the last ray block moves d_lobes by > 10 x the bound.
+    Two cases run once more with comp_rgb == weights == NULL (what the fine pass of the step does): bitwise-equal gradients.
+    Two run as rows [:256] and [256:]: the pixel-loss scale is 2 / (3B), so d_lobes = (B1 d1 + B2 d2) / B within the same bound
+    (against the float64 value of the whole batch), and comp_rgb of each part equals the whole's rows bit for bit."""
+    ops = _ops(); dev = _gpu()
+    K, B, S, white, n_sp = case
+    cfg, inputs, lobes, ref, floor, twin32 = C.stage_reference(case)
+    rays, raw_rgb, raw_sigma, z, px, sp_sigma, sp_rgb = inputs
+    out = _run_stage(ops, dev, cfg, inputs, lobes, n_sp)
+    again = _run_stage(ops, dev, cfg, inputs, lobes, n_sp)
+    close("comp_rgb", out["comp_rgb"], ref["comp_rgb"], rtol=1e-5, atol=2e-6)
+    close("weights", out["weights"], ref["weights"], rtol=1e-4, atol=2e-6)
+    close("ray_sse", out["ray_sse"], ref["ray_sse"], rtol=1e-4, atol=1e-7)
+    close("d_raw_rgb", out["d_raw_rgb"][:B * S], ref["d_raw_rgb"].reshape(B * S, -1), rtol=1e-4, atol=1e-8)
+    close("d_raw_sigma", out["d_raw_sigma"][:B * S], ref["d_raw_sigma"].reshape(-1), rtol=2e-4,
+          atol=1e-6 * max(1.0, float(ref["d_raw_sigma"].abs().max())))
+    if n_sp:
+        close("sparsity d_raw_sigma", out["d_raw_sigma"][B * S:], ref["d_sp_sigma"], rtol=1e-5, atol=1e-12)
+        close("sparsity exp", out["sp_exp"][:n_sp], torch.exp(-cfg.sparsity_length * torch.relu(sp_sigma.double())), rtol=1e-6, atol=1e-7)
+        assert bool((out["d_raw_rgb"][B * S:] == 0).all())
+    want = ref["d_lobes"]
+    assert float(want.norm()) > 0
+    rel = float((out["d_lobes"].cpu().double() - want).norm() / want.norm())
+    _worst["edges"] = max(_worst["edges"], rel / floor)
+    print(f"SG{K} B={B} S={S} white={int(white)} n_sp={n_sp}: d_lobes rel L2 {rel:.3e}, float32 twin {twin32:.3e}, floor {floor:.3e}, "
+          f"ratio {rel / floor:.2f} (worst so far {_worst['edges']:.2f})")
+    assert rel <= 4 * floor, (rel, floor)
+    for k in ("d_lobes", "comp_rgb", "d_raw_rgb", "d_raw_sigma", "ray_sse"):
+        assert torch.equal(out[k], again[k]), k
+    if (K, B, S) in C.STAGE_NULL_OUTPUTS:
+        bare = _run_stage(ops, dev, cfg, inputs, lobes, n_sp, want_rgb=False, want_weights=False)
+        assert bare["comp_rgb"] is None and bare["weights"] is None
+        for k in ("d_raw_rgb", "d_raw_sigma", "ray_sse", "d_lobes"):
+            assert torch.equal(out[k], bare[k]), k
+    if (K, B, S) in C.STAGE_PARTITION:
+        cut = C.PARTITION_AT
+        parts = [_run_stage(ops, dev, cfg, C.stage_rows(inputs, rows), lobes, n_sp) for rows in (slice(0, cut), slice(cut, B))]
+        joined = (cut * parts[0]["d_lobes"].cpu().double() + (B - cut) * parts[1]["d_lobes"].cpu().double()) / B
+        gap = float((out["d_lobes"].cpu().double() - joined).norm() / want.norm())
+        _worst["partition"] = max(_worst["partition"], gap / floor)
+        print(f"SG{K} B={B} S={S}: d_lobes whole vs rows [:{cut}] + [{cut}:] {gap:.3e} of the float64 norm, ratio to the floor "
+              f"{gap / floor:.2f} (worst so far {_worst['partition']:.2f})")
+        assert gap <= 4 * floor, (gap, floor)
+        assert torch.equal(parts[0]["comp_rgb"], out["comp_rgb"][:cut]) and torch.equal(parts[1]["comp_rgb"], out["comp_rgb"][cut:])
+
+
+def test_sg_shade_composite_train_refuses_more_samples_than_its_chunks_hold():
+    """S = 257 is one sample past the four chunks of 64: PxoError naming the sample range, nothing launched."""
+    ops = _ops(); dev = _gpu()
+    from plenoctree_amd._lib import PxoError
+    K, B, S = 4, 2, 257
+    cfg = C.stage_cfg(K, True)
+    with pytest.raises(PxoError, match=r"samples per ray 257 not in \[1,256\]"):
+        _run_stage(ops, dev, cfg, C.stage_inputs(K, B, S, 0, C.stage_seed(K, S)), torch.from_numpy(G.lobes(K)), 0)
 
 
 @pytest.mark.parametrize("K,Nc", [(25, 64), (4, 100), (25, 128)])
@@ -187,6 +249,62 @@ def test_sg_train_step_against_the_references_train_step(prec_name, prec):
     assert rel_sg <= 4 * floor_sg, (rel_sg, floor_sg)
     _, st1, grad1, sg1 = _step_once(ops, dev, prec, skip=1)
     _, st2, grad2, sg2 = _step_once(ops, dev, prec)
+    assert torch.equal(grad1, grad) and torch.equal(sg1, sg_grad) and st1 == st
+    assert torch.equal(grad2, grad) and torch.equal(sg2, sg_grad) and st2 == st
+
+
+def _step_case_once(ops, dev, case, prec=0, skip=0):
+    """_step_once's calling pattern on the inputs of a tests/_sg_train_cases.py case."""
+    cfg, flat, sgp, rays, px, t_rand, u, sp = C.step_inputs(case)
+    pcfg = pxo_cfg(ops, cfg)
+    pcfg.mlp_precision, pcfg.skip_zero_rows = prec, skip
+    flat, sgp = flat.to(dev), sgp.to(dev)
+    n = flat.numel() // 2
+    packed = [ops.pack_weights(pcfg, flat[i * n:(i + 1) * n].contiguous()) for i in range(2)]
+    o, d, v = (x.contiguous().to(dev) for x in rays)
+    B = o.shape[0]
+    grads, sg_grads, stats = torch.zeros_like(flat), torch.full_like(sgp, 7.0), torch.zeros(6, device=dev)
+    ws = torch.empty(ops.sg_train_workspace_bytes(pcfg, B), dtype=torch.uint8, device=dev)
+    ops.sg_train_fwd_bwd(pcfg, flat, sgp, packed, o, d, v, px.to(dev), grads, sg_grads, stats, ws, randomized=True,
+                         t_rand=t_rand.to(dev), u=u.to(dev) if cfg.num_fine_samples > 0 else None, sp_points=sp.to(dev))
+    torch.cuda.synchronize()
+    from plenoctree_amd.nerf_sh.nerf import utils
+    return dict(zip(utils.Stats._fields, stats.cpu().tolist())), grads.cpu(), sg_grads.cpu()
+
+
+@pytest.mark.parametrize("case,prec_name,prec", [(c, "f32", 0) for c in C.STEP_CASES] + [(c, "bf16x6", 2) for c in C.STEP_BF16X6],
+                         ids=lambda v: C.step_id(v) if isinstance(v, tuple) else None)
+def test_sg_train_step_past_64_ray_blocks_at_every_lobe_count(case, prec_name, prec):
+    """pxo_sg_train_fwd_bwd against the float64 twin (T.loss_and_grad, computed here once per case) where the fixture of the test
+    above does not reach: every lobe count, 65 and 129 ray blocks per pass (the two-pass lobe reduction takes a second and a
+    third stride), Nf = 0 (the second pass NULL), weight decay on and off.  Inputs: tests/_sg_train_cases.py.  Stats: G1's
+    tolerances.  SG gradient: relative L2 over [3K] <= 4 x the float32 twin's own figure for the case (the rule of the test
+    above); each MLP's gradient: relative L2 <= 2 x the float32 twin's (G1's rule; MLP_1 without a fine level and without weight
+    decay is exactly zero on both sides).  tests/test_sg_train_cpu.py caps those floors (SG 1e-4, MLP 5e-3) and shows that
+    leaving out the last ray block, or either pass, moves the SG gradient by > 10 x the bound.  skip_zero_rows 0 / 1 and a
+    repeated call: bitwise equal; no entry of sg_grads keeps its pre-fill."""
+    ops = _ops(); dev = _gpu()
+    K = case[0]
+    want_stats, want, want_sg, floors = C.step_reference(case)
+    st, grad, sg_grad = _step_case_once(ops, dev, case, prec)
+    n = grad.numel() // 2
+    rel = lambda a, b: float((a.double() - b).norm() / b.norm()) if float(b.norm()) > 0 else float(a.double().norm())
+    rel_sg, rels = rel(sg_grad, want_sg), (rel(grad[:n], want[:n]), rel(grad[n:], want[n:]))
+    ratio = lambda a, f: a / f if f > 0 else (0.0 if a == 0 else float("inf"))
+    _worst["step_sg"] = max(_worst["step_sg"], ratio(rel_sg, floors[0]))
+    _worst["step_mlp"] = max(_worst["step_mlp"], ratio(rels[0], floors[1]), ratio(rels[1], floors[2]))
+    print(f"HIP ({prec_name}) vs float64 twin, {C.step_id(case)}: SG gradient {rel_sg:.2e} (float32 twin {floors[0]:.2e}, ratio "
+          f"{ratio(rel_sg, floors[0]):.2f}); MLP_0 {rels[0]:.2e} ({floors[1]:.2e}, {ratio(rels[0], floors[1]):.2f}), MLP_1 "
+          f"{rels[1]:.2e} ({floors[2]:.2e}, {ratio(rels[1], floors[2]):.2f}); worst so far SG {_worst['step_sg']:.2f}, MLP "
+          f"{_worst['step_mlp']:.2f}")
+    for k in ("loss", "loss_c", "weight_l2", "psnr", "psnr_c"):
+        assert st[k] == pytest.approx(want_stats[k], rel=2e-5), (k, st[k], want_stats[k])
+    assert st["loss_sp"] == pytest.approx(want_stats["loss_sp"], rel=5e-3, abs=1e-9)
+    assert float(want_sg.norm()) > 0 and not bool((sg_grad == 7.0).any())
+    assert rel_sg <= 4 * floors[0], (rel_sg, floors[0])
+    assert rels[0] <= 2 * floors[1] and rels[1] <= 2 * floors[2], (rels, floors)
+    st1, grad1, sg1 = _step_case_once(ops, dev, case, prec, skip=1)
+    st2, grad2, sg2 = _step_case_once(ops, dev, case, prec)
     assert torch.equal(grad1, grad) and torch.equal(sg1, sg_grad) and st1 == st
     assert torch.equal(grad2, grad) and torch.equal(sg2, sg_grad) and st2 == st
 

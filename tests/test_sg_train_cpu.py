@@ -1,7 +1,8 @@
 """CPU tests of NeRF-SG training: the new ABI symbols and their argument checks, the flag route of nerf_sh.train, checkpoints
 that carry the SG leaves' Adam moments, the layout of the gradient arena, the lobe chain rule of the float64 twin
-(tests/_sg_train_oracle.py) against central differences, and the twin against the reference's own train_step
-(tests/golden/sg_train_grad.npz, written by tests/golden/make_golden_sg_grad.py)."""
+(tests/_sg_train_oracle.py) against central differences, the twin against the reference's own train_step
+(tests/golden/sg_train_grad.npz, written by tests/golden/make_golden_sg_grad.py), and the conditions on the twin that keep the
+GPU tests over tests/_sg_train_cases.py from passing vacuously."""
 import ctypes
 import os
 import re
@@ -12,6 +13,7 @@ import pytest
 import torch
 
 import _octree_sg_cases as G
+import _sg_train_cases as C
 import _sg_train_oracle as T
 from oracle import nerf_oracle as O
 from plenoctree_amd import _lib, build
@@ -269,3 +271,69 @@ def test_twin_against_the_references_train_step_with_sg_leaves(golden_dir):
     rel = float((sg32.double() - want_sg).norm() / want_sg.norm())
     print(f"twin float32 SG gradient vs float64: {rel:.3e} (the reference's own float32: {float(g['grad_f32_vs_f64_rel_l2_sg']):.3e})")
     assert rel < 3 * float(g["grad_f32_vs_f64_rel_l2_sg"])
+
+
+# ---- the cases of tests/test_gpu_sg_train.py cannot pass vacuously --------------------------------------------------------------
+def test_stage_case_lists_name_cases_that_exist():
+    have = {c[:3] for c in C.STAGE_CASES}
+    assert len(have) == len(C.STAGE_CASES) == 12 and set(C.STAGE_NULL_OUTPUTS) <= have and set(C.STAGE_PARTITION) <= have
+    assert {c[0] for c in C.STAGE_CASES} == set(G.KS) and {c[2] for c in C.STAGE_CASES} >= {1, 63, 65, 256}
+    assert {-(-c[1] // C.RAYS_PER_BLOCK) for c in C.STAGE_CASES} >= {64, 65, 129}
+    assert {c[3] for c in C.STAGE_CASES} == {True, False} and {c[4] for c in C.STAGE_CASES} == {0, 257}
+    assert all(c[1] > C.PARTITION_AT for c in C.STAGE_CASES if c[:3] in C.STAGE_PARTITION)
+    assert not any(c[0] == 1 and c[2] == 1 for c in C.STAGE_CASES)       # K = 1 at S = 1: the sharp lobe alone, |d_lobes| = 6e-11
+    assert C.RAYS_PER_BLOCK == _lib.SG_RAYS_PER_BLOCK
+    assert {c[0] for c in C.STEP_CASES} == set(G.KS) and all(-(-c[1] // C.RAYS_PER_BLOCK) in (65, 129) for c in C.STEP_CASES)
+    assert any(c[3] == 0 for c in C.STEP_CASES) and {c[4] > 0 for c in C.STEP_CASES} == {True, False}
+
+
+@pytest.mark.parametrize("case", C.STAGE_CASES, ids=C.stage_id)
+def test_stage_cases_have_a_lobe_gradient_worth_comparing(case):
+    """On the twin alone: |d_lobes| > 1e-4, no all-zero lobe row, and the float32 twin within 1e-6 of the float64 one (so that
+    4 x floor stays a bound that a wrong kernel misses).  Past 64 ray blocks, d_lobes without the last ray block's rays (the
+    loss scale of the full batch kept) differs from the full one by >= 10 x the bound of the GPU test: a second stage that drops
+    its last block fails there."""
+    K, B, S, white, n_sp = case
+    cfg, inputs, lobes, ref, floor, twin32 = C.stage_reference(case)
+    d = ref["d_lobes"]
+    assert tuple(d.shape) == (K, 4) and float(d.norm()) > 1e-4, float(d.norm())
+    assert bool((d.abs().amax(dim=-1) > 0).all())
+    assert twin32 < 1e-6 and C.LOBE_FLOOR <= floor < 1e-6, (twin32, floor)
+    nb = -(-B // C.RAYS_PER_BLOCK)
+    if nb > 64:
+        rows = C.last_block(B)
+        assert rows.start == (nb - 1) * C.RAYS_PER_BLOCK and 1 <= B - rows.start <= C.RAYS_PER_BLOCK
+        share = C.stage_twin(cfg, C.stage_rows(inputs, rows), lobes, torch.float64)["d_lobes"] * ((B - rows.start) / B)
+        head = C.stage_twin(cfg, C.stage_rows(inputs, slice(0, rows.start)), lobes, torch.float64)["d_lobes"] * (rows.start / B)
+        assert float((head + share - d).norm()) <= 1e-12 * float(d.norm())            # the loss is a sum over rays
+        print(f"{C.stage_id(case)}: the last ray block carries {float(share.norm() / d.norm()):.3e} of d_lobes, 10 x bound {40 * floor:.3e}")
+        assert float(share.norm()) >= 10 * 4 * floor * float(d.norm())
+
+
+@pytest.mark.parametrize("case", C.STEP_CASES, ids=C.step_id)
+def test_step_cases_keep_their_bounds_tight_and_see_a_dropped_block_or_pass(case):
+    """On the twin alone.  Caps (not tolerances) on the float32 twin's own error, which the GPU test multiplies by 4 (SG) and 2
+    (MLP): SG <= 1e-4, each MLP <= 5e-3.  The float64 SG gradient with the last ray block left out (the loss scale of the full B
+    kept), with the first pass left out and with the second pass left out each differ from the full gradient by >= 10 x the SG
+    bound of the GPU test: a reduction that drops its last block, part_a or part_b fails there."""
+    K, B, Nc, Nf, wd = case
+    stats, grad, sg_grad, floors = C.step_reference(case)
+    print(f"{C.step_id(case)}: float32 twin vs float64: SG {floors[0]:.3e}, MLP_0 {floors[1]:.3e}, MLP_1 {floors[2]:.3e}")
+    assert 0 < floors[0] <= 1e-4 and 0 < floors[1] <= 5e-3 and floors[2] <= 5e-3, floors
+    n = grad.numel() // 2
+    assert float(grad[:n].norm()) > 0 and (float(grad[n:].norm()) > 0) == (Nf > 0 or wd > 0)
+    bound = 4 * floors[0] * float(sg_grad.norm())
+    first, second = C.step_pass_gradients(case)
+    assert (second is None) == (Nf == 0)
+    cfg, flat, sgp, *_ = C.step_inputs(case, torch.float64)
+    decay = wd * 2.0 * sgp / (flat.numel() + sgp.numel())
+    total = first + (0 if second is None else second) + decay
+    assert float((total - sg_grad).norm()) <= 1e-12 * float(sg_grad.norm())           # the passes and the decay are all there is
+    last = C.step_rows_gradient(case, C.last_block(B))
+    print(f"{C.step_id(case)}: shares of the SG gradient: last ray block {float(last.norm() / sg_grad.norm()):.3e}, first pass "
+          f"{float(first.norm() / sg_grad.norm()):.3e}, second pass "
+          f"{'-' if second is None else format(float(second.norm() / sg_grad.norm()), '.3e')}; 10 x bound {40 * floors[0]:.3e}")
+    assert float(last.norm()) >= 10 * bound and float(first.norm()) >= 10 * bound
+    assert second is None or float(second.norm()) >= 10 * bound
+    if wd > 0:
+        assert float(decay.norm()) >= 10 * bound                                      # the weight-decay term would be missed too
