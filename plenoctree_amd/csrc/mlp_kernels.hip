@@ -20,27 +20,13 @@
 //    1 KiB rows copied out of the LDS tile, together with a 1-bit relu mask in fragment order, so
 //    the backward-data kernel never re-reads them; bias gradients leave as one [9][256] partial per tile slot
 //    (schedule-independent bits; summed in a fixed order by reduce_jobs_kernel).
-#include "pxo_common.h"
+#include "pxo_mlp.h"
 
 namespace pxo {
 
 // ------------------------------------------------------------------------------------------
 // weight packing
 // ------------------------------------------------------------------------------------------
-// W_l[k_in][n_out] of the reference layout with zero padding; l == 8 denotes the fused head
-// (cols [0,C) = Dense_9, col C = Dense_8).
-__device__ __forceinline__ float src_weight(const float* __restrict__ p, int deg, int l, int k, int n) {
-  const int C = rgb_channels(deg);
-  if (l < 8) {
-    if (k >= layer_in(l) || n >= kW) return 0.f;
-    return p[leaf_kernel_off(l, deg) + (int64_t)k * kW + n];
-  }
-  if (k >= kW) return 0.f;
-  if (n < C) return p[leaf_kernel_off(9, deg) + (int64_t)k * C + n];
-  if (n == C) return p[leaf_kernel_off(8, deg) + k];
-  return 0.f;
-}
-
 __global__ void pack_fwd_kernel(const float* __restrict__ p, int deg, float* __restrict__ out) {
   const int nhb = head_blocks(deg);
   const int64_t total = fwd_image_floats(deg);
@@ -49,14 +35,7 @@ __global__ void pack_fwd_kernel(const float* __restrict__ p, int deg, float* __r
        idx += (int64_t)gridDim.x * blockDim.x) {
     float v;
     if (idx >= bias_off) {
-      int b = (int)(idx - bias_off);
-      if (b < 8 * kW) {
-        v = p[leaf_bias_off(b / kW, deg) + (b % kW)];
-      } else {
-        int n = b - 8 * kW;
-        const int C = rgb_channels(deg);
-        v = n < C ? p[leaf_bias_off(9, deg) + n] : (n == C ? p[leaf_bias_off(8, deg)] : 0.f);
-      }
+      v = fwd_image_bias(p, deg, (int)(idx - bias_off));
     } else {
       int l = 0;
       while (l < 8 && idx >= fwd_layer_off(l + 1)) ++l;
@@ -105,20 +84,6 @@ int launch_pack(const PxoCfg* cfg, const float* mlp_params, float* fwd, float* b
 // ------------------------------------------------------------------------------------------
 // positional encoding
 // ------------------------------------------------------------------------------------------
-// column `col` of posenc(p, 0, 10) padded to 64: [p | sin(p*2^l) | sin(p*2^l + pi/2) | 0]
-// (nerf_sh/nerf/model_utils.py:160-173, default order: xb index = l*3 + axis).
-__device__ __forceinline__ float enc_value(float p0, float p1, float p2, int col) {
-  if (col < 3) return col == 0 ? p0 : (col == 1 ? p1 : p2);
-  if (col >= kEnc) return 0.f;
-  int idx = col - 3;
-  const bool shifted = idx >= 30;
-  if (shifted) idx -= 30;
-  const int l = idx / 3, a = idx - 3 * l;
-  float xb = (a == 0 ? p0 : (a == 1 ? p1 : p2)) * (float)(1 << l);
-  if (shifted) xb = xb + 1.5707963267948966f;
-  return sinf(xb);
-}
-
 __global__ void posenc_kernel(const float* __restrict__ x, int64_t N, float* __restrict__ enc) {
   int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (idx >= N * kEnc) return;
@@ -132,27 +97,6 @@ int launch_posenc(const float* x, int64_t N, float* enc, hipStream_t s) {
   int64_t total = N * kEnc;
   hipLaunchKernelGGL(posenc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, N, enc);
   return check_launch("posenc");
-}
-
-// dense-grid point source for octree.extraction step1 / auto_scale
-// (octree/extraction.py:250-262, :290-303): n -> (ix, iy, iz), x slowest.
-struct GridSpec {
-  int enabled;
-  int reso;
-  int x0;
-  float off[3];
-  float scale[3];
-};
-
-__device__ __forceinline__ void grid_point(const GridSpec& g, int64_t n, float& px, float& py, float& pz) {
-  const int r = g.reso;
-  int iz = (int)(n % r);
-  int64_t t = n / r;
-  int iy = (int)(t % r);
-  int ix = (int)(t / r) + g.x0;
-  px = ((((float)ix + 0.5f) / (float)r) - g.off[0]) / g.scale[0];
-  py = ((((float)iy + 0.5f) / (float)r) - g.off[1]) / g.scale[1];
-  pz = ((((float)iz + 0.5f) / (float)r) - g.off[2]) / g.scale[2];
 }
 
 // writes posenc of the tile's 32*RBN points into lds[:, 0:64]; GRID = false (the training kernels: points always come from
@@ -261,13 +205,6 @@ __device__ __forceinline__ void load_b(const WImage& w, int wu, int g, int kg_st
 // sched_barriers pin "issue next loads, then 16 MFMAs": without them hipcc (at the VGPR cap) sinks
 // each load to just before its use and exposes the LDS/L2 latency on every k-group.
 constexpr int kBDist = 3;   // k-groups of look-ahead for the weight fragments (2 measured 0.25 % slower; four register sets either way)
-#define PXO_PIN() __builtin_amdgcn_sched_barrier(0)
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt: a wave would wait at every barrier
-// for the acknowledgement of the activation-tile stores it has just issued (and for its prefetched weight fragments);
-// nothing that crosses waves inside these kernels lives in global memory.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 // the first kBDist weight fragments of a GEMM (issued by the caller ahead of time, e.g. before the previous layer's
 // epilogue, so that their L2 latency is not exposed when the loop starts)
 template <int CBN>
@@ -443,12 +380,7 @@ __device__ __forceinline__ void store_wave_cols(const float* __restrict__ lds, f
   }
 }
 
-// relu mask, one bit per accumulator element in (row block, column block, register) order, packed MSB-first:
-// the forward epilogue shifts the bit "v > 0" in from the carry (mw = 2 mw + bit: compare + add-with-carry), the
-// backward epilogue shifts it out again into the carry that selects the gradient (add + select).
-__device__ __forceinline__ void mask_push(uint32_t& mw, float v) {
-  asm volatile("v_cmp_lt_f32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mw) : "v"(v) : "vcc");
-}
+// the relu-mask bit of the next accumulator element (pxo_mlp.h mask_push wrote it) selects its gradient: add + select
 __device__ __forceinline__ float mask_pop(uint32_t& mw, float x) {
   float r;
   asm volatile("v_add_co_u32 %0, vcc, %0, %0\n\tv_cndmask_b32 %1, 0, %2, vcc" : "+v"(mw), "=v"(r) : "v"(x) : "vcc");
@@ -635,35 +567,6 @@ __device__ __forceinline__ void fwd_tile(float* __restrict__ lds, const float* _
   }
 }
 
-// Tile schedules of the persistent workgroups (both kernels of this file):
-//   static  (DYN = false)  workgroup b runs slots b, b + grid, b + 2 grid, ...
-//   dynamic (DYN = true)   workgroup b runs slot b first and then TAKES slots from a device counter (zero at launch):
-//                          slot = grid + atomicAdd(counter, 1).  The ticket for the NEXT slot is drawn by thread 0 when a
-//                          tile starts (the atomic's round trip rides with the tile's first loads) and handed over
-//                          through LDS when the tile ends: the schedule costs two LDS barriers per tile.
-// Results do not depend on the schedule: a slot's rows, relu-mask words and bias partial are a function of the slot alone.
-// Why dynamic: with one 8-wave workgroup per CU at the full register / LDS budget nothing else can be co-resident, so a
-// collective's kernel on the high-priority exchange stream (dist.GradReducer) takes whole CUs when it starts at a kernel
-// boundary; under the static stride the workgroups that start late on those CUs become the launch's tail, under the counter
-// their share is absorbed by all the others (scripts/contention_probe.py).  Skipping mode (bwd) needs it for load balance.
-struct TileTicket {
-  int* next;                       // LDS word
-  unsigned int* counter;           // device word, zero when the launch starts
-  // thread 0 draws the ticket when the tile starts and keeps it in a register: the atomic's round trip then overlaps the
-  // tile's first loads (its return is waited for with them) instead of holding thread 0's wave -- and with it the whole
-  // workgroup at the tile's first barrier -- for ~1 us
-  __device__ __forceinline__ int draw(int tid) const {
-    return tid == 0 ? (int)gridDim.x + (int)atomicAdd(counter, 1u) : 0;
-  }
-  __device__ __forceinline__ int64_t take(int tid, int ticket) const {
-    if (tid == 0) *next = ticket;
-    lds_barrier();                 // the ticket is in LDS (and every wave is through the tile)
-    const int v = __builtin_amdgcn_readfirstlane(*next);
-    lds_barrier();                 // everyone has read it before thread 0 overwrites it
-    return v;
-  }
-};
-
 template <int NHB, bool SAVE, bool RGB, bool DYN = false>
 __global__ __launch_bounds__(kMlpThreads, kMlpWgPerCu * kMlpWaves / 4) void mlp_fwd_kernel(
     const float* __restrict__ pk, const float* __restrict__ pts, GridSpec grid, int64_t M, int deg, TileSched ts,
@@ -695,47 +598,33 @@ __global__ __launch_bounds__(kMlpThreads, kMlpWgPerCu * kMlpWaves / 4) void mlp_
   }
 }
 
-static unsigned mlp_grid(int64_t M) {
+// one persistent workgroup per CU slot, or one per tile when there are fewer tiles: the grid of every float32 and bf16x6
+// launch, and the one mlp_bwd_partials counts tile slots with
+unsigned mlp_grid(int64_t M) {
   const int64_t tiles = num_tiles(M), cap = kMlpWgPerCu * (int64_t)num_cus();
   return (unsigned)(tiles < cap ? tiles : cap);
-}
-
-template <int NHB>
-static int launch_fwd_nhb(const PxoCfg* cfg, const float* pk, const float* pts, const GridSpec& grid,
-                          int64_t M, float* raw_rgb, float* raw_sigma, float* acts, float* enc,
-                          uint32_t* mask, unsigned int* tile_counter, hipStream_t s) {
-  KernelTimer timer(PXO_PROF_MLP_FWD, M, s);
-  dim3 grid_dim(mlp_grid(M)), block(kMlpThreads);
-  const TileSched ts = tile_sched(M, grid_dim.x);
-  // the training instantiations (saved tensors) take their tiles from `tile_counter` when the caller provides one
-  // (pre-zeroed, see launch_uniform_jobs); the forward-only ones keep the static stride
-  if (acts && raw_rgb && tile_counter)
-    hipLaunchKernelGGL((mlp_fwd_kernel<NHB, true, true, true>), grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, ts,
-                       raw_rgb, raw_sigma, acts, enc, mask, tile_counter);
-  else if (acts && raw_rgb)
-    hipLaunchKernelGGL((mlp_fwd_kernel<NHB, true, true>), grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, ts,
-                       raw_rgb, raw_sigma, acts, enc, mask, tile_counter);
-  else if (acts)
-    hipLaunchKernelGGL((mlp_fwd_kernel<NHB, true, false>), grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, ts,
-                       raw_rgb, raw_sigma, acts, enc, mask, tile_counter);
-  else if (raw_rgb)
-    hipLaunchKernelGGL((mlp_fwd_kernel<NHB, false, true>), grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, ts,
-                       raw_rgb, raw_sigma, acts, enc, mask, tile_counter);
-  else
-    hipLaunchKernelGGL((mlp_fwd_kernel<NHB, false, false>), grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, ts,
-                       raw_rgb, raw_sigma, acts, enc, mask, tile_counter);
-  return check_launch("mlp_fwd");
 }
 
 static int launch_fwd_any(const PxoCfg* cfg, const float* pk, const float* pts, const GridSpec& grid,
                           int64_t M, float* raw_rgb, float* raw_sigma, float* acts, float* enc,
                           uint32_t* mask, unsigned int* tile_counter, hipStream_t s) {
   if (M == 0) return PXO_OK;
-  switch (head_blocks(cfg->sh_deg)) {
-    case 1: return launch_fwd_nhb<1>(cfg, pk, pts, grid, M, raw_rgb, raw_sigma, acts, enc, mask, tile_counter, s);
-    case 2: return launch_fwd_nhb<2>(cfg, pk, pts, grid, M, raw_rgb, raw_sigma, acts, enc, mask, tile_counter, s);
-    default: return launch_fwd_nhb<3>(cfg, pk, pts, grid, M, raw_rgb, raw_sigma, acts, enc, mask, tile_counter, s);
-  }
+  KernelTimer timer(PXO_PROF_MLP_FWD, M, s);
+  dim3 grid_dim(mlp_grid(M)), block(kMlpThreads);
+  const TileSched ts = tile_sched(M, grid_dim.x);
+  head_switch(cfg->sh_deg, [&](auto nhb) {
+    constexpr int NHB = decltype(nhb)::value;
+    // the training instantiations (saved tensors) take their tiles from `tile_counter` when the caller provides one
+    // (pre-zeroed, see launch_uniform_jobs); the forward-only ones keep the static stride
+    const auto kernel = acts && raw_rgb && tile_counter ? mlp_fwd_kernel<NHB, true, true, true>
+                        : acts && raw_rgb               ? mlp_fwd_kernel<NHB, true, true>
+                        : acts                          ? mlp_fwd_kernel<NHB, true, false>
+                        : raw_rgb                       ? mlp_fwd_kernel<NHB, false, true>
+                                                        : mlp_fwd_kernel<NHB, false, false>;
+    hipLaunchKernelGGL(kernel, grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, ts, raw_rgb, raw_sigma, acts, enc, mask,
+                       tile_counter);
+  });
+  return check_launch("mlp_fwd");
 }
 
 int launch_mlp_fwd(const PxoCfg* cfg, const float* packed_fwd, const float* pts, int64_t M,
@@ -747,25 +636,20 @@ int launch_mlp_fwd(const PxoCfg* cfg, const float* packed_fwd, const float* pts,
     if (acts || enc || mask) { set_error("mlp_fwd: mlp_precision bf16x3 is inference-only (no saved tensors)"); return PXO_ERR_UNSUPPORTED; }
     return launch_mlp_fwd_x3(cfg, packed_fwd, pts, 0, 0, nullptr, nullptr, M, raw_rgb, raw_sigma, s);
   }
-  GridSpec g;
-  g.enabled = 0; g.reso = 1; g.x0 = 0;
-  for (int i = 0; i < 3; ++i) { g.off[i] = 0.f; g.scale[i] = 1.f; }
-  return launch_fwd_any(cfg, packed_fwd, pts, g, M, raw_rgb, raw_sigma, acts, enc, mask, tile_counter, s);
+  return launch_fwd_any(cfg, packed_fwd, pts, make_grid_spec(false, 0, 0, nullptr, nullptr), M, raw_rgb, raw_sigma, acts, enc,
+                        mask, tile_counter, s);
 }
 
 int launch_mlp_fwd_grid(const PxoCfg* cfg, const float* packed_fwd, int reso, int x0, int x1,
                         const float* off, const float* scale, float* sigma_out, hipStream_t s) {
-  if (cfg->mlp_precision == PXO_MLP_BF16X6)
-    return launch_mlp_fwd_x6(cfg, packed_fwd, nullptr, reso, x0, off, scale, (int64_t)(x1 - x0) * reso * reso, nullptr, sigma_out,
-                             nullptr, nullptr, nullptr, nullptr, s);
-  if (cfg->mlp_precision == PXO_MLP_BF16X3)
-    return launch_mlp_fwd_x3(cfg, packed_fwd, nullptr, reso, x0, off, scale, (int64_t)(x1 - x0) * reso * reso, nullptr,
-                             sigma_out, s);
-  GridSpec g;
-  g.enabled = 1; g.reso = reso; g.x0 = x0;
-  for (int i = 0; i < 3; ++i) { g.off[i] = off[i]; g.scale[i] = scale[i]; }
   const int64_t M = (int64_t)(x1 - x0) * reso * reso;
-  return launch_fwd_any(cfg, packed_fwd, nullptr, g, M, nullptr, sigma_out, nullptr, nullptr, nullptr, nullptr, s);
+  if (cfg->mlp_precision == PXO_MLP_BF16X6)
+    return launch_mlp_fwd_x6(cfg, packed_fwd, nullptr, reso, x0, off, scale, M, nullptr, sigma_out, nullptr, nullptr, nullptr,
+                             nullptr, s);
+  if (cfg->mlp_precision == PXO_MLP_BF16X3)
+    return launch_mlp_fwd_x3(cfg, packed_fwd, nullptr, reso, x0, off, scale, M, nullptr, sigma_out, s);
+  return launch_fwd_any(cfg, packed_fwd, nullptr, make_grid_spec(true, reso, x0, off, scale), M, nullptr, sigma_out, nullptr,
+                        nullptr, nullptr, nullptr, s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -915,7 +799,7 @@ __global__ __launch_bounds__(kMlpThreads, kMlpWgPerCu * kMlpWaves / 4) void mlp_
     for (int64_t slot = blockIdx.x; slot < ts.n_full; slot += gridDim.x) run(slot);
     for (int64_t h = blockIdx.x; h < ts.n_half; h += gridDim.x) run(ts.n_full + h);
   } else {
-    // tiles taken from the device counter (TileTicket above).  In skipping mode a skipped tile costs ~1 % of a live one, so
+    // tiles taken from the device counter (pxo_mlp.h TileTicket).  In skipping mode a skipped tile costs ~1 % of a live one, so
     // the static stride would leave the workgroups that drew few live tiles idle (measured: the kernel at 0.60 of its dense
     // time with 13 % of the rows live).  Results do not depend on the order (per-slot partials, disjoint dz rows).
     const TileTicket tk{nz + kTM / kLiveRows, tile_counter};
@@ -944,23 +828,13 @@ int launch_mlp_bwd_data(const PxoCfg* cfg, const float* packed_bwd, const float*
   KernelTimer timer(PXO_PROF_MLP_BWD_DATA, M, s);
   dim3 grid_dim(mlp_grid(M)), block(kMlpThreads);
   const TileSched ts = tile_sched(M, grid_dim.x);
-#define PXO_BWD_(NHB_, SKIP_, DYN_)                                                                                       \
-  hipLaunchKernelGGL((mlp_bwd_data_kernel<NHB_, SKIP_, DYN_>), grid_dim, block, 0, s, packed_bwd, d_raw_rgb, d_raw_sigma, \
-                     mask, M, cfg->sh_deg, ts, dz, dbias_partial, chunk_live, tile_counter)
-#define PXO_BWD(NHB_)                                                       \
-  do {                                                                      \
-    if (chunk_live && tile_counter) PXO_BWD_(NHB_, true, true);             \
-    else if (chunk_live) PXO_BWD_(NHB_, true, false);                       \
-    else if (tile_counter) PXO_BWD_(NHB_, false, true);                     \
-    else PXO_BWD_(NHB_, false, false);                                      \
-  } while (0)
-  switch (head_blocks(cfg->sh_deg)) {
-    case 1: PXO_BWD(1); break;
-    case 2: PXO_BWD(2); break;
-    default: PXO_BWD(3); break;
-  }
-#undef PXO_BWD
-#undef PXO_BWD_
+  head_switch(cfg->sh_deg, [&](auto nhb) {
+    constexpr int NHB = decltype(nhb)::value;
+    const auto kernel = chunk_live ? (tile_counter ? mlp_bwd_data_kernel<NHB, true, true> : mlp_bwd_data_kernel<NHB, true, false>)
+                                   : (tile_counter ? mlp_bwd_data_kernel<NHB, false, true> : mlp_bwd_data_kernel<NHB, false, false>);
+    hipLaunchKernelGGL(kernel, grid_dim, block, 0, s, packed_bwd, d_raw_rgb, d_raw_sigma, mask, M, cfg->sh_deg, ts, dz,
+                       dbias_partial, chunk_live, tile_counter);
+  });
   return check_launch("mlp_bwd_data");
 }
 

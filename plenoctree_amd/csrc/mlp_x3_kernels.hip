@@ -22,7 +22,7 @@
 //  * the product is computed TRANSPOSED (weights as the A operand, activations as B): a lane then owns 4 consecutive
 //    output features of one sample per register quad, so the epilogue (bias, ReLU, split) packs 4 bf16 and writes
 //    one ds_write_b64 per plane instead of 8 scattered 2-byte writes.
-#include "pxo_common.h"
+#include "pxo_mlp.h"
 
 namespace pxo {
 
@@ -50,18 +50,6 @@ __device__ __forceinline__ void split_bf16_pair(float a, float b, uint32_t& hi, 
 // ------------------------------------------------------------------------------------------
 // weight packing: element e of lane l in block (kg, cb, part) = part(W[k = 16 kg + 8 (l >> 5) + e][n = 32 cb + (l & 31)])
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float x3_src_weight(const float* __restrict__ p, int deg, int l, int k, int n) {
-  const int C = rgb_channels(deg);
-  if (l < 8) {
-    if (k >= layer_in(l) || n >= kW) return 0.f;
-    return p[leaf_kernel_off(l, deg) + (int64_t)k * kW + n];
-  }
-  if (k >= kW) return 0.f;
-  if (n < C) return p[leaf_kernel_off(9, deg) + (int64_t)k * C + n];
-  if (n == C) return p[leaf_kernel_off(8, deg) + k];
-  return 0.f;
-}
-
 __global__ void pack_fwd_x3_kernel(const float* __restrict__ p, int deg, float* __restrict__ out) {
   const int nhb = head_blocks(deg);
   const int64_t total = fwd_image_floats(deg);
@@ -70,15 +58,7 @@ __global__ void pack_fwd_x3_kernel(const float* __restrict__ p, int deg, float* 
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
     if (idx >= bias_off) {
-      const int b = (int)(idx - bias_off);
-      float v;
-      if (b < 8 * kW) {
-        v = p[leaf_bias_off(b / kW, deg) + (b % kW)];
-      } else {
-        const int n = b - 8 * kW, C = rgb_channels(deg);
-        v = n < C ? p[leaf_bias_off(9, deg) + n] : (n == C ? p[leaf_bias_off(8, deg)] : 0.f);
-      }
-      out[idx] = v;
+      out[idx] = fwd_image_bias(p, deg, (int)(idx - bias_off));
       continue;
     }
     int l = 0;
@@ -96,7 +76,7 @@ __global__ void pack_fwd_x3_kernel(const float* __restrict__ p, int deg, float* 
     for (int j = 0; j < 2; ++j) {
       const int k = 16 * kg + 8 * (lane >> 5) + 2 * s + j;
       __bf16 hi, lo;
-      split_bf16(x3_src_weight(p, deg, l, k, n), hi, lo);
+      split_bf16(src_weight(p, deg, l, k, n), hi, lo);
       pair[j] = part == 0 ? hi : lo;
     }
     uint32_t bits;
@@ -182,7 +162,6 @@ __device__ __forceinline__ void mfma3(const X3Frag (&w)[CBN], const X3Frag (&x)[
 // read starting at wp (>= kgroups), and a call with `preloaded` finds w[0..2] already holding its k-groups 0..2 --
 // the L2 latency of a layer's first fragments is then hidden under the previous layer's tail and its epilogue.
 // xh / xl: this lane's row (lane & 31) and k offset 8 (lane >> 5) inside the planes.
-#define PXO_X3_PIN() __builtin_amdgcn_sched_barrier(0)
 template <int RBN, int CBN>
 __device__ __forceinline__ void gemm_x3(const __bf16* __restrict__ xh, const __bf16* __restrict__ xl,
                                         const X3Image& im, int wu, int kgroups, int avail, bool preloaded, int kg_stride,
@@ -200,73 +179,47 @@ __device__ __forceinline__ void gemm_x3(const __bf16* __restrict__ xh, const __b
   for (int g = 0; g < kgroups; g += 4) {
     LOADX(g + 1, x1);
     LOADW(g + 3, w[3]);
-    PXO_X3_PIN();
+    PXO_PIN();
     mfma3<RBN, CBN>(w[0], x0, acc);
-    PXO_X3_PIN();
+    PXO_PIN();
     LOADX(g + 2, x0);
     LOADW(g + 4, w[0]);
-    PXO_X3_PIN();
+    PXO_PIN();
     mfma3<RBN, CBN>(w[1], x1, acc);
-    PXO_X3_PIN();
+    PXO_PIN();
     LOADX(g + 3, x1);
     LOADW(g + 5, w[1]);
-    PXO_X3_PIN();
+    PXO_PIN();
     mfma3<RBN, CBN>(w[2], x0, acc);
-    PXO_X3_PIN();
+    PXO_PIN();
     LOADX((g + 4 < kgroups ? g + 4 : kgroups - 1), x0);
     LOADW(g + 6, w[2]);
-    PXO_X3_PIN();
+    PXO_PIN();
     mfma3<RBN, CBN>(w[3], x1, acc);
-    PXO_X3_PIN();
+    PXO_PIN();
   }
-}
-
-// dense-grid point source (same formula as mlp_kernels.hip; octree/extraction.py:290-303)
-struct X3Grid {
-  int enabled, reso, x0;
-  float off[3], scale[3];
-};
-
-__device__ __forceinline__ float x3_enc_value(float p0, float p1, float p2, int col) {
-  if (col < 3) return col == 0 ? p0 : (col == 1 ? p1 : p2);
-  if (col >= kEnc) return 0.f;
-  int idx = col - 3;
-  const bool shifted = idx >= 30;
-  if (shifted) idx -= 30;
-  const int l = idx / 3, a = idx - 3 * l;
-  float xb = (a == 0 ? p0 : (a == 1 ? p1 : p2)) * (float)(1 << l);
-  if (shifted) xb = xb + 1.5707963267948966f;
-  return sinf(xb);
 }
 
 // posenc of the tile's points, split, into planes[:, 0:64]; `keep` receives this thread's four 16-byte pieces (hi, lo of its
 // two 8-column halves) so that the skip layer can put them back (posenc_restore_x3) instead of evaluating 16 sinf per point a
 // second time
 __device__ __forceinline__ void posenc_tile_x3(__bf16* __restrict__ ph, __bf16* __restrict__ pl, const float* __restrict__ pts,
-                                               const X3Grid& grid, int64_t row0, int64_t M, int tid, uint4 (&keep)[4]) {
+                                               const GridSpec& grid, int64_t row0, int64_t M, int tid, uint4 (&keep)[4]) {
   static_assert(kXThreads / kXRows == 4, "4 parts x 16 columns");
   const int row = tid % kXRows, part = tid / kXRows;
   const int64_t grow = row0 + row;
   float p0 = 0.f, p1 = 0.f, p2 = 0.f;
   if (grow < M) {
-    if (grid.enabled) {
-      const int r = grid.reso;
-      const int iz = (int)(grow % r);
-      const int64_t t = grow / r;
-      const int iy = (int)(t % r), ix = (int)(t / r) + grid.x0;
-      p0 = ((((float)ix + 0.5f) / (float)r) - grid.off[0]) / grid.scale[0];
-      p1 = ((((float)iy + 0.5f) / (float)r) - grid.off[1]) / grid.scale[1];
-      p2 = ((((float)iz + 0.5f) / (float)r) - grid.off[2]) / grid.scale[2];
-    } else {
-      p0 = pts[grow * 3]; p1 = pts[grow * 3 + 1]; p2 = pts[grow * 3 + 2];
-    }
+    // through locals of its own: with p0..p2 handed over directly hipcc allocates this kernel's registers differently
+    if (grid.enabled) { float gx, gy, gz; grid_point(grid, grow, gx, gy, gz); p0 = gx; p1 = gy; p2 = gz; }
+    else { p0 = pts[grow * 3]; p1 = pts[grow * 3 + 1]; p2 = pts[grow * 3 + 2]; }
   }
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     uint32_t vh[4], vl[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      split_bf16_pair(x3_enc_value(p0, p1, p2, part * 16 + h * 8 + 2 * i), x3_enc_value(p0, p1, p2, part * 16 + h * 8 + 2 * i + 1),
+      split_bf16_pair(enc_value(p0, p1, p2, part * 16 + h * 8 + 2 * i), enc_value(p0, p1, p2, part * 16 + h * 8 + 2 * i + 1),
                       vh[i], vl[i]);
     keep[2 * h] = make_uint4(vh[0], vh[1], vh[2], vh[3]);
     keep[2 * h + 1] = make_uint4(vl[0], vl[1], vl[2], vl[3]);
@@ -288,7 +241,7 @@ __device__ __forceinline__ void posenc_restore_x3(__bf16* __restrict__ ph, __bf1
 // ------------------------------------------------------------------------------------------
 template <int NHB, bool RGB>
 __global__ __launch_bounds__(kXThreads, kXWgPerCu * kXWaves / 4) void mlp_fwd_x3_kernel(
-    const float* __restrict__ pk, const float* __restrict__ pts, X3Grid grid, int64_t M, int deg,
+    const float* __restrict__ pk, const float* __restrict__ pts, GridSpec grid, int64_t M, int deg,
     float* __restrict__ raw_rgb, float* __restrict__ raw_sigma) {
   __shared__ __attribute__((aligned(16))) __bf16 plane_h[kXRows * kLDB];
   __shared__ __attribute__((aligned(16))) __bf16 plane_l[kXRows * kLDB];
@@ -397,30 +350,19 @@ __global__ __launch_bounds__(kXThreads, kXWgPerCu * kXWaves / 4) void mlp_fwd_x3
   }
 }
 
-template <int NHB>
-static int launch_x3_nhb(const PxoCfg* cfg, const float* pk, const float* pts, const X3Grid& grid, int64_t M,
-                         float* raw_rgb, float* raw_sigma, hipStream_t s) {
-  KernelTimer timer(PXO_PROF_MLP_FWD, M, s);
-  const int64_t tiles = (M + kXRows - 1) / kXRows, cap = (int64_t)kXWgPerCu * num_cus();
-  dim3 grid_dim((unsigned)(tiles < cap ? tiles : cap)), block(kXThreads);
-  if (raw_rgb)
-    hipLaunchKernelGGL((mlp_fwd_x3_kernel<NHB, true>), grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, raw_rgb, raw_sigma);
-  else
-    hipLaunchKernelGGL((mlp_fwd_x3_kernel<NHB, false>), grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, raw_rgb, raw_sigma);
-  return check_launch("mlp_fwd(bf16x3)");
-}
-
 int launch_mlp_fwd_x3(const PxoCfg* cfg, const float* packed_fwd, const float* pts, int reso, int x0,
                       const float* off, const float* scale, int64_t M, float* raw_rgb, float* raw_sigma, hipStream_t s) {
   if (M == 0) return PXO_OK;
-  X3Grid g;
-  g.enabled = pts == nullptr; g.reso = reso > 0 ? reso : 1; g.x0 = x0;
-  for (int i = 0; i < 3; ++i) { g.off[i] = off ? off[i] : 0.f; g.scale[i] = scale ? scale[i] : 1.f; }
-  switch (head_blocks(cfg->sh_deg)) {
-    case 1: return launch_x3_nhb<1>(cfg, packed_fwd, pts, g, M, raw_rgb, raw_sigma, s);
-    case 2: return launch_x3_nhb<2>(cfg, packed_fwd, pts, g, M, raw_rgb, raw_sigma, s);
-    default: return launch_x3_nhb<3>(cfg, packed_fwd, pts, g, M, raw_rgb, raw_sigma, s);
-  }
+  const GridSpec g = make_grid_spec(pts == nullptr, reso, x0, off, scale);
+  KernelTimer timer(PXO_PROF_MLP_FWD, M, s);
+  const int64_t tiles = (M + kXRows - 1) / kXRows, cap = (int64_t)kXWgPerCu * num_cus();
+  dim3 grid_dim((unsigned)(tiles < cap ? tiles : cap)), block(kXThreads);
+  head_switch(cfg->sh_deg, [&](auto nhb) {
+    constexpr int NHB = decltype(nhb)::value;
+    const auto kernel = raw_rgb ? mlp_fwd_x3_kernel<NHB, true> : mlp_fwd_x3_kernel<NHB, false>;
+    hipLaunchKernelGGL(kernel, grid_dim, block, 0, s, packed_fwd, pts, g, M, cfg->sh_deg, raw_rgb, raw_sigma);
+  });
+  return check_launch("mlp_fwd(bf16x3)");
 }
 
 }  // namespace pxo

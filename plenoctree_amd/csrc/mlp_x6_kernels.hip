@@ -24,7 +24,7 @@
 // product is computed transposed (weights = A operand, activations = B operand): a lane owns 4 consecutive features of one
 // sample per register quad, so the epilogue writes one ds_write_b64 per plane and one 16-byte global store per quad.
 // Every wave owns 64 rows x 32 features: per 16-deep k-group 6 ds_read_b128 + 3 buffer_load_b128 feed 12 MFMAs.
-#include "pxo_common.h"
+#include "pxo_mlp.h"
 #include "pxo_x6.h"
 
 namespace pxo {
@@ -40,19 +40,6 @@ static_assert(kYWaves * 32 == kW, "one 32-feature block per wave");
 // ------------------------------------------------------------------------------------------
 // weight packing
 // ------------------------------------------------------------------------------------------
-// W_l[k_in][n_out] of the reference layout with zero padding; l == 8: the fused head (cols [0,C) = Dense_9, col C = Dense_8)
-__device__ __forceinline__ float x6_src_weight(const float* __restrict__ p, int deg, int l, int k, int n) {
-  const int C = rgb_channels(deg);
-  if (l < 8) {
-    if (k >= layer_in(l) || n >= kW) return 0.f;
-    return p[leaf_kernel_off(l, deg) + (int64_t)k * kW + n];
-  }
-  if (k >= kW) return 0.f;
-  if (n < C) return p[leaf_kernel_off(9, deg) + (int64_t)k * C + n];
-  if (n == C) return p[leaf_kernel_off(8, deg) + k];
-  return 0.f;
-}
-
 // one thread per 4-byte slot = elements (2s, 2s + 1) of a lane's 16-byte fragment of part `part`
 // forward: A[feature n][k] = W_l[k][n]
 __global__ void pack_fwd_x6_kernel(const float* __restrict__ p, int deg, float* __restrict__ out) {
@@ -61,15 +48,7 @@ __global__ void pack_fwd_x6_kernel(const float* __restrict__ p, int deg, float* 
   const int64_t bias_off = x6_fwd_bias_off(deg);
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     if (idx >= bias_off) {
-      const int b = (int)(idx - bias_off);
-      float v;
-      if (b < 8 * kW) {
-        v = p[leaf_bias_off(b / kW, deg) + (b % kW)];
-      } else {
-        const int n = b - 8 * kW, C = rgb_channels(deg);
-        v = n < C ? p[leaf_bias_off(9, deg) + n] : (n == C ? p[leaf_bias_off(8, deg)] : 0.f);
-      }
-      out[idx] = v;
+      out[idx] = fwd_image_bias(p, deg, (int)(idx - bias_off));
       continue;
     }
     int l = 0;
@@ -87,7 +66,7 @@ __global__ void pack_fwd_x6_kernel(const float* __restrict__ p, int deg, float* 
     for (int j = 0; j < 2; ++j) {
       const int k = 16 * kg + 8 * (lane >> 5) + 2 * s + j;
       __bf16 a, b, c;
-      split3(x6_src_weight(p, deg, l, k, n), a, b, c);
+      split3(src_weight(p, deg, l, k, n), a, b, c);
       pair[j] = part == 0 ? a : (part == 1 ? b : c);
     }
     uint32_t bits;
@@ -115,7 +94,7 @@ __global__ void pack_bwd_x6_kernel(const float* __restrict__ p, int deg, float* 
     for (int j = 0; j < 2; ++j) {
       const int k = 16 * kg + 8 * (lane >> 5) + 2 * s + j;
       __bf16 a, b, c;
-      split3(x6_src_weight(p, deg, l, n, k), a, b, c);
+      split3(src_weight(p, deg, l, n, k), a, b, c);
       pair[j] = part == 0 ? a : (part == 1 ? b : c);
     }
     uint32_t bits;
@@ -199,10 +178,6 @@ __device__ __forceinline__ void mfma6_first(const X6W& w, const X6X<RBN>& x, con
 // k-groups of the next one: `avail` = k-groups that may be read starting at wu (>= kgroups), and a call with `preloaded` finds
 // w[0..2] already holding its k-groups 0..2 -- the L2 latency of a layer's first fragments hides under the previous layer's
 // tail and its epilogue.
-#define PXO_X6_PIN() __builtin_amdgcn_sched_barrier(0)
-__device__ __forceinline__ void lds_barrier6() {       // orders LDS traffic only (see mlp_kernels.hip lds_barrier)
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 // INIT: the accumulators are written, not read, by the first k-group (hi starts from *init, lo from 0)
 template <int RBN, bool INIT = false>
 __device__ __forceinline__ void gemm_x6(const __bf16* __restrict__ xp, const X6Image& im, int wu, int kgroups, int avail,
@@ -219,32 +194,28 @@ __device__ __forceinline__ void gemm_x6(const __bf16* __restrict__ xp, const X6I
   for (int g = 0; g < kgroups; g += 4) {
     load_x6<RBN>(xp, g + 1, x1);
     load_w6(im, wu, cl(g + 3), kg_stride, w[3]);
-    PXO_X6_PIN();
+    PXO_PIN();
     if (INIT && g == 0) mfma6_first<RBN>(w[0], x0, *init, hi, lo);
     else mfma6<RBN>(w[0], x0, hi, lo);
-    PXO_X6_PIN();
+    PXO_PIN();
     load_x6<RBN>(xp, g + 2, x0);
     load_w6(im, wu, cl(g + 4), kg_stride, w[0]);
-    PXO_X6_PIN();
+    PXO_PIN();
     mfma6<RBN>(w[1], x1, hi, lo);
-    PXO_X6_PIN();
+    PXO_PIN();
     load_x6<RBN>(xp, g + 3, x1);
     load_w6(im, wu, cl(g + 5), kg_stride, w[1]);
-    PXO_X6_PIN();
+    PXO_PIN();
     mfma6<RBN>(w[2], x0, hi, lo);
-    PXO_X6_PIN();
+    PXO_PIN();
     load_x6<RBN>(xp, (g + 4 < kgroups ? g + 4 : kgroups - 1), x0);
     load_w6(im, wu, cl(g + 6), kg_stride, w[2]);
-    PXO_X6_PIN();
+    PXO_PIN();
     mfma6<RBN>(w[3], x1, hi, lo);
-    PXO_X6_PIN();
+    PXO_PIN();
   }
 }
 
-// relu mask: one bit per accumulator element in (row block, quad, element) order, MSB first (mlp_kernels.hip mask_push / pop)
-__device__ __forceinline__ void mask_push6(uint32_t& mw, float v) {
-  asm volatile("v_cmp_lt_f32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mw) : "v"(v) : "vcc");
-}
 // relu(s) and its mask bit from one compare: v = s > 0 ? s : 0, mw = 2 mw + (s > 0).  The condition lives in its own SGPR pair
 // (VOP3 forms), not in VCC: consecutive elements do not serialise on one register and the compiler may interleave them.
 __device__ __forceinline__ float relu_push6(uint32_t& mw, float s) {
@@ -302,49 +273,23 @@ __device__ __forceinline__ void store_planes4(__bf16* __restrict__ planes, int o
   *reinterpret_cast<uint2*>(planes + 2 * kPlane + off) = make_uint2(c01, c23);
 }
 
-// dense-grid point source (same formula as mlp_kernels.hip grid_point; octree/extraction.py:290-303)
-struct X6Grid {
-  int enabled, reso, x0;
-  float off[3], scale[3];
-};
-
-__device__ __forceinline__ float x6_enc_value(float p0, float p1, float p2, int col) {
-  if (col < 3) return col == 0 ? p0 : (col == 1 ? p1 : p2);
-  if (col >= kEnc) return 0.f;
-  int idx = col - 3;
-  const bool shifted = idx >= 30;
-  if (shifted) idx -= 30;
-  const int l = idx / 3, a = idx - 3 * l;
-  float xb = (a == 0 ? p0 : (a == 1 ? p1 : p2)) * (float)(1 << l);
-  if (shifted) xb = xb + 1.5707963267948966f;
-  return sinf(xb);
-}
-
 // posenc of the sub-tile's points, split, into planes[:, 0:64]: thread = (row = tid & 63, columns 8 wave .. 8 wave + 7 -- the
-// column set is wave-uniform, so the branches of x6_enc_value are); `keep` receives the thread's three 16-byte pieces so that the
+// column set is wave-uniform, so the branches of enc_value are); `keep` receives the thread's three 16-byte pieces so that the
 // skip layer can put them back without evaluating the sines again; SAVE: the float32 values leave for the weight gradients
 template <bool SAVE, bool GRID>
-__device__ __forceinline__ void posenc_tile_x6(__bf16* __restrict__ planes, const float* __restrict__ pts, const X6Grid& grid,
+__device__ __forceinline__ void posenc_tile_x6(__bf16* __restrict__ planes, const float* __restrict__ pts, const GridSpec& grid,
                                                int64_t row0, int64_t M, int tid, float* __restrict__ enc_out, uint4 (&keep)[3]) {
   const int row = tid & 63, part = tid >> 6;
   const int64_t grow = row0 + row;
   float p0 = 0.f, p1 = 0.f, p2 = 0.f;
   if (grow < M) {
-    if (GRID && grid.enabled) {
-      const int r = grid.reso;
-      const int iz = (int)(grow % r);
-      const int64_t t = grow / r;
-      const int iy = (int)(t % r), ix = (int)(t / r) + grid.x0;
-      p0 = ((((float)ix + 0.5f) / (float)r) - grid.off[0]) / grid.scale[0];
-      p1 = ((((float)iy + 0.5f) / (float)r) - grid.off[1]) / grid.scale[1];
-      p2 = ((((float)iz + 0.5f) / (float)r) - grid.off[2]) / grid.scale[2];
-    } else {
-      p0 = pts[grow * 3]; p1 = pts[grow * 3 + 1]; p2 = pts[grow * 3 + 2];
-    }
+    // through locals of its own: with p0..p2 handed over directly hipcc allocates this kernel's registers differently
+    if (GRID && grid.enabled) { float gx, gy, gz; grid_point(grid, grow, gx, gy, gz); p0 = gx; p1 = gy; p2 = gz; }
+    else { p0 = pts[grow * 3]; p1 = pts[grow * 3 + 1]; p2 = pts[grow * 3 + 2]; }
   }
   float e[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) e[i] = x6_enc_value(p0, p1, p2, part * 8 + i);
+  for (int i = 0; i < 8; ++i) e[i] = enc_value(p0, p1, p2, part * 8 + i);
   if (SAVE && grow < M) {
     float* dst = enc_out + grow * kEncPad + part * 8;
     *reinterpret_cast<f32x4*>(dst) = f32x4{e[0], e[1], e[2], e[3]};
@@ -365,21 +310,6 @@ __device__ __forceinline__ void posenc_restore_x6(__bf16* __restrict__ planes, i
   for (int i = 0; i < 3; ++i) *reinterpret_cast<uint4*>(planes + i * kPlane + row * kLDB + part * 8) = keep[i];
 }
 
-// the persistent workgroups' tile schedule: identical to mlp_kernels.hip (TileTicket) -- slot b first, then slots taken from
-// a device counter; results do not depend on it (a slot's rows, mask words and bias partial are functions of the slot alone)
-struct X6Ticket {
-  int* next;                       // LDS word
-  unsigned int* counter;           // device word, zero when the launch starts
-  __device__ __forceinline__ int draw(int tid) const { return tid == 0 ? (int)gridDim.x + (int)atomicAdd(counter, 1u) : 0; }
-  __device__ __forceinline__ int64_t take(int tid, int ticket) const {
-    if (tid == 0) *next = ticket;
-    lds_barrier6();
-    const int v = __builtin_amdgcn_readfirstlane(*next);
-    lds_barrier6();
-    return v;
-  }
-};
-
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
@@ -387,7 +317,7 @@ struct X6Ticket {
 // relu-mask words, [layer][thread] at stride 2 * kYThreads words per layer (SAVE only).
 template <int NHB, bool SAVE, bool RGB, bool GRID>
 __device__ __forceinline__ void fwd_subtile_x6(__bf16* __restrict__ planes, const float* __restrict__ s_bias,
-                                               const float* __restrict__ pk, const float* __restrict__ pts, const X6Grid& grid,
+                                               const float* __restrict__ pk, const float* __restrict__ pts, const GridSpec& grid,
                                                int64_t M, int deg, int64_t row0, float* __restrict__ raw_rgb,
                                                float* __restrict__ raw_sigma, float* __restrict__ acts,
                                                float* __restrict__ enc_out, uint32_t* __restrict__ mask_sub, int tid, int wave) {
@@ -408,10 +338,10 @@ __device__ __forceinline__ void fwd_subtile_x6(__bf16* __restrict__ planes, cons
   int pw2 = pw + 2 * kPlane;
   asm volatile("" : "+v"(pw2));
 
-  lds_barrier6();   // the previous sub-tile's head GEMM has consumed the planes
+  lds_barrier();   // the previous sub-tile's head GEMM has consumed the planes
   uint4 enc_keep[3];
   posenc_tile_x6<SAVE, GRID>(planes, pts, grid, row0, M, tid, enc_out, enc_keep);
-  lds_barrier6();
+  lds_barrier();
 
   f32x16 hi[kYRB], lo[kYRB];
   X6W w[4];
@@ -431,9 +361,9 @@ __device__ __forceinline__ void fwd_subtile_x6(__bf16* __restrict__ planes, cons
     kg0 += nkg;
     if (l == 5) {
       // skip connection (model_utils.py:70-71): the 64 encoded columns are a second K segment, put back from registers
-      lds_barrier6();
+      lds_barrier();
       posenc_restore_x6(planes, tid, enc_keep);
-      lds_barrier6();
+      lds_barrier();
       gemm_x6<kYRB>(xp, wimg, wu0 + kg0 * kKgStride, 4, kTrunkKg - kg0, true, kKgStride, w, hi, lo);
       kg0 += 4;
     }
@@ -474,12 +404,12 @@ __device__ __forceinline__ void fwd_subtile_x6(__bf16* __restrict__ planes, cons
       pc[r][1] = pair_quads(pq[2], pq[3]);
     }
     if (SAVE) mask_sub[(int64_t)l * (2 * kYThreads) + 2 * tid] = (mwr[0] << 16) | mwr[1];
-    lds_barrier6();  // every wave has consumed the input planes
+    lds_barrier();  // every wave has consumed the input planes
 #pragma unroll
     for (int r = 0; r < kYRB; ++r)
 #pragma unroll
       for (int p2 = 0; p2 < 2; ++p2) store_chunk(planes, pw, pw2, r * 32 * kLDB + 16 * p2, pc[r][p2]);
-    lds_barrier6();
+    lds_barrier();
   }
 
   // heads (model_utils.py:72-74, :91-93): [raw_rgb | raw_sigma] = h7 @ [Dense_9 | Dense_8] + b.  The 32-column head blocks are too
@@ -504,7 +434,7 @@ __device__ __forceinline__ void fwd_subtile_x6(__bf16* __restrict__ planes, cons
     // read back row-major: the sub-tile's rows of raw_rgb are ONE contiguous block of global memory, written coalesced
     constexpr int RS = NJ * 32 + 4;
     float* red = reinterpret_cast<float*>(planes);
-    lds_barrier6();                                      // every wave is through with the planes
+    lds_barrier();                                      // every wave is through with the planes
     if (active) {
 #pragma unroll
       for (int r = 0; r < kYRB; ++r)
@@ -515,7 +445,7 @@ __device__ __forceinline__ void fwd_subtile_x6(__bf16* __restrict__ planes, cons
           *reinterpret_cast<f32x4*>(red + (ks * kYRows + r * 32 + (lane & 31)) * RS + cbj * 32 + 8 * q + 4 * (lane >> 5)) = v;
         }
     }
-    lds_barrier6();
+    lds_barrier();
     const float* hb = bias + 8 * kW;
     const int col0 = (RGB ? 0 : NHB - 1) * 32;           // head column of the first staged column
     if (RGB) {
@@ -540,7 +470,7 @@ __device__ __forceinline__ void fwd_subtile_x6(__bf16* __restrict__ planes, cons
 
 template <int NHB, bool SAVE, bool RGB, bool GRID, bool DYN>
 __global__ __launch_bounds__(kYThreads, 2) void mlp_fwd_x6_kernel(
-    const float* __restrict__ pk, const float* __restrict__ pts, X6Grid grid, int64_t M, int deg, TileSched ts,
+    const float* __restrict__ pk, const float* __restrict__ pts, GridSpec grid, int64_t M, int deg, TileSched ts,
     float* __restrict__ raw_rgb, float* __restrict__ raw_sigma, float* __restrict__ acts, float* __restrict__ enc_out,
     uint32_t* __restrict__ mask, unsigned int* __restrict__ tile_counter) {
   __shared__ __attribute__((aligned(16))) __bf16 planes[3 * kPlane];
@@ -569,7 +499,7 @@ __global__ __launch_bounds__(kYThreads, 2) void mlp_fwd_x6_kernel(
   if (!DYN) {
     for (int64_t slot = blockIdx.x; slot < n_slots; slot += gridDim.x) run(slot);
   } else {
-    const X6Ticket tk{s_next, tile_counter};
+    const TileTicket tk{s_next, tile_counter};
     for (int64_t slot = blockIdx.x; slot < n_slots;) {
       const int ticket = tk.draw(tid);
       run(slot);
@@ -578,47 +508,27 @@ __global__ __launch_bounds__(kYThreads, 2) void mlp_fwd_x6_kernel(
   }
 }
 
-// The reduce of the bias partials (launch_mlp_bwd_weights, wgrad_kernels.hip) counts this kernel's tile slots with
-// mlp_bwd_partials(M), i.e. tile_sched(M, mlp_grid(M)).  That is this launch's schedule only while mlp_grid == x6_grid.
-static_assert(kMlpWgPerCu == 1, "x6_grid launches one workgroup per CU: mlp_bwd_partials must count this grid's slots");
-static unsigned x6_grid(int64_t M) {
-  const int64_t tiles = num_tiles(M), cap = (int64_t)num_cus();
-  return (unsigned)(tiles < cap ? tiles : cap);
-}
-
-template <int NHB>
-static int launch_fwd_x6_nhb(const PxoCfg* cfg, const float* pk, const float* pts, const X6Grid& grid, int64_t M,
-                             float* raw_rgb, float* raw_sigma, float* acts, float* enc, uint32_t* mask,
-                             unsigned int* tile_counter, hipStream_t s) {
-  KernelTimer timer(PXO_PROF_MLP_FWD, M, s);
-  dim3 grid_dim(x6_grid(M)), block(kYThreads);
-  const TileSched ts = tile_sched(M, grid_dim.x);
-#define PXO_X6_FWD(SAVE_, RGB_, GRID_, DYN_)                                                                               \
-  hipLaunchKernelGGL((mlp_fwd_x6_kernel<NHB, SAVE_, RGB_, GRID_, DYN_>), grid_dim, block, 0, s, pk, pts, grid, M, cfg->sh_deg, \
-                     ts, raw_rgb, raw_sigma, acts, enc, mask, tile_counter)
-  if (acts && raw_rgb && tile_counter) PXO_X6_FWD(true, true, false, true);
-  else if (acts && raw_rgb) PXO_X6_FWD(true, true, false, false);
-  else if (acts) PXO_X6_FWD(true, false, false, false);
-  else if (grid.enabled) PXO_X6_FWD(false, false, true, false);
-  else if (raw_rgb) PXO_X6_FWD(false, true, false, false);
-  else PXO_X6_FWD(false, false, false, false);
-#undef PXO_X6_FWD
-  return check_launch("mlp_fwd(bf16x6)");
-}
-
 int launch_mlp_fwd_x6(const PxoCfg* cfg, const float* packed_fwd, const float* pts, int reso, int x0, const float* off,
                       const float* scale, int64_t M, float* raw_rgb, float* raw_sigma, float* acts, float* enc,
                       uint32_t* mask, unsigned int* tile_counter, hipStream_t s) {
   if (M == 0) return PXO_OK;
-  X6Grid g;
-  g.enabled = pts == nullptr; g.reso = reso > 0 ? reso : 1; g.x0 = x0;
-  for (int i = 0; i < 3; ++i) { g.off[i] = off ? off[i] : 0.f; g.scale[i] = scale ? scale[i] : 1.f; }
+  const GridSpec g = make_grid_spec(pts == nullptr, reso, x0, off, scale);
   if (g.enabled && (raw_rgb || acts)) { set_error("mlp_fwd(bf16x6): the dense-grid source is sigma-only"); return PXO_ERR_ARG; }
-  switch (head_blocks(cfg->sh_deg)) {
-    case 1: return launch_fwd_x6_nhb<1>(cfg, packed_fwd, pts, g, M, raw_rgb, raw_sigma, acts, enc, mask, tile_counter, s);
-    case 2: return launch_fwd_x6_nhb<2>(cfg, packed_fwd, pts, g, M, raw_rgb, raw_sigma, acts, enc, mask, tile_counter, s);
-    default: return launch_fwd_x6_nhb<3>(cfg, packed_fwd, pts, g, M, raw_rgb, raw_sigma, acts, enc, mask, tile_counter, s);
-  }
+  KernelTimer timer(PXO_PROF_MLP_FWD, M, s);
+  dim3 grid_dim(mlp_grid(M)), block(kYThreads);
+  const TileSched ts = tile_sched(M, grid_dim.x);
+  head_switch(cfg->sh_deg, [&](auto nhb) {
+    constexpr int NHB = decltype(nhb)::value;             // <NHB, SAVE, RGB, GRID, DYN>
+    const auto kernel = acts && raw_rgb && tile_counter ? mlp_fwd_x6_kernel<NHB, true, true, false, true>
+                        : acts && raw_rgb               ? mlp_fwd_x6_kernel<NHB, true, true, false, false>
+                        : acts                          ? mlp_fwd_x6_kernel<NHB, true, false, false, false>
+                        : g.enabled                     ? mlp_fwd_x6_kernel<NHB, false, false, true, false>
+                        : raw_rgb                       ? mlp_fwd_x6_kernel<NHB, false, true, false, false>
+                                                        : mlp_fwd_x6_kernel<NHB, false, false, false, false>;
+    hipLaunchKernelGGL(kernel, grid_dim, block, 0, s, packed_fwd, pts, g, M, cfg->sh_deg, ts, raw_rgb, raw_sigma, acts, enc, mask,
+                       tile_counter);
+  });
+  return check_launch("mlp_fwd(bf16x6)");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -668,9 +578,9 @@ __device__ __forceinline__ bool bwd_subtile_x6(__bf16* __restrict__ planes, floa
   // this lane's bias accumulators: lane 31 / 63 of a wave writes the sums of features 32 wave + 4 (lane >> 5) + 8 q + t
   float* dbp = db_acc + wave * 32 + 4 * (lane >> 5);
 
-  lds_barrier6();   // the previous sub-tile is through with the planes, the staging tile and nz
+  lds_barrier();   // the previous sub-tile is through with the planes, the staging tile and nz
   if (SKIP && tid < kChunks) nz[tid] = 0;
-  if (SKIP) lds_barrier6();
+  if (SKIP) lds_barrier();
   // d_raw sub-tile -> stage[:, 0:NHP] with the head's column order (d_raw_rgb == NULL: sigma-only rows)
   for (int idx = tid; idx < kYRows * NHP; idx += kYThreads) {
     const int row = idx / NHP, col = idx - row * NHP;
@@ -683,7 +593,7 @@ __device__ __forceinline__ bool bwd_subtile_x6(__bf16* __restrict__ planes, floa
     stage[row * kLDS + col] = v;
     if (SKIP && v != 0.f) nz[row / kLiveRows] = 1;                // same value from every writer
   }
-  lds_barrier6();
+  lds_barrier();
   if (SKIP) {
     // see mlp_kernels.hip bwd_tile: rows with an exactly zero upstream gradient add exactly nothing anywhere
     int any = 0;
@@ -714,7 +624,7 @@ __device__ __forceinline__ bool bwd_subtile_x6(__bf16* __restrict__ planes, floa
     *reinterpret_cast<uint4*>(planes + kPlane + row * kLDB + grp * 8) = make_uint4(b[0], b[1], b[2], b[3]);
     *reinterpret_cast<uint4*>(planes + 2 * kPlane + row * kLDB + grp * 8) = make_uint4(c[0], c[1], c[2], c[3]);
   }
-  lds_barrier6();
+  lds_barrier();
 
   f32x16 hi[kYRB], lo[kYRB];
   X6W w[4];
@@ -765,13 +675,13 @@ __device__ __forceinline__ bool bwd_subtile_x6(__bf16* __restrict__ planes, floa
       }
     }
     if (l > 0) mw = mask_sub[(int64_t)(l - 1) * (2 * kYThreads) + 2 * tid];     // next layer's mask, fetched under the GEMM
-    lds_barrier6();  // every wave has consumed the planes (and, at l == 0, the slot's bias sums are complete)
+    lds_barrier();  // every wave has consumed the planes (and, at l == 0, the slot's bias sums are complete)
     if (l == 0) break;
 #pragma unroll
     for (int r = 0; r < kYRB; ++r)
 #pragma unroll
       for (int p2 = 0; p2 < 2; ++p2) store_chunk(planes, pw, pw2, r * 32 * kLDB + 16 * p2, pc[r][p2]);
-    lds_barrier6();
+    lds_barrier();
     gemm_x6<kYRB, true>(xp, wimg, wu0 + kg0 * kKgStride, 16, kStreamKg - kg0, true, kKgStride, w, hi, lo, &zero16);
     kg0 += 16;
   }
@@ -819,7 +729,7 @@ __global__ __launch_bounds__(kYThreads, 2) void mlp_bwd_data_x6_kernel(
   if (!DYN) {
     for (int64_t slot = blockIdx.x; slot < n_slots; slot += gridDim.x) run(slot);
   } else {
-    const X6Ticket tk{nz + 4, tile_counter};
+    const TileTicket tk{nz + 4, tile_counter};
     for (int64_t slot = blockIdx.x; slot < n_slots;) {
       const int ticket = tk.draw(tid);
       run(slot);
@@ -833,25 +743,15 @@ int launch_mlp_bwd_data_x6(const PxoCfg* cfg, const float* packed_bwd, const flo
                            unsigned int* tile_counter, hipStream_t s, bool db_all) {
   if (M == 0) return PXO_OK;
   KernelTimer timer(PXO_PROF_MLP_BWD_DATA, M, s);
-  dim3 grid_dim(x6_grid(M)), block(kYThreads);
+  dim3 grid_dim(mlp_grid(M)), block(kYThreads);
   const TileSched ts = tile_sched(M, grid_dim.x);
-#define PXO_X6_BWD_(NHB_, SKIP_, DYN_)                                                                                        \
-  hipLaunchKernelGGL((mlp_bwd_data_x6_kernel<NHB_, SKIP_, DYN_>), grid_dim, block, 0, s, packed_bwd, d_raw_rgb, d_raw_sigma, \
-                     mask, M, cfg->sh_deg, ts, dz, dbias_partial, chunk_live, tile_counter, db_all ? 1 : 0)
-#define PXO_X6_BWD(NHB_)                                                    \
-  do {                                                                      \
-    if (chunk_live && tile_counter) PXO_X6_BWD_(NHB_, true, true);          \
-    else if (chunk_live) PXO_X6_BWD_(NHB_, true, false);                    \
-    else if (tile_counter) PXO_X6_BWD_(NHB_, false, true);                  \
-    else PXO_X6_BWD_(NHB_, false, false);                                   \
-  } while (0)
-  switch (head_blocks(cfg->sh_deg)) {
-    case 1: PXO_X6_BWD(1); break;
-    case 2: PXO_X6_BWD(2); break;
-    default: PXO_X6_BWD(3); break;
-  }
-#undef PXO_X6_BWD
-#undef PXO_X6_BWD_
+  head_switch(cfg->sh_deg, [&](auto nhb) {
+    constexpr int NHB = decltype(nhb)::value;
+    const auto kernel = chunk_live ? (tile_counter ? mlp_bwd_data_x6_kernel<NHB, true, true> : mlp_bwd_data_x6_kernel<NHB, true, false>)
+                                   : (tile_counter ? mlp_bwd_data_x6_kernel<NHB, false, true> : mlp_bwd_data_x6_kernel<NHB, false, false>);
+    hipLaunchKernelGGL(kernel, grid_dim, block, 0, s, packed_bwd, d_raw_rgb, d_raw_sigma, mask, M, cfg->sh_deg, ts, dz,
+                       dbias_partial, chunk_live, tile_counter, db_all ? 1 : 0);
+  });
   return check_launch("mlp_bwd_data(bf16x6)");
 }
 

@@ -158,7 +158,8 @@ int check_launch(const char* what);
 
 int validate_cfg(const PxoCfg* cfg);
 int num_cus();
-int mlp_bwd_partials(int64_t M);   // number of [9][256] tile partials (slots) mlp_bwd_data writes for M rows
+unsigned mlp_grid(int64_t M);      // persistent workgroups of a float32 / bf16x6 fused-MLP launch over M rows (mlp_kernels.hip)
+int mlp_bwd_partials(int64_t M);   // number of [9][256] tile partials (slots) mlp_bwd_data writes for M rows: tile_sched(M, mlp_grid(M))
 
 // HIP-event bracket around one kernel launch (active for the tags in pxo_profile_enable's mask)
 struct KernelTimer {
@@ -173,7 +174,7 @@ int launch_mlp_fwd_grid(const PxoCfg* cfg, const float* packed_fwd, int reso, in
 // ---- launchers implemented in the kernel translation units -----------------------------
 int launch_pack(const PxoCfg* cfg, const float* mlp_params, float* fwd, float* bwd, hipStream_t s);
 // tile_counter (may be NULL = static tile stride): a ZERO device word; the persistent workgroups of the training
-// instantiation then take their tiles from it (mlp_kernels.hip TileTicket)
+// instantiation then take their tiles from it (pxo_mlp.h TileTicket)
 int launch_mlp_fwd(const PxoCfg* cfg, const float* packed_fwd, const float* pts, int64_t M,
                    float* raw_rgb, float* raw_sigma, float* acts, float* enc, uint32_t* mask,
                    hipStream_t s, unsigned int* tile_counter = nullptr);

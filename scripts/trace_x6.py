@@ -44,20 +44,20 @@ def patch(s):
     s = rep(s, "float* __restrict__ enc_out, uint32_t* __restrict__ mask_sub, int tid, int wave) {",
             "float* __restrict__ enc_out, uint32_t* __restrict__ mask_sub, int tid, int wave,\n"
             "                                               unsigned long long* s_trace, int& s_tn, bool trace_on) {")
-    s = rep(s, "  lds_barrier6();   // the previous sub-tile's head GEMM has consumed the planes\n  uint4 enc_keep[3];",
-            "  { const int l = 15; STAMP(14); }\n  lds_barrier6();   // the previous sub-tile's head GEMM has consumed the planes\n  uint4 enc_keep[3];")
-    s = rep(s, "  posenc_tile_x6<SAVE, GRID>(planes, pts, grid, row0, M, tid, enc_out, enc_keep);\n  lds_barrier6();\n",
-            "  posenc_tile_x6<SAVE, GRID>(planes, pts, grid, row0, M, tid, enc_out, enc_keep);\n  lds_barrier6();\n  { const int l = 15; STAMP(15); }\n")
+    s = rep(s, "  lds_barrier();   // the previous sub-tile's head GEMM has consumed the planes\n  uint4 enc_keep[3];",
+            "  { const int l = 15; STAMP(14); }\n  lds_barrier();   // the previous sub-tile's head GEMM has consumed the planes\n  uint4 enc_keep[3];")
+    s = rep(s, "  posenc_tile_x6<SAVE, GRID>(planes, pts, grid, row0, M, tid, enc_out, enc_keep);\n  lds_barrier();\n",
+            "  posenc_tile_x6<SAVE, GRID>(planes, pts, grid, row0, M, tid, enc_out, enc_keep);\n  lds_barrier();\n  { const int l = 15; STAMP(15); }\n")
     s = rep(s, "    const int nkg = l == 0 ? 4 : 16;\n    gemm_x6<kYRB, true>(", "    const int nkg = l == 0 ? 4 : 16;\n    STAMP(0);\n    gemm_x6<kYRB, true>(")
     s = rep(s, "    // Epilogue, first half -- registers and global memory only, so it needs no barrier:",
             "    STAMP(1);\n    // Epilogue, first half -- registers and global memory only, so it needs no barrier:")
-    s = rep(s, "    lds_barrier6();  // every wave has consumed the input planes\n",
-            "    STAMP(2);\n    lds_barrier6();  // every wave has consumed the input planes\n    STAMP(3);\n")
-    s = rep(s, "      for (int p2 = 0; p2 < 2; ++p2) store_chunk(planes, pw, pw2, r * 32 * kLDB + 16 * p2, pc[r][p2]);\n    lds_barrier6();\n  }\n\n  // heads",
-            "      for (int p2 = 0; p2 < 2; ++p2) store_chunk(planes, pw, pw2, r * 32 * kLDB + 16 * p2, pc[r][p2]);\n    STAMP(4);\n    lds_barrier6();\n    STAMP(5);\n  }\n\n  // heads")
+    s = rep(s, "    lds_barrier();  // every wave has consumed the input planes\n",
+            "    STAMP(2);\n    lds_barrier();  // every wave has consumed the input planes\n    STAMP(3);\n")
+    s = rep(s, "      for (int p2 = 0; p2 < 2; ++p2) store_chunk(planes, pw, pw2, r * 32 * kLDB + 16 * p2, pc[r][p2]);\n    lds_barrier();\n  }\n\n  // heads",
+            "      for (int p2 = 0; p2 < 2; ++p2) store_chunk(planes, pw, pw2, r * 32 * kLDB + 16 * p2, pc[r][p2]);\n    STAMP(4);\n    lds_barrier();\n    STAMP(5);\n  }\n\n  // heads")
     # heads: after the sliced GEMM (6), after the partial sums are staged (7), after the outputs are written (13)
-    s = rep(s, "    lds_barrier6();                                      // every wave is through with the planes\n",
-            "    { const int l = 15; STAMP(6); }\n    lds_barrier6();                                      // every wave is through with the planes\n")
+    s = rep(s, "    lds_barrier();                                      // every wave is through with the planes\n",
+            "    { const int l = 15; STAMP(6); }\n    lds_barrier();                                      // every wave is through with the planes\n")
     s = rep(s, "    const float* hb = bias + 8 * kW;\n    const int col0 =", "    { const int l = 15; STAMP(7); }\n    const float* hb = bias + 8 * kW;\n    const int col0 =")
     s = rep(s, "      raw_sigma[row0 + tid] = v + hb[C];\n    }\n  }\n}\n\ntemplate <int NHB, bool SAVE, bool RGB, bool GRID, bool DYN>",
             "      raw_sigma[row0 + tid] = v + hb[C];\n    }\n  }\n  { const int l = 15; STAMP(13); }\n}\n\ntemplate <int NHB, bool SAVE, bool RGB, bool GRID, bool DYN>")
@@ -69,8 +69,8 @@ def patch(s):
     assert s.count("mslot + sub, tid, wave);") == 1 and s.count("raw_rgb, raw_sigma, acts, enc_out, mslot, tid, wave);") == 1
     s = s.replace("mslot + sub, tid, wave);", "mslot + sub, tid, wave, s_trace, s_tn, trace_on);")
     s = s.replace("raw_rgb, raw_sigma, acts, enc_out, mslot, tid, wave);", "raw_rgb, raw_sigma, acts, enc_out, mslot, tid, wave, s_trace, s_tn, false);")
-    s = rep(s, "      run(slot);\n      slot = tk.take(tid, ticket);\n    }\n  }\n}\n\nstatic unsigned x6_grid(int64_t M) {",
-            "      run(slot);\n      slot = tk.take(tid, ticket);\n    }\n  }\n  if (trace_on) {\n    const int w = wave >> 2;\n    for (int i = 0; i < s_tn; ++i) g_trace[w][i] = s_trace[i];\n    g_trace_n[w] = s_tn;\n  }\n}\n\nstatic unsigned x6_grid(int64_t M) {")
+    s = rep(s, "      run(slot);\n      slot = tk.take(tid, ticket);\n    }\n  }\n}\n\nint launch_mlp_fwd_x6(",
+            "      run(slot);\n      slot = tk.take(tid, ticket);\n    }\n  }\n  if (trace_on) {\n    const int w = wave >> 2;\n    for (int i = 0; i < s_tn; ++i) g_trace[w][i] = s_trace[i];\n    g_trace_n[w] = s_tn;\n  }\n}\n\nint launch_mlp_fwd_x6(")
     s = s.replace("}  // namespace pxo", '''}  // namespace pxo
 extern "C" int pxo_debug_trace(unsigned long long* out, int which, int cap) {
   int n = 0;

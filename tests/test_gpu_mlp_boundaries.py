@@ -3,7 +3,7 @@
 What decides a launch's work split is a function of M (rows) and of the CU count:
   tile_sched (pxo_common.h)      whole rounds of full tiles (pxo_tile_rows() rows, one workgroup per CU), then a ragged
                                  last round that runs as half-height tiles only if it fits one round at half height
-  mlp_grid / x6_grid             one workgroup per CU, or one per tile when there are fewer tiles than CUs
+  mlp_grid                       one workgroup per CU, or one per tile when there are fewer tiles than CUs
   bf16x3                         half-height tiles, two workgroups per CU: a round is the same pxo_tile_rows() * CUs rows
   wgrad_split (wgrad_kernels)    256x256 products: one row range per CU from 1024 rows per CU, 4 CUs / 7 below;
                                  skinny products (enc-based pair, heads): 2 CUs ranges from 512 rows per CU, CUs below
