@@ -241,6 +241,28 @@ int pxo_sample_batch(uint64_t seed, uint64_t stream_id, const float* c2w, int W,
 int pxo_generate_rays_multi(const float* c2w, int n_cams, int W, int H, float focal, const int64_t* ray_ids,
                             int64_t B, float* origins, float* directions, float* viewdirs, void* stream);
 
+/* ---- forward-facing (LLFF) scenes in normalised device coordinates (entry points added without a change of
+ * PXO_ABI_VERSION: no struct and no existing call changes) ----
+ * pxo_generate_rays_ndc: the rays of pxo_generate_rays (n_cams == 1) / pxo_generate_rays_multi (n_cams > 1, c2w [n_cams,3,4],
+ * ray id r -> camera r / (W*H), pixel r % (W*H)) taken through convert_to_ndc (nerf_sh/nerf/datasets.py:40-60; the reference
+ * calls it with near = 1.0 = ndc_near, LLFF._generate_rays :337-345), in float32, in the reference's operation order, with
+ * IEEE divisions:
+ *   t = -(ndc_near + o_z) / d_z,  o <- o + t d,
+ *   o' = (-(2f/W) o_x/o_z, -(2f/H) o_y/o_z, 1 + 2 ndc_near / o_z),
+ *   d' = (-(2f/W) (d_x/d_z - o_x/o_z), -(2f/H) (d_y/d_z - o_y/o_z), -2 ndc_near / o_z).
+ * Every origin then has o'_z = -1 and every ray o'_z + d'_z = 1: the scene lies between ray depths 0 and 1 (near 0, far 1).
+ * viewdirs are the WORLD-space unit directions, bit for bit those of pxo_generate_rays (the reference keeps them).  ray_ids
+ * may be NULL (ids 0..B-1: a whole image of the first camera, or the whole table).  ndc_near > 0. */
+int pxo_generate_rays_ndc(const float* c2w, int n_cams, int W, int H, float focal, float ndc_near, const int64_t* ray_ids,
+                          int64_t B, float* origins, float* directions, float* viewdirs, void* stream);
+
+/* pxo_sample_batch with the ray of pxo_generate_rays_ndc: pixel id i = element first + i of pxo_randint's stream
+ * (seed, stream_id) mod W*H, its NDC ray, its colour from image_rgb [H*W,3] -- bit for bit what pxo_randint,
+ * pxo_generate_rays_ndc and the gather give.  pixel_ids [B] may be NULL. */
+int pxo_sample_batch_ndc(uint64_t seed, uint64_t stream_id, const float* c2w, int W, int H, float focal, float ndc_near,
+                         const float* image_rgb, int64_t B, int64_t first, int64_t* pixel_ids, float* origins,
+                         float* directions, float* viewdirs, float* pixels, void* stream);
+
 /* Step 2 of the extraction (octree/extraction.py:391-393, SH/SG formats): mean over the S samples
  * of each leaf of cat([raw_rgb, raw_sigma]); out [n_cells, 3K+1]. */
 int pxo_mean_over_samples(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, int64_t n_cells,

@@ -121,6 +121,9 @@ SIGNATURES = {
     "pxo_generate_rays": (c_int, [P, c_int, c_int, c_float, P, c_int64, P, P, P, P]),
     "pxo_sample_batch": (c_int, [c_uint64, c_uint64, P, c_int, c_int, c_float, P, c_int64, c_int64, P, P, P, P, P, P]),
     "pxo_generate_rays_multi": (c_int, [P, c_int, c_int, c_int, c_float, P, c_int64, P, P, P, P]),
+    "pxo_generate_rays_ndc": (c_int, [P, c_int, c_int, c_int, c_float, c_float, P, c_int64, P, P, P, P]),
+    "pxo_sample_batch_ndc": (c_int, [c_uint64, c_uint64, P, c_int, c_int, c_float, c_float, P, c_int64, c_int64, P, P, P, P, P,
+                                     P]),
     "pxo_mean_over_samples": (c_int, [CFG, P, P, c_int64, c_int, P, P]),
     "pxo_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_int64, c_float, P]),
     "pxo_adam_pack_step": (c_int, [CFG, P, P, P, P, c_float, c_int64, c_float, P, P, P, P, P]),

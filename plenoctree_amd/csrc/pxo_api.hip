@@ -569,6 +569,27 @@ int pxo_generate_rays_multi(const float* c2w, int n_cams, int W, int H, float fo
                               (hipStream_t)stream);
 }
 
+int pxo_generate_rays_ndc(const float* c2w, int n_cams, int W, int H, float focal, float ndc_near, const int64_t* ray_ids,
+                          int64_t B, float* origins, float* directions, float* viewdirs, void* stream) {
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(B >= 0 && n_cams >= 1 && W >= 1 && H >= 1 && focal > 0.f && ndc_near > 0.f && c2w && origins && directions &&
+                  viewdirs && (ray_ids || B <= (int64_t)n_cams * W * H),
+              "pxo_generate_rays_ndc: bad arguments");
+  return launch_generate_rays_ndc(c2w, n_cams, W, H, focal, ndc_near, ray_ids, B, origins, directions, viewdirs,
+                                  (hipStream_t)stream);
+}
+
+int pxo_sample_batch_ndc(uint64_t seed, uint64_t stream_id, const float* c2w, int W, int H, float focal, float ndc_near,
+                         const float* image_rgb, int64_t B, int64_t first, int64_t* pixel_ids, float* origins,
+                         float* directions, float* viewdirs, float* pixels, void* stream) {
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(B >= 0 && first >= 0 && W >= 1 && H >= 1 && focal > 0.f && ndc_near > 0.f && c2w && image_rgb && origins &&
+                  directions && viewdirs && pixels,
+              "pxo_sample_batch_ndc: bad arguments");
+  return launch_sample_batch_ndc(seed, stream_id, c2w, W, H, focal, ndc_near, image_rgb, B, first, pixel_ids, origins,
+                                 directions, viewdirs, pixels, (hipStream_t)stream);
+}
+
 int pxo_mean_over_samples(const PxoCfg* cfg, const float* raw_rgb, const float* raw_sigma, int64_t n_cells, int S,
                           float* out, void* stream) {
   PXO_TRY(validate_cfg(cfg));

@@ -750,6 +750,33 @@ __device__ __forceinline__ void pixel_ray(const float* __restrict__ c2w, int W, 
   for (int a = 0; a < 3; ++a) v[i * 3 + a] = dir[a] / n;
 }
 
+// convert_to_ndc (nerf_sh/nerf/datasets.py:40-60) of the ray pixel_ray wrote to row i, in place, in the reference's operation
+// order and with IEEE divisions: the origin moves along the ray to the plane z = -near, then both are projected -- a point
+// o + t d of the forward-facing frustum (t from 0 to infinity) becomes o' + t' d' with t' from 0 to 1, o'_z = -1 and
+// o'_z + d'_z = 1.  The viewdir is not touched: the reference keeps the world-space unit direction (LLFF._generate_rays,
+// :337-345).  The row is read back from where the same thread just wrote it, so that pixel_ray and with it the code of the
+// kernels of the bounded scenes stay exactly as they are.
+__device__ __forceinline__ void ndc_row(int W, int H, float focal, float near, int64_t i, float* __restrict__ o,
+                                        float* __restrict__ d) {
+  float org[3], dir[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    org[a] = o[i * 3 + a];
+    dir[a] = d[i * 3 + a];
+  }
+  const float t = -(near + org[2]) / dir[2];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) org[a] = org[a] + t * dir[a];
+  const float cw = (2.f * focal) / (float)W, ch = (2.f * focal) / (float)H;
+  const float ox_oz = org[0] / org[2], oy_oz = org[1] / org[2];
+  o[i * 3 + 0] = -cw * ox_oz;
+  o[i * 3 + 1] = -ch * oy_oz;
+  o[i * 3 + 2] = 1.f + 2.f * near / org[2];
+  d[i * 3 + 0] = -cw * (dir[0] / dir[2] - ox_oz);
+  d[i * 3 + 1] = -ch * (dir[1] / dir[2] - oy_oz);
+  d[i * 3 + 2] = -2.f * near / org[2];
+}
+
 __global__ void generate_rays_kernel(const float* __restrict__ c2w_all, int n_cams, int W, int H, float focal,
                                      const int64_t* __restrict__ pix, int64_t B, float* __restrict__ o,
                                      float* __restrict__ d, float* __restrict__ v) {
@@ -773,6 +800,34 @@ int launch_generate_rays(const float* c2w, int n_cams, int W, int H, float focal
   hipLaunchKernelGGL(generate_rays_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, c2w, n_cams, W, H, focal,
                      pix, B, o, d, v);
   return check_launch("generate_rays");
+}
+
+// generate_rays_kernel followed by convert_to_ndc: the rays an LLFF scene trains and renders with (LLFF._generate_rays,
+// nerf_sh/nerf/datasets.py:327-345).  A kernel of its own, so that the launches of the bounded scenes stay as they are.
+__global__ void generate_rays_ndc_kernel(const float* __restrict__ c2w_all, int n_cams, int W, int H, float focal, float near,
+                                         const int64_t* __restrict__ pix, int64_t B, float* __restrict__ o,
+                                         float* __restrict__ d, float* __restrict__ v) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  int64_t p = pix ? pix[i] : i;
+  const float* __restrict__ c2w = c2w_all;
+  if (n_cams > 1) {
+    const int64_t hw = (int64_t)W * H;
+    int64_t cam = p / hw;
+    if (cam >= n_cams) cam = n_cams - 1;
+    p -= cam * hw;
+    c2w += cam * 12;
+  }
+  pixel_ray(c2w, W, H, focal, p, i, o, d, v);
+  ndc_row(W, H, focal, near, i, o, d);
+}
+
+int launch_generate_rays_ndc(const float* c2w, int n_cams, int W, int H, float focal, float near, const int64_t* pix, int64_t B,
+                             float* o, float* d, float* v, hipStream_t s) {
+  if (B == 0) return PXO_OK;
+  hipLaunchKernelGGL(generate_rays_ndc_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, c2w, n_cams, W, H, focal,
+                     near, pix, B, o, d, v);
+  return check_launch("generate_rays_ndc");
 }
 
 // uniform integers in [0, n) from the Philox stream (the role of np.random.randint in
@@ -921,6 +976,47 @@ int launch_sample_batch(uint64_t seed, uint64_t stream_id, const float* c2w, int
   hipLaunchKernelGGL(sample_batch_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, seed, stream_id, c2w, W, H, focal,
                      image, B, first, ids, o, d, v, pixels);
   return check_launch("sample_batch");
+}
+
+// element e of randint_kernel's stream (seed, stream_id): 64-bit pair e % 2 of Philox block e / 2, mod n -- what
+// sample_batch_kernel spells out in its body, which stays as it is so that its code does not move
+__device__ __forceinline__ int64_t randint_element(uint64_t seed, uint64_t stream_id, int64_t e, int64_t n) {
+  const int64_t q = e >> 1;
+  uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  const int h = (int)(e & 1);
+  const uint64_t r64 = ((uint64_t)(h ? c[2] : c[0]) << 32) | (h ? c[3] : c[1]);
+  return (int64_t)(r64 % (uint64_t)n);
+}
+
+// sample_batch_kernel for an LLFF scene: the same draw and gather, the ray taken through convert_to_ndc -- bit for bit
+// randint_kernel + generate_rays_ndc_kernel + the gather
+__global__ void sample_batch_ndc_kernel(uint64_t seed, uint64_t stream_id, const float* __restrict__ c2w, int W, int H,
+                                        float focal, float near, const float* __restrict__ image, int64_t B, int64_t first,
+                                        int64_t* __restrict__ ids, float* __restrict__ o, float* __restrict__ d,
+                                        float* __restrict__ v, float* __restrict__ pixels) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const int64_t p = randint_element(seed, stream_id, first + i, (int64_t)W * H);
+  if (ids) ids[i] = p;
+  pixel_ray(c2w, W, H, focal, p, i, o, d, v);
+  ndc_row(W, H, focal, near, i, o, d);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) pixels[i * 3 + a] = image[p * 3 + a];
+}
+
+int launch_sample_batch_ndc(uint64_t seed, uint64_t stream_id, const float* c2w, int W, int H, float focal, float near,
+                            const float* image, int64_t B, int64_t first, int64_t* ids, float* o, float* d, float* v,
+                            float* pixels, hipStream_t s) {
+  if (B == 0) return PXO_OK;
+  hipLaunchKernelGGL(sample_batch_ndc_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, seed, stream_id, c2w, W, H,
+                     focal, near, image, B, first, ids, o, d, v, pixels);
+  return check_launch("sample_batch_ndc");
 }
 
 int launch_uniform_jobs(uint64_t seed, const UniformJob* jobs, int n_jobs, hipStream_t s, const float* sq_x, int64_t sq_n,

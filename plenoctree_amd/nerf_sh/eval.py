@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from .. import dist
-from .nerf import datasets, models, sg, utils, viewdirs
+from .nerf import llff, models, sg, utils, viewdirs
 
 
 def save_outputs(out_dir, idx, rgb, disp):
@@ -43,21 +43,31 @@ def main(argv=None):
         sg.check_dirs(args)          # a NeRF-SG (--sg_dim K --sh_deg -1): rendering opts in the same way
     else:
         utils.check_flags(args, world_size=comm.world)
-    dataset = datasets.get_dataset("test", args, device)
+    dataset = llff.get_dataset("test", args, device)
     if args.use_viewdirs:
         model, state = viewdirs.restore_for_render(args, device, say=print if comm.rank == 0 else (lambda *a, **k: None))
     elif args.sg_dim > 0:
         model, state = sg.restore(args, device, say=print if comm.rank == 0 else (lambda *a, **k: None))
     else:
         model, state = models.get_model_state(args, device, restore=True)
-    out_dir = os.path.join(args.train_dir, "test_preds")
+    # eval.py:63-65: a --render_path run (LLFF scenes) renders the dataset's camera path, which has no ground truth
+    render_path = bool(args.render_path)
+    out_dir = os.path.join(args.train_dir, "path_renders" if render_path else "test_preds")
     if args.save_output and comm.rank == 0:
         os.makedirs(out_dir, exist_ok=True)
     psnrs, ssims = [], []
     for idx in range(0, dataset.size, max(args.approx_eval_skip, 1)):
         ex = dataset.get_image(idx)
-        rgb, disp, acc = utils.render_image(lambda r: model.apply(state, r, False), ex["rays"], chunk=args.chunk,
+        rgb, disp, acc = utils.render_image(lambda r: model.apply(state, r, False), ex["rays"],
+                                            normalize_disp=(args.dataset == "llff"), chunk=args.chunk,      # eval.py:89
                                             world_size=comm.world, rank=comm.rank, gather=comm.all_gather_cat)
+        disp = disp[..., 0] if disp.dim() == 3 else disp                        # eval.py:110: pred_disp[Ellipsis, 0]
+        if render_path:
+            if comm.rank == 0:
+                print(f"Rendered {idx + 1}/{dataset.size}", flush=True)
+                if args.save_output:
+                    save_outputs(out_dir, idx, rgb, disp)
+            continue
         psnr = utils.compute_psnr(((rgb - ex["pixels"]) ** 2).mean().item())
         psnrs.append(psnr)
         if comm.rank == 0:
@@ -65,10 +75,10 @@ def main(argv=None):
                 ssim = float(utils.compute_ssim(rgb.clamp(0.0, 1.0), ex["pixels"], max_val=1.0))
                 ssims.append(ssim)
                 print(f"PSNR = {psnr:.4f}, SSIM = {ssim:.4f}", flush=True)
-                save_outputs(out_dir, idx, rgb, disp[..., 0] if disp.dim() == 3 else disp)      # eval.py:110: pred_disp[Ellipsis, 0]
+                save_outputs(out_dir, idx, rgb, disp)
             else:
                 print(f"PSNR = {psnr:.4f}", flush=True)
-    if comm.rank == 0:
+    if comm.rank == 0 and not render_path:
         print(f"Average PSNR {float(np.mean(psnrs)):.4f} over {len(psnrs)} images", flush=True)
         if args.save_output:
             save_summary(out_dir, state.step, psnrs, ssims)

@@ -3,6 +3,10 @@ elevation -> rays -> deterministic render -> PNG frames under <train_dir>/video/
 the reference writes an mp4 through imageio, which is not installed here).
 
     python -m plenoctree_amd.nerf_sh.gen_video --train_dir D --config blender --num_views 40 [--write_poses poses.txt]
+
+A forward-facing scene has no turntable: its model lives in normalised device coordinates, inside the frustum of the capture.
+`--config llff --data_dir DATA --render_path true` renders the scene's own camera path instead (the 120-pose spiral of the LLFF
+loader, or the circle of `--spherify`), at the size of the loaded images, to <train_dir>/video/path/frames.
 """
 import os
 import sys
@@ -11,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import dist, ops
-from .nerf import models, sg, utils, viewdirs
+from .nerf import llff, models, sg, utils, viewdirs
 
 
 def define_flags():
@@ -53,15 +57,25 @@ def main(argv=None):
         sg.check_dirs(args, require_data=False)
     else:
         utils.check_flags(args, require_data=False, world_size=comm.world)
-    say("* Generating poses", flush=True)
-    poses = render_poses(args)
+    path_ds = None
+    if args.dataset == "llff":
+        if not args.render_path or args.data_dir is None:
+            raise ValueError("gen_video on an llff scene renders the scene's camera path: pass --render_path true and --data_dir "
+                             "(turntable poses lie outside the frustum an NDC model is trained in)")
+        say("* Loading the camera path", flush=True)
+        path_ds = llff.get_dataset("test", args, device)
+        poses, args.num_views = path_ds.render_poses, path_ds.size
+        args.height, args.width, focal = path_ds.h, path_ds.w, path_ds.focal
+    else:
+        say("* Generating poses", flush=True)
+        poses = render_poses(args)
+        focal = 0.5 * args.width / np.tan(0.5 * args.camera_angle_x)
+        if args.intrin is not None:
+            K = np.loadtxt(args.intrin)
+            focal = (K[0, 0] + K[1, 1]) * 0.5
     if args.write_poses and comm.rank == 0:
         np.savetxt(args.write_poses, poses.reshape(-1, 4))
         print("Saved poses to", args.write_poses, flush=True)
-    focal = 0.5 * args.width / np.tan(0.5 * args.camera_angle_x)
-    if args.intrin is not None:
-        K = np.loadtxt(args.intrin)
-        focal = (K[0, 0] + K[1, 1]) * 0.5
     say("* Creating model", flush=True)
     if args.use_viewdirs:      # a view-dependent ("vanilla") NeRF: opts in explicitly, like octree.extraction
         model, state = viewdirs.restore_for_render(args, device, say=say, require_data=False)
@@ -69,18 +83,22 @@ def main(argv=None):
         model, state = sg.restore(args, device, say=say, require_data=False)
     else:
         model, state = models.get_model_state(args, device, restore=True)
-    video_dir = os.path.join(args.train_dir, "video", "e{:03}".format(int(-args.elevation * 10)))
+    video_dir = os.path.join(args.train_dir, "video", "path" if path_ds is not None else "e{:03}".format(int(-args.elevation * 10)))
     frames_dir = os.path.join(video_dir, "frames")
     say(" Saving to", video_dir, flush=True)
     if comm.rank == 0:
         os.makedirs(frames_dir, exist_ok=True)
-    c2w = torch.from_numpy(np.ascontiguousarray(poses[:, :3, :4])).to(device)
+    c2w = None if path_ds is not None else torch.from_numpy(np.ascontiguousarray(poses[:, :3, :4])).to(device)
     frames = []
     for i in range(args.num_views):
         say(f"** View {i + 1}/{args.num_views} = {i / args.num_views * 100}%", flush=True)
-        rays = utils.Rays(*[r.reshape(args.height, args.width, 3)
-                            for r in ops.generate_rays(c2w[i], args.width, args.height, focal)])
-        rgb, disp, acc = utils.render_image(lambda r: model.apply(state, r, False), rays, chunk=args.chunk,
+        if path_ds is not None:
+            rays = path_ds.get_image(i)["rays"]
+        else:
+            rays = utils.Rays(*[r.reshape(args.height, args.width, 3)
+                                for r in ops.generate_rays(c2w[i], args.width, args.height, focal)])
+        rgb, disp, acc = utils.render_image(lambda r: model.apply(state, r, False), rays,
+                                            normalize_disp=(args.dataset == "llff"), chunk=args.chunk,     # gen_video.py:158
                                             world_size=comm.world, rank=comm.rank, gather=comm.all_gather_cat)
         if comm.rank == 0:
             utils.save_img(rgb, os.path.join(frames_dir, f"{i:04}.png"))

@@ -78,7 +78,7 @@ def analytic_scene_rgb(origins, directions, white_bkgd=True, return_alpha=False)
 
 
 class HipFeeder:
-    """Batch sampling and ray generation on the MI355X (pxo_randint, pxo_generate_rays[_multi]): no host->device
+    """Batch sampling and ray generation on the MI355X (pxo_randint, pxo_generate_rays[_multi | _ndc]): no host->device
     copy inside the step loop, so the host never waits for the GPU and launches run ahead of the kernels.  This is the
     only feeder of the product; the CPU host-logic tests install their own (tests/_cpu_feeder.py) through
     `Dataset.feeder_factory`."""
@@ -104,6 +104,16 @@ class HipFeeder:
         """randint + generate_rays + the gather of the image's colours in one launch (pxo_sample_batch): the same values as
         the three calls above, bit for bit.  `first`: rows = elements first .. first + count - 1 of the draw."""
         return self.ops.sample_batch(seed, draw, c2w, w, h, focal, image_rgb, count, first=first)
+
+    # the same three for a forward-facing scene (llff.py): the ray taken through the reference's convert_to_ndc inside the launch
+    def generate_rays_ndc(self, c2w, w, h, focal, ray_indices, ndc_near=1.0):
+        return self.ops.generate_rays_ndc(c2w, w, h, focal, ray_indices, ndc_near=ndc_near)
+
+    def generate_rays_multi_ndc(self, c2w_all, w, h, focal, ray_ids, ndc_near=1.0):
+        return self.ops.generate_rays_multi_ndc(c2w_all, w, h, focal, ray_ids, ndc_near=ndc_near)
+
+    def sample_batch_ndc(self, seed, draw, count, c2w, w, h, focal, image_rgb, first=0, ndc_near=1.0):
+        return self.ops.sample_batch_ndc(seed, draw, c2w, w, h, focal, image_rgb, count, first=first, ndc_near=ndc_near)
 
 
 class Dataset:

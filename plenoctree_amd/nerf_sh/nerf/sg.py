@@ -180,6 +180,8 @@ def _unbuilt_flags(args):
         bad.append("noise_std < 0")
     if getattr(args, "render_path", False) or getattr(args, "spherify", False):
         bad.append("render_path / spherify (LLFF scenes)")
+    if getattr(args, "dataset", None) == "llff":
+        bad.append("dataset=llff (LLFF scenes: an SG model on a forward-facing scene is not built)")
     if args.legacy_posenc_order:
         bad.append("legacy_posenc_order")
     if (args.net_activation.lower(), args.rgb_activation.lower(), args.sigma_activation.lower()) != ("relu", "sigmoid", "relu"):

@@ -43,7 +43,7 @@ def define_flags(parser=None):
     a("--train_dir", type=str, default=None)
     a("--data_dir", type=str, default=None)
     a("--config", type=str, default=None)
-    a("--dataset", type=str, default="blender", choices=["blender", "nsvf", "synthetic"])
+    a("--dataset", type=str, default="blender", choices=["blender", "nsvf", "synthetic", "llff"])
     a("--image_batching", type=_bool, default=False)
     a("--white_bkgd", type=_bool, default=True)
     a("--batch_size", type=int, default=1024)
@@ -109,11 +109,13 @@ def define_flags(parser=None):
     a("--chunk", type=int, default=8192)
     a("--approx_eval_skip", type=int, default=1)     # evaluate only every x images (utils.py:225-229)
     a("--seed", type=int, default=20200823)
-    # reference flags of parts that are not built here (LLFF scenes, the view-conditioned vanilla-NeRF head): accepted with
-    # the reference's defaults so that its command lines and presets parse; check_supported rejects what would use them
+    # the flags of forward-facing (LLFF) scenes: they take effect with --dataset llff (nerf/llff.py) and are rejected by
+    # check_supported with any other dataset
     a("--spherify", type=_bool, default=False)             # utils.py:89
     a("--render_path", type=_bool, default=False)          # :90-94
     a("--llffhold", type=int, default=8)                   # :95-100
+    # reference flags of a part that is not built here (training the view-conditioned vanilla-NeRF head): accepted with the
+    # reference's defaults so that its command lines and presets parse; check_supported rejects what would use them
     a("--net_depth_condition", type=int, default=1)        # :108
     a("--net_width_condition", type=int, default=128)      # :109
     return p
@@ -148,7 +150,7 @@ def check_flags(args, require_data=True, require_batch_size_div=False, world_siz
 
 
 def check_supported(args):
-    """The HIP path builds the SH configurations of config/blender.yaml and config/tt.yaml."""
+    """The HIP path builds the SH configurations of config/blender.yaml, config/tt.yaml and config/llff.yaml."""
     bad = []
     if args.use_viewdirs:
         bad.append("use_viewdirs=true (vanilla NeRF head)")
@@ -162,7 +164,7 @@ def check_supported(args):
         bad.append("min/max_deg_point != 0/10")
     if args.noise_std is not None and args.noise_std < 0:
         bad.append("noise_std < 0")
-    if getattr(args, "render_path", False) or getattr(args, "spherify", False):
+    if (getattr(args, "render_path", False) or getattr(args, "spherify", False)) and args.dataset != "llff":
         bad.append("render_path / spherify (LLFF scenes)")
     if args.legacy_posenc_order:
         bad.append("legacy_posenc_order")

@@ -129,6 +129,8 @@ def _unbuilt_flags(args, projection):
         bad.append(f"projection_samples={args.projection_samples} (need >= 1)")
     if getattr(args, "render_path", False) or getattr(args, "spherify", False):
         bad.append("render_path / spherify (LLFF scenes)")
+    if getattr(args, "dataset", None) == "llff":
+        bad.append("dataset=llff (LLFF scenes: the view-conditioned head on a forward-facing scene is not built)")
     if (args.net_activation.lower(), args.sigma_activation.lower()) != ("relu", "relu"):
         bad.append("activations other than relu")
     return bad

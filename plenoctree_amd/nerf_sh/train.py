@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .. import dist
-from .nerf import checkpoints, datasets, models, sg, utils
+from .nerf import checkpoints, llff, models, sg, utils
 
 
 def main(argv=None):
@@ -50,12 +50,12 @@ def main(argv=None):
     if args.per_host_image and not args.image_batching:
         # the reference on ONE host with N local devices: one image per step, its batch_size pixels drawn once and sharded
         # (datasets.py:159-166, utils.py:518-522); every rank carries host 0's seed and takes its contiguous piece of the draw
-        dataset = datasets.get_dataset("train", args, device, batch_size=per_rank, seed=20201473,
+        dataset = llff.get_dataset("train", args, device, batch_size=per_rank, seed=20201473,
                                        shard=(comm.rank, comm.world))
     else:
         # every rank its own host (np.random.seed(20201473 + jax.host_id()), train.py:128): its own image, its own pixels
-        dataset = datasets.get_dataset("train", args, device, batch_size=per_rank, seed=20201473 + comm.rank)
-    test_dataset = datasets.get_dataset("test", args, device)
+        dataset = llff.get_dataset("train", args, device, batch_size=per_rank, seed=20201473 + comm.rank)
+    test_dataset = llff.get_dataset("test", args, device)
     if args.sg_dim > 0:
         model, state = sg.get_train_state(args, device)
         train_step = sg.train_step
@@ -108,7 +108,8 @@ def main(argv=None):
             ex = next(test_dataset)
             t0 = time.time()
             rgb, disp, acc = utils.render_image(
-                lambda r: model.apply(state, r, args.randomized, seed=step), ex["rays"], chunk=args.chunk,
+                lambda r: model.apply(state, r, args.randomized, seed=step), ex["rays"],
+                normalize_disp=(args.dataset == "llff"), chunk=args.chunk,          # train.py:259
                 world_size=comm.world, rank=comm.rank, gather=comm.all_gather_cat)
             torch.cuda.synchronize()
             if h0:                                                   # train.py:262-296

@@ -511,6 +511,47 @@ def generate_rays_multi(c2w_all, W, H, focal, ray_ids):
     return o, d, v
 
 
+def generate_rays_ndc(c2w, W, H, focal, pixel_ids=None, count=None, ndc_near=1.0):
+    """generate_rays taken through the reference's convert_to_ndc (forward-facing scenes): (origins, directions) in normalised
+    device coordinates, viewdirs the world-space unit directions."""
+    _require_gpu()
+    c2w = c2w[:3, :4].contiguous()
+    B = pixel_ids.shape[0] if pixel_ids is not None else (count if count is not None else W * H)
+    dev = c2w.device
+    o, d, v = _new(B, 3, device=dev), _new(B, 3, device=dev), _new(B, 3, device=dev)
+    if pixel_ids is not None and pixel_ids.dtype != torch.int64:
+        raise PxoError("pixel_ids must be int64")
+    check(_lib.load().pxo_generate_rays_ndc(_f(c2w), 1, W, H, float(focal), float(ndc_near), _p(pixel_ids), B, _f(o), _f(d),
+                                            _f(v), _stream()), "pxo_generate_rays_ndc")
+    return o, d, v
+
+
+def generate_rays_multi_ndc(c2w_all, W, H, focal, ray_ids, ndc_near=1.0):
+    """generate_rays_multi taken through convert_to_ndc (image_batching over a forward-facing scene)."""
+    _require_gpu()
+    if ray_ids.dtype != torch.int64:
+        raise PxoError("ray_ids must be int64")
+    c2w_all = c2w_all[:, :3, :4].contiguous()
+    B = ray_ids.shape[0]
+    dev = c2w_all.device
+    o, d, v = _new(B, 3, device=dev), _new(B, 3, device=dev), _new(B, 3, device=dev)
+    check(_lib.load().pxo_generate_rays_ndc(_f(c2w_all), c2w_all.shape[0], W, H, float(focal), float(ndc_near), _p(ray_ids), B,
+                                            _f(o), _f(d), _f(v), _stream()), "pxo_generate_rays_ndc")
+    return o, d, v
+
+
+def sample_batch_ndc(seed, stream_id, c2w, W, H, focal, image_rgb, B, want_ids=False, first=0, ndc_near=1.0):
+    """sample_batch with NDC rays, in one launch: (origins, directions, viewdirs, pixels[, pixel_ids])."""
+    _require_gpu()
+    c2w = c2w[:3, :4].contiguous()
+    dev = c2w.device
+    o, d, v, px = _new(B, 3, device=dev), _new(B, 3, device=dev), _new(B, 3, device=dev), _new(B, 3, device=dev)
+    ids = _new(B, device=dev, dtype=torch.int64) if want_ids else None
+    check(_lib.load().pxo_sample_batch_ndc(seed, stream_id, _f(c2w), W, H, float(focal), float(ndc_near), _f(image_rgb), B,
+                                           int(first), _p(ids), _f(o), _f(d), _f(v), _f(px), _stream()), "pxo_sample_batch_ndc")
+    return (o, d, v, px, ids) if want_ids else (o, d, v, px)
+
+
 def mean_over_samples(cfg, raw_rgb, raw_sigma, samples_per_cell, out=None):
     _require_gpu()
     n = raw_sigma.numel() // samples_per_cell

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Writes the analytic scene of datasets.Synthetic in the reference's two ON-DISK formats, so that the drop-in CLIs can be run
+"""Writes the analytic scene of datasets.Synthetic in the reference's three ON-DISK formats, so that the drop-in CLIs can be run
 through the real loaders at full size (no NeRF-Synthetic / Tanks&Temples scene exists on the boxes):
 
   blender   NeRF-Synthetic directory (nerf_sh/nerf/datasets.py:189-232): transforms_{train,val,test}.json with camera_angle_x and
@@ -8,14 +8,19 @@ through the real loaders at full size (no NeRF-Synthetic / Tanks&Temples scene e
   nsvf      NSVF directory (nerf_sh/nerf/datasets.py:491-552; bbox.txt as octree/nerf/datasets.py:73-77): intrinsics.txt, bbox.txt,
             pose/<p>_<i>.txt (camera-to-world in the OpenCV axes the loader converts FROM), rgb/<p>_<i>.png (8-bit RGB on white),
             prefix 0_ train / 1_ val / 2_ test
+  llff      forward-facing capture (nerf_sh/nerf/datasets.py:235-353): poses_bounds.npy ([n,17]: the 3 x 5 block [R | t | (h, w, f)]
+            of every view in LLFF's (down, right, backwards) axis order, then its near / far depth bound) and images_<factor>/
+            (or images/ with --factor 0) as 8-bit RGB on black.  A rig of its own: --llff_views cameras near z = +4 that look
+            down -z with a small jitter, the three spheres in front of them
 
-The pixel values are those of datasets.Synthetic with synthetic_8bit (colours rounded to k / 255 -- what a PNG holds) and the
+The pixel values of the first two are those of datasets.Synthetic with synthetic_8bit (colours rounded to k / 255 -- what a PNG holds) and the
 poses its float32 matrices printed with 9 significant digits (exact round trip), so a run on these files and a run on the
 Synthetic class with the same options see the SAME bits: rays, pixels, batches (tests/test_gpu_formats.py).  Runs on the GPU
 box (the scene is evaluated by the device feeder).
 
   python scripts/export_scene.py blender /tmp/scene_blender --size 800 800 --views 100 8 8
   python scripts/export_scene.py nsvf /tmp/scene_nsvf --size 1080 1920 --views 100 8 8
+  python scripts/export_scene.py llff /tmp/scene_llff --size 756 1008 --factor 4 --llff_views 20
 """
 import argparse
 import json
@@ -103,13 +108,66 @@ def write_nsvf(path, h, w, n_train, n_val, n_test, device):
     return {"format": "nsvf", "path": path, "size": [h, w], "views": [n_train, n_val, n_test], "focal": focal}
 
 
+LLFF_NEAR, LLFF_FAR = 2.6, 5.6      # depth bounds of every view of the rig below, in its own units
+
+
+def llff_rig(n_views, seed=3):
+    """[n,3,4] float64 camera-to-world matrices (right, up, backwards columns): positions within +-0.45 of (0, 0, 4) in x / y
+    and +-0.1 in z, looking down -z with up to about 3 degrees of rotation jitter.  The spheres reach z = 0.85, so the nearest
+    content is 3.05 in front of the nearest camera: beyond LLFF_NEAR, which the loader's rescale by 1 / (0.75 LLFF_NEAR) puts
+    at 1.33 -- behind the NDC near plane at 1 for every camera of the rig (their z differs by at most 0.2 / 1.95 = 0.10)."""
+    rs = np.random.RandomState(seed)
+    out = []
+    for _ in range(n_views):
+        wx, wy, wz = rs.uniform(-0.05, 0.05, 3)
+        skew = np.array([[0.0, -wz, wy], [wz, 0.0, -wx], [-wy, wx, 0.0]])
+        rot = np.linalg.qr(np.eye(3) + skew)[0]
+        rot = rot * np.sign(np.diag(rot))                    # qr fixes the columns up to sign: keep them near the identity's
+        pos = np.array([rs.uniform(-0.45, 0.45), rs.uniform(-0.45, 0.45), 4.0 + rs.uniform(-0.1, 0.1)])
+        out.append(np.concatenate([rot, pos[:, None]], 1))
+    return np.stack(out)
+
+
+def write_llff(path, h, w, n_views, factor, device):
+    """h x w images into images_<factor>/ (images/ for factor 0); poses_bounds.npy describes the full-size capture
+    (h factor) x (w factor), as LLFF's own files do -- the loader takes the size from the images and divides the focal length."""
+    from PIL import Image
+    from plenoctree_amd.nerf_sh.nerf import datasets, utils
+    full = max(int(factor), 1)
+    focal = 0.5 * w / np.tan(0.5 * 0.6911112)
+    rig = llff_rig(n_views)
+    imgdir = os.path.join(path, "images" + (f"_{factor}" if factor > 0 else ""))
+    os.makedirs(imgdir, exist_ok=True)
+    rows = []
+    for i, c2w in enumerate(rig):
+        rays = utils.generate_rays(w, h, np.float32(focal), c2w[None].astype(np.float32))
+        o = torch.from_numpy(np.ascontiguousarray(rays.origins[0].reshape(-1, 3))).to(device)
+        d = torch.from_numpy(np.ascontiguousarray(rays.directions[0].reshape(-1, 3))).to(device)
+        rgb = datasets.analytic_scene_rgb(o, d, white_bkgd=False)
+        rgb8 = torch.round(rgb * 255.0).to(torch.uint8).reshape(h, w, 3).cpu().numpy()
+        Image.fromarray(rgb8, "RGB").save(os.path.join(imgdir, f"image{i:03d}.png"), compress_level=9 if h * w < 4096 else 1)
+        hwf = np.array([h * full, w * full, focal * full])
+        # (right, up, backwards) -> LLFF's (down, right, backwards): the loader maps the columns back (:280-284)
+        block = np.stack([-c2w[:, 1], c2w[:, 0], c2w[:, 2], c2w[:, 3], hwf], 1)
+        rows.append(np.concatenate([block.ravel(), [LLFF_NEAR, LLFF_FAR]]))
+    np.save(os.path.join(path, "poses_bounds.npy"), np.stack(rows))
+    return {"format": "llff", "path": path, "size": [h, w], "views": n_views, "factor": factor, "focal": focal}
+
+
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("format", choices=["blender", "nsvf"])
+    p.add_argument("format", choices=["blender", "nsvf", "llff"])
     p.add_argument("path")
     p.add_argument("--size", type=int, nargs=2, default=None, metavar=("H", "W"))
     p.add_argument("--views", type=int, nargs=3, default=[100, 8, 8], metavar=("TRAIN", "VAL", "TEST"))
+    p.add_argument("--factor", type=int, default=4, help="llff: the images go to images_<factor>/ (0: images/)")
+    p.add_argument("--llff_views", type=int, default=20)
     a = p.parse_args()
+    if a.format == "llff":          # host rays, the scene evaluated where torch has a device
+        dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
+        h, w = a.size or (756, 1008)
+        print(json.dumps(write_llff(a.path, h, w, a.llff_views, a.factor, dev)))
+        return
     dev = torch.device("cuda:0")
     h, w = a.size or ((800, 800) if a.format == "blender" else (1080, 1920))
     fn = write_blender if a.format == "blender" else write_nsvf
