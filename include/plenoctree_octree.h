@@ -183,6 +183,47 @@ int pxo_octree_render_sg_bwd(const PxoTree* tree, const float* lobes, const PxoC
                              const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts,
                              const float* out_rgb, const float* grad_out, float* grad_data, void* stream);
 
+/* ---- forward-facing (LLFF) scenes in normalised device coordinates  (svox.NDCConfig / RenderOptions.ndc_*;
+ *      octree/extraction.py:184-195, octree/nerf/utils.py:456-474, octree/optimization.py:170-216) ----
+ * The tree of such a scene lives in the NDC cube (--radius 1 1 1 --center 0 0 0); rays arrive in WORLD space, exactly as
+ * for the world-space entry points (from `cam`, or as origins / dirs / viewdirs), and are converted per ray, in float32,
+ * one rounding per operation, IEEE divisions, in this order (o, d: world origin and direction):
+ *   1. View direction.  vdir is the WORLD-space unit direction, taken before the conversion: what the camera produces in
+ *      camera mode, the `viewdirs` argument in explicit-ray mode.  The SH basis is evaluated on vdir, never on the NDC
+ *      direction (the NeRF was trained with world viewdirs, so the baked coefficients expect them).
+ *   2. Conversion (convert_to_ndc, octree/nerf/datasets.py:37-57).  t = -(near + o_z) / d_z;  o = o + t d;  then
+ *        cw = (2 focal) / width,  ch = (2 focal) / height,  ox = o_x / o_z,  oy = o_y / o_z,
+ *        o' = (-cw ox, -ch oy, 1 + (2 near) / o_z),   d' = (-cw (d_x / d_z - ox), -ch (d_y / d_z - oy), (-2 near) / o_z).
+ *      The result does not depend on the length of d.
+ *   3. Normalisation.  n = sqrtf((d'_x^2 + d'_y^2) + d'_z^2),  d' = d' / n.
+ *   4. The world-space code from here: o', d' go through the tree transform, the march, shading, early stop, its rescale
+ *      and the background exactly as o, d do in the world-space twin.  delta_scale is therefore a length in NDC space,
+ *      the quantity a NeRF trained in NDC integrates sigma over.
+ *   5. Misses.  A ray is a miss unless d_z < 0, the six components of o', d' of step 2 are finite and 0 < n < inf.  A
+ *      miss gets the background colour, a zero gradient and no weight; it is decided before the march.
+ * svox's own NDC kernel was not available to compare against: this arithmetic is fixed by the reference's convert_to_ndc and
+ * by the NeRF side of this library (pxo_generate_rays_ndc), which the tree has to reproduce.
+ * Each entry point takes the arguments of its world-space twin plus `ndc` and keeps the twin's contracts (camera or
+ * explicit rays, the out_rgb rule of the backward, accumulation, workspace, asynchrony, pxo_octree_set_lanes_per_ray and
+ * every PXO_TUNE_* knob: all of their choices run the NDC set-up).  SH trees only.  PXO_ERR_ARG on a null ndc, width < 1,
+ * height < 1, focal <= 0, near <= 0, or tree->basis_dim outside {1, 4, 9, 16, 25}.  In camera mode ndc->width / height /
+ * focal describe the projection the scene was trained with; they are independent of cam (callers normally pass equal
+ * values). */
+typedef struct PxoNdc {
+  int32_t width, height;
+  float focal, near;
+} PxoNdc;
+int pxo_octree_render_ndc_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                              const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream,
+                              const PxoNdc* ndc);
+int pxo_octree_render_ndc_bwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                              const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* out_rgb,
+                              const float* grad_out, float* grad_data, void* stream, const PxoNdc* ndc);
+int pxo_grid_weight_render_ndc(const float* sigma_grid, int reso, const float* c2w_all, int n_cams, float fx, float fy,
+                               int width, int height, const PxoRenderOpts* opts, const float offset[3],
+                               const float invradius[3], float* grid_weight, void* ws, size_t ws_bytes, void* stream,
+                               const PxoNdc* ndc);
+
 /* ---- compressed trees rendered in place  (the palette form octree/compression.py:88-139 writes) ----
  *
  * File arrays (K = basis_dim, r = n_retained, Kq = K - r, C = n_internal * 8 cells, P = 2^bits palette entries):

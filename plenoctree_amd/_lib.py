@@ -72,6 +72,10 @@ class PxoCamera(Structure):
     _fields_ = [("c2w", c_void_p), ("fx", c_float), ("fy", c_float), ("width", c_int32), ("height", c_int32)]
 
 
+class PxoNdc(Structure):
+    _fields_ = [("width", c_int32), ("height", c_int32), ("focal", c_float), ("near", c_float)]
+
+
 class PxoQuantLayout(Structure):
     _fields_ = [("idx_offset", c_int64), ("palette_offset", c_int64), ("sigma_offset", c_int64),
                 ("retained_offset", c_int64), ("total_bytes", c_int64), ("idx_stride", c_int32), ("ret_stride", c_int32)]
@@ -187,6 +191,12 @@ SIGNATURES = {
                                          POINTER(PxoRenderOpts), P, P]),
     "pxo_octree_render_sg_bwd": (c_int, [POINTER(PxoTree), P, POINTER(PxoCamera), P, P, P, c_int64,
                                          POINTER(PxoRenderOpts), P, P, P, P]),
+    "pxo_octree_render_ndc_fwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
+                                          POINTER(PxoRenderOpts), P, P, POINTER(PxoNdc)]),
+    "pxo_octree_render_ndc_bwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
+                                          POINTER(PxoRenderOpts), P, P, P, P, POINTER(PxoNdc)]),
+    "pxo_grid_weight_render_ndc": (c_int, [P, c_int, P, c_int, c_float, c_float, c_int, c_int, POINTER(PxoRenderOpts),
+                                           F3, F3, P, P, c_size_t, P, POINTER(PxoNdc)]),
     "pxo_octree_quant_pack_bytes": (c_int, [c_int64, c_int, c_int, c_int, POINTER(PxoQuantLayout)]),
     "pxo_octree_quant_pack": (c_int, [P, P, P, c_int, P, c_int64, c_int, c_int, c_int, P, c_size_t, P]),
     "pxo_octree_render_quant_fwd": (c_int, [POINTER(PxoQuantTree), POINTER(PxoCamera), P, P, P, c_int64,
@@ -226,7 +236,11 @@ def load(path=None):
             "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = ctypes.CDLL(path)
     for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise PxoError(f"{path} does not export {name}: the library is older than this binding; rebuild it with "
+                           "`python -m plenoctree_amd.build`") from None
         fn.restype = restype
         fn.argtypes = argtypes
     # the struct layouts of this module are those of include/plenoctree_hip.h at ABI_VERSION: a stale library (or a stale

@@ -338,6 +338,32 @@ __device__ __forceinline__ void to_tree_ray(const float (&origin)[3], const floa
   dda_unit(r.o, r.invdir, r.tmin, r.tmax);
 }
 
+// NDC set-up of the pxo_*_ndc entry points (plenoctree_octree.h, items 2, 3 and 5): the world-space ray (o, d) becomes the
+// unit-direction ray of normalised device coordinates, in place, between camera_ray / the explicit-ray loads and to_tree_ray.
+// convert_to_ndc (octree/nerf/datasets.py:37-57) in its operation order, IEEE divisions, no contraction -- the expressions of
+// ndc_row in render_kernels.hip, restated here so that that file's instruction streams stay as they are.  Returns false for a
+// miss (d_z >= 0, a non-finite component, or a direction that cannot be normalised): the caller then marches nothing, so no
+// NaN reaches a loop condition.  n.width == 0 marks a world-space launch (every caller tests it first: kernel-uniform).
+__device__ __forceinline__ bool ndc_ray(const PxoNdc& n, float (&o)[3], float (&d)[3]) {
+  const float dz = d[2];
+  const float t = -(n.near + o[2]) / d[2];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) o[a] = o[a] + t * d[a];
+  const float cw = (2.f * n.focal) / (float)n.width, ch = (2.f * n.focal) / (float)n.height;
+  const float ox_oz = o[0] / o[2], oy_oz = o[1] / o[2];
+  const float no[3] = {-cw * ox_oz, -ch * oy_oz, 1.f + 2.f * n.near / o[2]};
+  const float nd[3] = {-cw * (d[0] / d[2] - ox_oz), -ch * (d[1] / d[2] - oy_oz), -2.f * n.near / o[2]};
+  const float nrm = sqrtf((nd[0] * nd[0] + nd[1] * nd[1]) + nd[2] * nd[2]);
+  bool ok = dz < 0.0f && nrm > 0.0f && nrm < INFINITY;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ok = ok && fabsf(no[a]) < INFINITY && fabsf(nd[a]) < INFINITY;       // false for NaN as well
+    o[a] = no[a];
+    d[a] = nd[a] / nrm;
+  }
+  return ok;
+}
+
 __device__ __forceinline__ float clamp_coord(float x) { return fminf(fmaxf(x, 0.0f), 1.0f - 1e-6f); }
 
 // dda_unit for a point INSIDE the unit cell (0 <= cen < 1), as every march step calls it.  The entry distance is then
@@ -462,7 +488,7 @@ template <bool BRICK, bool POW2>
 __device__ __forceinline__ void grid_weight_body(const float* __restrict__ sigma, int reso, const float* __restrict__ c2w_all,
                                                  int n_cams, float fx, float fy, int W, int H, const PxoRenderOpts& opt,
                                                  const Vec3& offset, const Vec3& invradius, int* __restrict__ weight_bits,
-                                                 uint32_t* __restrict__ s_lut = nullptr, int order = 0) {
+                                                 const PxoNdc& ndc, uint32_t* __restrict__ s_lut = nullptr, int order = 0) {
   const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
   const GwTile gt = gw_tile(blockIdx.x, tiles_x, tiles_y, order);
   if (gt.tile < 0 || gt.cam >= n_cams) return;                 // padding of the supertile order (workgroup-uniform)
@@ -486,6 +512,7 @@ __device__ __forceinline__ void grid_weight_body(const float* __restrict__ sigma
   if (cam >= n_cams || px >= W || py >= H) return;
   float origin[3], dir[3];
   camera_ray(c2w_all + (int64_t)cam * 12, fx, fy, W, H, px, py, origin, dir);
+  if (ndc.width > 0 && !ndc_ray(ndc, origin, dir)) return;     // an NDC miss leaves no weight
   TreeRay r;
   to_tree_ray(origin, dir, offset.v, invradius.v, r);
   if (r.tmax < 0.0f || r.tmin > r.tmax) return;
@@ -566,7 +593,8 @@ template <int kWin>
 __device__ __forceinline__ void grid_weight_slab_body(const float* __restrict__ sigma, int reso, const float* __restrict__ c2w_all,
                                                       int n_cams, float fx, float fy, int W, int H, const PxoRenderOpts& opt,
                                                       const Vec3& offset, const Vec3& invradius, int* __restrict__ weight_bits,
-                                                      float* __restrict__ s_sigma, int* __restrict__ s_w, int order) {
+                                                      float* __restrict__ s_sigma, int* __restrict__ s_w, int order,
+                                                      const PxoNdc& ndc) {
   __shared__ int s_first;
   const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
   const GwTile gt = gw_tile(blockIdx.x, tiles_x, tiles_y, order);
@@ -584,6 +612,12 @@ __device__ __forceinline__ void grid_weight_slab_body(const float* __restrict__ 
   {
     float oc[3], dc[3];
     camera_ray(c2w, fx, fy, W, H, min(tx0 + 8, W - 1), min(ty0 + 8, H - 1), oc, dc);
+    // NDC: the sweep follows the converted centre ray.  Should that ray be a miss, any finite ray will do (the window only decides
+    // which samples come from LDS); every NDC ray advances along +z, so the cube's axis is taken.
+    if (ndc.width > 0 && !ndc_ray(ndc, oc, dc)) {
+      oc[0] = oc[1] = 0.0f; oc[2] = -1.0f;
+      dc[0] = dc[1] = 0.0f; dc[2] = 1.0f;
+    }
     to_tree_ray(oc, dc, offset.v, invradius.v, rc);
   }
   const float ad0 = fabsf(rc.d[0]), ad1 = fabsf(rc.d[1]), ad2 = fabsf(rc.d[2]);
@@ -604,6 +638,7 @@ __device__ __forceinline__ void grid_weight_slab_body(const float* __restrict__ 
     float origin[3], dir[3];
     TreeRay r;
     camera_ray(c2w, fx, fy, W, H, min(px, W - 1), min(py, H - 1), origin, dir);
+    if (ndc.width > 0) alive = ndc_ray(ndc, origin, dir) && alive;       // a miss is decided here, before anything marches
     to_tree_ray(origin, dir, offset.v, invradius.v, r);
     alive = alive && !(r.tmax < 0.0f || r.tmin > r.tmax) && r.tmin < r.tmax;
     const int perm[3] = {A, B, C};
@@ -719,23 +754,23 @@ template <bool BRICK, bool POW2>
 __global__ __launch_bounds__(256) void grid_weight_kernel(const float* __restrict__ sigma, int reso,
                                                            const float* __restrict__ c2w_all, int n_cams, float fx, float fy,
                                                            int W, int H, PxoRenderOpts opt, Vec3 offset, Vec3 invradius,
-                                                           int* __restrict__ weight_bits) {
-  grid_weight_body<BRICK, POW2>(sigma, reso, c2w_all, n_cams, fx, fy, W, H, opt, offset, invradius, weight_bits);
+                                                           int* __restrict__ weight_bits, PxoNdc ndc) {
+  grid_weight_body<BRICK, POW2>(sigma, reso, c2w_all, n_cams, fx, fy, W, H, opt, offset, invradius, weight_bits, ndc);
 }
 
 // bricked power-of-two grids: either marcher, chosen per launch (workgroup-uniform)
 __global__ __launch_bounds__(256) void grid_weight_pow2_kernel(const float* __restrict__ sigma, int reso,
                                                                 const float* __restrict__ c2w_all, int n_cams, float fx, float fy,
                                                                 int W, int H, PxoRenderOpts opt, Vec3 offset, Vec3 invradius,
-                                                                int* __restrict__ weight_bits, GwSelect sel) {
+                                                                int* __restrict__ weight_bits, GwSelect sel, PxoNdc ndc) {
   // one block of workgroup scratch for either marcher: the slab marcher's sigma / weight windows, or the per-sample marcher's
   // index tables (3 x 512 words fit the sigma window)
   constexpr int kWin = 6;
   __shared__ __attribute__((aligned(16))) float s_sigma[kWin * kWin * 64];
   __shared__ int s_w[kWin * kWin * 64];
   static_assert(kWin * kWin * 64 >= 3 * kGwLutMax, "the index tables live in the sigma window");
-  if (sel.dense()) grid_weight_slab_body<kWin>(sigma, reso, c2w_all, n_cams, fx, fy, W, H, opt, offset, invradius, weight_bits, s_sigma, s_w, sel.order);
-  else grid_weight_body<true, true>(sigma, reso, c2w_all, n_cams, fx, fy, W, H, opt, offset, invradius, weight_bits,
+  if (sel.dense()) grid_weight_slab_body<kWin>(sigma, reso, c2w_all, n_cams, fx, fy, W, H, opt, offset, invradius, weight_bits, s_sigma, s_w, sel.order, ndc);
+  else grid_weight_body<true, true>(sigma, reso, c2w_all, n_cams, fx, fy, W, H, opt, offset, invradius, weight_bits, ndc,
                                     reinterpret_cast<uint32_t*>(s_sigma), sel.order);
 }
 
@@ -791,6 +826,7 @@ struct RenderArgs {
   int64_t B;
   PxoRenderOpts opt;
   const float* lobes;                          // NULL: SH tree; else the [basis_dim,4] lobes of an SG tree (kernel-uniform)
+  PxoNdc ndc;                                  // width == 0: world-space rays; else the NDC set-up of ndc_ray (kernel-uniform)
 };
 // the per-ray basis of either tree format; everything after it sees only basis[k]
 __device__ __forceinline__ void ray_basis(const RenderArgs& A, int basis_dim, const float (&vdir)[3], float* Y) {
@@ -908,11 +944,14 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
 
   const int K = A.tree.basis_dim, D = A.tree.data_dim;
   const float bg = A.opt.background_brightness;
+  bool ndc_miss = false;
+  if constexpr (!AUX)                          // the extra outputs are world-space distances: no NDC form of them
+    if (A.ndc.width > 0) ndc_miss = !ndc_ray(A.ndc, origin, dir);        // vdir stays the world-space direction
   TreeRay r;
   to_tree_ray(origin, dir, A.tree.offset, A.tree.invradius, r);
   CellExit cell_exit;
   cell_exit.init(r.invdir);
-  const bool miss = r.tmax < 0.0f || r.tmin > r.tmax;
+  const bool miss = ndc_miss || r.tmax < 0.0f || r.tmin > r.tmax;
   static_assert(!AUX || MODE == 0, "alpha / depth / surface: forward only");
   if (MODE == 0 && miss) {
     for (int c = l; c < 3; c += kRow) out_rgb[ray * 3 + c] = bg;
@@ -1182,6 +1221,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_bwd4_kernel(Rend
   const int K = A.tree.basis_dim, D = A.tree.data_dim;
   const int Kc = KF > 0 ? KF : K;
   const float bg = A.opt.background_brightness;
+  if (A.ndc.width > 0) active = ndc_ray(A.ndc, origin, dir) && active;   // an NDC miss: no march, no gradient
   TreeRay r;
   to_tree_ray(origin, dir, A.tree.offset, A.tree.invradius, r);
   CellExit cell_exit;
@@ -1973,9 +2013,20 @@ int pxo_grid_weight_workspace_bytes(int reso, size_t* bytes) {
 static int g_gw_marcher = -1;   // -1: chosen on the device; 0 / 1: forced (pxo_octree_set_tuning)
 static int g_gw_tile_order = 0; // gw_tile: 0 linear, 1 XCD supertiles (PXO_TUNE_GW_TILE_ORDER)
 
-int pxo_grid_weight_render(const float* sigma_grid, int reso, const float* c2w_all, int n_cams, float fx, float fy,
-                           int width, int height, const PxoRenderOpts* opts, const float offset[3],
-                           const float invradius[3], float* grid_weight, void* ws, size_t ws_bytes, void* stream) {
+static const PxoNdc kNoNdc = {0, 0, 0.0f, 0.0f};   // PxoNdc::width == 0: a world-space launch
+
+static int check_ndc(const PxoNdc* ndc, const char* who) {
+  PXO_REQUIRE(ndc, "%s: null ndc", who);
+  PXO_REQUIRE(ndc->width >= 1 && ndc->height >= 1, "%s: ndc width %d / height %d must be >= 1", who, ndc->width, ndc->height);
+  PXO_REQUIRE(ndc->focal > 0.0f && ndc->near > 0.0f, "%s: ndc focal %g and near %g must be > 0", who, (double)ndc->focal,
+              (double)ndc->near);
+  return PXO_OK;
+}
+
+static int grid_weight_render_impl(const float* sigma_grid, int reso, const float* c2w_all, int n_cams, float fx, float fy,
+                                   int width, int height, const PxoRenderOpts* opts, const float offset[3],
+                                   const float invradius[3], float* grid_weight, void* ws, size_t ws_bytes, void* stream,
+                                   const PxoNdc& ndc) {
   if (int rc = check_opts(opts, "pxo_grid_weight_render")) return rc;
   PXO_REQUIRE(reso >= 1 && reso <= 2048 && n_cams >= 0 && width >= 1 && height >= 1, "pxo_grid_weight_render: bad sizes");
   PXO_REQUIRE(fx > 0.0f && fy > 0.0f, "pxo_grid_weight_render: focal length must be > 0");
@@ -1989,7 +2040,7 @@ int pxo_grid_weight_render(const float* sigma_grid, int reso, const float* c2w_a
   const int64_t n = (int64_t)reso * reso * reso;
   if (reso % 4 != 0) {   // grids that do not tile into bricks (never the case for 2^(depth+1), depth >= 1)
     hipLaunchKernelGGL((grid_weight_kernel<false, false>), dim3(gw_grid), dim3(256), 0, s, sigma_grid, reso, c2w_all,
-                       n_cams, fx, fy, width, height, *opts, o, ir, reinterpret_cast<int*>(grid_weight));
+                       n_cams, fx, fy, width, height, *opts, o, ir, reinterpret_cast<int*>(grid_weight), ndc);
     return check_launch("grid_weight_render");
   }
   const size_t need = (size_t)2 * n * sizeof(float) + 256;
@@ -2016,14 +2067,31 @@ int pxo_grid_weight_render(const float* sigma_grid, int reso, const float* c2w_a
     const int64_t per_cam = gw_blocks_per_cam((width + 15) / 16, (height + 15) / 16, g_gw_tile_order);
     PXO_REQUIRE(per_cam * n_cams < ((int64_t)1 << 31), "pxo_grid_weight_render: too many tiles for one launch");
     hipLaunchKernelGGL(grid_weight_pow2_kernel, dim3((unsigned)(per_cam * n_cams)), dim3(256), 0, s, (const float*)sigma_b, reso, c2w_all, n_cams, fx,
-                       fy, width, height, *opts, o, ir, reinterpret_cast<int*>(weight_b), GwSelect{occupied, n, force, g_gw_tile_order});
+                       fy, width, height, *opts, o, ir, reinterpret_cast<int*>(weight_b), GwSelect{occupied, n, force, g_gw_tile_order}, ndc);
   }
   else
     hipLaunchKernelGGL((grid_weight_kernel<true, false>), dim3(gw_grid), dim3(256), 0, s, (const float*)sigma_b, reso, c2w_all,
-                       n_cams, fx, fy, width, height, *opts, o, ir, reinterpret_cast<int*>(weight_b));
+                       n_cams, fx, fy, width, height, *opts, o, ir, reinterpret_cast<int*>(weight_b), ndc);
   hipLaunchKernelGGL(unbrick_max_kernel, dim3((unsigned)blocks_for(n, 256)), dim3(256), 0, s, (const float*)weight_b, reso,
                      grid_weight);
   return check_launch("grid_weight_render");
+}
+
+int pxo_grid_weight_render(const float* sigma_grid, int reso, const float* c2w_all, int n_cams, float fx, float fy,
+                           int width, int height, const PxoRenderOpts* opts, const float offset[3],
+                           const float invradius[3], float* grid_weight, void* ws, size_t ws_bytes, void* stream) {
+  return grid_weight_render_impl(sigma_grid, reso, c2w_all, n_cams, fx, fy, width, height, opts, offset, invradius, grid_weight,
+                                 ws, ws_bytes, stream, kNoNdc);
+}
+
+// the same launches -- either marcher, either tile order, bricked or not -- with the NDC set-up switched on
+int pxo_grid_weight_render_ndc(const float* sigma_grid, int reso, const float* c2w_all, int n_cams, float fx, float fy,
+                               int width, int height, const PxoRenderOpts* opts, const float offset[3],
+                               const float invradius[3], float* grid_weight, void* ws, size_t ws_bytes, void* stream,
+                               const PxoNdc* ndc) {
+  if (int rc = check_ndc(ndc, "pxo_grid_weight_render_ndc")) return rc;
+  return grid_weight_render_impl(sigma_grid, reso, c2w_all, n_cams, fx, fy, width, height, opts, offset, invradius, grid_weight,
+                                 ws, ws_bytes, stream, *ndc);
 }
 
 // Lanes per ray of the renderer launches.  Measured on the 512^3 / 800x800 / SH16 benchmark (profiles/README.md):
@@ -2068,6 +2136,7 @@ static int render_args(const PxoTree* tree, const PxoCamera* cam, const float* o
   A.B = B;
   A.has_cam = cam != nullptr;
   A.lobes = nullptr;                            // the SG entry points set it after their own checks
+  A.ndc = PxoNdc{0, 0, 0.0f, 0.0f};             // the NDC entry points set it after their own checks
   int64_t blocks;
   if (cam) {
     PXO_REQUIRE(cam->c2w && cam->width >= 1 && cam->height >= 1 && cam->fx > 0.0f && cam->fy > 0.0f, "%s: bad camera", who);
@@ -2144,12 +2213,13 @@ static int check_sg(const PxoTree* tree, const float* lobes, const char* who) {
 
 static int octree_render_fwd_impl(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                                   const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* lobes,
-                                  float* out_rgb, void* stream, const char* who) {
+                                  float* out_rgb, void* stream, const char* who, const PxoNdc& ndc = kNoNdc) {
   RenderArgs A;
   unsigned grid;
   int row;
   if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, false, A, grid, row)) return rc;
   A.lobes = lobes;
+  A.ndc = ndc;
   if (B == 0) return PXO_OK;
   PXO_REQUIRE(out_rgb, "%s: null output", who);
   const float* none = nullptr;
@@ -2227,12 +2297,13 @@ int pxo_octree_render_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const f
 static int octree_render_bwd_impl(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                                   const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* lobes,
                                   const float* out_rgb, const float* grad_out, float* grad_data, void* stream,
-                                  const char* who) {
+                                  const char* who, const PxoNdc& ndc = kNoNdc) {
   RenderArgs A;
   unsigned grid;
   int row;
   if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, true, A, grid, row)) return rc;
   A.lobes = lobes;
+  A.ndc = ndc;
   if (B == 0) return PXO_OK;
   PXO_REQUIRE(grad_out && grad_data, "%s: null pointer", who);
   // the gradient pass marches exactly (no early stop, no 1/(1-T) rescale): a forward image made with
@@ -2279,6 +2350,24 @@ int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float
                           const float* grad_out, float* grad_data, void* stream) {
   return octree_render_bwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, nullptr, out_rgb, grad_out, grad_data, stream,
                                 "pxo_octree_render_bwd");
+}
+
+// NDC twins: every launch render_row / the PXO_TUNE_* knobs can select carries RenderArgs::ndc, so each of them runs the
+// NDC set-up (none falls back to the world-space march).  render_args checks the SH format.
+int pxo_octree_render_ndc_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                              const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream,
+                              const PxoNdc* ndc) {
+  if (int rc = check_ndc(ndc, "pxo_octree_render_ndc_fwd")) return rc;
+  return octree_render_fwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, nullptr, out_rgb, stream,
+                                "pxo_octree_render_ndc_fwd", *ndc);
+}
+
+int pxo_octree_render_ndc_bwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                              const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* out_rgb,
+                              const float* grad_out, float* grad_data, void* stream, const PxoNdc* ndc) {
+  if (int rc = check_ndc(ndc, "pxo_octree_render_ndc_bwd")) return rc;
+  return octree_render_bwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, nullptr, out_rgb, grad_out, grad_data, stream,
+                                "pxo_octree_render_ndc_bwd", *ndc);
 }
 
 int pxo_octree_render_sg_bwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,

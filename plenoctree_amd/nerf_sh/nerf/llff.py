@@ -9,8 +9,10 @@ front of that plane lies between ray depths 0 and 1 (the preset's near / far).  
 captures) the poses are put on a unit sphere instead and the rays stay in world space.
 
 The images are resident on the device like the other loaders'; NDC rays are computed on the device inside the launches
-that feed a step (pxo_generate_rays_ndc, pxo_sample_batch_ndc).  Built for the NeRF side only: the octree renderer has no
-NDC (svox.NDCConfig is refused), so octree.extraction / optimization / evaluation keep refusing `llff`."""
+that feed a step (pxo_generate_rays_ndc, pxo_sample_batch_ndc).  The octree entry points (octree.extraction / optimization /
+evaluation) take their dataset from `get_dataset` below as well; what they use of it is world-space -- `camtoworlds`, `focal`,
+`h`, `w` and the images -- because the octree marchers convert each camera ray to NDC themselves (svox.NDCConfig; DESIGN
+section 13.1).  `datasets.get_dataset` keeps refusing `llff`."""
 import functools
 import os
 

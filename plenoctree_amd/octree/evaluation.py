@@ -7,6 +7,9 @@ mean PSNR of its renders of the test split; test images are sharded over the GPU
                                  with float32 depth / surface / alpha; distances are Euclidean, from the camera origin)
         [--write_points F.ply]  (every --points_stride-th pixel of every view whose transmittance falls to --surface_thresh,
                                  back-projected to its surface distance and coloured by the render)
+
+An LLFF scene that is not --spherify is rendered in NDC (octree/nerf/utils.py:451-457); --keep_compressed, --write_aux and
+--write_points are refused there by name, a compressed tree is re-inflated to floats and renders like any float tree.
 """
 import os
 import sys
@@ -15,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import dist
-from ..nerf_sh.nerf import datasets, utils
+from ..nerf_sh.nerf import llff, utils
 from . import aux_io, extraction
 from .svox import N3Tree
 
@@ -88,6 +91,9 @@ def main(argv=None):
         # checked BEFORE anything is rendered: imageio / ffmpeg are not installed, so only the animated GIF writer is built
         raise ValueError(f"--write_vid {args.write_vid}: only animated GIF output is built (no imageio/ffmpeg here); "
                          "give a .gif path")
+    extraction.check_octree_flags(args, "octree.evaluation", (("--keep_compressed", args.keep_compressed),
+                                                              ("--write_aux", args.write_aux is not None),
+                                                              ("--write_points", args.write_points is not None)))
     want_aux = args.write_aux is not None or args.write_points is not None
     if want_aux and args.points_stride < 1:
         raise ValueError(f"--points_stride {args.points_stride}: must be >= 1")
@@ -96,7 +102,7 @@ def main(argv=None):
     comm = dist.init_from_env()
     torch.cuda.set_device(comm.local_rank)
     device = torch.device("cuda", comm.local_rank)
-    dataset = datasets.get_dataset("test", args, device)
+    dataset = llff.get_dataset("test", args, device)
     if comm.rank == 0:
         print("N3Tree load", args.input, flush=True)
     check_sg_flags(args)

@@ -8,6 +8,9 @@
   step 2  3-D antialiasing (:355-394)      S samples per deepest-level cell -> MLP_1 -> mean -> tree data,
                                            nodes sharded over the GPUs
   finish  relu on sigma, save npz, evaluate (:503-516)
+  --config llff (forward-facing scene, not --spherify): the grid and the tree span the NDC cube (--radius 1 1 1 --center 0 0 0,
+          --z_min / --z_max to drop planes); the weight mask and the evaluation convert every world-space camera ray to NDC
+          (svox.NDCConfig).  With --spherify the scene is an ordinary world-space one.
   --sg_dim K --sh_deg -1 (a NeRF-SG, :436-442, :481-499): the same steps with the MLP head of K lobes; the tree is `SG<K>` and
   carries the lobes (softplus(sg_lambda), spher2cart(sg_mu_spher)) as extra_data
 
@@ -23,8 +26,32 @@ import torch
 
 from .. import dist, ops
 from .. import octree_ops as oops
-from ..nerf_sh.nerf import datasets, models, utils
-from .svox import N3Tree, VolumeRenderer
+from ..nerf_sh.nerf import llff, models, utils
+from .svox import N3Tree, NDCConfig, VolumeRenderer
+
+
+def uses_ndc(args):
+    """Whether the octree of this run lives in NDC: an LLFF scene that is not --spherify (octree/extraction.py:187,
+    octree/nerf/utils.py:451; octree/optimization.py:170 leaves the spherify test out, which would render a spherified scene
+    in a space its NeRF never saw -- all three entry points here use this one rule)."""
+    return getattr(args, "dataset", None) == "llff" and not getattr(args, "spherify", False)
+
+
+def ndc_config(args, dataset):
+    """svox.NDCConfig of the run's dataset (octree/extraction.py:187-191), or None for a world-space scene."""
+    return NDCConfig(width=dataset.w, height=dataset.h, focal=dataset.focal) if uses_ndc(args) else None
+
+
+def check_octree_flags(args, who, ndc_refused=()):
+    """What the octree entry points refuse by name on LLFF scenes: --render_path (the camera path has no ground truth and
+    no octree-side writer), and on an NDC scene the flags in `ndc_refused` (name, is-set pairs)."""
+    if getattr(args, "render_path", False):
+        raise NotImplementedError(f"{who}: --render_path is not built on the octree side (render the camera path with "
+                                  "nerf_sh.eval / nerf_sh.gen_video)")
+    bad = [name for name, on in ndc_refused if on]
+    if bad and uses_ndc(args):
+        raise NotImplementedError(f"{who}: {', '.join(bad)} not built for an NDC scene (--dataset llff without --spherify): "
+                                  "palette-form rendering and the alpha / depth / surface outputs have no NDC form")
 
 
 def tree_transform(center, radius):
@@ -94,15 +121,16 @@ def eval_leaf_samples(model, state, points, samples_per_cell):
     return ops.mean_over_samples(model.cfg, rgb, sigma, samples_per_cell)
 
 
-def calculate_grid_weights(dataset, sigmas, reso, invradius, offset, step_size, comm=None):
-    """calculate_grid_weights (:181-214): per-voxel maximum over the training cameras, camera-sharded."""
+def calculate_grid_weights(dataset, sigmas, reso, invradius, offset, step_size, comm=None, ndc=None):
+    """calculate_grid_weights (:181-214): per-voxel maximum over the training cameras, camera-sharded.  ndc: the NDCConfig of a
+    forward-facing scene (the grid then spans the NDC cube and every camera ray is converted), None otherwise."""
     comm = comm or dist.Comm()
     opts = oops.render_opts(step_size=step_size, sigma_thresh=0.0, stop_thresh=0.0)
     cams = torch.from_numpy(np.ascontiguousarray(dataset.camtoworlds[comm.rank::comm.world, :3, :4])).to(sigmas.device)
     weight = torch.zeros(reso ** 3, dtype=torch.float32, device=sigmas.device)
     if cams.shape[0]:
         oops.grid_weight_render(sigmas, reso, cams, dataset.focal, dataset.focal, dataset.w, dataset.h, opts, offset,
-                                invradius, grid_weight=weight)
+                                invradius, grid_weight=weight, **({} if ndc is None else {"ndc": ndc}))
     return comm.all_reduce_max(weight)
 
 
@@ -132,7 +160,8 @@ def step1(args, tree, model, state, dataset, comm):
     if args.masking_mode == "sigma":
         mask = oops.threshold_mask(sig, -np.log(1.0 - args.alpha_thresh) / approx_delta)
     elif args.masking_mode == "weight":
-        weights = calculate_grid_weights(dataset, sig, reso, tree.invradius, tree.offset, args.renderer_step_size, comm)
+        weights = calculate_grid_weights(dataset, sig, reso, tree.invradius, tree.offset, args.renderer_step_size, comm,
+                                         ndc=ndc_config(args, dataset))
         mask = oops.threshold_mask(weights, args.weight_thresh)
         del weights
     else:
@@ -225,9 +254,10 @@ def eval_octree(tree, dataset, args, comm=None, want_frames=False, want_ssim=Fal
     """eval_octree (octree/nerf/utils.py:448-497): mean PSNR (and SSIM if asked) of the octree renders of a split;
     images are sharded over the ranks.  LPIPS needs pretrained VGG weights, which cannot be fetched here.
     aux_sink (off by default): called as aux_sink(idx, c2w, res) for every view of this rank with the dict of
-    VolumeRenderer.render_persp_aux; the view is then rendered by that call (same rgb) instead of render_persp."""
+    VolumeRenderer.render_persp_aux; the view is then rendered by that call (same rgb) instead of render_persp.
+    An LLFF scene that is not --spherify is rendered in NDC (octree/nerf/utils.py:451-457)."""
     comm = comm or dist.Comm()
-    r = VolumeRenderer(tree, step_size=args.renderer_step_size)
+    r = VolumeRenderer(tree, step_size=args.renderer_step_size, ndc=ndc_config(args, dataset))
     acc = torch.zeros(3, dtype=torch.float64, device=tree.device)
     frames = []
     for idx in range(comm.rank, dataset.size, comm.world):
@@ -335,6 +365,7 @@ def main(argv=None, record_projection=False):
     from ..nerf_sh.nerf import sg
     sg.apply_cli(args, argv)                 # --sg_dim K --sh_deg -1 on the command line win over the preset's sh_deg
     args._record_projection = bool(record_projection)
+    check_octree_flags(args, "octree.extraction")
     if not torch.cuda.is_available():
         raise SystemExit("octree.extraction needs a ROCm GPU; the HIP path has no CPU fallback")
     comm = dist.init_from_env()
@@ -360,7 +391,7 @@ def main(argv=None, record_projection=False):
         say("* Loading NeRF", flush=True)
         model, state = models.get_model_state(args, device, restore=False)
         say(load_nerf_checkpoint(args, state), flush=True)
-    dataset = datasets.get_dataset("train", args, device)
+    dataset = llff.get_dataset("train", args, device)      # `llff` is built there, every other name by the plain table
     if args.bbox_from_data:                                  # :447-451 (NSVF datasets carry bbox.txt)
         bbox = getattr(dataset, "bbox", None)
         if bbox is None:
@@ -414,7 +445,7 @@ def main(argv=None, record_projection=False):
         print("* Saving", args.output, flush=True)
         tree.save(args.output, compress=False)
     if args.eval:
-        test = datasets.get_dataset("test", args, device)
+        test = llff.get_dataset("test", args, device)
         say("* Evaluation (before fine tune)", flush=True)
         psnr, _ = eval_octree(tree, test, args, comm)
         say("Average PSNR", psnr, flush=True)

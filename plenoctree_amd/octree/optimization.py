@@ -12,6 +12,9 @@ point; it can overshoot or trip the "Stop since overfitting" break and is opt-in
 invariant to the choice.
 
     python -m plenoctree_amd.octree.optimization --input tree.npz --output tree_opt.npz --config blender --data_dir ...
+
+An LLFF scene that is not --spherify is trained and validated in NDC (svox.NDCConfig of the dataset's size and focal length).
+The reference tests only the config name there (octree/optimization.py:170); this follows extraction and evaluation.
 """
 import os
 import sys
@@ -21,7 +24,8 @@ import torch
 
 from .. import dist, ops
 from .. import octree_ops as oops
-from ..nerf_sh.nerf import datasets, utils
+from ..nerf_sh.nerf import llff, utils
+from . import extraction
 from .svox import N3Tree, VolumeRenderer
 
 
@@ -80,7 +84,7 @@ def train_image(renderer, opt, c2w, gt, H, W, focal):
     im = renderer.render_persp(c2w, width=W, height=H, fx=focal, fast=False)
     sse, g = oops.image_mse(im, gt, want_grad=True)
     oops.octree_render_persp_bwd(renderer.tree.view(), c2w, W, H, focal, renderer._opts(False), g, opt.grad, out_rgb=im,
-                                 **renderer.tree.basis_kwargs())       # SG trees: their lobes
+                                 **renderer._basis_kwargs())           # SG trees: their lobes; NDC scenes: their projection
     return sse
 
 
@@ -103,12 +107,12 @@ def run_validation(renderer, c2ws, images, H, W, focal, comm, vis=None):
 
 
 @torch.no_grad()
-def fit(args, tree, train, val, H, W, focal, comm, say=print):
+def fit(args, tree, train, val, H, W, focal, comm, say=print, ndc=None):
     """The epoch loop of octree/optimization.py:189-243.  train/val = (c2w [n,4,4], list of [H,W,3] images).
     Rank r takes image j0 + r of every group of `world` images; the group's gradients are summed with one
     all-reduce and applied as one step (on their sum or mean, --dp_grad_reduce).  Returns (history, best tree on the CPU or None)."""
     (train_c2w, train_gt), (test_c2w, test_gt) = train, val
-    renderer = VolumeRenderer(tree, step_size=args.renderer_step_size)
+    renderer = VolumeRenderer(tree, step_size=args.renderer_step_size, ndc=ndc)
     opt = TreeOptimizer(tree, args)
     say("Using SGD, lr" if args.sgd else "Using Adam, lr", args.lr, flush=True)
     if comm.world > 1 and args.sgd and getattr(args, "dp_grad_reduce", "mean") == "sum":
@@ -152,6 +156,7 @@ def fit(args, tree, train, val, H, W, focal, comm, say=print):
 def main(argv=None):
     args = define_flags().parse_args(argv)
     utils.update_flags(args)
+    extraction.check_octree_flags(args, "octree.optimization")
     if not torch.cuda.is_available():
         raise SystemExit("octree.optimization needs a ROCm GPU; the HIP path has no CPU fallback")
     comm = dist.init_from_env()
@@ -161,7 +166,7 @@ def main(argv=None):
     say = print if comm.rank == 0 else (lambda *a, **k: None)
 
     def get_data(stage):
-        ds = datasets.get_dataset(stage, args, device)
+        ds = llff.get_dataset(stage, args, device)
         c2w = torch.from_numpy(np.ascontiguousarray(ds.camtoworlds)).float().to(device)
         gt = [ds.get_image(i)["pixels"].contiguous() for i in range(ds.size)]
         return ds, c2w, gt
@@ -178,7 +183,8 @@ def main(argv=None):
         _, test_c2w, test_gt = get_data("test" if args.dataset == "synthetic" else "val")
     say("N3Tree load", flush=True)
     tree = N3Tree.load(args.input, map_location=device)
-    history, best_tree = fit(args, tree, (train_c2w, train_gt), (test_c2w, test_gt), H, W, focal, comm, say)
+    history, best_tree = fit(args, tree, (train_c2w, train_gt), (test_c2w, test_gt), H, W, focal, comm, say,
+                             ndc=extraction.ndc_config(args, ds))
     if not args.nosave and comm.rank == 0:
         if best_tree is not None:
             print("Saving best model to", args.output, flush=True)

@@ -16,7 +16,8 @@ run UNCHANGED with `sys.modules["svox"]` pointing here (tests/test_reference_dri
                                                                                    octree/optimization.py:167-240
     svox.VolumeRenderer(t, step_size, ndc).render_persp(c2w, height, width, fx, fast, cuda)
                                                                   octree/nerf/utils.py:456-474, octree/optimization.py:174-216
-    svox.NDCConfig(width, height, focal)                          (constructed only for LLFF configs: not supported)
+    svox.NDCConfig(width, height, focal)                          octree/nerf/utils.py:456-459, octree/optimization.py:170-173
+                                                                  (LLFF scenes: the tree lives in the NDC cube, see VolumeRenderer)
     svox.helpers._get_c_extension(): RenderOptions(), CameraSpec(), grid_weight_render(...)    octree/extraction.py:181-214
 
 Two ways to build a tree: the generic `tree[points].refine()` above (leaf lookup in HIP, structure edits as tensor
@@ -93,10 +94,17 @@ def parse_data_format(fmt, data_dim):
 
 
 class NDCConfig:
-    """svox.NDCConfig (forward-facing LLFF scenes).  Constructible, but the renderer rejects it: NDC is out of scope."""
+    """svox.NDCConfig (forward-facing LLFF scenes): the projection the scene's NeRF was trained with -- image width, height and
+    focal length in pixels, near plane at `near` (the reference always uses 1).  A plain record; VolumeRenderer(ndc=...) and
+    the weight mask read it."""
 
     def __init__(self, width, height, focal, near=1.0):
-        self.width, self.height, self.focal, self.near = width, height, focal, near
+        self.width, self.height, self.focal, self.near = int(width), int(height), float(focal), float(near)
+        if self.width < 1 or self.height < 1 or not self.focal > 0.0 or not self.near > 0.0:
+            raise ValueError(f"NDCConfig: width {width} / height {height} must be >= 1, focal {focal} and near {near} > 0")
+
+    def __repr__(self):
+        return f"svox.NDCConfig(width={self.width}, height={self.height}, focal={self.focal}, near={self.near})"
 
 
 class N3TreeView:
@@ -647,7 +655,7 @@ class _RenderPersp(torch.autograd.Function):
         tree = renderer.tree
         ctx.args = (renderer, c2w, width, height, fx, fy, opts)
         out = oops.octree_render_persp(oops.tree_view(tree.child, data.detach(), tree.offset, tree.invradius), c2w, width,
-                                       height, fx, opts, fy, **tree.basis_kwargs())
+                                       height, fx, opts, fy, **renderer._basis_kwargs())
         ctx.save_for_backward(out)
         return out
 
@@ -658,16 +666,30 @@ class _RenderPersp(torch.autograd.Function):
         grad = torch.zeros_like(tree.data.data)
         out, = ctx.saved_tensors
         oops.octree_render_persp_bwd(tree.view(), c2w, width, height, fx, opts, grad_out.contiguous(), grad, fy, out_rgb=out,
-                                     **tree.basis_kwargs())
+                                     **renderer._basis_kwargs())
         return grad, None, None, None, None, None, None, None
 
 
 class VolumeRenderer:
-    """svox.VolumeRenderer for perspective cameras (no NDC: the LLFF forward-facing configs are out of scope)."""
+    """svox.VolumeRenderer for perspective cameras.
+
+    ndc: None, or the NDCConfig of a forward-facing (LLFF) scene whose tree lives in the NDC cube.  Cameras and rays are still
+    given in world space; every ray is converted as include/plenoctree_octree.h ("forward-facing scenes") and DESIGN section 13
+    define: the SH basis on the world-space direction, convert_to_ndc, a unit NDC direction, then the unchanged march (step
+    lengths are NDC lengths, what the NeRF integrated sigma over).  svox's own NDC kernel could not be compared.  Float SH
+    trees only: a QuantizedN3Tree, an SG tree and the alpha / depth / surface outputs are refused by name."""
 
     def __init__(self, tree, step_size=1e-3, background_brightness=1.0, ndc=None):
         if ndc is not None:
-            raise NotImplementedError("NDC rendering (LLFF forward-facing scenes) is not supported")
+            if not isinstance(ndc, NDCConfig):
+                raise NotImplementedError(f"VolumeRenderer(ndc=...): NDC rendering takes an svox.NDCConfig, got {type(ndc).__name__}")
+            if isinstance(tree, QuantizedN3Tree):
+                raise NotImplementedError("VolumeRenderer(ndc=...) on a QuantizedN3Tree: NDC rendering of the palette form is not "
+                                          "built; load the tree without keep_quantized")
+            if getattr(tree, "extra_data", None) is not None:
+                raise NotImplementedError(f"VolumeRenderer(ndc=...) on an SG tree ({tree.data_format}): NDC rendering is built for "
+                                          "SH trees only")
+        self.ndc = ndc
         self.tree = tree
         self.step_size = float(step_size)
         self.background_brightness = float(background_brightness)
@@ -676,9 +698,26 @@ class VolumeRenderer:
         thr = 1e-2 if fast else 0.0              # svox: fast = early stopping + skip of near-empty cells
         return oops.render_opts(self.step_size, self.background_brightness, thr, thr)
 
+    def _basis_kwargs(self):
+        """What selects the launch in octree_ops: the lobes of an SG tree, the projection of an NDC scene, nothing otherwise."""
+        kw = dict(self.tree.basis_kwargs())
+        if self.ndc is not None:
+            kw["ndc"] = self.ndc
+        return kw
+
+    def _check_ndc_camera(self, width, height, fx, fy):
+        """An NDC tree was built for ONE projection: a camera of another size or focal length renders rubbish without a word."""
+        n = self.ndc
+        if n is None:
+            return
+        if int(width) != n.width or int(height) != n.height or float(fx) != n.focal or (fy is not None and float(fy) != n.focal):
+            raise ValueError(f"render_persp(width={width}, height={height}, fx={fx}, fy={fy}) does not match the renderer's "
+                             f"{n!r}: an NDC tree renders only the projection it was extracted for")
+
     def render_persp(self, c2w, width=800, height=800, fx=1111.111, fy=None, fast=False, cuda=True):
         """[H,W,3] image.  With grad mode on and a tree whose `data` requires grad the exact render (fast=False, as in
         octree/optimization.py:216) is differentiable; the early-stopping preset (fast=True, evaluation) never is."""
+        self._check_ndc_camera(width, height, fx, fy)
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.tree.device)
         if isinstance(self.tree, QuantizedN3Tree):
             # nothing in a compressed tree requires grad: rendered directly, with grad mode on as well, `fast` both ways
@@ -692,18 +731,22 @@ class VolumeRenderer:
                 raise oops.PxoError("render_persp(fast=True) is not differentiable: call it under torch.no_grad(), "
                                     "or use fast=False to optimise the tree")
             return _RenderPersp.apply(data, self, c2w, width, height, fx, fy, self._opts(False))
-        return oops.octree_render_persp(self.tree.view(), c2w, width, height, fx, self._opts(fast), fy, **self.tree.basis_kwargs())
+        return oops.octree_render_persp(self.tree.view(), c2w, width, height, fx, self._opts(fast), fy, **self._basis_kwargs())
 
     def forward(self, origins, dirs, viewdirs, fast=False):
-        """Colours [B,3] of explicit world-space rays (unit `dirs`)."""
+        """Colours [B,3] of explicit world-space rays (unit `dirs`); with `ndc` the rays are converted per ray and `viewdirs`
+        (world space) shade them."""
         if isinstance(self.tree, QuantizedN3Tree):
             return oops.octree_render_quant_rays(self.tree.quant_view(), origins, dirs, viewdirs, self._opts(fast))
-        return oops.octree_render_rays(self.tree.view(), origins, dirs, viewdirs, self._opts(fast), **self.tree.basis_kwargs())
+        return oops.octree_render_rays(self.tree.view(), origins, dirs, viewdirs, self._opts(fast), **self._basis_kwargs())
 
     __call__ = forward
 
     # ---- additions (no svox counterpart): opacity, expected distance and surface distance from the same march ----
     def _aux_view(self, what):
+        if self.ndc is not None:
+            raise NotImplementedError(f"{what} with NDC: alpha / depth / surface are not built for an NDC scene (the distances "
+                                      "would be NDC lengths, not world distances)")
         if getattr(self.tree, "extra_data", None) is not None:
             raise NotImplementedError(f"{what} on an SG tree ({self.tree.data_format}): alpha / depth / surface are built for SH "
                                       "trees only")
@@ -757,13 +800,14 @@ class _CameraSpec:
 def _grid_weight_render(grid_data, cam, opts, offset, invradius):
     """_C.grid_weight_render (octree/extraction.py:205-211): (max compositing weight per voxel, hit mask) of one camera
     through the dense sigma grid [reso, reso, reso]."""
-    if getattr(opts, "ndc_width", -1) > 0:
-        raise NotImplementedError("NDC grid_weight_render (LLFF forward-facing scenes) is not supported")
+    ndc = None
+    if getattr(opts, "ndc_width", -1) > 0:              # octree/extraction.py:190-193: set for LLFF scenes, -1 otherwise
+        ndc = NDCConfig(opts.ndc_width, opts.ndc_height, opts.ndc_focal)
     reso = grid_data.shape[0]
     o = oops.render_opts(opts.step_size, opts.background_brightness, opts.sigma_thresh, opts.stop_thresh)
     c2w = torch.as_tensor(cam.c2w, dtype=torch.float32, device=grid_data.device)[None, :3, :4]
     w = oops.grid_weight_render(grid_data.contiguous().reshape(-1), reso, c2w, cam.fx, cam.fy, cam.width, cam.height, o,
-                                offset, invradius)
+                                offset, invradius, **({} if ndc is None else {"ndc": ndc}))
     w = w.reshape(reso, reso, reso)
     return w, w > 0
 

@@ -106,8 +106,22 @@ def tree_relu_sigma(data):
     check(_lib.load().pxo_tree_relu_sigma(_f(data), data.numel() // dim, dim, _stream()), "pxo_tree_relu_sigma")
 
 
-def grid_weight_render(sigma_grid, reso, c2w_all, fx, fy, width, height, opts, offset, invradius, grid_weight=None):
-    """Per-voxel maximum compositing weight over all pixels of the given cameras (c2w_all [n,3,4] or [n,4,4])."""
+def ndc_spec(width, height, focal, near=1.0):
+    """PxoNdc: the projection an LLFF scene was trained with (include/plenoctree_octree.h, "forward-facing scenes")."""
+    return _lib.PxoNdc(int(width), int(height), float(focal), float(near))
+
+
+def _ndc(ndc):
+    """PxoNdc of anything that carries width / height / focal (and optionally near): a PxoNdc, an svox NDCConfig."""
+    if isinstance(ndc, _lib.PxoNdc):
+        return ndc
+    return ndc_spec(ndc.width, ndc.height, ndc.focal, getattr(ndc, "near", 1.0))
+
+
+def grid_weight_render(sigma_grid, reso, c2w_all, fx, fy, width, height, opts, offset, invradius, grid_weight=None, ndc=None):
+    """Per-voxel maximum compositing weight over all pixels of the given cameras (c2w_all [n,3,4] or [n,4,4]).  ndc: None for
+    a world-space grid, or the projection (ndc_spec / NDCConfig) of a forward-facing scene whose grid spans the NDC cube
+    (pxo_grid_weight_render_ndc)."""
     _require_gpu()
     lib = _lib.load()
     dev = sigma_grid.device
@@ -117,9 +131,12 @@ def grid_weight_render(sigma_grid, reso, c2w_all, fx, fy, width, height, opts, o
     nbytes = ctypes.c_size_t(0)
     check(lib.pxo_grid_weight_workspace_bytes(reso, ctypes.byref(nbytes)), "pxo_grid_weight_workspace_bytes")
     ws = _new(max(nbytes.value, 16), device=dev, dtype=torch.uint8)
-    check(lib.pxo_grid_weight_render(_f(sigma_grid.reshape(-1)), reso, _f(c2w), c2w.shape[0], float(fx), float(fy),
-                                     int(width), int(height), ctypes.byref(opts), _vec3(offset), _vec3(invradius),
-                                     _f(grid_weight), _p(ws), nbytes.value, _stream()), "pxo_grid_weight_render")
+    args = (_f(sigma_grid.reshape(-1)), reso, _f(c2w), c2w.shape[0], float(fx), float(fy), int(width), int(height),
+            ctypes.byref(opts), _vec3(offset), _vec3(invradius), _f(grid_weight), _p(ws), nbytes.value, _stream())
+    if ndc is None:
+        check(lib.pxo_grid_weight_render(*args), "pxo_grid_weight_render")
+    else:
+        check(lib.pxo_grid_weight_render_ndc(*args, ctypes.byref(_ndc(ndc))), "pxo_grid_weight_render_ndc")
     return grid_weight
 
 
@@ -149,9 +166,20 @@ def _lobes(lobes, tree):
     return _f(lobes)
 
 
-def _render_fwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out):
-    """pxo_octree_render_fwd, or pxo_octree_render_sg_fwd when the tree's SG lobes are given."""
-    if lobes is None:
+def _no_sg_ndc(lobes, ndc):
+    if lobes is not None and ndc is not None:
+        raise NotImplementedError("NDC rendering of an SG tree is not built: the NDC launches (pxo_octree_render_ndc_*) take SH "
+                                  "trees only")
+
+
+def _render_fwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out, ndc=None):
+    """pxo_octree_render_fwd; pxo_octree_render_sg_fwd when the tree's SG lobes are given; pxo_octree_render_ndc_fwd when the
+    scene's NDC projection is."""
+    _no_sg_ndc(lobes, ndc)
+    if ndc is not None:
+        check(_lib.load().pxo_octree_render_ndc_fwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts),
+                                                    _f(out), _stream(), ctypes.byref(_ndc(ndc))), "pxo_octree_render_ndc_fwd")
+    elif lobes is None:
         check(_lib.load().pxo_octree_render_fwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts), _f(out),
                                                 _stream()), "pxo_octree_render_fwd")
     else:
@@ -160,9 +188,15 @@ def _render_fwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out):
     return out
 
 
-def _render_bwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out_rgb, grad_out, grad_data):
-    """pxo_octree_render_bwd, or pxo_octree_render_sg_bwd when the tree's SG lobes are given."""
-    if lobes is None:
+def _render_bwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out_rgb, grad_out, grad_data, ndc=None):
+    """pxo_octree_render_bwd; pxo_octree_render_sg_bwd when the tree's SG lobes are given; pxo_octree_render_ndc_bwd when the
+    scene's NDC projection is."""
+    _no_sg_ndc(lobes, ndc)
+    if ndc is not None:
+        check(_lib.load().pxo_octree_render_ndc_bwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts),
+                                                    _f(out_rgb), _f(grad_out), _f(grad_data), _stream(),
+                                                    ctypes.byref(_ndc(ndc))), "pxo_octree_render_ndc_bwd")
+    elif lobes is None:
         check(_lib.load().pxo_octree_render_bwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts),
                                                 _f(out_rgb), _f(grad_out), _f(grad_data), _stream()), "pxo_octree_render_bwd")
     else:
@@ -197,21 +231,24 @@ def set_tuning(knob, value):
     check(_lib.load().pxo_octree_set_tuning(int(knob), int(value)), "pxo_octree_set_tuning")
 
 
-def octree_render_persp(tree, c2w, width, height, fx, opts, fy=None, lobes=None):
+def octree_render_persp(tree, c2w, width, height, fx, opts, fy=None, lobes=None, ndc=None):
     """[H,W,3] image of a pinhole camera (VolumeRenderer.render_persp).  lobes: the [K,4] extra_data of an SG tree (the
-    spherical-Gaussian basis instead of SH), None for an SH tree."""
+    spherical-Gaussian basis instead of SH), None for an SH tree.  ndc: the projection (ndc_spec / NDCConfig) of a
+    forward-facing scene whose tree lives in the NDC cube, None for a world-space tree."""
     _require_gpu()
     cam, keep = _camera(c2w, width, height, fx, fy)
     out = _new(height, width, 3, device=keep.device)
-    return _render_fwd(tree, lobes, ctypes.byref(cam), None, None, None, width * height, opts, out)
+    return _render_fwd(tree, lobes, ctypes.byref(cam), None, None, None, width * height, opts, out, ndc=ndc)
 
 
-def octree_render_persp_bwd(tree, c2w, width, height, fx, opts, grad_out, grad_data, fy=None, out_rgb=None, lobes=None):
+def octree_render_persp_bwd(tree, c2w, width, height, fx, opts, grad_out, grad_data, fy=None, out_rgb=None, lobes=None,
+                            ndc=None):
     """Accumulates d sum(image * grad_out) / d data into grad_data; `out_rgb` = the exact forward image of the same
-    camera (saves one of the two marches) or None.  lobes: as in octree_render_persp."""
+    camera (saves one of the two marches) or None.  lobes, ndc: as in octree_render_persp."""
     _require_gpu()
     cam, keep = _camera(c2w, width, height, fx, fy)
-    return _render_bwd(tree, lobes, ctypes.byref(cam), None, None, None, width * height, opts, out_rgb, grad_out, grad_data)
+    return _render_bwd(tree, lobes, ctypes.byref(cam), None, None, None, width * height, opts, out_rgb, grad_out, grad_data,
+                       ndc=ndc)
 
 
 def octree_count_work(tree, c2w, width, height, fx, opts, fy=None, count_leaves=True):
@@ -243,12 +280,13 @@ def grid_weight_count_work(sigma_grid, reso, c2w_all, fx, fy, width, height, opt
             "distinct_voxels": int(seen.sum(dtype=torch.int64)) if count_voxels else None}
 
 
-def octree_render_rays(tree, origins, dirs, viewdirs, opts, lobes=None):
-    """[B,3] colours of explicit world-space rays with unit dirs (VolumeRenderer.forward).  lobes: as in octree_render_persp."""
+def octree_render_rays(tree, origins, dirs, viewdirs, opts, lobes=None, ndc=None):
+    """[B,3] colours of explicit world-space rays with unit dirs (VolumeRenderer.forward).  lobes, ndc: as in
+    octree_render_persp (with ndc the rays are still given in world space; they are converted per ray)."""
     _require_gpu()
     B = origins.shape[0]
     out = _new(B, 3, device=origins.device)
-    return _render_fwd(tree, lobes, None, _f(origins), _f(dirs), _f(viewdirs), B, opts, out)
+    return _render_fwd(tree, lobes, None, _f(origins), _f(dirs), _f(viewdirs), B, opts, out, ndc=ndc)
 
 
 # ---- compressed trees rendered in place (the palette form of octree/compression.py:88-139) ----
@@ -355,10 +393,10 @@ def octree_render_aux_rays(tree, origins, dirs, viewdirs, opts, surface_thresh=0
     return out, aux
 
 
-def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None, lobes=None):
+def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None, lobes=None, ndc=None):
     _require_gpu()
     return _render_bwd(tree, lobes, None, _f(origins), _f(dirs), _f(viewdirs), origins.shape[0], opts, out_rgb, grad_out,
-                       grad_data)
+                       grad_data, ndc=ndc)
 
 
 def image_mse(im, gt, want_grad=True):
