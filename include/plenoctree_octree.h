@@ -307,6 +307,51 @@ int pxo_grid_weight_count_work(const float* sigma_grid, int reso, const float* c
                                const float invradius[3], unsigned long long* counts, uint8_t* voxel_seen,
                                void* stream);
 
+/* ---- per-leaf compositing weights  (svox N3Tree.accumulate_weights; no call site in the reference: the published svox
+ *      interface, parity unpinned) ----
+ * For every ray, the march of pxo_octree_render_fwd without shading, operation for operation: the ray from camera_ray
+ * (cameras) or the explicit loads, the NDC conversion above when `ndc` is given (NULL: world space), the tree transform, the
+ * clamp of the position to [0, 1 - 1e-6], the leaf lookup, the step  delta = cell_exit(local) * 2^-(depth+1) + step_size,
+ * the test sigma > sigma_thresh, light *= att with a stop once light <= stop_thresh, and the end of the march when
+ * !(t + delta > t).  For every shaded sample in leaf l,
+ *   w = light * (1 - expf(-(delta * delta_scale) * sigma))
+ * which is the forward kernel's compositing weight of that sample, taken before any early-stop rescale.
+ *   op == 0 (max)  weights[l] = max(weights[l], w)      op == 1 (sum)  weights[l] += w   (atomic, any order)
+ * weights: float32 [n_internal*8], indexed by the flat cell index node*8 + cell that addresses the rows of `data`; the caller
+ * zeroes it and it ACCUMULATES across calls (max: the result does not depend on the order of rays or calls, bit for bit).
+ * Cells that are not leaves are never written.  Rays that miss the volume and NDC misses contribute nothing.
+ * sigma is read at data[l * data_dim + data_dim - 1]: SH and SG float trees alike; no basis is evaluated, no lobes needed,
+ * basis_dim is not looked at.
+ * _cams: c2w_all [n_cams,12] device, as pxo_grid_weight_render takes it; one launch covers all n_cams * width * height rays
+ * (ray = (camera * height + py) * width + px).  _rays: origins / dirs [B,3] in world space, unit dirs.
+ * PXO_ERR_ARG: op outside {0, 1}, n_cams < 0, B < 0, width / height < 1, a focal length <= 0, and with non-empty work a null
+ * tree / options / ray or camera array / weights, step_size <= 0 or a bad ndc.  n_cams == 0 and B == 0 return 0 without
+ * a launch. */
+int pxo_octree_weight_accum_cams(const PxoTree* tree, const float* c2w_all, int n_cams, float fx, float fy,
+                                 int width, int height, const PxoRenderOpts* opts, int op,
+                                 float* weights, void* stream, const PxoNdc* ndc /* NULL: world space */);
+int pxo_octree_weight_accum_rays(const PxoTree* tree, const float* origins, const float* dirs, int64_t B,
+                                 const PxoRenderOpts* opts, int op, float* weights, void* stream,
+                                 const PxoNdc* ndc);
+
+/* ---- structural collapse of a tree under a keep mask over its cells  (no svox counterpart) ----
+ * keep: uint8 [n*8] over cells.  A leaf cell is dead when keep == 0; a node is dead when each of its 8 cells is a dead leaf
+ * or points to a dead node; the root is never removed.  A dead node disappears and the parent cell that pointed to it
+ * becomes a dead leaf.  Three steps:
+ *   pxo_tree_collapse_mark   node_dead uint8 [n]: bottom-up, one pass per depth max_depth .. 1, nodes selected by
+ *                            parent_depth[:,1] (so node order does not matter); max_depth = the deepest node's depth
+ *   the caller               new_index int64 [n] = exclusive scan of (node_dead == 0); n_new = number of survivors
+ *   pxo_tree_collapse_emit   new_child [n_new,8]: index(new child) - index(new node), 0 where the cell is a leaf or its
+ *                            child died; new_parent_depth [n_new,2]; new_data [n_new,8,data_dim]: a survivor's rows copied,
+ *                            every dead leaf cell (old, or made by a node's removal) an all-zero row; old2new int64 [n]
+ *                            (-1 for removed nodes)
+ * Survivors keep their relative storage order: a breadth-first tree stays breadth-first. */
+int pxo_tree_collapse_mark(const int32_t* child, const int32_t* parent_depth, const uint8_t* keep, int64_t n, int max_depth,
+                           uint8_t* node_dead, void* stream);
+int pxo_tree_collapse_emit(const int32_t* child, const int32_t* parent_depth, const float* data, int data_dim,
+                           const uint8_t* keep, const uint8_t* node_dead, const int64_t* new_index, int64_t n, int64_t n_new,
+                           int32_t* new_child, int32_t* new_parent_depth, float* new_data, int64_t* old2new, void* stream);
+
 /* mse = mean((clamp(im,0,1) - gt)^2) and its gradient w.r.t. im  (octree/optimization.py:217-219);
  * n = number of floats.  sse_out: device scalar receiving sum of squares (mse = sse/n); grad may be NULL. */
 int pxo_image_mse(const float* im, const float* gt, int64_t n, float* grad, float* sse_out, void* stream);

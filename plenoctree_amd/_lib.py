@@ -206,6 +206,12 @@ SIGNATURES = {
     "pxo_octree_count_work": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), POINTER(PxoRenderOpts), P, P, P]),
     "pxo_grid_weight_count_work": (c_int, [P, c_int, P, c_int, c_float, c_float, c_int, c_int, POINTER(PxoRenderOpts),
                                            F3, F3, P, P, P]),
+    "pxo_octree_weight_accum_cams": (c_int, [POINTER(PxoTree), P, c_int, c_float, c_float, c_int, c_int, POINTER(PxoRenderOpts),
+                                             c_int, P, P, POINTER(PxoNdc)]),
+    "pxo_octree_weight_accum_rays": (c_int, [POINTER(PxoTree), P, P, c_int64, POINTER(PxoRenderOpts), c_int, P, P,
+                                             POINTER(PxoNdc)]),
+    "pxo_tree_collapse_mark": (c_int, [P, P, P, c_int64, c_int, P, P]),
+    "pxo_tree_collapse_emit": (c_int, [P, P, P, c_int, P, P, P, c_int64, c_int64, P, P, P, P, P]),
     "pxo_image_mse": (c_int, [P, P, c_int64, P, P, P]),
     "pxo_sgd_step": (c_int, [P, P, P, c_int64, c_float, c_float, c_int, c_int, P]),
 }

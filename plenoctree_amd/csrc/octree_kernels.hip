@@ -1860,6 +1860,151 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(std
     for (int c = l; c < 3; c += kRow) A.out[ray * 3 + c] = c == 0 ? aux[0] : (c == 1 ? aux[1] : aux[2]);
 }
 
+// ------------------------------------------------------------------------------------------
+// per-leaf compositing weights (svox N3Tree.accumulate_weights; pxo_octree_weight_accum_* in plenoctree_octree.h)
+// The forward renderer's march without shading, as octree_count_kernel repeats it -- same ray set-up (NDC included), leaf
+// lookup, step rule, sigma test, attenuation, early stop and `!(tn > t)` guard, hence the same sample sequence -- and for
+// every shaded sample its `weight`, light * (1 - expf(-(delta * delta_scale) * sigma)), merged into weights[leaf].  One thread
+// per ray; in camera mode ray = (camera * H + py) * W + px over all cameras of c2w_all ([n_cams,12]).
+//   OP 0  max: weights are >= 0, so their float order is the order of their bit patterns as signed integers (the weight-mask
+//         marchers' atomicMax); a plain load in front keeps samples that cannot raise the value from issuing an atomic
+//   OP 1  sum: float atomic add
+// ------------------------------------------------------------------------------------------
+struct WeightArgs {
+  PxoTree tree;
+  const float* c2w_all;                        // camera mode (non-NULL): [n_cams,12]
+  float fx, fy;
+  int W, H;
+  const float* origins;                        // explicit rays: [n_rays,3] each
+  const float* dirs;
+  int64_t n_rays;                              // camera mode: n_cams * W * H
+  PxoRenderOpts opt;
+  PxoNdc ndc;                                  // width == 0: world-space rays
+  float* weights;                              // [n_internal*8]
+};
+
+template <int OP>
+__global__ __launch_bounds__(256) void octree_weight_kernel(WeightArgs A) {
+  __shared__ int s_stack[256][kMaxD + 2];
+  const int64_t ray = blockIdx.x * (int64_t)256 + threadIdx.x;
+  if (ray >= A.n_rays) return;                 // no barrier below
+  float origin[3], dir[3];
+  if (A.c2w_all) {
+    const int64_t per_cam = (int64_t)A.W * A.H;
+    const int64_t cam = ray / per_cam;
+    const int pix = (int)(ray - cam * per_cam);
+    camera_ray(A.c2w_all + cam * 12, A.fx, A.fy, A.W, A.H, pix % A.W, pix / A.W, origin, dir);
+  } else {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      origin[a] = A.origins[ray * 3 + a];
+      dir[a] = A.dirs[ray * 3 + a];
+    }
+  }
+  bool ndc_miss = false;
+  if (A.ndc.width > 0) ndc_miss = !ndc_ray(A.ndc, origin, dir);
+  TreeRay r;
+  to_tree_ray(origin, dir, A.tree.offset, A.tree.invradius, r);
+  CellExit cell_exit;
+  cell_exit.init(r.invdir);
+  if (ndc_miss || r.tmax < 0.0f || r.tmin > r.tmax) return;
+  const int D = A.tree.data_dim;
+  const float* __restrict__ data = A.tree.data;
+  const int32_t* __restrict__ child = A.tree.child;
+  float* weights = A.weights;
+  Marcher mk;
+  mk.init(s_stack[threadIdx.x]);
+  float t = r.tmin, light = 1.0f;
+  while (t < r.tmax) {
+    float pos[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + t * r.d[a]);
+    int depth;
+    const int64_t leaf = mk.find(child, pos, depth);
+    const float cube = (float)(2u << depth);
+    float local[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) local[a] = __builtin_amdgcn_fractf(pos[a] * cube);
+    const float delta_t = cell_exit(local) * inv_cells(depth) + A.opt.step_size;
+    const float sg = data[leaf * D + D - 1];
+    if (sg > A.opt.sigma_thresh) {
+      const float dtw = delta_t * r.delta_scale;
+      const float att = expf(-dtw * sg);
+      const float weight = light * (1.0f - att);
+      if (OP == 0) {
+        if (weight > weights[leaf]) atomicMax(reinterpret_cast<int*>(weights + leaf), __float_as_int(weight));
+      } else {
+        if (weight > 0.0f) unsafeAtomicAdd(weights + leaf, weight);
+      }
+      light = light * att;
+      if (light <= A.opt.stop_thresh) break;
+    }
+    const float tn = t + delta_t;
+    if (!(tn > t)) break;
+    t = tn;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// structural collapse (pxo_tree_collapse_mark / _emit in plenoctree_octree.h)
+// ------------------------------------------------------------------------------------------
+// one pass per depth, deepest first: a node of depth d is dead when each of its cells is a leaf with keep == 0 or points
+// to a (depth d + 1, already decided) dead node.  Nodes are picked by their stored depth, not by their position.
+__global__ void tree_collapse_mark_kernel(const int32_t* __restrict__ child, const int32_t* __restrict__ parent_depth,
+                                          const uint8_t* __restrict__ keep, int64_t n, int d, uint8_t* __restrict__ node_dead) {
+  const int64_t node = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (node >= n || parent_depth[node * 2 + 1] != d) return;
+  bool dead = true;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int skip = child[node * 8 + c];
+    dead = dead && (skip == 0 ? keep[node * 8 + c] == 0 : node_dead[node + skip] != 0);
+  }
+  node_dead[node] = dead ? 1 : 0;
+}
+
+// a cell of a surviving node keeps its row unless it is a dead leaf or pointed to a dead node
+__device__ __forceinline__ bool collapse_cell_live(const int32_t* __restrict__ child, const uint8_t* __restrict__ keep,
+                                                   const uint8_t* __restrict__ node_dead, int64_t cell) {
+  const int skip = child[cell];
+  return skip == 0 ? keep[cell] != 0 : node_dead[(cell >> 3) + skip] == 0;
+}
+
+// one thread per old cell: child offsets between the survivors' new positions; cell 0 also writes the node's own records
+__global__ void tree_collapse_struct_kernel(const int32_t* __restrict__ child, const int32_t* __restrict__ parent_depth,
+                                            const uint8_t* __restrict__ node_dead, const int64_t* __restrict__ new_index,
+                                            int64_t n, int32_t* __restrict__ new_child, int32_t* __restrict__ new_parent_depth,
+                                            int64_t* __restrict__ old2new) {
+  const int64_t cell = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (cell >= n * 8) return;
+  const int64_t node = cell >> 3;
+  const int c = (int)(cell & 7);
+  const bool dead = node_dead[node] != 0;
+  if (c == 0) old2new[node] = dead ? -1 : new_index[node];
+  if (dead) return;
+  const int64_t m = new_index[node];
+  const int skip = child[cell];
+  new_child[m * 8 + c] = (skip != 0 && node_dead[node + skip] == 0) ? (int32_t)(new_index[node + skip] - m) : 0;
+  if (c == 0) {
+    const int32_t p = parent_depth[node * 2];            // the parent of a survivor survives; the root's record is (0, 0)
+    new_parent_depth[m * 2] = (int32_t)(new_index[p >> 3] * 8 + (p & 7));
+    new_parent_depth[m * 2 + 1] = parent_depth[node * 2 + 1];
+  }
+}
+
+// one thread per old data element: survivors' rows move to their new place, rows of dead leaf cells become zero
+__global__ void tree_collapse_data_kernel(const int32_t* __restrict__ child, const float* __restrict__ data, int D,
+                                          const uint8_t* __restrict__ keep, const uint8_t* __restrict__ node_dead,
+                                          const int64_t* __restrict__ new_index, int64_t n, float* __restrict__ new_data) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n * 8 * D) return;
+  const int64_t cell = i / D;
+  const int64_t node = cell >> 3;
+  if (node_dead[node]) return;
+  const float v = collapse_cell_live(child, keep, node_dead, cell) ? data[i] : 0.0f;
+  new_data[(new_index[node] * 8 + (cell & 7)) * D + (i - cell * D)] = v;
+}
+
 }  // namespace pxo
 
 // ==========================================================================================
@@ -2529,6 +2674,92 @@ int pxo_octree_count_work(const PxoTree* tree, const PxoCamera* cam, const PxoRe
   hipLaunchKernelGGL(octree_count_kernel, dim3((unsigned)blocks_for(rays, 256)), dim3(256), 0, (hipStream_t)stream, A, counts,
                      leaf_seen);
   return check_launch("octree_count_work");
+}
+
+// what the two weight entry points share: the checks on tree / options / op / ndc / weights and the launch
+static int weight_accum_launch(const PxoTree* tree, WeightArgs& A, const PxoRenderOpts* opts, int op, float* weights,
+                               void* stream, const PxoNdc* ndc, const char* who) {
+  if (int rc = check_opts(opts, who)) return rc;
+  PXO_REQUIRE(op == 0 || op == 1, "%s: op %d is neither 0 (max) nor 1 (sum)", who, op);
+  PXO_REQUIRE(tree && tree->child && tree->data, "%s: null tree", who);
+  PXO_REQUIRE(tree->data_dim >= 1, "%s: data_dim %d < 1", who, tree->data_dim);
+  PXO_REQUIRE(tree->n_internal >= 1 && tree->n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
+  PXO_REQUIRE(weights, "%s: null weights", who);
+  if (ndc)
+    if (int rc = check_ndc(ndc, who)) return rc;
+  const int64_t blocks = blocks_for(A.n_rays, 256);
+  PXO_REQUIRE(blocks < ((int64_t)1 << 31), "%s: too many rays for one launch", who);
+  A.tree = *tree;
+  A.opt = *opts;
+  A.ndc = ndc ? *ndc : kNoNdc;
+  A.weights = weights;
+  if (op == 0)
+    hipLaunchKernelGGL(octree_weight_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
+  else
+    hipLaunchKernelGGL(octree_weight_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
+  return check_launch(who);
+}
+
+int pxo_octree_weight_accum_cams(const PxoTree* tree, const float* c2w_all, int n_cams, float fx, float fy, int width,
+                                 int height, const PxoRenderOpts* opts, int op, float* weights, void* stream,
+                                 const PxoNdc* ndc) {
+  const char* who = "pxo_octree_weight_accum_cams";
+  PXO_REQUIRE(op == 0 || op == 1, "%s: op %d is neither 0 (max) nor 1 (sum)", who, op);
+  PXO_REQUIRE(n_cams >= 0, "%s: n_cams %d < 0", who, n_cams);
+  PXO_REQUIRE(width >= 1 && height >= 1 && fx > 0.0f && fy > 0.0f, "%s: bad camera (width, height >= 1, focal lengths > 0)", who);
+  if (n_cams == 0) return PXO_OK;
+  PXO_REQUIRE(c2w_all, "%s: null c2w_all", who);
+  WeightArgs A{};
+  A.c2w_all = c2w_all;
+  A.fx = fx; A.fy = fy; A.W = width; A.H = height;
+  A.n_rays = (int64_t)n_cams * width * height;
+  return weight_accum_launch(tree, A, opts, op, weights, stream, ndc, who);
+}
+
+int pxo_octree_weight_accum_rays(const PxoTree* tree, const float* origins, const float* dirs, int64_t B,
+                                 const PxoRenderOpts* opts, int op, float* weights, void* stream, const PxoNdc* ndc) {
+  const char* who = "pxo_octree_weight_accum_rays";
+  PXO_REQUIRE(op == 0 || op == 1, "%s: op %d is neither 0 (max) nor 1 (sum)", who, op);
+  PXO_REQUIRE(B >= 0, "%s: B < 0", who);
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(origins && dirs, "%s: null ray arrays", who);
+  WeightArgs A{};
+  A.origins = origins; A.dirs = dirs;
+  A.n_rays = B;
+  return weight_accum_launch(tree, A, opts, op, weights, stream, ndc, who);
+}
+
+int pxo_tree_collapse_mark(const int32_t* child, const int32_t* parent_depth, const uint8_t* keep, int64_t n, int max_depth,
+                           uint8_t* node_dead, void* stream) {
+  PXO_REQUIRE(n >= 1 && n < ((int64_t)1 << 28), "pxo_tree_collapse_mark: n out of range");
+  PXO_REQUIRE(max_depth >= 0 && max_depth <= kMaxD, "pxo_tree_collapse_mark: max_depth %d outside [0, %d]", max_depth, kMaxD);
+  PXO_REQUIRE(child && parent_depth && keep && node_dead, "pxo_tree_collapse_mark: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(node_dead, 0, (size_t)n, s) != hipSuccess) {      // the root (depth 0) is never removed
+    set_error("pxo_tree_collapse_mark: hipMemsetAsync failed");
+    return PXO_ERR_HIP;
+  }
+  for (int d = max_depth; d >= 1; --d)
+    hipLaunchKernelGGL(tree_collapse_mark_kernel, dim3((unsigned)blocks_for(n, 256)), dim3(256), 0, s, child, parent_depth, keep,
+                       n, d, node_dead);
+  return check_launch("tree_collapse_mark");
+}
+
+int pxo_tree_collapse_emit(const int32_t* child, const int32_t* parent_depth, const float* data, int data_dim,
+                           const uint8_t* keep, const uint8_t* node_dead, const int64_t* new_index, int64_t n, int64_t n_new,
+                           int32_t* new_child, int32_t* new_parent_depth, float* new_data, int64_t* old2new, void* stream) {
+  PXO_REQUIRE(n >= 1 && n < ((int64_t)1 << 28) && n_new >= 1 && n_new <= n, "pxo_tree_collapse_emit: n / n_new out of range");
+  PXO_REQUIRE(data_dim >= 1 && data_dim <= 256, "pxo_tree_collapse_emit: data_dim %d outside [1, 256]", data_dim);
+  PXO_REQUIRE(child && parent_depth && data && keep && node_dead && new_index && new_child && new_parent_depth && new_data &&
+              old2new, "pxo_tree_collapse_emit: null pointer");
+  const int64_t data_blocks = blocks_for(n * 8 * data_dim, 256);
+  PXO_REQUIRE(data_blocks < ((int64_t)1 << 31), "pxo_tree_collapse_emit: too many data elements for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(tree_collapse_struct_kernel, dim3((unsigned)blocks_for(n * 8, 256)), dim3(256), 0, s, child, parent_depth,
+                     node_dead, new_index, n, new_child, new_parent_depth, old2new);
+  hipLaunchKernelGGL(tree_collapse_data_kernel, dim3((unsigned)data_blocks), dim3(256), 0, s, child, data, data_dim, keep,
+                     node_dead, new_index, n, new_data);
+  return check_launch("tree_collapse_emit");
 }
 
 int pxo_grid_weight_count_work(const float* sigma_grid, int reso, const float* c2w_all, int n_cams, float fx, float fy,

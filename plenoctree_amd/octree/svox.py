@@ -19,6 +19,8 @@ run UNCHANGED with `sys.modules["svox"]` pointing here (tests/test_reference_dri
     svox.NDCConfig(width, height, focal)                          octree/nerf/utils.py:456-459, octree/optimization.py:170-173
                                                                   (LLFF scenes: the tree lives in the NDC cube, see VolumeRenderer)
     svox.helpers._get_c_extension(): RenderOptions(), CameraSpec(), grid_weight_render(...)    octree/extraction.py:181-214
+    with tree.accumulate_weights(op) as accum: ...; accum.value      no call site in the reference: svox's published interface
+                                                                  (octree/pruning.py here); prune_ / refine_leaves are additions
 
 Two ways to build a tree: the generic `tree[points].refine()` above (leaf lookup in HIP, structure edits as tensor
 index operations, as svox itself does them), and `refine_from_mask` -- the whole init_grid_depth refinement of the
@@ -208,6 +210,7 @@ class N3Tree:
         self._leaves = None            # packed indices of all leaves, svox order
         self._level_order = True       # nodes stored breadth-first, levels contiguous (fast-path methods need it)
         self._sample_seed, self._sample_calls = 0, 0
+        self._weight_accum = None      # the active WeightAccumulator (accumulate_weights), if any
 
     # ---- structure -------------------------------------------------------------------------------
     @property
@@ -385,7 +388,53 @@ class N3Tree:
         t.extra_data = None if self.extra_data is None else self.extra_data.detach().clone().to(dev)
         t.level_nodes = list(self.level_nodes)
         t._leaves = None
+        t._weight_accum = None                   # an accumulator belongs to the tree it was opened on
         return t
+
+    # ---- leaf weights (svox N3Tree.accumulate_weights; published interface, parity unpinned) -------------------------
+    def accumulate_weights(self, op="sum"):
+        """Context manager: while it is active every VolumeRenderer.render_persp / forward call on this tree also accumulates,
+        per leaf, the compositing weights of its samples (`op`: "sum" or "max" over all rays rendered inside the block).
+
+            with tree.accumulate_weights(op="max") as accum:
+                renderer.render_persp(c2w, ...)
+            accum.value            # [n_internal, 2, 2, 2]; accum() is the same tensor
+
+        The images rendered inside the block are those rendered outside it.  Blocks do not nest, and the tree's structure must
+        not change inside one (refine, prune_, refine_from_mask): the next render then raises."""
+        return WeightAccumulator(self, op)
+
+    # ---- additions (no svox counterpart): prune by a mask over cells, split a chosen set of leaves --------------------
+    def _cell_mask(self, mask, what):
+        mask = torch.as_tensor(mask, device=self.device)
+        if mask.dtype != torch.bool or mask.numel() != self.n_internal * 8:
+            raise ValueError(f"{what}: the mask must be bool over the tree's {self.n_internal} x 2 x 2 x 2 cells, got "
+                             f"{mask.dtype} with {mask.numel()} entries")
+        return mask.reshape(-1)
+
+    def prune_(self, keep, collapse=True):
+        """Zeroes every leaf whose `keep` (bool over cells, e.g. `accum.value > thresh`) is False and, with `collapse`, removes
+        every node left with nothing but dead leaves below it, bottom-up, folding it back into one zero leaf of its parent (the
+        root stays).  Entries of `keep` at cells that are not leaves are ignored.  Returns the number of nodes removed."""
+        keep = self._cell_mask(keep, "prune_")
+        n0 = self.n_internal
+        with torch.no_grad():
+            if not collapse:
+                dead = (self.child.view(-1) == 0) & ~keep
+                self.data.data.view(-1, self.data_dim)[dead] = 0
+                return 0
+            child, pd, data, _ = oops.tree_collapse(self.child, self.parent_depth, self.data.data, keep)
+            self.child, self.parent_depth = child, pd
+            self.data = torch.nn.Parameter(data, requires_grad=self.data.requires_grad)
+            self.level_nodes = [int(c) for c in torch.bincount(pd[:, 1].long()).tolist()]
+            self._leaves = None                  # survivors keep their order: _level_order stays as it was
+        return n0 - self.n_internal
+
+    def refine_leaves(self, mask):
+        """Splits every leaf whose `mask` (bool over cells) is True into 2^3 children holding its value; leaves already at
+        depth_limit stay.  Entries at cells that are not leaves are ignored.  Returns the number of nodes added."""
+        mask = self._cell_mask(mask, "refine_leaves")
+        return self._refine_packed(torch.nonzero(mask & (self.child.view(-1) == 0)).reshape(-1))
 
     # ---- npz (svox N3Tree.save / load; keys as consumed by octree/compression.py:76-86) ------------------
     def save(self, path, shrink=True, compress=True):
@@ -429,6 +478,42 @@ class N3Tree:
         n = _load_geometry(t, z, dev)
         t.data = torch.nn.Parameter(torch.from_numpy(z["data"][:n].astype(np.float32)).to(dev))
         return t
+
+
+class WeightAccumulator:
+    """What `with tree.accumulate_weights(op) as accum` yields: `accum.value` (also `accum()`) is the [n_internal, 2, 2, 2]
+    float32 tensor of per-leaf weights, zero at cells that are not leaves and at leaves no ray rendered inside the block has
+    shaded.  It stays readable after the block."""
+
+    def __init__(self, tree, op):
+        if op not in oops.WEIGHT_OPS:
+            raise ValueError(f"accumulate_weights(op={op!r}): op must be 'sum' or 'max'")
+        self.tree, self.op, self.value = tree, op, None
+        self._child = None
+
+    def __enter__(self):
+        t = self.tree
+        if t._weight_accum is not None:
+            raise PxoError("accumulate_weights: this tree already has an active accumulator (the blocks do not nest)")
+        self._child = t.child                    # every structure edit replaces tree.child by a new tensor
+        self.value = torch.zeros(t.n_internal, 2, 2, 2, dtype=torch.float32, device=t.device)
+        t._weight_accum = self
+        return self
+
+    def __exit__(self, *exc):
+        self.tree._weight_accum = None
+        self._child = None
+        return False
+
+    def __call__(self):
+        return self.value
+
+    def _buffer(self):
+        """The flat accumulator for a launch; refuses a tree that was refined / pruned / rebuilt since the block opened."""
+        if self.tree.child is not self._child:
+            raise PxoError("accumulate_weights: the tree's structure changed inside the block (refine / prune_ / "
+                           "refine_from_mask): the accumulated weights no longer address its cells")
+        return self.value.view(-1)
 
 
 def _checked_extra_data(extra_data, data_format, dev):
@@ -625,6 +710,15 @@ class QuantizedN3Tree:
     def relu_sigma_(self):
         self._read_only("relu_sigma_")
 
+    def accumulate_weights(self, op="sum"):
+        self._read_only("accumulate_weights")
+
+    def prune_(self, keep, collapse=True):
+        self._read_only("prune_")
+
+    def refine_leaves(self, mask):
+        self._read_only("refine_leaves")
+
     def view(self):
         self._read_only("view()")
 
@@ -723,7 +817,13 @@ class VolumeRenderer:
             # nothing in a compressed tree requires grad: rendered directly, with grad mode on as well, `fast` both ways
             return oops.octree_render_quant_persp(self.tree.quant_view(), c2w, width, height, fx, self._opts(fast), fy)
         data = self.tree.data
-        if torch.is_grad_enabled() and data.requires_grad:
+        differentiable = torch.is_grad_enabled() and data.requires_grad
+        accum = self.tree._weight_accum
+        if accum is not None and not (differentiable and fast):
+            # one more launch on the same camera and options; the rgb launches and their results are untouched
+            oops.octree_weight_accum_cams(self.tree.view(), c2w[None], width, height, fx, self._opts(fast), accum.op,
+                                          accum._buffer(), fy, ndc=self.ndc)
+        if differentiable:
             if fast:
                 # every fast=True call site of the reference sits under torch.no_grad() (octree/nerf/utils.py:276,
                 # octree/evaluation.py:73); silently returning a detached image would surface later as an obscure
@@ -738,6 +838,10 @@ class VolumeRenderer:
         (world space) shade them."""
         if isinstance(self.tree, QuantizedN3Tree):
             return oops.octree_render_quant_rays(self.tree.quant_view(), origins, dirs, viewdirs, self._opts(fast))
+        accum = self.tree._weight_accum
+        if accum is not None:
+            oops.octree_weight_accum_rays(self.tree.view(), origins, dirs, self._opts(fast), accum.op, accum._buffer(),
+                                          ndc=self.ndc)
         return oops.octree_render_rays(self.tree.view(), origins, dirs, viewdirs, self._opts(fast), **self._basis_kwargs())
 
     __call__ = forward

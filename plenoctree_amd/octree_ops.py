@@ -280,6 +280,79 @@ def grid_weight_count_work(sigma_grid, reso, c2w_all, fx, fy, width, height, opt
             "distinct_voxels": int(seen.sum(dtype=torch.int64)) if count_voxels else None}
 
 
+WEIGHT_OPS = {"max": 0, "sum": 1}
+
+
+def _weight_op(op):
+    if op not in WEIGHT_OPS:
+        raise PxoError(f"weight accumulation op {op!r} is neither 'sum' nor 'max'")
+    return WEIGHT_OPS[op]
+
+
+def _weights_buffer(tree, weights, dev):
+    """The [n_internal*8] float32 accumulator of the weight launches: a fresh zeroed one, or the caller's, checked."""
+    cells = tree.n_internal * 8
+    if weights is None:
+        return torch.zeros(cells, dtype=torch.float32, device=dev)
+    if weights.dtype != torch.float32 or weights.numel() != cells or not weights.is_contiguous() or not weights.is_cuda:
+        raise PxoError(f"weights must be a contiguous float32 tensor of {cells} cells on the GPU")
+    return weights
+
+
+def octree_weight_accum_cams(tree, c2w_all, width, height, fx, opts, op="max", weights=None, fy=None, ndc=None):
+    """Accumulates, per leaf of `tree` (a PxoTree), the compositing weights the forward renderer gives its samples over every
+    pixel of the cameras c2w_all ([n,3,4] or [n,4,4]) into `weights` ([n_internal*8] float32, zeros when None): op "max" or
+    "sum" (pxo_octree_weight_accum_cams).  ndc: as in octree_render_persp.  Returns `weights`."""
+    _require_gpu()
+    c2w = c2w_all[:, :3, :4].contiguous().to(dtype=torch.float32)
+    weights = _weights_buffer(tree, weights, c2w.device)
+    check(_lib.load().pxo_octree_weight_accum_cams(ctypes.byref(tree), _f(c2w), c2w.shape[0], float(fx),
+                                                   float(fx if fy is None else fy), int(width), int(height), ctypes.byref(opts),
+                                                   _weight_op(op), _f(weights), _stream(),
+                                                   None if ndc is None else ctypes.byref(_ndc(ndc))),
+          "pxo_octree_weight_accum_cams")
+    return weights
+
+
+def octree_weight_accum_rays(tree, origins, dirs, opts, op="max", weights=None, ndc=None):
+    """octree_weight_accum_cams for explicit world-space rays [B,3] with unit dirs (pxo_octree_weight_accum_rays)."""
+    _require_gpu()
+    weights = _weights_buffer(tree, weights, origins.device)
+    check(_lib.load().pxo_octree_weight_accum_rays(ctypes.byref(tree), _f(origins), _f(dirs), origins.shape[0],
+                                                   ctypes.byref(opts), _weight_op(op), _f(weights), _stream(),
+                                                   None if ndc is None else ctypes.byref(_ndc(ndc))),
+          "pxo_octree_weight_accum_rays")
+    return weights
+
+
+def tree_collapse(child, parent_depth, data, keep):
+    """Removes every node all of whose cells are dead (keep == 0 leaves, or children that are themselves removed; the root
+    stays) and zeroes the rows of dead leaf cells: (child, parent_depth, data, old2new) of the collapsed tree, old2new int64
+    [n] with -1 for removed nodes (pxo_tree_collapse_mark, a scan, pxo_tree_collapse_emit).  keep: bool / uint8 over cells."""
+    _require_gpu()
+    lib = _lib.load()
+    n, D, dev = child.shape[0], data.shape[-1], child.device
+    if child.dtype != torch.int32 or parent_depth.dtype != torch.int32 or data.dtype != torch.float32:
+        raise PxoError("tree_collapse: child / parent_depth must be int32, data float32")
+    if keep.numel() != n * 8 or data.numel() != n * 8 * D or parent_depth.numel() != n * 2:
+        raise PxoError(f"tree_collapse: keep / data / parent_depth do not match the {n} nodes of child")
+    child, parent_depth, data = child.contiguous(), parent_depth.contiguous(), data.detach().contiguous()
+    keep = keep.reshape(-1).to(torch.uint8).contiguous()
+    node_dead = _new(n, device=dev, dtype=torch.uint8)
+    check(lib.pxo_tree_collapse_mark(_p(child), _p(parent_depth), _p(keep), n, int(parent_depth[:, 1].max()), _p(node_dead),
+                                     _stream()), "pxo_tree_collapse_mark")
+    alive = (node_dead == 0).to(torch.int64)
+    new_index = (torch.cumsum(alive, 0) - alive).contiguous()            # exclusive scan of the survivors
+    n_new = int(alive.sum())
+    new_child = _new(n_new, 2, 2, 2, device=dev, dtype=torch.int32)
+    new_pd = _new(n_new, 2, device=dev, dtype=torch.int32)
+    new_data = _new(n_new, 2, 2, 2, D, device=dev)
+    old2new = _new(n, device=dev, dtype=torch.int64)
+    check(lib.pxo_tree_collapse_emit(_p(child), _p(parent_depth), _f(data), D, _p(keep), _p(node_dead), _p(new_index), n, n_new,
+                                     _p(new_child), _p(new_pd), _f(new_data), _p(old2new), _stream()), "pxo_tree_collapse_emit")
+    return new_child, new_pd, new_data, old2new
+
+
 def octree_render_rays(tree, origins, dirs, viewdirs, opts, lobes=None, ndc=None):
     """[B,3] colours of explicit world-space rays with unit dirs (VolumeRenderer.forward).  lobes, ndc: as in
     octree_render_persp (with ndc the rays are still given in world space; they are converted per ray)."""
