@@ -77,7 +77,8 @@ def pxo_cfg(ops, cfg):
                         sh_deg=cfg.sh_deg, white_bkgd=int(cfg.white_bkgd), lindisp=int(cfg.lindisp),
                         sparsity_npoints=cfg.sparsity_npoints, near_=cfg.near, far_=cfg.far,
                         sparsity_weight=cfg.sparsity_weight, sparsity_length=cfg.sparsity_length,
-                        sparsity_radius=cfg.sparsity_radius, weight_decay_mult=cfg.weight_decay_mult)
+                        sparsity_radius=cfg.sparsity_radius, weight_decay_mult=cfg.weight_decay_mult,
+                        noise_std=0.0 if cfg.noise_std is None else cfg.noise_std)
 
 
 def split_mlp(flat, cfg, which):
@@ -89,8 +90,9 @@ def _psnr(a, b):
     return float(-10.0 * torch.log10(((a.double() - b.double()) ** 2).mean()))
 
 
-def oracle_render_chunked(flat, rays, cfg, t_rand, u, dtype=torch.float32, chunk=1024):
-    """O.render over ray chunks (bounds host memory at BASELINE sizes): [(rgb,disp,acc)_c, (rgb,disp,acc)_f]."""
+def oracle_render_chunked(flat, rays, cfg, t_rand, u, dtype=torch.float32, chunk=1024, noise_c=None, noise_f=None):
+    """O.render over ray chunks (bounds host memory at BASELINE sizes): [(rgb,disp,acc)_c, (rgb,disp,acc)_f].
+    noise_c [B,Nc] / noise_f [B,Nc+Nf]: the standard-normal draws of add_gaussian_noise (cfg.noise_std set), cut with the rays."""
     cast = lambda t: None if t is None else t.to(dtype)
     params = O.unflatten_params(flat.to(dtype), cfg)
     parts = []
@@ -99,7 +101,9 @@ def oracle_render_chunked(flat, rays, cfg, t_rand, u, dtype=torch.float32, chunk
             sl = slice(i0, i0 + chunk)
             r = O.Rays(*[cast(x[sl]) for x in rays])
             parts.append(O.render(params, r, cfg, None if t_rand is None else cast(t_rand[sl]),
-                                  None if u is None else cast(u[sl])))
+                                  None if u is None else cast(u[sl]),
+                                  noise_c=None if noise_c is None else cast(noise_c[sl]),
+                                  noise_f=None if noise_f is None else cast(noise_f[sl])))
     return [tuple(torch.cat([p[lvl][j] for p in parts]) for j in range(3)) for lvl in range(len(parts[0]))]
 
 
@@ -139,42 +143,49 @@ def oracle_loss_and_grad_chunked(flat, rays, px, cfg, t_rand, u, sp_points, dtyp
     return stats, p.grad.detach()
 
 
-def hip_sample_positions(ops, pcfg, packed, rays_dev, t_rand_dev, u_dev):
+def hip_sample_positions(ops, pcfg, packed, rays_dev, t_rand_dev, u_dev, noise_c=None, noise_f=None):
     """(z_coarse [B,Nc], z_fine [B,Nc+Nf]) exactly as the HIP path draws them: the same C-ABI kernels
-    pxo_train_fwd_bwd sequences (sample_along_rays -> mlp_fwd -> shade_composite_fwd -> sample_pdf)."""
+    pxo_train_fwd_bwd sequences (sample_along_rays -> mlp_fwd [-> add_gaussian_noise] -> shade_composite_fwd -> sample_pdf).
+    noise_c [B*Nc] (device): the coarse level's standard-normal draws, added as pcfg.noise_std * noise_c where the whole path
+    adds its Philox draws.  noise_f is taken so that a call site hands over both levels' draws; the fine level's own noise acts
+    after the positions are fixed, so they do not depend on it."""
     o, d, v = rays_dev
-    z_c, pts = ops.sample_along_rays(o, d, pcfg.num_coarse_samples, pcfg.near_, pcfg.far_, t_rand_dev)
+    z_c, pts = ops.sample_along_rays(o, d, pcfg.num_coarse_samples, pcfg.near_, pcfg.far_, t_rand_dev, lindisp=pcfg.lindisp)
     if pcfg.num_fine_samples == 0:
         return z_c, None
     raw_rgb, raw_sigma = ops.mlp_fwd(pcfg, packed[0][0], pts)
+    if noise_c is not None:
+        ops.add_gaussian_noise(raw_sigma, pcfg.noise_std, noise=noise_c.reshape(-1).contiguous())
     _, _, _, w = ops.shade_composite_fwd(pcfg, raw_rgb, raw_sigma, z_c, d, v)
     z_f, _ = ops.sample_pdf(z_c, w, o, d, pcfg.num_fine_samples, u_dev)
     return z_c, z_f
 
 
-def oracle_loss_and_grad_given_z(flat, rays, px, cfg, z_c, z_f, sp_points, dtype=torch.float64):
+def oracle_loss_and_grad_given_z(flat, rays, px, cfg, z_c, z_f, sp_points, dtype=torch.float64, noise_c=None, noise_f=None):
     """loss_fn (nerf_sh/train.py:68-114) and its gradient with the SAMPLE POSITIONS given instead of drawn.
 
     No gradient flows through the positions (lax.stop_gradient, nerf_sh/nerf/model_utils.py:286), so with z fixed
     this is the same differentiable function as O.loss_fn -- minus the ill-conditioned inverse-CDF step, whose own
     parity is tested through F(z) = u (test_sample_pdf) and through the rendered colours.  Composition follows
-    O.render / nerf_sh/nerf/models.py:216-348 (cast_rays -> MLP -> eval_sh/sigmoid/relu -> volumetric_rendering)."""
+    O.render / nerf_sh/nerf/models.py:216-348 (cast_rays -> MLP -> eval_sh/sigmoid/relu -> volumetric_rendering).
+    noise_c [B,Nc] / noise_f [B,Nc+Nf]: the standard-normal draws of add_gaussian_noise on the raw sigma of each level's ray
+    samples (cfg.noise_std set; models.py:258-264,318-324); the sparsity points get none, as in eval_points_raw."""
     cast = lambda t: t.to(dtype)
     p = flat.to(dtype).detach().clone().requires_grad_(True)
     params = O.unflatten_params(p, cfg)
     o, d, v = [cast(x) for x in rays]
     tgt = cast(px)
 
-    def level(mlp, z):
+    def level(mlp, z, noise):
         z = cast(z)
-        rgb, sigma, _, _ = O._shade(mlp, O.cast_rays(z, o, d), v, cfg)
+        rgb, sigma, _, _ = O._shade(mlp, O.cast_rays(z, o, d), v, cfg, None if noise is None else cast(noise))
         return O.volumetric_rendering(rgb, sigma, z, d, cfg.white_bkgd)[0]
 
     fine = cfg.num_fine_samples > 0
-    rgb_c = level(params[0], z_c)
+    rgb_c = level(params[0], z_c, noise_c)
     loss_c = ((rgb_c - tgt) ** 2).mean()
     if fine:
-        loss = ((level(params[1], z_f) - tgt) ** 2).mean()
+        loss = ((level(params[1], z_f, noise_f) - tgt) ** 2).mean()
     else:
         loss, loss_c = loss_c, torch.zeros((), dtype=dtype)
     total = loss + loss_c
@@ -209,6 +220,26 @@ def philox_uniform(seed, stream_id, n, lo=0.0, hi=1.0):
             if 4 * q + i < n:
                 r01 = np.float32(w[i] >> 8) * np.float32(1.0 / 16777216.0)
                 out[4 * q + i] = np.float32(lo) + (np.float32(hi) - np.float32(lo)) * r01
+    return out
+
+
+def philox_normal(seed, stream_id, n, first=0):
+    """What pxo_add_gaussian_noise draws for elements first .. first + n - 1 of stream (seed, stream_id), in float64
+    (include/plenoctree_hip.h, pxo_add_gaussian_noise): block q = the counter, words (0,1) -> elements 4q and 4q+1, words
+    (2,3) -> 4q+2 and 4q+3 by Box-Muller, u1 = ((w >> 8) + 1) / 2^24 in (0,1], u2 = (w' >> 8) / 2^24,
+    z = sqrt(-2 ln u1) (cos, sin)(2 pi u2)."""
+    import numpy as np
+    out = np.empty(n, np.float64)
+    for q in range(first // 4, (first + n + 3) // 4):
+        w = philox4x32_10((q & 0xFFFFFFFF, q >> 32, stream_id & 0xFFFFFFFF, stream_id >> 32), (seed & 0xFFFFFFFF, seed >> 32))
+        for h in range(2):
+            u1 = ((w[2 * h] >> 8) + 1) / 16777216.0
+            u2 = (w[2 * h + 1] >> 8) / 16777216.0
+            r = np.sqrt(-2.0 * np.log(u1))
+            for k, val in enumerate((r * np.cos(2 * np.pi * u2), r * np.sin(2 * np.pi * u2))):
+                i = 4 * q + 2 * h + k - first
+                if 0 <= i < n:
+                    out[i] = val
     return out
 
 

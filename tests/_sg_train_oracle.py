@@ -54,28 +54,30 @@ def stage(cfg, rays, raw_rgb, raw_sigma, z, px, lobes, sp_sigma=None, dtype=torc
                 d_raw_sigma=rs.grad, d_lobes=lb.grad, d_sp_sigma=None if sps is None else sps.grad)
 
 
-def _level(mlp, lobes, samples, viewdirs, z, directions, cfg):
+def _level(mlp, lobes, samples, viewdirs, z, directions, cfg, noise=None):
     raw_rgb, raw_sigma = O.mlp_forward(mlp, O.posenc(samples, cfg.min_deg_point, cfg.max_deg_point), cfg)
+    raw_sigma = O.add_gaussian_noise(raw_sigma, cfg.noise_std, noise)      # models.py:258-264 / :318-324, before the relu
     return O.volumetric_rendering(shade(raw_rgb, lobes, viewdirs), torch.relu(raw_sigma), z, directions, cfg.white_bkgd)
 
 
-def render(params, sg_params, rays, cfg, t_rand=None, u=None):
-    """NerfModel.__call__ with sg_dim = cfg.sh_dim (models.py:216-348): [(rgb, disp, acc)_coarse, (rgb, disp, acc)_fine]."""
+def render(params, sg_params, rays, cfg, t_rand=None, u=None, noise_c=None, noise_f=None):
+    """NerfModel.__call__ with sg_dim = cfg.sh_dim (models.py:216-348): [(rgb, disp, acc)_coarse, (rgb, disp, acc)_fine].
+    noise_c [B,Nc] / noise_f [B,Nc+Nf]: the standard-normal draws of add_gaussian_noise when cfg.noise_std is set."""
     lobes = lobes_from_params(sg_params, cfg.sh_dim)
     z, samples = O.sample_along_rays(rays.origins, rays.directions, cfg.num_coarse_samples, cfg.near, cfg.far, t_rand, cfg.lindisp)
-    comp, disp, acc, w = _level(params[0], lobes, samples, rays.viewdirs, z, rays.directions, cfg)
+    comp, disp, acc, w = _level(params[0], lobes, samples, rays.viewdirs, z, rays.directions, cfg, noise_c)
     ret = [(comp, disp, acc)]
     if cfg.num_fine_samples > 0:
         z_mid = 0.5 * (z[..., 1:] + z[..., :-1])
         z, samples = O.sample_pdf(z_mid, w[..., 1:-1], rays.origins, rays.directions, z, cfg.num_fine_samples, u)
-        comp, disp, acc, _ = _level(params[1], lobes, samples, rays.viewdirs, z, rays.directions, cfg)
+        comp, disp, acc, _ = _level(params[1], lobes, samples, rays.viewdirs, z, rays.directions, cfg, noise_f)
         ret.append((comp, disp, acc))
     return ret
 
 
-def loss_fn(params, sg_params, rays, pixels, cfg, t_rand, u, sp_points):
+def loss_fn(params, sg_params, rays, pixels, cfg, t_rand, u, sp_points, noise_c=None, noise_f=None):
     """train.py:68-114 with the SG leaves in the params tree.  Returns (total, stats dict)."""
-    ret = render(params, sg_params, rays, cfg, t_rand, u)
+    ret = render(params, sg_params, rays, cfg, t_rand, u, noise_c, noise_f)
     zero = torch.zeros((), dtype=pixels.dtype)
     loss_sp = zero
     if cfg.sparsity_weight > 0.0:
@@ -92,11 +94,11 @@ def loss_fn(params, sg_params, rays, pixels, cfg, t_rand, u, sp_points):
     return loss + loss_c + loss_sp + cfg.weight_decay_mult * weight_l2, stats
 
 
-def loss_and_grad(flat_params, sg_params, rays, pixels, cfg, t_rand, u, sp_points):
+def loss_and_grad(flat_params, sg_params, rays, pixels, cfg, t_rand, u, sp_points, noise_c=None, noise_f=None):
     """jax.value_and_grad(loss_fn) (train.py:116): (total, stats, MLP gradient [2 n_mlp], SG gradient [3K])."""
     flat = flat_params.detach().clone().requires_grad_(True)
     sgp = sg_params.detach().clone().requires_grad_(True)
-    total, stats = loss_fn(O.unflatten_params(flat, cfg), sgp, rays, pixels, cfg, t_rand, u, sp_points)
+    total, stats = loss_fn(O.unflatten_params(flat, cfg), sgp, rays, pixels, cfg, t_rand, u, sp_points, noise_c, noise_f)
     total.backward()
     return total.detach(), {k: v.detach() for k, v in stats.items()}, flat.grad.detach(), sgp.grad.detach()
 

@@ -35,31 +35,33 @@ def fixture_rays(fx, dtype=torch.float32):
     return Rays(*[torch.from_numpy(fx[k]).to(dtype) for k in ("origins", "directions", "viewdirs")])
 
 
-def render_cfg(num_coarse_samples=64, num_fine_samples=128, near=2.0, far=6.0, white_bkgd=True, lindisp=False):
+def render_cfg(num_coarse_samples=64, num_fine_samples=128, near=2.0, far=6.0, white_bkgd=True, lindisp=False, noise_std=None):
     return SimpleNamespace(num_coarse_samples=num_coarse_samples, num_fine_samples=num_fine_samples, near=near, far=far,
-                           white_bkgd=white_bkgd, lindisp=lindisp)
+                           white_bkgd=white_bkgd, lindisp=lindisp, noise_std=noise_std)
 
 
-def host_render_f64(sd, rays, cfg, t_rand=None, u=None):
+def host_render_f64(sd, rays, cfg, t_rand=None, u=None, noise_c=None, noise_f=None):
     """[(rgb, disp, acc)_coarse, (rgb, disp, acc)_fine] in float64: sample_along_rays, volumetric_rendering and sample_pdf of the
-    oracle around host_model_f64 in its per-point form (viewdirs repeated per sample), sigmoid and relu."""
+    oracle around host_model_f64 in its per-point form (viewdirs repeated per sample), sigmoid and relu.  noise_c [B,Nc] /
+    noise_f [B,Nc+Nf]: the standard-normal draws of add_gaussian_noise on raw sigma (cfg.noise_std set), before the relu."""
     o, d, v = (r.double() for r in rays)
     t_rand = None if t_rand is None else t_rand.double()
     u = None if u is None else u.double()
 
-    def shade(mlp, samples):
+    def shade(mlp, samples, noise):
         B, S = samples.shape[:2]
         raw_rgb, raw_sigma = host_model_f64(sd, samples.reshape(-1, 3), v[:, None, :].expand(B, S, 3).reshape(-1, 3), mlp=mlp)
+        raw_sigma = O.add_gaussian_noise(raw_sigma, cfg.noise_std, None if noise is None else noise.double())
         return torch.sigmoid(raw_rgb).reshape(B, S, 3), torch.relu(raw_sigma).reshape(B, S, 1)
 
     z, samples = O.sample_along_rays(o, d, cfg.num_coarse_samples, cfg.near, cfg.far, t_rand, cfg.lindisp)
-    rgb, sigma = shade(0, samples)
+    rgb, sigma = shade(0, samples, noise_c)
     comp, disp, acc, weights = O.volumetric_rendering(rgb, sigma, z, d, cfg.white_bkgd)
     ret = [(comp, disp, acc)]
     if cfg.num_fine_samples > 0:
         z_mid = 0.5 * (z[..., 1:] + z[..., :-1])
         z, samples = O.sample_pdf(z_mid, weights[..., 1:-1], o, d, z, cfg.num_fine_samples, u)
-        rgb, sigma = shade(1, samples)
+        rgb, sigma = shade(1, samples, noise_f)
         comp, disp, acc, _ = O.volumetric_rendering(rgb, sigma, z, d, cfg.white_bkgd)
         ret.append((comp, disp, acc))
     return ret

@@ -180,7 +180,7 @@ def test_gaussian_noise_against_reference(golden_dir):
     words (host restatement, atol 2e-6 on values up to ~5), mean / variance of 2^20 draws, and the whole path with
     PxoCfg.noise_std > 0: deterministic per seed, different from the noise-free render, untouched when randomized = 0."""
     ops = _ops(); dev = _gpu()
-    from _helpers import philox4x32_10
+    from _helpers import philox_normal
     g = np.load(os.path.join(golden_dir, "nerf_model_noise.npz"))
     gw = np.load(os.path.join(golden_dir, "eval_points_sh16.npz"))
     std = float(g["noise_std"])
@@ -203,17 +203,7 @@ def test_gaussian_noise_against_reference(golden_dir):
     # Philox normals: element 4q + {0,1} from words (0,1) of block q, 4q + {2,3} from words (2,3)
     seed, sid, cnt = 0x1234567, 5, 37
     z = ops.add_gaussian_noise(torch.zeros(cnt, device=dev), 1.0, seed=seed, stream_id=sid).cpu().numpy()
-    want = np.empty(cnt)
-    for q in range((cnt + 3) // 4):
-        wds = philox4x32_10((q, 0, sid, 0), (seed, 0))
-        for h in range(2):
-            u1 = ((wds[2 * h] >> 8) + 1) / 16777216.0
-            u2 = (wds[2 * h + 1] >> 8) / 16777216.0
-            r = np.sqrt(-2.0 * np.log(u1))
-            for k, val in enumerate((r * np.cos(2 * np.pi * u2), r * np.sin(2 * np.pi * u2))):
-                if 4 * q + 2 * h + k < cnt:
-                    want[4 * q + 2 * h + k] = val
-    np.testing.assert_allclose(z, want, rtol=0, atol=2e-6)
+    np.testing.assert_allclose(z, philox_normal(seed, sid, cnt), rtol=0, atol=2e-6)
     big = ops.add_gaussian_noise(torch.zeros(1 << 20, device=dev), 2.0, seed=9, stream_id=3)
     assert abs(float(big.mean())) < 1e-2 and abs(float(big.var()) - 4.0) < 4e-2
     # whole path
