@@ -5,7 +5,7 @@ shared object is missing, and every call raises PxoError on a non-zero status.
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t,
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t,
                     c_uint64, c_void_p)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -212,6 +212,10 @@ SIGNATURES = {
                                              POINTER(PxoNdc)]),
     "pxo_tree_collapse_mark": (c_int, [P, P, P, c_int64, c_int, P, P]),
     "pxo_tree_collapse_emit": (c_int, [P, P, P, c_int, P, P, P, c_int64, c_int64, P, P, P, P, P]),
+    "pxo_mc_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "pxo_mc_count": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_size_t, POINTER(c_int64), P]),
+    "pxo_mc_emit": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_size_t, POINTER(c_int64), P, P, P, P]),
+    "pxo_tree_sigma_grid": (c_int, [POINTER(PxoTree), c_int, c_int, P, P, P]),
     "pxo_image_mse": (c_int, [P, P, c_int64, P, P, P]),
     "pxo_sgd_step": (c_int, [P, P, P, c_int64, c_float, c_float, c_int, c_int, P]),
 }

@@ -1,9 +1,11 @@
 """Mesh of a trained NeRF-SH's sigma isosurface (reference: nerf_sh/gen_mesh.py): sigma on a dense grid through the
-HIP point evaluator (the sigma-only head pass, same kernel as the extraction grid), marching cubes on the host, OBJ out.
+HIP point evaluator (the sigma-only head pass, same kernel as the extraction grid), marching cubes, OBJ out.
 
-    python -m plenoctree_amd.nerf_sh.gen_mesh --train_dir D --config blender --reso "300 300 300" --iso 6.0
+    python -m plenoctree_amd.nerf_sh.gen_mesh --train_dir D --config blender --reso "300 300 300" --iso 6.0 [--mc host]
 
-PyMCubes is not installed here; `isosurface.marching_cubes` takes its place (same vertices, see that module).
+PyMCubes is not installed here; `isosurface.marching_cubes` takes its place (same vertices, see that module).  By default
+the sigma grid stays on the GPU and is meshed there (plenoctree_amd.mesh_ops, the same definition and output order, so
+mesh.obj is byte-identical); `--mc host` copies the grid to the host and runs the numpy function instead.
 """
 import os
 import sys
@@ -14,6 +16,7 @@ import torch
 from . import isosurface
 from .nerf import models, utils
 
+MC_CHOICES = ("device", "host")
 
 def define_flags():
     """nerf_sh/gen_mesh.py:49-76."""
@@ -25,6 +28,8 @@ def define_flags():
     a("--iso", type=float, default=6.0, help="sigma isosurface")
     a("--coarse", type=utils._bool, nargs="?", const=True, default=False, help="force the coarse network")
     a("--point_chunk", type=int, default=720720, help="points per evaluator launch (--chunk is ignored)")
+    a("--mc", choices=MC_CHOICES, default="device",
+      help="where marching cubes runs: on the GPU that holds the sigma grid, or on the host (same mesh.obj, byte for byte)")
     return p
 
 
@@ -43,12 +48,21 @@ def sigma_grid(fn, c1, c2, reso, chunk, device):
     return out.reshape(*reso)
 
 
-def marching_cubes(fn, c1, c2, reso, isosurface_level, chunk, device):
+def marching_cubes(fn, c1, c2, reso, isosurface_level, chunk, device, mc="device"):
     """:88-130.  Vertices are scaled by (c2 - c1) / reso exactly as the reference does (:127) - note the samples sit
-    at spacing (c2 - c1) / (reso - 1), so the reference's mesh is shrunk by (reso-1)/reso towards c1; kept for parity."""
-    sigmas = sigma_grid(fn, c1, c2, reso, chunk, device).cpu().numpy()
+    at spacing (c2 - c1) / (reso - 1), so the reference's mesh is shrunk by (reso-1)/reso towards c1; kept for parity.
+    mc: "device" meshes a sigma grid that lives on a GPU there (mesh_ops.marching_cubes) and only the mesh comes back;
+    "host", or a grid on the CPU, goes through isosurface.marching_cubes.  The two return identical arrays."""
+    if mc not in MC_CHOICES:
+        raise ValueError(f"mc must be one of {MC_CHOICES}, got {mc!r}")
+    sigmas = sigma_grid(fn, c1, c2, reso, chunk, device)
     print("* Running marching cubes", flush=True)
-    vertices, triangles = isosurface.marching_cubes(sigmas, isosurface_level)
+    if mc == "device" and sigmas.is_cuda:
+        from .. import mesh_ops
+        vertices, triangles, _ = mesh_ops.marching_cubes(sigmas, isosurface_level)
+        vertices, triangles = vertices.cpu().numpy(), triangles.cpu().numpy()
+    else:
+        vertices, triangles = isosurface.marching_cubes(sigmas.cpu().numpy(), isosurface_level)
     c1, c2 = np.array(c1), np.array(c2)
     vertices = vertices * ((c2 - c1) / np.array(reso))
     return vertices + c1, triangles
@@ -87,7 +101,7 @@ def main(argv=None):
     def fn(points):
         return model.eval_points_raw(state, points, coarse=args.coarse, want_rgb=False)[1]
 
-    verts, faces = marching_cubes(fn, c1, c2, reso, args.iso, args.point_chunk, device)
+    verts, faces = marching_cubes(fn, c1, c2, reso, args.iso, args.point_chunk, device, mc=args.mc)
     mesh_path = os.path.join(args.train_dir, "mesh.obj")
     print(" Saving to", mesh_path, flush=True)
     save_obj(verts, faces, mesh_path)
