@@ -14,11 +14,17 @@
 // scan per level (rank of a cell = its node index inside the level), and the 8 children of cell m are the
 // contiguous cells 8m..8m+7 of the next level.  No sort, no pointer chasing, all streams are linear.
 //
-// Renderer: one ray per row of ROW = 8 or 16 lanes of the wave (8 or 4 rays per wave64).  The lanes of a row walk
-// the tree together (uniform control flow inside a row), each lane owns data channels lane, lane+ROW, ... of the
-// leaf, so a leaf's 3*K coefficients are fetched as coalesced 32/64-byte row loads and reduced with row-local
-// DPP shuffles.  The node path of the previous sample is kept in LDS; the descent for the next sample
-// resumes at the deepest node the two positions share instead of the root.
+// Renderer: one ray per row of ROW = 4 (the default), 8 or 16 lanes of the wave (16, 8 or 4 rays per wave64: a pixel
+// patch, RowGeom).  The lanes of a row walk the tree together (uniform control flow inside a row) and share a leaf's 3*K
+// coefficients: at 4 lanes per colour channel in float4 groups (KF), at 8 / 16 lanes as groups of 4 consecutive floats
+// (VEC), in the 8 / 16-lane gradient kernel as single floats; the partial sums are reduced with row-local DPP shuffles.
+// The node path of the previous sample is kept in LDS; the descent for the next sample resumes at the deepest node the
+// two positions share instead of the root (Marcher).
+// The five tree marchers (octree_render_kernel, octree_render_bwd4_kernel, octree_render_quant_kernel, octree_count_kernel,
+// octree_weight_kernel) share locate_leaf (the leaf at a ray parameter and the step past it); the three renderers share
+// row_ray (which ray a row of lanes takes).  The channel-aligned SH dot (octree_render_kernel, octree_render_bwd4_kernel)
+// and the forward compositing (octree_render_kernel, octree_render_quant_kernel) are written out in both places: behind a
+// function of any form the kernels compile to other registers and occupancies (profiles/EXPERIMENTS.md).
 #include <type_traits>
 
 #include "pxo_common.h"
@@ -779,11 +785,13 @@ __global__ __launch_bounds__(256) void grid_weight_pow2_kernel(const float* __re
 // ------------------------------------------------------------------------------------------
 constexpr int kRenderThreads = 256;
 
-// lanes per ray: ROW in {4, 8, 16}; the wave carries 64/ROW rays as a WTX x WTY pixel patch
+// lanes per ray: ROW in {4, 8, 16}; the wave carries 64/ROW rays as a WTX x WTY pixel patch (patch_wtx: the launch shape on
+// the host takes the width from the same function)
+__host__ __device__ constexpr int patch_wtx(int row) { return 64 / row <= 4 ? 2 : (64 / row <= 16 ? 4 : 8); }
 template <int ROW> struct RowGeom {
   static constexpr int kRaysPerWave = 64 / ROW;
   static constexpr int kRaysPerBlock = kRenderThreads / ROW;
-  static constexpr int kWTX = kRaysPerWave <= 4 ? 2 : (kRaysPerWave <= 16 ? 4 : 8);
+  static constexpr int kWTX = patch_wtx(ROW);
   static constexpr int kWTY = kRaysPerWave / kWTX;
   static constexpr int kMaxLoads = (75 + ROW - 1) / ROW;      // SH25: 75 coefficients
   static constexpr int kMaxGroups = (19 + ROW - 1) / ROW;     // ... as 19 groups of 4 consecutive floats
@@ -887,6 +895,60 @@ struct Marcher {
   }
 };
 
+// One sample of a tree march: the leaf at parameter tt of ray r and the step to the next sample.  Neither depends on the
+// leaf's DATA, which is what the renderers' software pipeline rests on.
+__device__ __forceinline__ void locate_leaf(const TreeRay& r, const CellExit& cell_exit, Marcher& mk, const int32_t* child,
+                                            float step_size, float tt, int64_t& leaf, float& delta) {
+  float pos[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + tt * r.d[a]);
+  int depth;
+  leaf = mk.find(child, pos, depth);
+  const float cube = (float)(2u << depth);
+  float local[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) local[a] = __builtin_amdgcn_fractf(pos[a] * cube);
+  delta = cell_exit(local) * inv_cells(depth) + step_size;
+}
+
+// Which ray row `row` of a renderer's workgroup takes, with its world-space origin, direction and view direction.  Camera
+// mode: the block's 4 waves form a 2 x 2 arrangement of WTX x WTY pixel patches; explicit rays: blockIdx * kRaysPerBlock + row.
+// A row past the image or the ray count is not active and leaves the three vectors untouched.  A: any renderer's argument
+// block.  (ray and active come back by value: handed over by reference they would stay in memory until this function is
+// inlined, and every kernel that calls it compiles to other code -- profiles/EXPERIMENTS.md.)
+struct RowId { int64_t ray; bool active; };
+template <int ROW, typename Args>
+__device__ __forceinline__ RowId row_ray(const Args& A, int row, float (&origin)[3], float (&dir)[3], float (&vdir)[3]) {
+  using G = RowGeom<ROW>;
+  RowId id;
+  if (A.has_cam) {
+    const int W = A.cam.width, H = A.cam.height;
+    const int tiles_x = (W + 2 * G::kWTX - 1) / (2 * G::kWTX);
+    const int bx = (int)(blockIdx.x % tiles_x), by = (int)(blockIdx.x / tiles_x);
+    const int wv = row / G::kRaysPerWave, q = row % G::kRaysPerWave;
+    const int px = (bx * 2 + (wv & 1)) * G::kWTX + q % G::kWTX, py = (by * 2 + (wv >> 1)) * G::kWTY + q / G::kWTX;
+    id.active = px < W && py < H;
+    id.ray = (int64_t)py * W + px;
+    if (id.active) {
+      camera_ray(A.cam.c2w, A.cam.fx, A.cam.fy, W, H, px, py, origin, dir);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) vdir[a] = dir[a];
+    }
+  } else {
+    id.ray = blockIdx.x * (int64_t)G::kRaysPerBlock + row;
+    id.active = id.ray < A.B;
+    if (id.active) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        origin[a] = A.origins[id.ray * 3 + a];
+        dir[a] = A.dirs[id.ray * 3 + a];
+        vdir[a] = A.viewdirs[id.ray * 3 + a];
+      }
+    }
+  }
+  return id;
+}
+
 // MODE 0: forward (writes out_rgb).  MODE 1: gradient w.r.t. tree data (two marches per ray).
 // VEC (forward only): lane l owns the float groups l, l+ROW, ... (4 consecutive data indices each) instead of the single
 // indices l, l+ROW, ...: a leaf's coefficients arrive in ceil(3K/4/ROW) 16-byte loads per lane (SH16, 8 lanes: 2 instead
@@ -911,36 +973,10 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
   __shared__ int s_stack[kRaysPerBlock][kMaxD + 2];
   __shared__ float s_basis[kRaysPerBlock][25];
   const int row = threadIdx.x / kRow, l = threadIdx.x % kRow;
-  int64_t ray;
   float origin[3], dir[3], vdir[3];
-  bool active = true;
-  if (A.has_cam) {
-    // the block's 4 waves form a 2 x 2 arrangement of WTX x WTY pixel patches
-    const int W = A.cam.width, H = A.cam.height;
-    const int tiles_x = (W + 2 * G::kWTX - 1) / (2 * G::kWTX);
-    const int bx = (int)(blockIdx.x % tiles_x), by = (int)(blockIdx.x / tiles_x);
-    const int wv = row / G::kRaysPerWave, q = row % G::kRaysPerWave;
-    const int px = (bx * 2 + (wv & 1)) * G::kWTX + q % G::kWTX, py = (by * 2 + (wv >> 1)) * G::kWTY + q / G::kWTX;
-    active = px < W && py < H;
-    ray = (int64_t)py * W + px;
-    if (active) {
-      camera_ray(A.cam.c2w, A.cam.fx, A.cam.fy, W, H, px, py, origin, dir);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) vdir[a] = dir[a];
-    }
-  } else {
-    ray = blockIdx.x * (int64_t)kRaysPerBlock + row;
-    active = ray < A.B;
-    if (active) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        origin[a] = A.origins[ray * 3 + a];
-        dir[a] = A.dirs[ray * 3 + a];
-        vdir[a] = A.viewdirs[ray * 3 + a];
-      }
-    }
-  }
-  if (!active) return;                         // whole rows leave together; no block-level barrier below
+  const RowId id = row_ray<ROW>(A, row, origin, dir, vdir);
+  if (!id.active) return;                      // whole rows leave together; no block-level barrier below
+  const int64_t ray = id.ray;
 
   const int K = A.tree.basis_dim, D = A.tree.data_dim;
   const float bg = A.opt.background_brightness;
@@ -1016,21 +1052,11 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
     float out[3] = {0.f, 0.f, 0.f};
     float aux[3] = {0.f, 0.f, INFINITY};         // AUX: alpha, depth, surface
     bool stopped = false;
-    // One sample = the leaf at parameter tt and the step to the next sample; neither depends on the leaf's DATA.  The march is
-    // software-pipelined on that: a sample's sigma is requested, then the NEXT sample is located (its child-pointer loads
+    // locate_leaf does not depend on the leaf's DATA.  The march is software-pipelined on that: a sample's sigma is requested, then the NEXT sample is located (its child-pointer loads
     // travel together with the sigma request), and only then is the current sample shaded -- per sample one dependent L2 round
     // trip less (lookup || sigma -> coefficients instead of lookup -> sigma -> coefficients).  Same samples, same arithmetic.
     auto locate = [&](float tt, int64_t& leaf_o, float& delta_o) {
-      float pos[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + tt * r.d[a]);
-      int depth;
-      leaf_o = mk.find(child, pos, depth);
-      const float cube = (float)(2u << depth);
-      float local[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) local[a] = __builtin_amdgcn_fractf(pos[a] * cube);
-      delta_o = cell_exit(local) * inv_cells(depth) + A.opt.step_size;
+      locate_leaf(r, cell_exit, mk, child, A.opt.step_size, tt, leaf_o, delta_o);
     };
     int64_t leaf = 0;
     float delta_t = 0.0f;
@@ -1190,34 +1216,10 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_bwd4_kernel(Rend
   static_assert(UPD == 0 || WC > 0, "the ray-parallel update needs the cache");
   const int row = threadIdx.x / kRow, l = threadIdx.x % kRow, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int tagv = -1;                                 // lane i: the leaf whose row sits in slot i of this wave's cache (-1: empty)
-  int64_t ray = 0;
   float origin[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 1.f}, vdir[3] = {0.f, 0.f, 1.f};
-  bool active = true;
-  if (A.has_cam) {
-    const int W = A.cam.width, H = A.cam.height;
-    const int tiles_x = (W + 2 * G::kWTX - 1) / (2 * G::kWTX);
-    const int bx = (int)(blockIdx.x % tiles_x), by = (int)(blockIdx.x / tiles_x);
-    const int wv = row / G::kRaysPerWave, q = row % G::kRaysPerWave;
-    const int px = (bx * 2 + (wv & 1)) * G::kWTX + q % G::kWTX, py = (by * 2 + (wv >> 1)) * G::kWTY + q / G::kWTX;
-    active = px < W && py < H;
-    ray = (int64_t)py * W + px;
-    if (active) {
-      camera_ray(A.cam.c2w, A.cam.fx, A.cam.fy, W, H, px, py, origin, dir);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) vdir[a] = dir[a];
-    }
-  } else {
-    ray = blockIdx.x * (int64_t)kRaysPerBlock + row;
-    active = ray < A.B;
-    if (active) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        origin[a] = A.origins[ray * 3 + a];
-        dir[a] = A.dirs[ray * 3 + a];
-        vdir[a] = A.viewdirs[ray * 3 + a];
-      }
-    }
-  }
+  const RowId id = row_ray<kRow>(A, row, origin, dir, vdir);            // an inactive row keeps the finite ray above
+  const int64_t ray = id.ray;
+  bool active = id.active;
   const int K = A.tree.basis_dim, D = A.tree.data_dim;
   const int Kc = KF > 0 ? KF : K;
   const float bg = A.opt.background_brightness;
@@ -1304,16 +1306,9 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_bwd4_kernel(Rend
       int leaf_i = 0;
       float e0 = 0.f, e1 = 0.f, e2 = 0.f, es = 0.f;
       if (running) {
-        float pos[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + t * r.d[a]);
-        int depth;
-        const int64_t leaf = mk.find(child, pos, depth);
-        const float cube = (float)(2u << depth);
-        float local[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) local[a] = __builtin_amdgcn_fractf(pos[a] * cube);
-        const float delta_t = cell_exit(local) * inv_cells(depth) + A.opt.step_size;
+        int64_t leaf;
+        float delta_t;
+        locate_leaf(r, cell_exit, mk, child, A.opt.step_size, t, leaf, delta_t);
         const float* __restrict__ val = data + leaf * D;
         const float sg = val[D - 1];
         if (sg > A.opt.sigma_thresh) {
@@ -1513,17 +1508,10 @@ __global__ __launch_bounds__(256) void octree_count_kernel(RenderArgs A, unsigne
       mk.init(s_stack[threadIdx.x]);
       float t = r.tmin, light = 1.0f;
       while (t < r.tmax) {
-        float pos[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + t * r.d[a]);
-        int depth;
-        const int64_t leaf = mk.find(child, pos, depth);
+        int64_t leaf;
+        float delta_t;
+        locate_leaf(r, cell_exit, mk, child, A.opt.step_size, t, leaf, delta_t);
         c[3] += (unsigned long long)mk.loads;
-        const float cube = (float)(2u << depth);
-        float local[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) local[a] = __builtin_amdgcn_fractf(pos[a] * cube);
-        const float delta_t = cell_exit(local) * inv_cells(depth) + A.opt.step_size;
         const float sg = data[leaf * D + D - 1];
         c[1] += 1;
         if (sg > A.opt.sigma_thresh) {
@@ -1703,35 +1691,10 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(std
   __shared__ int s_stack[kRaysPerBlock][kMaxD + 2];
   __shared__ float s_basis[kRaysPerBlock][25];
   const int row = threadIdx.x / kRow, l = threadIdx.x % kRow;
-  int64_t ray;
   float origin[3], dir[3], vdir[3];
-  bool active = true;
-  if (A.has_cam) {
-    const int W = A.cam.width, H = A.cam.height;
-    const int tiles_x = (W + 2 * G::kWTX - 1) / (2 * G::kWTX);
-    const int bx = (int)(blockIdx.x % tiles_x), by = (int)(blockIdx.x / tiles_x);
-    const int wv = row / G::kRaysPerWave, q = row % G::kRaysPerWave;
-    const int px = (bx * 2 + (wv & 1)) * G::kWTX + q % G::kWTX, py = (by * 2 + (wv >> 1)) * G::kWTY + q / G::kWTX;
-    active = px < W && py < H;
-    ray = (int64_t)py * W + px;
-    if (active) {
-      camera_ray(A.cam.c2w, A.cam.fx, A.cam.fy, W, H, px, py, origin, dir);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) vdir[a] = dir[a];
-    }
-  } else {
-    ray = blockIdx.x * (int64_t)kRaysPerBlock + row;
-    active = ray < A.B;
-    if (active) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        origin[a] = A.origins[ray * 3 + a];
-        dir[a] = A.dirs[ray * 3 + a];
-        vdir[a] = A.viewdirs[ray * 3 + a];
-      }
-    }
-  }
-  if (!active) return;                         // whole rows leave together; no block-level barrier below
+  const RowId id = row_ray<ROW>(A, row, origin, dir, vdir);
+  if (!id.active) return;                      // whole rows leave together; no block-level barrier below
+  const int64_t ray = id.ray;
 
   const int K = A.tree.basis_dim, R = A.tree.n_retained, Kq = K - R, bits = A.tree.bits;
   const int groups = A.tree.idx_stride >> 2;
@@ -1772,16 +1735,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(std
   bool stopped = false;
   // the float kernel's software pipeline: sigma requested, the next sample located, then the current one shaded
   auto locate = [&](float tt, int64_t& leaf_o, float& delta_o) {
-    float pos[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + tt * r.d[a]);
-    int depth;
-    leaf_o = mk.find(child, pos, depth);
-    const float cube = (float)(2u << depth);
-    float local[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) local[a] = __builtin_amdgcn_fractf(pos[a] * cube);
-    delta_o = cell_exit(local) * inv_cells(depth) + A.opt.step_size;
+    locate_leaf(r, cell_exit, mk, child, A.opt.step_size, tt, leaf_o, delta_o);
   };
   int64_t leaf = 0;
   float delta_t = 0.0f;
@@ -1862,7 +1816,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(std
 
 // ------------------------------------------------------------------------------------------
 // per-leaf compositing weights (svox N3Tree.accumulate_weights; pxo_octree_weight_accum_* in plenoctree_octree.h)
-// The forward renderer's march without shading, as octree_count_kernel repeats it -- same ray set-up (NDC included), leaf
+// The forward renderer's march without shading, as octree_count_kernel repeats it (both on locate_leaf) -- same ray set-up (NDC included), leaf
 // lookup, step rule, sigma test, attenuation, early stop and `!(tn > t)` guard, hence the same sample sequence -- and for
 // every shaded sample its `weight`, light * (1 - expf(-(delta * delta_scale) * sigma)), merged into weights[leaf].  One thread
 // per ray; in camera mode ray = (camera * H + py) * W + px over all cameras of c2w_all ([n_cams,12]).
@@ -1916,16 +1870,9 @@ __global__ __launch_bounds__(256) void octree_weight_kernel(WeightArgs A) {
   mk.init(s_stack[threadIdx.x]);
   float t = r.tmin, light = 1.0f;
   while (t < r.tmax) {
-    float pos[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + t * r.d[a]);
-    int depth;
-    const int64_t leaf = mk.find(child, pos, depth);
-    const float cube = (float)(2u << depth);
-    float local[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) local[a] = __builtin_amdgcn_fractf(pos[a] * cube);
-    const float delta_t = cell_exit(local) * inv_cells(depth) + A.opt.step_size;
+    int64_t leaf;
+    float delta_t;
+    locate_leaf(r, cell_exit, mk, child, A.opt.step_size, t, leaf, delta_t);
     const float sg = data[leaf * D + D - 1];
     if (sg > A.opt.sigma_thresh) {
       const float dtw = delta_t * r.delta_scale;
@@ -2013,6 +1960,77 @@ __global__ void tree_collapse_data_kernel(const int32_t* __restrict__ child, con
 using namespace pxo;
 
 static inline int64_t blocks_for(int64_t n, int threads) { return (n + threads - 1) / threads; }
+
+// ---- renderer launches (templates: outside the C linkage block) ----
+// What the float and the palette renderers share of a launch at `row` lanes per ray: the checks on the camera or the ray
+// arrays, the rays' part of the argument block (Args: RenderArgs or QuantRenderArgs) and the block count.
+template <typename Args>
+static int launch_shape(const PxoCamera* cam, const float* origins, const float* dirs, const float* viewdirs, int64_t B, int row,
+                        const char* who, Args& A, unsigned& grid) {
+  PXO_REQUIRE(B >= 0, "%s: B < 0", who);
+  A.B = B;
+  A.has_cam = cam != nullptr;
+  int64_t blocks;
+  if (cam) {
+    PXO_REQUIRE(cam->c2w && cam->width >= 1 && cam->height >= 1 && cam->fx > 0.0f && cam->fy > 0.0f, "%s: bad camera", who);
+    PXO_REQUIRE(B == (int64_t)cam->width * cam->height, "%s: B must be width*height in camera mode", who);
+    A.cam = *cam;
+    A.origins = A.dirs = A.viewdirs = nullptr;
+    const int tx = 2 * patch_wtx(row), ty = 2 * (64 / row / patch_wtx(row));      // a block's 2 x 2 patches (row_ray)
+    blocks = (int64_t)((cam->width + tx - 1) / tx) * ((cam->height + ty - 1) / ty);
+  } else {
+    PXO_REQUIRE(B == 0 || (origins && dirs && viewdirs), "%s: null ray arrays", who);
+    A.cam = PxoCamera{};
+    A.origins = origins; A.dirs = dirs; A.viewdirs = viewdirs;
+    blocks = blocks_for(B, kRenderThreads / row);
+  }
+  PXO_REQUIRE(blocks < ((int64_t)1 << 31), "%s: too many rays for one launch", who);
+  grid = (unsigned)blocks;
+  return PXO_OK;
+}
+
+// Forward launch of a float tree.  4 lanes per ray: the channel-aligned kernel with the tree's basis_dim as a compile-time
+// constant; 8 / 16 lanes: groups of four consecutive floats.
+template <bool AUX>
+static void launch_render_fwd(const std::conditional_t<AUX, RenderAuxArgs, RenderArgs>& A, int row, unsigned grid, float* out_rgb,
+                              void* stream) {
+  auto kernel = row == 8 ? octree_render_kernel<0, 8, true, 0, AUX> : octree_render_kernel<0, 16, true, 0, AUX>;
+  if (row == 4) {
+    switch (A.tree.basis_dim) {
+      case 1: kernel = octree_render_kernel<0, 4, true, 1, AUX>; break;
+      case 4: kernel = octree_render_kernel<0, 4, true, 4, AUX>; break;
+      case 9: kernel = octree_render_kernel<0, 4, true, 9, AUX>; break;
+      case 16: kernel = octree_render_kernel<0, 4, true, 16, AUX>; break;
+      case 25: kernel = octree_render_kernel<0, 4, true, 25, AUX>; break;
+      default: kernel = octree_render_kernel<0, 4, true, -1, AUX>; break;
+    }
+  }
+  const float* none = nullptr;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr);
+}
+
+template <bool AUX>
+static void launch_quant_fwd(const std::conditional_t<AUX, QuantRenderAuxArgs, QuantRenderArgs>& A, int row, unsigned grid,
+                             float* out_rgb, void* stream) {
+  const auto kernel = row == 4   ? octree_render_quant_kernel<4, AUX>
+                      : row == 8 ? octree_render_quant_kernel<8, AUX>
+                                 : octree_render_quant_kernel<16, AUX>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb);
+}
+
+// The 4-lane backward kernel for `wc_rows` rows of write-combining cache (0: direct scatter) and the cache's update form.
+using Bwd4Kernel = void (*)(RenderArgs, const float*, const float*, float*);
+template <int KF>
+static Bwd4Kernel bwd4_kernel(int wc_rows, bool ray_parallel) {
+  switch (wc_rows) {
+    case 4: return ray_parallel ? octree_render_bwd4_kernel<KF, 4, 1> : octree_render_bwd4_kernel<KF, 4, 0>;
+    case 8: return ray_parallel ? octree_render_bwd4_kernel<KF, 8, 1> : octree_render_bwd4_kernel<KF, 8, 0>;
+    case 16: return ray_parallel ? octree_render_bwd4_kernel<KF, 16, 1> : octree_render_bwd4_kernel<KF, 16, 0>;
+    case 32: return ray_parallel ? octree_render_bwd4_kernel<KF, 32, 1> : octree_render_bwd4_kernel<KF, 32, 0>;
+    case 64: return ray_parallel ? octree_render_bwd4_kernel<KF, 64, 1> : octree_render_bwd4_kernel<KF, 64, 0>;
+    default: return octree_render_bwd4_kernel<KF, 0, 0>;
+  }
+}
 
 extern "C" {
 
@@ -2251,11 +2269,7 @@ int pxo_grid_weight_render_ndc(const float* sigma_grid, int reso, const float* c
 // forward image / 11.20 ms without, against 10.86 / 11.90 ms for the 16-lane kernel (SH25: 14.46 / 15.49 against 14.87 / 16.02).
 // So: 4 lanes both ways.  pxo_octree_set_lanes_per_ray forces a value for A/B runs and the per-instantiation tests.
 static int g_row_override[2] = {0, 0};   // [forward, backward]; 0 = the measured default
-static int render_row(bool backward, int data_dim) {
-  if (g_row_override[backward ? 1 : 0]) return g_row_override[backward ? 1 : 0];
-  (void)data_dim;
-  return 4;
-}
+static int render_row(bool backward) { return g_row_override[backward ? 1 : 0] ? g_row_override[backward ? 1 : 0] : 4; }
 
 // Rows of the backward kernel's per-wave write-combining cache.  Measured (800x800, SH16, reusing the forward image):
 // 9.7 ms direct scatter, 5.0 / 4.8 / 4.4 / 4.3 ms with 4 / 8 / 16 / 32 rows; two-march form 10.3 -> 6.3 / 6.1 / 5.6 / 6.3 (32 rows
@@ -2263,42 +2277,29 @@ static int render_row(bool backward, int data_dim) {
 // selects another instantiation for A/B runs (0 = direct scatter); anything else is rejected there.
 static int g_bwd_wc_rows = 16;
 static int g_bwd_update = 0;     // PXO_TUNE_BWD_UPDATE: 0 the whole wave on one sample's row, 1 every ray's 4 lanes on its own row
-static int bwd_wc_slots() { return g_bwd_wc_rows; }
+
+// the colour format of a tree; name: "SH" or "SG", for the message
+static int check_format(int K, int data_dim, const char* name, const char* who) {
+  const bool sg = name[1] == 'G';
+  PXO_REQUIRE(K == 1 || K == 4 || K == 9 || K == 16 || K == 25, "%s: basis_dim %d is not %s %s format (%s1,4,9,16,25)", who, K,
+              sg ? "a supported" : "an", name, sg ? "sg_dim " : "");
+  PXO_REQUIRE(data_dim == 3 * K + 1, "%s: data_dim %d != 3*basis_dim+1", who, data_dim);
+  return PXO_OK;
+}
 
 static int render_args(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                        const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const char* who, bool backward,
                        RenderArgs& A, unsigned& grid, int& row) {
   if (int rc = check_opts(opts, who)) return rc;
   PXO_REQUIRE(tree && tree->child && tree->data, "%s: null tree", who);
-  const int K = tree->basis_dim;
-  PXO_REQUIRE(K == 1 || K == 4 || K == 9 || K == 16 || K == 25, "%s: basis_dim %d is not an SH format (1,4,9,16,25)", who, K);
-  PXO_REQUIRE(tree->data_dim == 3 * K + 1, "%s: data_dim %d != 3*basis_dim+1", who, tree->data_dim);
+  if (int rc = check_format(tree->basis_dim, tree->data_dim, "SH", who)) return rc;
   PXO_REQUIRE(tree->n_internal >= 1 && tree->n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
-  PXO_REQUIRE(B >= 0, "%s: B < 0", who);
-  row = render_row(backward, tree->data_dim);
+  row = render_row(backward);
   A.tree = *tree;
   A.opt = *opts;
-  A.B = B;
-  A.has_cam = cam != nullptr;
   A.lobes = nullptr;                            // the SG entry points set it after their own checks
-  A.ndc = PxoNdc{0, 0, 0.0f, 0.0f};             // the NDC entry points set it after their own checks
-  int64_t blocks;
-  if (cam) {
-    PXO_REQUIRE(cam->c2w && cam->width >= 1 && cam->height >= 1 && cam->fx > 0.0f && cam->fy > 0.0f, "%s: bad camera", who);
-    PXO_REQUIRE(B == (int64_t)cam->width * cam->height, "%s: B must be width*height in camera mode", who);
-    A.cam = *cam;
-    A.origins = A.dirs = A.viewdirs = nullptr;
-    const int rpw = 64 / row, wtx = rpw <= 4 ? 2 : (rpw <= 16 ? 4 : 8), tx = 2 * wtx, ty = 2 * (rpw / wtx);
-    blocks = (int64_t)((cam->width + tx - 1) / tx) * ((cam->height + ty - 1) / ty);
-  } else {
-    PXO_REQUIRE(B == 0 || (origins && dirs && viewdirs), "%s: null ray arrays", who);
-    A.cam = PxoCamera{};
-    A.origins = origins; A.dirs = dirs; A.viewdirs = viewdirs;
-    blocks = blocks_for(B, kRenderThreads / row);
-  }
-  PXO_REQUIRE(blocks < ((int64_t)1 << 31), "%s: too many rays for one launch", who);
-  grid = (unsigned)blocks;
-  return PXO_OK;
+  A.ndc = kNoNdc;                               // the NDC entry points set it after their own checks
+  return launch_shape(cam, origins, dirs, viewdirs, B, row, who, A, grid);
 }
 
 int pxo_octree_set_lanes_per_ray(int forward, int backward) {
@@ -2349,9 +2350,7 @@ int pxo_octree_get_tuning(int knob, int* value) {
 // names SG, not SH.
 static int check_sg(const PxoTree* tree, const float* lobes, const char* who) {
   PXO_REQUIRE(tree, "%s: null tree", who);
-  const int K = tree->basis_dim;
-  PXO_REQUIRE(K == 1 || K == 4 || K == 9 || K == 16 || K == 25, "%s: basis_dim %d is not a supported SG format (sg_dim 1,4,9,16,25)", who, K);
-  PXO_REQUIRE(tree->data_dim == 3 * K + 1, "%s: data_dim %d != 3*basis_dim+1", who, tree->data_dim);
+  if (int rc = check_format(tree->basis_dim, tree->data_dim, "SG", who)) return rc;
   PXO_REQUIRE(lobes, "%s: null lobes (an SG tree needs its [basis_dim,4] extra_data)", who);
   return PXO_OK;
 }
@@ -2367,23 +2366,7 @@ static int octree_render_fwd_impl(const PxoTree* tree, const PxoCamera* cam, con
   A.ndc = ndc;
   if (B == 0) return PXO_OK;
   PXO_REQUIRE(out_rgb, "%s: null output", who);
-  const float* none = nullptr;
-  switch (row) {
-    case 4:
-#define PXO_FWD4(KF_) hipLaunchKernelGGL((octree_render_kernel<0, 4, true, KF_>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr)
-      switch (tree->basis_dim) {
-        case 1: PXO_FWD4(1); break;
-        case 4: PXO_FWD4(4); break;
-        case 9: PXO_FWD4(9); break;
-        case 16: PXO_FWD4(16); break;
-        case 25: PXO_FWD4(25); break;
-        default: PXO_FWD4(-1); break;
-      }
-#undef PXO_FWD4
-      break;
-    case 8: hipLaunchKernelGGL((octree_render_kernel<0, 8, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr); break;
-    default: hipLaunchKernelGGL((octree_render_kernel<0, 16, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr); break;
-  }
+  launch_render_fwd<false>(A, row, grid, out_rgb, stream);
   return check_launch(who);
 }
 
@@ -2419,23 +2402,7 @@ int pxo_octree_render_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const f
   PXO_REQUIRE(out_rgb && out_aux, "%s: null output", who);
   A.out = out_aux;
   A.surface_thresh = surface_thresh;
-  const float* none = nullptr;
-  switch (row) {
-    case 4:
-#define PXO_AUX4(KF_) hipLaunchKernelGGL((octree_render_kernel<0, 4, true, KF_, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr)
-      switch (tree->basis_dim) {
-        case 1: PXO_AUX4(1); break;
-        case 4: PXO_AUX4(4); break;
-        case 9: PXO_AUX4(9); break;
-        case 16: PXO_AUX4(16); break;
-        case 25: PXO_AUX4(25); break;
-        default: PXO_AUX4(-1); break;
-      }
-#undef PXO_AUX4
-      break;
-    case 8: hipLaunchKernelGGL((octree_render_kernel<0, 8, true, 0, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr); break;
-    default: hipLaunchKernelGGL((octree_render_kernel<0, 16, true, 0, true>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr); break;
-  }
+  launch_render_fwd<true>(A, row, grid, out_rgb, stream);
   return check_launch("octree_render_aux_fwd");
 }
 
@@ -2456,36 +2423,15 @@ static int octree_render_bwd_impl(const PxoTree* tree, const PxoCamera* cam, con
   PXO_REQUIRE(out_rgb == nullptr || opts->stop_thresh == 0.0f,
               "%s: out_rgb must come from an exact march (stop_thresh == 0), got stop_thresh %g", who,
               (double)opts->stop_thresh);
-  switch (row) {
-    case 4:
-#define PXO_BWD4W(KF_, WC_)                                                                                                         \
-  do {                                                                                                                            \
-    if (g_bwd_update == 1 && WC_ > 0)                                                                                             \
-      hipLaunchKernelGGL((octree_render_bwd4_kernel<KF_, WC_, (WC_ > 0 ? 1 : 0)>), dim3(grid), dim3(kRenderThreads), 0,             \
-                         (hipStream_t)stream, A, out_rgb, grad_out, grad_data);                                                   \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((octree_render_bwd4_kernel<KF_, WC_, 0>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A,    \
-                         out_rgb, grad_out, grad_data);                                                                          \
-  } while (0)
-#define PXO_BWD4(KF_)                                     \
-  switch (bwd_wc_slots()) {                               \
-    case 4: PXO_BWD4W(KF_, 4); break;                     \
-    case 8: PXO_BWD4W(KF_, 8); break;                     \
-    case 16: PXO_BWD4W(KF_, 16); break;                   \
-    case 32: PXO_BWD4W(KF_, 32); break;                   \
-    case 64: PXO_BWD4W(KF_, 64); break;                   \
-    default: PXO_BWD4W(KF_, 0); break;                    \
-  }
-      switch (tree->basis_dim) {
-        case 16: PXO_BWD4(16); break;
-        case 25: PXO_BWD4(25); break;
-        default: PXO_BWD4(-1); break;
-      }
-#undef PXO_BWD4W
-#undef PXO_BWD4
-      break;
-    case 8: hipLaunchKernelGGL((octree_render_kernel<1, 8>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, (float*)nullptr, out_rgb, grad_out, grad_data); break;
-    default: hipLaunchKernelGGL((octree_render_kernel<1, 16>), dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, (float*)nullptr, out_rgb, grad_out, grad_data); break;
+  if (row == 4) {                                // SH16 / SH25 with K a compile-time constant
+    const int K = tree->basis_dim, wc = g_bwd_wc_rows;
+    const bool rp = g_bwd_update == 1;
+    const Bwd4Kernel kernel = K == 16 ? bwd4_kernel<16>(wc, rp) : K == 25 ? bwd4_kernel<25>(wc, rp) : bwd4_kernel<-1>(wc, rp);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, grad_out, grad_data);
+  } else {
+    const auto kernel = row == 8 ? octree_render_kernel<1, 8> : octree_render_kernel<1, 16>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, (float*)nullptr, out_rgb, grad_out,
+                       grad_data);
   }
   return check_launch(who);
 }
@@ -2526,7 +2472,7 @@ int pxo_octree_render_sg_bwd(const PxoTree* tree, const float* lobes, const PxoC
 // ---- compressed trees (octree/compression.py:88-139) ----
 static int quant_format_ok(int64_t n_internal, int basis_dim, int n_retained, int bits, const char* who) {
   const int K = basis_dim;
-  PXO_REQUIRE(K == 1 || K == 4 || K == 9 || K == 16 || K == 25, "%s: basis_dim %d is not an SH format (1,4,9,16,25)", who, K);
+  if (int rc = check_format(K, 3 * K + 1, "SH", who)) return rc;        // (the palette form has no data_dim of its own)
   PXO_REQUIRE(n_retained >= 0 && n_retained < K, "%s: n_retained %d must be in [0, basis_dim %d)", who, n_retained, K);
   PXO_REQUIRE(bits >= 1 && bits <= 16, "%s: bits %d must be in 1..16 (the map is uint16)", who, bits);
   PXO_REQUIRE(n_internal >= 1 && n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
@@ -2589,7 +2535,7 @@ int pxo_octree_quant_pack(const uint16_t* quant_map, const void* quant_colors, c
 // the argument checks and the launch shape of the palette renderers (with and without the extra outputs)
 static int quant_render_args(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                              const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const char* who, QuantRenderArgs& A,
-                             int64_t& blocks, int& row) {
+                             unsigned& grid, int& row) {
   if (int rc = check_opts(opts, who)) return rc;
   PXO_REQUIRE(tree && tree->child && tree->idx && tree->palette && tree->sigma, "%s: null tree", who);
   if (int rc = quant_format_ok(tree->n_internal, tree->basis_dim, tree->n_retained, tree->bits, who)) return rc;
@@ -2599,44 +2545,22 @@ static int quant_render_args(const PxoQuantTree* tree, const PxoCamera* cam, con
   PXO_REQUIRE(tree->n_retained == 0 || tree->retained, "%s: n_retained %d but retained is null", who, tree->n_retained);
   PXO_REQUIRE((((uintptr_t)tree->idx | (uintptr_t)tree->palette | (uintptr_t)tree->retained) & 7) == 0,
               "%s: idx, palette and retained must be 8-byte aligned", who);
-  PXO_REQUIRE(B >= 0, "%s: B < 0", who);
   A.tree = *tree;
   A.opt = *opts;
-  A.B = B;
-  A.has_cam = cam != nullptr;
-  row = g_row_override[0] ? g_row_override[0] : 4;     // unmeasured against 8 / 16 (see DESIGN): the float kernel's default
-  if (cam) {
-    PXO_REQUIRE(cam->c2w && cam->width >= 1 && cam->height >= 1 && cam->fx > 0.0f && cam->fy > 0.0f, "%s: bad camera", who);
-    PXO_REQUIRE(B == (int64_t)cam->width * cam->height, "%s: B must be width*height in camera mode", who);
-    A.cam = *cam;
-    A.origins = A.dirs = A.viewdirs = nullptr;
-    const int rpw = 64 / row, wtx = rpw <= 4 ? 2 : (rpw <= 16 ? 4 : 8), tx = 2 * wtx, ty = 2 * (rpw / wtx);
-    blocks = (int64_t)((cam->width + tx - 1) / tx) * ((cam->height + ty - 1) / ty);
-  } else {
-    PXO_REQUIRE(B == 0 || (origins && dirs && viewdirs), "%s: null ray arrays", who);
-    A.cam = PxoCamera{};
-    A.origins = origins; A.dirs = dirs; A.viewdirs = viewdirs;
-    blocks = blocks_for(B, kRenderThreads / row);
-  }
-  PXO_REQUIRE(blocks < ((int64_t)1 << 31), "%s: too many rays for one launch", who);
-  return PXO_OK;
+  row = render_row(false);                             // unmeasured against 8 / 16 (see DESIGN): the float kernel's default
+  return launch_shape(cam, origins, dirs, viewdirs, B, row, who, A, grid);
 }
 
 int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                                 const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
   const char* who = "pxo_octree_render_quant_fwd";
   QuantRenderArgs A;
-  int64_t blocks;
+  unsigned grid;
   int row;
-  if (int rc = quant_render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, A, blocks, row)) return rc;
+  if (int rc = quant_render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, A, grid, row)) return rc;
   if (B == 0) return PXO_OK;
   PXO_REQUIRE(out_rgb, "%s: null output", who);
-  const dim3 grid((unsigned)blocks), block(kRenderThreads);
-  switch (row) {
-    case 4: hipLaunchKernelGGL(octree_render_quant_kernel<4>, grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
-    case 8: hipLaunchKernelGGL(octree_render_quant_kernel<8>, grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
-    default: hipLaunchKernelGGL(octree_render_quant_kernel<16>, grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
-  }
+  launch_quant_fwd<false>(A, row, grid, out_rgb, stream);
   return check_launch("octree_render_quant_fwd");
 }
 
@@ -2645,20 +2569,15 @@ int pxo_octree_render_quant_aux_fwd(const PxoQuantTree* tree, const PxoCamera* c
                                     float* out_rgb, float* out_aux, void* stream) {
   const char* who = "pxo_octree_render_quant_aux_fwd";
   QuantRenderAuxArgs A;
-  int64_t blocks;
+  unsigned grid;
   int row;
-  if (int rc = quant_render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, A, blocks, row)) return rc;
+  if (int rc = quant_render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, A, grid, row)) return rc;
   if (int rc = check_surface_thresh(opts, surface_thresh, who)) return rc;
   if (B == 0) return PXO_OK;
   PXO_REQUIRE(out_rgb && out_aux, "%s: null output", who);
   A.out = out_aux;
   A.surface_thresh = surface_thresh;
-  const dim3 grid((unsigned)blocks), block(kRenderThreads);
-  switch (row) {
-    case 4: hipLaunchKernelGGL((octree_render_quant_kernel<4, true>), grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
-    case 8: hipLaunchKernelGGL((octree_render_quant_kernel<8, true>), grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
-    default: hipLaunchKernelGGL((octree_render_quant_kernel<16, true>), grid, block, 0, (hipStream_t)stream, A, out_rgb); break;
-  }
+  launch_quant_fwd<true>(A, row, grid, out_rgb, stream);
   return check_launch("octree_render_quant_aux_fwd");
 }
 
@@ -2676,11 +2595,11 @@ int pxo_octree_count_work(const PxoTree* tree, const PxoCamera* cam, const PxoRe
   return check_launch("octree_count_work");
 }
 
-// what the two weight entry points share: the checks on tree / options / op / ndc / weights and the launch
+// what the two weight entry points share: the checks on tree / options / ndc / weights and the launch (op: checked by the
+// entry points, ahead of their no-work return)
 static int weight_accum_launch(const PxoTree* tree, WeightArgs& A, const PxoRenderOpts* opts, int op, float* weights,
                                void* stream, const PxoNdc* ndc, const char* who) {
   if (int rc = check_opts(opts, who)) return rc;
-  PXO_REQUIRE(op == 0 || op == 1, "%s: op %d is neither 0 (max) nor 1 (sum)", who, op);
   PXO_REQUIRE(tree && tree->child && tree->data, "%s: null tree", who);
   PXO_REQUIRE(tree->data_dim >= 1, "%s: data_dim %d < 1", who, tree->data_dim);
   PXO_REQUIRE(tree->n_internal >= 1 && tree->n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);

@@ -172,38 +172,35 @@ def _no_sg_ndc(lobes, ndc):
                                   "trees only")
 
 
-def _render_fwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out, ndc=None):
-    """pxo_octree_render_fwd; pxo_octree_render_sg_fwd when the tree's SG lobes are given; pxo_octree_render_ndc_fwd when the
-    scene's NDC projection is."""
+def _render_entry(direction, tree, lobes, ndc):
+    """(entry point, its name, leading args, trailing args) of the float-tree renderer, direction "fwd" or "bwd":
+    pxo_octree_render_*; pxo_octree_render_sg_* when the tree's SG lobes are given (they follow the tree);
+    pxo_octree_render_ndc_* when the scene's NDC projection is (it ends the list)."""
     _no_sg_ndc(lobes, ndc)
-    if ndc is not None:
-        check(_lib.load().pxo_octree_render_ndc_fwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts),
-                                                    _f(out), _stream(), ctypes.byref(_ndc(ndc))), "pxo_octree_render_ndc_fwd")
-    elif lobes is None:
-        check(_lib.load().pxo_octree_render_fwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts), _f(out),
-                                                _stream()), "pxo_octree_render_fwd")
-    else:
-        check(_lib.load().pxo_octree_render_sg_fwd(ctypes.byref(tree), _lobes(lobes, tree), cam, origins, dirs, viewdirs, B,
-                                                   ctypes.byref(opts), _f(out), _stream()), "pxo_octree_render_sg_fwd")
+    kind = "ndc_" if ndc is not None else ("" if lobes is None else "sg_")
+    name = f"pxo_octree_render_{kind}{direction}"
+    lead = (ctypes.byref(tree),) if lobes is None else (ctypes.byref(tree), _lobes(lobes, tree))
+    return getattr(_lib.load(), name), name, lead, () if ndc is None else (ctypes.byref(_ndc(ndc)),)
+
+
+def _render_fwd(tree, lobes, rays, opts, out, ndc=None):
+    fn, name, lead, trail = _render_entry("fwd", tree, lobes, ndc)
+    check(fn(*lead, *rays, ctypes.byref(opts), _f(out), _stream(), *trail), name)
     return out
 
 
-def _render_bwd(tree, lobes, cam, origins, dirs, viewdirs, B, opts, out_rgb, grad_out, grad_data, ndc=None):
-    """pxo_octree_render_bwd; pxo_octree_render_sg_bwd when the tree's SG lobes are given; pxo_octree_render_ndc_bwd when the
-    scene's NDC projection is."""
-    _no_sg_ndc(lobes, ndc)
-    if ndc is not None:
-        check(_lib.load().pxo_octree_render_ndc_bwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts),
-                                                    _f(out_rgb), _f(grad_out), _f(grad_data), _stream(),
-                                                    ctypes.byref(_ndc(ndc))), "pxo_octree_render_ndc_bwd")
-    elif lobes is None:
-        check(_lib.load().pxo_octree_render_bwd(ctypes.byref(tree), cam, origins, dirs, viewdirs, B, ctypes.byref(opts),
-                                                _f(out_rgb), _f(grad_out), _f(grad_data), _stream()), "pxo_octree_render_bwd")
-    else:
-        check(_lib.load().pxo_octree_render_sg_bwd(ctypes.byref(tree), _lobes(lobes, tree), cam, origins, dirs, viewdirs, B,
-                                                   ctypes.byref(opts), _f(out_rgb), _f(grad_out), _f(grad_data), _stream()),
-              "pxo_octree_render_sg_bwd")
+def _render_bwd(tree, lobes, rays, opts, out_rgb, grad_out, grad_data, ndc=None):
+    fn, name, lead, trail = _render_entry("bwd", tree, lobes, ndc)
+    check(fn(*lead, *rays, ctypes.byref(opts), _f(out_rgb), _f(grad_out), _f(grad_data), _stream(), *trail), name)
     return grad_data
+
+
+def _rays(cam=None, origins=None, dirs=None, viewdirs=None):
+    """(camera, origins, dirs, viewdirs, B) as every renderer entry point takes them: a PxoCamera with its pixel count, or
+    three [B,3] ray arrays."""
+    if cam is not None:
+        return ctypes.byref(cam), None, None, None, cam.width * cam.height
+    return None, _f(origins), _f(dirs), _f(viewdirs), origins.shape[0]
 
 
 def _camera(c2w, width, height, fx, fy):
@@ -238,7 +235,7 @@ def octree_render_persp(tree, c2w, width, height, fx, opts, fy=None, lobes=None,
     _require_gpu()
     cam, keep = _camera(c2w, width, height, fx, fy)
     out = _new(height, width, 3, device=keep.device)
-    return _render_fwd(tree, lobes, ctypes.byref(cam), None, None, None, width * height, opts, out, ndc=ndc)
+    return _render_fwd(tree, lobes, _rays(cam), opts, out, ndc=ndc)
 
 
 def octree_render_persp_bwd(tree, c2w, width, height, fx, opts, grad_out, grad_data, fy=None, out_rgb=None, lobes=None,
@@ -247,8 +244,7 @@ def octree_render_persp_bwd(tree, c2w, width, height, fx, opts, grad_out, grad_d
     camera (saves one of the two marches) or None.  lobes, ndc: as in octree_render_persp."""
     _require_gpu()
     cam, keep = _camera(c2w, width, height, fx, fy)
-    return _render_bwd(tree, lobes, ctypes.byref(cam), None, None, None, width * height, opts, out_rgb, grad_out, grad_data,
-                       ndc=ndc)
+    return _render_bwd(tree, lobes, _rays(cam), opts, out_rgb, grad_out, grad_data, ndc=ndc)
 
 
 def octree_count_work(tree, c2w, width, height, fx, opts, fy=None, count_leaves=True):
@@ -357,9 +353,8 @@ def octree_render_rays(tree, origins, dirs, viewdirs, opts, lobes=None, ndc=None
     """[B,3] colours of explicit world-space rays with unit dirs (VolumeRenderer.forward).  lobes, ndc: as in
     octree_render_persp (with ndc the rays are still given in world space; they are converted per ray)."""
     _require_gpu()
-    B = origins.shape[0]
-    out = _new(B, 3, device=origins.device)
-    return _render_fwd(tree, lobes, None, _f(origins), _f(dirs), _f(viewdirs), B, opts, out, ndc=ndc)
+    out = _new(origins.shape[0], 3, device=origins.device)
+    return _render_fwd(tree, lobes, _rays(None, origins, dirs, viewdirs), opts, out, ndc=ndc)
 
 
 # ---- compressed trees rendered in place (the palette form of octree/compression.py:88-139) ----
@@ -417,18 +412,17 @@ def octree_render_quant_persp(qtree, c2w, width, height, fx, opts, fy=None):
     _require_gpu()
     cam, keep = _camera(c2w, width, height, fx, fy)
     out = _new(height, width, 3, device=keep.device)
-    check(_lib.load().pxo_octree_render_quant_fwd(ctypes.byref(qtree), ctypes.byref(cam), None, None, None, width * height,
-                                                  ctypes.byref(opts), _f(out), _stream()), "pxo_octree_render_quant_fwd")
+    check(_lib.load().pxo_octree_render_quant_fwd(ctypes.byref(qtree), *_rays(cam), ctypes.byref(opts), _f(out), _stream()),
+          "pxo_octree_render_quant_fwd")
     return out
 
 
 def octree_render_quant_rays(qtree, origins, dirs, viewdirs, opts):
     """octree_render_rays on a PxoQuantTree."""
     _require_gpu()
-    B = origins.shape[0]
-    out = _new(B, 3, device=origins.device)
-    check(_lib.load().pxo_octree_render_quant_fwd(ctypes.byref(qtree), None, _f(origins), _f(dirs), _f(viewdirs), B,
-                                                  ctypes.byref(opts), _f(out), _stream()), "pxo_octree_render_quant_fwd")
+    out = _new(origins.shape[0], 3, device=origins.device)
+    check(_lib.load().pxo_octree_render_quant_fwd(ctypes.byref(qtree), *_rays(None, origins, dirs, viewdirs), ctypes.byref(opts),
+                                                  _f(out), _stream()), "pxo_octree_render_quant_fwd")
     return out
 
 
@@ -449,8 +443,7 @@ def octree_render_aux_persp(tree, c2w, width, height, fx, opts, fy=None, surface
     cam, keep = _camera(c2w, width, height, fx, fy)
     out = _new(height, width, 3, device=keep.device)
     aux = _new(height, width, 3, device=keep.device)
-    check(fn(ctypes.byref(tree), ctypes.byref(cam), None, None, None, width * height, ctypes.byref(opts),
-             float(surface_thresh), _f(out), _f(aux), _stream()), name)
+    check(fn(ctypes.byref(tree), *_rays(cam), ctypes.byref(opts), float(surface_thresh), _f(out), _f(aux), _stream()), name)
     return out, aux
 
 
@@ -458,18 +451,16 @@ def octree_render_aux_rays(tree, origins, dirs, viewdirs, opts, surface_thresh=0
     """(rgb [B,3], aux [B,3]) of explicit world-space rays with unit dirs; see octree_render_aux_persp."""
     _require_gpu()
     fn, name = _aux_entry(tree)
-    B = origins.shape[0]
-    out = _new(B, 3, device=origins.device)
-    aux = _new(B, 3, device=origins.device)
-    check(fn(ctypes.byref(tree), None, _f(origins), _f(dirs), _f(viewdirs), B, ctypes.byref(opts), float(surface_thresh),
-             _f(out), _f(aux), _stream()), name)
+    out = _new(origins.shape[0], 3, device=origins.device)
+    aux = _new(origins.shape[0], 3, device=origins.device)
+    check(fn(ctypes.byref(tree), *_rays(None, origins, dirs, viewdirs), ctypes.byref(opts), float(surface_thresh), _f(out),
+             _f(aux), _stream()), name)
     return out, aux
 
 
 def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None, lobes=None, ndc=None):
     _require_gpu()
-    return _render_bwd(tree, lobes, None, _f(origins), _f(dirs), _f(viewdirs), origins.shape[0], opts, out_rgb, grad_out,
-                       grad_data, ndc=ndc)
+    return _render_bwd(tree, lobes, _rays(None, origins, dirs, viewdirs), opts, out_rgb, grad_out, grad_data, ndc=ndc)
 
 
 def image_mse(im, gt, want_grad=True):
