@@ -391,7 +391,8 @@ int pxo_mc_emit(const float* vol, int nx, int ny, int nz, double iso, const int8
 int pxo_tree_sigma_grid(const PxoTree* tree, int depth, int pad, float* sigma, int64_t* packed, void* stream);
 
 /* mse = mean((clamp(im,0,1) - gt)^2) and its gradient w.r.t. im  (octree/optimization.py:217-219);
- * n = number of floats.  sse_out: device scalar receiving sum of squares (mse = sse/n); grad may be NULL. */
+ * n = number of floats.  sse_out: device scalar receiving sum of squares (mse = sse/n); grad may be NULL.
+ * The clamp is torch.clamp's: a NaN in im stays NaN and makes sse NaN (its own gradient is 0), +-inf clamp to 1 / 0. */
 int pxo_image_mse(const float* im, const float* gt, int64_t n, float* grad, float* sse_out, void* stream);
 
 /* torch.optim.SGD step on the tree data (octree/optimization.py:176-181): with momentum mu > 0,

@@ -1580,14 +1580,18 @@ __global__ __launch_bounds__(256) void grid_count_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------
 // image loss and SGD
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void image_mse_kernel(const float* __restrict__ im, const float* __restrict__ gt, int64_t n,
+constexpr int kMseBlock = 256;          // threads of a workgroup of image_mse_kernel
+constexpr int kMsePerThread = 8;        // elements per thread the launcher sizes the grid for ...
+constexpr int kMseMaxBlocks = 4096;     // ... up to this many workgroups; a larger image takes more grid-stride iterations
+
+__global__ __launch_bounds__(kMseBlock) void image_mse_kernel(const float* __restrict__ im, const float* __restrict__ gt, int64_t n,
                                                          float* __restrict__ grad, float* __restrict__ sse) {
   __shared__ float s_part[4];
   float acc = 0.0f;
   const float scale = 2.0f / (float)n;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float v = im[i];
-    const float c = fminf(fmaxf(v, 0.0f), 1.0f);
+    const float c = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);      // comparisons, not fmaxf / fminf: a NaN pixel stays NaN, as torch.clamp keeps it
     const float e = c - gt[i];
     acc += e * e;
     if (grad) grad[i] = (v >= 0.0f && v <= 1.0f) ? scale * e : 0.0f;
@@ -2707,8 +2711,9 @@ int pxo_image_mse(const float* im, const float* gt, int64_t n, float* grad, floa
     set_error("pxo_image_mse: hipMemsetAsync failed");
     return PXO_ERR_HIP;
   }
-  const int64_t blocks = blocks_for(n, 256 * 8);
-  hipLaunchKernelGGL(image_mse_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, im, gt, n, grad, sse_out);
+  const int64_t blocks = blocks_for(n, kMseBlock * kMsePerThread);
+  hipLaunchKernelGGL(image_mse_kernel, dim3((unsigned)(blocks > kMseMaxBlocks ? kMseMaxBlocks : blocks)), dim3(kMseBlock), 0, s, im, gt, n,
+                     grad, sse_out);
   return check_launch("image_mse");
 }
 

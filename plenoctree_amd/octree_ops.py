@@ -463,6 +463,9 @@ def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_d
     return _render_bwd(tree, lobes, _rays(None, origins, dirs, viewdirs), opts, out_rgb, grad_out, grad_data, ndc=ndc)
 
 
+MSE_BLOCK, MSE_PER_THREAD, MSE_MAX_BLOCKS = 256, 8, 4096     # pxo_image_mse's launch (kMseBlock, kMsePerThread, kMseMaxBlocks)
+
+
 def image_mse(im, gt, want_grad=True):
     """(sse device scalar, grad or None) of mean((clamp(im,0,1)-gt)^2)  (octree/optimization.py:217-219)."""
     _require_gpu()

@@ -116,15 +116,16 @@ def render_persp(tree, c2w, opt, ndc, width=W, height=H, fx=FX):
     return render_rays(tree, o, d, d, opt, ndc).reshape(height, width, 3)
 
 
-def render_rays_torch(tree, data, origins, dirs, vdirs, opt, ndc):
-    """float64 autograd through oracle.render_rays_torch over the NDC sample sequence; a miss is the constant background."""
+def render_rays_torch(tree, data, origins, dirs, vdirs, opt, ndc, dtype=torch.float64):
+    """float64 autograd through oracle.render_rays_torch over the NDC sample sequence; a miss is the constant background.
+    dtype: the compositing precision, handed on to oracle.render_rays_torch."""
     conv = [ndc_ray(o, d, ndc) for o, d in zip(origins, dirs)]
     hit = np.array([c[2] for c in conv])
-    out = torch.full((len(conv), 3), float(opt.background_brightness), dtype=torch.float64)
+    out = torch.full((len(conv), 3), float(opt.background_brightness), dtype=dtype)
     if hit.any():
         no = np.stack([c[0] for c in conv])[hit]
         nd = np.stack([c[1] for c in conv])[hit]
-        res = T.render_rays_torch(tree, data, no, nd, np.asarray(vdirs, f32)[hit], opt)
+        res = T.render_rays_torch(tree, data, no, nd, np.asarray(vdirs, f32)[hit], opt, dtype=dtype)
         out = out.index_put((torch.from_numpy(np.nonzero(hit)[0]),), res)
     return out
 
