@@ -389,6 +389,27 @@ int pxo_mc_emit(const float* vol, int nx, int ny, int nz, double iso, const int8
  * for 1 <= depth <= PXO_TREE_MAX_DEPTH + 1, finer or coarser than the tree's own cells alike.  0 <= pad <= 64.  offset /
  * invradius of the tree are not used: the grid spans the tree's unit cube. */
 int pxo_tree_sigma_grid(const PxoTree* tree, int depth, int pad, float* sigma, int64_t* packed, void* stream);
+/* ---- per-vertex normals and colour  (the reference's gen_mesh.py:77-82 defines no colour flag and its save_obj, :133-158,
+ * is never given a vert_rgb: "# TODO: implement color") ----
+ * Sigma gradient at every vertex of the mesh pxo_mc_count / pxo_mc_emit made on the same vol / iso / ws / counts, in the
+ * vertices' order: gradients float64 [V, 3], index units, equal to plenoctree_amd/nerf_sh/isosurface.py:vertex_gradients
+ * element for element.  Grid-point gradient g(p)[a] in float64 from the float32 samples, one rounding per operation:
+ *   (vol[p + e_a] - vol[p - e_a]) * 0.5  where both neighbours exist,  vol[p + e_a] - vol[p]  at the lower border,
+ *   vol[p] - vol[p - e_a]  at the upper border;
+ * vertex on the edge (lo, hi = lo + e_a), with the f = (iso - v0) / (v1 - v0) that places it:  (1 - f) g(lo) + f g(hi).
+ * inside_idx is pxo_mc_emit's output (it names one end of each vertex's edge; the id arrays emit left in `ws` tell which
+ * edge).  One vertex per lane.  Asynchronous.  Preconditions and refusals are pxo_mc_emit's; V == 0 launches nothing. */
+int pxo_mc_vertex_gradients(const float* vol, int nx, int ny, int nz, double iso, const void* ws, size_t ws_bytes,
+                            const int64_t* counts, const int64_t* inside_idx, double* gradients, void* stream);
+/* out_rgb[i, c] = sigmoid(sum_k Y_k(dirs[i]) * coef[r * row_stride + c * K + k]),  r = rows ? rows[i] : i,  K = basis_dim,
+ * float32, one point per lane, the sum in the order of k.  Y is the SH basis for lobes == NULL, else the SG basis
+ * exp(lambda_k (mu_k . d - 1)) / K of lobes float32 [K, 4] rows (lambda, mu) -- the functions the octree renderers call.
+ * dirs float32 [n, 3] (unit vectors; not normalised here), rows int64 [n] or NULL, out_rgb float32 [n, 3].  A negative row
+ * gives colour 0; rows are not checked against the length of coef (the caller's to bound).  row_stride = 3 K + 1 with rows reads
+ * a tree's leaves in place; row_stride = 3 K without rows reads a NeRF's raw_rgb.  basis_dim outside {1, 4, 9, 16, 25},
+ * row_stride < 3 K or n outside [0, 2^31): PXO_ERR_ARG.  Asynchronous; n == 0 launches nothing. */
+int pxo_shade_points(const float* coef, int64_t row_stride, const int64_t* rows, const float* dirs, int64_t n, int basis_dim,
+                     const float* lobes, float* out_rgb, void* stream);
 
 /* mse = mean((clamp(im,0,1) - gt)^2) and its gradient w.r.t. im  (octree/optimization.py:217-219);
  * n = number of floats.  sse_out: device scalar receiving sum of squares (mse = sse/n); grad may be NULL.

@@ -216,6 +216,8 @@ SIGNATURES = {
     "pxo_mc_count": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_size_t, POINTER(c_int64), P]),
     "pxo_mc_emit": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_size_t, POINTER(c_int64), P, P, P, P]),
     "pxo_tree_sigma_grid": (c_int, [POINTER(PxoTree), c_int, c_int, P, P, P]),
+    "pxo_mc_vertex_gradients": (c_int, [P, c_int, c_int, c_int, c_double, P, c_size_t, POINTER(c_int64), P, P, P]),
+    "pxo_shade_points": (c_int, [P, c_int64, P, P, c_int64, c_int, P, P, P]),
     "pxo_image_mse": (c_int, [P, P, c_int64, P, P, P]),
     "pxo_sgd_step": (c_int, [P, P, P, c_int64, c_float, c_float, c_int, c_int, P]),
 }

@@ -1,6 +1,6 @@
 // Isosurface meshing on the device (gfx950): marching cubes on a dense float32 grid, and the sampler that puts a PlenOctree's
-// sigma onto such a grid.  Entry points: pxo_mc_workspace_bytes / pxo_mc_count / pxo_mc_emit / pxo_tree_sigma_grid
-// (include/plenoctree_octree.h, "isosurface meshing"); definition and output order are those of
+// sigma onto such a grid.  Entry points: pxo_mc_workspace_bytes / pxo_mc_count / pxo_mc_emit / pxo_tree_sigma_grid /
+// pxo_mc_vertex_gradients / pxo_shade_points (include/plenoctree_octree.h, "isosurface meshing"); definition and output order are those of
 // plenoctree_amd/nerf_sh/isosurface.py:marching_cubes, so the arrays compare with ==.
 //
 // Compiled with -ffp-contract=off (plenoctree_amd/build.py): a vertex is  index + (iso - v0) / (v1 - v0)  in float64, one IEEE
@@ -14,7 +14,13 @@
 //   vertices   rank inside the wave from a 64-bit ballot + popcount, wave totals through LDS, block offset from the scan:
 //              writes the vertex, its inside end point and its id into the dense per-axis id array
 //   triangles  wave scan of the triangle counts; every triangle looks its three edges' ids up in the id arrays
+//
+// Per-vertex attributes, one vertex per lane (the reference's gen_mesh.py:77-82 has no colour flag, and its save_obj, :133-158,
+// takes a vert_rgb that no caller passes: "# TODO: implement color"):
+//   pxo_mc_vertex_gradients  the sigma gradient at every vertex (isosurface.py:vertex_gradients, float64, compares with ==)
+//   pxo_shade_points         sigmoid of the SH or SG sum of a coefficient row along a direction, float32
 #include "pxo_common.h"
+#include "pxo_sh.h"
 #include "../../include/plenoctree_octree.h"
 
 namespace pxo {
@@ -312,6 +318,91 @@ __global__ __launch_bounds__(256) void tree_sigma_grid_kernel(const int32_t* __r
   if (packed) packed[p] = leaf;
 }
 
+// ---- what turns the mesh into an asset: a normal and a colour per vertex (the reference's gen_mesh.py:77-82 defines no colour
+// flag and its save_obj, :133-158, is never handed one: "# TODO: implement color") ------------------------------------------
+constexpr int kVgBlock = 256;        // vertices per workgroup of the gradient kernel, points per workgroup of the shader
+
+// g(p)[a] of isosurface.py:vertex_gradients: the central difference halved where both neighbours exist, the one-sided
+// difference at a border.  float64 from the float32 samples, one rounding per operation.
+__device__ inline double mc_point_gradient(const float* __restrict__ vol, int64_t p, int c, int extent, int64_t stride) {
+  const bool lo = c > 0, hi = c + 1 < extent;
+  const double d = (double)vol[hi ? p + stride : p] - (double)vol[lo ? p - stride : p];
+  return lo && hi ? d * 0.5 : d;
+}
+
+// One vertex per lane.  The vertex's edge is found from what the emit pass left: inside_idx names one end point q of the edge;
+// the edge is (q, q + e_a) if that edge crosses and carries this vertex's id in the id array of its axis, else (q - e_a, q).
+// (An inside point between two outside ones owns a vertex on either side, so the flag alone does not decide.)  An inside_idx
+// that names no such edge -- not this workspace's -- gives a zero gradient and reads nothing out of range.
+__global__ __launch_bounds__(kVgBlock) void mc_vertex_gradient_kernel(const float* __restrict__ vol, McGrid g, double iso,
+                                                                      const uint8_t* __restrict__ flags, McIds ids,
+                                                                      const int64_t* __restrict__ inside_idx, int64_t base_y,
+                                                                      int64_t base_z, int64_t n_vert,
+                                                                      double* __restrict__ gradients) {
+  const int64_t id = blockIdx.x * (int64_t)kVgBlock + threadIdx.x;
+  if (id >= n_vert) return;
+  const int a = id < base_y ? 0 : (id < base_z ? 1 : 2);
+  const int64_t stride = a == 0 ? g.sx : (a == 1 ? g.sy : 1);
+  const int64_t q = inside_idx[id];
+  double out[3] = {0.0, 0.0, 0.0};
+  if (q >= 0 && q < g.n) {
+    int64_t lo = -1;
+    if (((flags[q] >> a) & 1u) && ids.a[a][q] == (int32_t)id) lo = q;
+    else if (q >= stride && ((flags[q - stride] >> a) & 1u) && ids.a[a][q - stride] == (int32_t)id) lo = q - stride;
+    if (lo >= 0) {
+      int c[3];
+      mc_coords(g, lo, c[0], c[1], c[2]);
+      const int ext[3] = {g.nx, g.ny, g.nz};
+      if (c[a] + 1 < ext[a]) {                   // always, for an edge classify flagged; keeps hi inside the grid regardless
+        const int64_t hi = lo + stride;
+        const int64_t st[3] = {g.sx, g.sy, 1};
+        const double v0 = (double)vol[lo], v1 = (double)vol[hi];
+        const double f = (iso - v0) / (v1 - v0);
+        const double f0 = 1.0 - f;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          const double g0 = mc_point_gradient(vol, lo, c[b], ext[b], st[b]);
+          const double g1 = mc_point_gradient(vol, hi, c[b] + (b == a ? 1 : 0), ext[b], st[b]);
+          out[b] = f0 * g0 + f * g1;
+        }
+      }
+    }
+  }
+  gradients[id * 3] = out[0];
+  gradients[id * 3 + 1] = out[1];
+  gradients[id * 3 + 2] = out[2];
+}
+
+// One point per lane: out[i, c] = sigmoid(sum_k Y_k(dirs[i]) coef[r row_stride + c K + k]), r = rows ? rows[i] : i; a negative
+// row is colour 0.  Y: the leaf basis of pxo_sh.h, SH without lobes, SG with them.  float32, the sum in the order of k.
+template <int K>
+__global__ __launch_bounds__(kVgBlock) void shade_points_kernel(const float* __restrict__ coef, int64_t row_stride,
+                                                                const int64_t* __restrict__ rows, const float* __restrict__ dirs,
+                                                                int64_t n, const float* __restrict__ lobes,
+                                                                float* __restrict__ out_rgb) {
+  const int64_t i = blockIdx.x * (int64_t)kVgBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = rows ? rows[i] : i;
+  float rgb[3] = {0.0f, 0.0f, 0.0f};
+  if (r >= 0) {
+    const float x = dirs[i * 3], y = dirs[i * 3 + 1], z = dirs[i * 3 + 2];
+    float Y[K];
+    if (lobes) sg_basis_dyn(K, lobes, x, y, z, Y);
+    else sh_basis_dyn(K, x, y, z, Y);
+    const float* row = coef + r * row_stride;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float s = 0.0f;
+#pragma unroll
+      for (int k = 0; k < K; ++k) s += Y[k] * row[c * K + k];
+      rgb[c] = 1.0f / (1.0f + expf(-s));
+    }
+  }
+  out_rgb[i * 3] = rgb[0];
+  out_rgb[i * 3 + 1] = rgb[1];
+  out_rgb[i * 3 + 2] = rgb[2];
+}
+
 static int mc_grid(const char* who, int nx, int ny, int nz, McGrid* g) {
   PXO_REQUIRE(nx >= 0 && ny >= 0 && nz >= 0, "%s: negative grid size", who);
   int64_t n = 0;
@@ -406,6 +497,55 @@ int pxo_mc_emit(const float* vol, int nx, int ny, int nz, double iso, const int8
     hipLaunchKernelGGL(mc_triangle_kernel, dim3((unsigned)w.nb), dim3(kMcBlock), 0, s, g, (const uint8_t*)(base + w.case_off), flags,
                        tri_table, boff + 3 * w.nb, n_tri, ids, triangles);
   return check_launch("mc_emit");
+}
+
+int pxo_mc_vertex_gradients(const float* vol, int nx, int ny, int nz, double iso, const void* ws, size_t ws_bytes,
+                            const int64_t* counts, const int64_t* inside_idx, double* gradients, void* stream) {
+  PXO_REQUIRE(counts, "pxo_mc_vertex_gradients: null pointer");
+  McGrid g;
+  if (int rc = mc_grid("pxo_mc_vertex_gradients", nx, ny, nz, &g)) return rc;
+  PXO_REQUIRE(counts[0] >= 0 && counts[1] >= 0 && counts[2] >= 0 && counts[3] >= 0, "pxo_mc_vertex_gradients: negative count");
+  const int64_t lim = (int64_t)1 << 31;
+  PXO_REQUIRE(counts[0] < lim && counts[1] < lim && counts[2] < lim && counts[0] + counts[1] + counts[2] < lim,
+              "pxo_mc_vertex_gradients: %lld vertices exceed the int32 vertex-id range (2^31)",
+              (long long)counts[0] + (long long)counts[1] + (long long)counts[2]);
+  PXO_REQUIRE(counts[3] < lim, "pxo_mc_vertex_gradients: %lld triangles exceed the int32 range (2^31)", (long long)counts[3]);
+  const int64_t n_vert = counts[0] + counts[1] + counts[2];
+  if (mc_empty(g) || n_vert == 0) return PXO_OK;
+  PXO_REQUIRE(vol && ws && inside_idx && gradients, "pxo_mc_vertex_gradients: null pointer");
+  const McWs w = mc_ws(g.n);
+  if (ws_bytes < (size_t)w.total) {
+    set_error("pxo_mc_vertex_gradients: workspace %zu < %lld", ws_bytes, (long long)w.total);
+    return PXO_ERR_WORKSPACE;
+  }
+  char* base = (char*)ws;
+  McIds ids;
+  for (int a = 0; a < 3; ++a) ids.a[a] = (int32_t*)(base + w.id_off[a]);
+  hipLaunchKernelGGL(mc_vertex_gradient_kernel, dim3((unsigned)((n_vert + kVgBlock - 1) / kVgBlock)), dim3(kVgBlock), 0,
+                     (hipStream_t)stream, vol, g, iso, (const uint8_t*)(base + w.flag_off), ids, inside_idx, counts[0],
+                     counts[0] + counts[1], n_vert, gradients);
+  return check_launch("mc_vertex_gradients");
+}
+
+int pxo_shade_points(const float* coef, int64_t row_stride, const int64_t* rows, const float* dirs, int64_t n, int basis_dim,
+                     const float* lobes, float* out_rgb, void* stream) {
+  PXO_REQUIRE(basis_dim == 1 || basis_dim == 4 || basis_dim == 9 || basis_dim == 16 || basis_dim == 25,
+              "pxo_shade_points: basis_dim %d not in {1, 4, 9, 16, 25}", basis_dim);
+  PXO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "pxo_shade_points: %lld points outside [0, 2^31)", (long long)n);
+  PXO_REQUIRE(row_stride >= 3 * (int64_t)basis_dim, "pxo_shade_points: row_stride %lld < 3 * basis_dim = %d",
+              (long long)row_stride, 3 * basis_dim);
+  if (n == 0) return PXO_OK;
+  PXO_REQUIRE(coef && dirs && out_rgb, "pxo_shade_points: null pointer");
+  const dim3 grid((unsigned)((n + kVgBlock - 1) / kVgBlock)), block(kVgBlock);
+  hipStream_t s = (hipStream_t)stream;
+  switch (basis_dim) {
+#define PXO_SHADE_CASE(K)                                                                                                   \
+    case K: hipLaunchKernelGGL(shade_points_kernel<K>, grid, block, 0, s, coef, row_stride, rows, dirs, n, lobes, out_rgb); \
+      break;
+    PXO_SHADE_CASE(1) PXO_SHADE_CASE(4) PXO_SHADE_CASE(9) PXO_SHADE_CASE(16) PXO_SHADE_CASE(25)
+#undef PXO_SHADE_CASE
+  }
+  return check_launch("shade_points");
 }
 
 int pxo_tree_sigma_grid(const PxoTree* tree, int depth, int pad, float* sigma, int64_t* packed, void* stream) {

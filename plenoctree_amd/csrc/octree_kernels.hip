@@ -805,24 +805,7 @@ __device__ __forceinline__ float row_sum(float v) {   // sum over the ROW lanes 
   return v;
 }
 
-// first `basis_dim` SH basis values (the bands of a lower degree are a prefix of the degree-4 list)
-__device__ __forceinline__ void sh_basis_dyn(int basis_dim, float x, float y, float z, float* Y) {
-  float tmp[25];
-  sh_basis<4>(x, y, z, tmp);
-#pragma unroll
-  for (int i = 0; i < 25; ++i)
-    if (i < basis_dim) Y[i] = tmp[i];
-}
-
-// spherical-Gaussian basis of an SG<K> tree (nerf_sh/nerf/sg.py:35-66, svox data_format SG<K>): lobes [K,4] rows
-// (lambda, mu.x, mu.y, mu.z), basis_i = exp(lambda_i (mu_i . d - 1)) / K -- float32, evaluated in exactly that order
-__device__ __forceinline__ void sg_basis_dyn(int basis_dim, const float* __restrict__ lobes, float x, float y, float z, float* Y) {
-  const float inv_k = 1.0f / (float)basis_dim;
-  for (int i = 0; i < basis_dim; ++i) {
-    const float lam = lobes[4 * i], dot = lobes[4 * i + 1] * x + lobes[4 * i + 2] * y + lobes[4 * i + 3] * z;
-    Y[i] = expf(lam * (dot - 1.0f)) * inv_k;
-  }
-}
+// sh_basis_dyn / sg_basis_dyn, the per-ray basis of either tree format: pxo_sh.h (shared with pxo_shade_points)
 
 struct RenderArgs {
   PxoTree tree;

@@ -45,4 +45,27 @@ __device__ __forceinline__ void sh_basis(float x, float y, float z, float (&Y)[(
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// The basis of a PlenOctree's leaves by run-time width, as the octree renderers and pxo_shade_points evaluate it (both are
+// compiled with -ffp-contract=off, so one definition gives one result)
+// ------------------------------------------------------------------------------------------
+// first `basis_dim` SH basis values (the bands of a lower degree are a prefix of the degree-4 list)
+__device__ __forceinline__ void sh_basis_dyn(int basis_dim, float x, float y, float z, float* Y) {
+  float tmp[25];
+  sh_basis<4>(x, y, z, tmp);
+#pragma unroll
+  for (int i = 0; i < 25; ++i)
+    if (i < basis_dim) Y[i] = tmp[i];
+}
+
+// spherical-Gaussian basis of an SG<K> tree (nerf_sh/nerf/sg.py:35-66, svox data_format SG<K>): lobes [K,4] rows
+// (lambda, mu.x, mu.y, mu.z), basis_i = exp(lambda_i (mu_i . d - 1)) / K -- float32, evaluated in exactly that order
+__device__ __forceinline__ void sg_basis_dyn(int basis_dim, const float* __restrict__ lobes, float x, float y, float z, float* Y) {
+  const float inv_k = 1.0f / (float)basis_dim;
+  for (int i = 0; i < basis_dim; ++i) {
+    const float lam = lobes[4 * i], dot = lobes[4 * i + 1] * x + lobes[4 * i + 2] * y + lobes[4 * i + 3] * z;
+    Y[i] = expf(lam * (dot - 1.0f)) * inv_k;
+  }
+}
+
 }  // namespace pxo

@@ -1,5 +1,6 @@
 """torch-tensor front end of the isosurface entry points of include/plenoctree_octree.h: marching cubes on a device grid
-(pxo_mc_count / pxo_mc_emit) and the sampler of a PlenOctree's sigma onto its dense cell grid (pxo_tree_sigma_grid).
+(pxo_mc_count / pxo_mc_emit), the sampler of a PlenOctree's sigma onto its dense cell grid (pxo_tree_sigma_grid), and the two
+stages that give a mesh normals and view-dependent colour (pxo_mc_vertex_gradients, pxo_shade_points).
 
 The definition is that of nerf_sh/isosurface.py:marching_cubes, output order included: the device arrays equal the host
 function's element for element.  The case table is uploaded from that module (once per device); the library holds none.
@@ -47,28 +48,26 @@ def mc_workspace_bytes(nx, ny, nz):
     return n.value
 
 
-def marching_cubes(vol, iso):
-    """vol: float32 [nx, ny, nz] on the GPU -> (vertices [V,3] float64 in index units, triangles [T,3] int64, inside_idx [V]
-    int64), device tensors equal to isosurface.marching_cubes(vol.cpu().numpy(), iso); inside_idx is the linear grid index of
-    the end point of each vertex's edge whose value is >= iso.  ValueError for a volume with non-finite values."""
+def _mesh(vol, iso, who, gradients):
+    """The count -> emit (-> gradient) sequence behind marching_cubes, mesh_with_gradients and vertex_gradients."""
     _require_gpu()
     if vol.dim() != 3:
-        raise ValueError("marching_cubes expects a 3-D array")
+        raise ValueError(f"{who} expects a 3-D array")
     if not vol.is_cuda or vol.dtype != torch.float32:
-        raise PxoError("mesh_ops.marching_cubes takes a float32 volume on the GPU (the host function is isosurface.marching_cubes)")
+        raise PxoError(f"mesh_ops.{who} takes a float32 volume on the GPU (the host function is isosurface.{who})")
     dev = vol.device
     nx, ny, nz = (int(s) for s in vol.shape)
     iso = float(iso)
 
     def empty(n_vert=0):
         return (torch.zeros(n_vert, 3, dtype=torch.float64, device=dev), torch.zeros(0, 3, dtype=torch.int64, device=dev),
-                torch.zeros(n_vert, dtype=torch.int64, device=dev))
+                torch.zeros(n_vert, dtype=torch.int64, device=dev), torch.zeros(n_vert, 3, dtype=torch.float64, device=dev))
 
     if min(nx, ny, nz) < 2:
         return empty()
     vol = vol.contiguous()
     if not bool(torch.isfinite(vol).all()):
-        raise ValueError("marching_cubes: the volume holds non-finite values (NaN/inf sigma would give NaN vertices)")
+        raise ValueError(f"{who}: the volume holds non-finite values (NaN/inf sigma would give NaN vertices)")
     lib = _lib.load()
     table, count = _device_tables(dev)
     nbytes = mc_workspace_bytes(nx, ny, nz)
@@ -83,7 +82,95 @@ def marching_cubes(vol, iso):
     inside_idx = _new(n_vert, device=dev, dtype=torch.int64)
     check(lib.pxo_mc_emit(_f(vol), nx, ny, nz, iso, _p(table), _p(ws), nbytes, counts, _p(vertices), _p(triangles),
                           _p(inside_idx), _stream()), "pxo_mc_emit")
-    return vertices, triangles, inside_idx
+    grad = None
+    if gradients:
+        grad = _new(n_vert, 3, device=dev, dtype=torch.float64)
+        check(lib.pxo_mc_vertex_gradients(_f(vol), nx, ny, nz, iso, _p(ws), nbytes, counts, _p(inside_idx), _p(grad), _stream()),
+              "pxo_mc_vertex_gradients")
+    return vertices, triangles, inside_idx, grad
+
+
+def marching_cubes(vol, iso):
+    """vol: float32 [nx, ny, nz] on the GPU -> (vertices [V,3] float64 in index units, triangles [T,3] int64, inside_idx [V]
+    int64), device tensors equal to isosurface.marching_cubes(vol.cpu().numpy(), iso); inside_idx is the linear grid index of
+    the end point of each vertex's edge whose value is >= iso.  ValueError for a volume with non-finite values."""
+    return _mesh(vol, iso, "marching_cubes", False)[:3]
+
+
+def mesh_with_gradients(vol, iso):
+    """marching_cubes(vol, iso) plus the sigma gradient at every vertex (float64 [V,3], index units, on the device; equal to
+    isosurface.vertex_gradients(vol.cpu().numpy(), iso)): one count, one emit, one gradient launch on the same workspace."""
+    return _mesh(vol, iso, "marching_cubes", True)
+
+
+def vertex_gradients(vol, iso):
+    """pxo_mc_vertex_gradients: float64 [V,3] on the device, equal to isosurface.vertex_gradients(vol.cpu().numpy(), iso)
+    element for element.  A field without a crossing gives an empty array and launches nothing."""
+    return _mesh(vol, iso, "vertex_gradients", True)[3]
+
+
+def unit_normals(gradients, step):
+    """n = -(grad / s) / |grad / s| in float64 (torch tensor or numpy array in, the same kind out): `step` is the world length
+    of one index step per axis; the normal points towards lower sigma, out of the solid.  A zero gradient gives (0, 0, 0)."""
+    if torch.is_tensor(gradients):
+        g = gradients.double() / torch.as_tensor(step, dtype=torch.float64, device=gradients.device)
+        length = g.norm(dim=1, keepdim=True)
+        return torch.where(length > 0, -g / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(g))
+    g = np.asarray(gradients, np.float64) / np.asarray(step, np.float64)
+    length = np.sqrt((g * g).sum(1, keepdims=True))
+    return np.where(length > 0, -g / np.where(length > 0, length, 1.0), 0.0)
+
+
+def shading_dirs(normals):
+    """d = -n in float32, the ray direction of a camera looking straight at the surface (what both renderers feed their basis);
+    (0, 0, 1) where n = 0.  numpy or torch in, the same kind out."""
+    if torch.is_tensor(normals):
+        d = (-normals).float()
+        d[(normals == 0).all(1)] = torch.tensor([0.0, 0.0, 1.0], device=d.device)
+        return d.contiguous()
+    d = (-np.asarray(normals)).astype(np.float32)
+    d[(np.asarray(normals) == 0).all(1)] = (0.0, 0.0, 1.0)
+    return np.ascontiguousarray(d)
+
+
+SHADE_DIMS = (1, 4, 9, 16, 25)
+
+
+def shade_points(coef, dirs, basis_dim, rows=None, lobes=None):
+    """pxo_shade_points: out[i, c] = sigmoid(sum_k Y_k(dirs[i]) coef[r, c K + k]), r = rows[i] if rows is given else i; float32
+    [n, 3] on the device.  coef: float32 [R, S] with S >= 3 K (a tree's leaves [n_internal * 8, 3 K + 1] are read in place, a
+    NeRF's raw_rgb [n, 3 K] likewise); dirs float32 [n, 3]; rows int64 [n], a negative row gives colour 0 and a row >= R is
+    refused; lobes float32 [K, 4] selects the SG basis, None the SH basis."""
+    _require_gpu()
+    K = int(basis_dim)
+    if K not in SHADE_DIMS:
+        raise PxoError(f"shade_points: basis_dim {K} not in {SHADE_DIMS}")
+    if coef.dim() != 2 or coef.dtype != torch.float32 or not coef.is_cuda or not coef.is_contiguous():
+        raise PxoError("shade_points takes contiguous float32 coefficients [R, S] on the GPU")
+    if coef.shape[1] < 3 * K:
+        raise PxoError(f"shade_points: rows of {coef.shape[1]} floats hold no 3 x {K} coefficients")
+    dev = coef.device
+    dirs = dirs.to(device=dev, dtype=torch.float32).contiguous()
+    n = int(dirs.shape[0])
+    if dirs.dim() != 2 or dirs.shape[1] != 3:
+        raise PxoError("shade_points: dirs must be [n, 3]")
+    if rows is None:
+        if n > coef.shape[0]:
+            raise PxoError(f"shade_points: {n} points but {coef.shape[0]} coefficient rows")
+    else:
+        rows = rows.to(device=dev, dtype=torch.int64).contiguous()
+        if tuple(rows.shape) != (n,):
+            raise PxoError(f"shade_points: rows has shape {tuple(rows.shape)}, dirs {tuple(dirs.shape)}")
+        if n and int(rows.max()) >= coef.shape[0]:
+            raise PxoError(f"shade_points: row {int(rows.max())} outside the {coef.shape[0]} coefficient rows")
+    if lobes is not None:
+        lobes = lobes.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(lobes.shape) != (K, 4):
+            raise PxoError(f"shade_points: lobes of shape {tuple(lobes.shape)}, basis_dim {K} needs ({K}, 4)")
+    out = _new(n, 3, device=dev)
+    check(_lib.load().pxo_shade_points(_f(coef), int(coef.shape[1]), _p(rows), _f(dirs), n, K, _p(lobes), _f(out), _stream()),
+          "pxo_shade_points")
+    return out
 
 
 def tree_sigma_grid(tree_view, depth, pad=1, want_packed=True, device=None):

@@ -135,3 +135,47 @@ def marching_cubes(vol, iso):
     tri_local = local[ci, ti].astype(np.int64)
     triangles = cell_edges[ci[:, None], tri_local]
     return vertices, triangles
+
+
+def _point_gradient(vol, pts, b):
+    """g(p)[b] at the grid points pts [n, 3] (int64): float64 from the samples, one rounding per operation."""
+    n = vol.shape[b]
+    c = pts[:, b]
+    lo, hi = c > 0, c + 1 < n
+    up, dn = pts.copy(), pts.copy()
+    up[:, b] = np.where(hi, c + 1, c)
+    dn[:, b] = np.where(lo, c - 1, c)
+    d = vol[tuple(up.T)].astype(np.float64) - vol[tuple(dn.T)].astype(np.float64)
+    return np.where(lo & hi, d * 0.5, d)
+
+
+def vertex_gradients(vol, iso):
+    """vol [nx, ny, nz] -> gradient of vol at every vertex of marching_cubes(vol, iso), in that function's vertex order (all
+    x-edges, then y, then z; C order of the edge's lower end point): float64 [V, 3] in index units.
+
+    The reference stops at geometry (gen_mesh.py:77-82 has no colour flag, save_obj :133-158 is never given a vert_rgb); a normal
+    is what view-dependent colour and a shaded import need.  Grid-point gradient g(p)[a], in float64 from the samples:
+    (vol[p + e_a] - vol[p - e_a]) * 0.5 where both neighbours exist, vol[p + e_a] - vol[p] at the lower border, vol[p] -
+    vol[p - e_a] at the upper one.  A vertex on the edge (lo, hi = lo + e_a) sits at f = (iso - v0) / (v1 - v0), the value that
+    places it, and has the gradient (1 - f) g(lo) + f g(hi).  The unit normal -grad / |grad| points towards lower values."""
+    vol = np.ascontiguousarray(vol)
+    if vol.ndim != 3:
+        raise ValueError("vertex_gradients expects a 3-D array")
+    if min(vol.shape) < 2:
+        return np.zeros((0, 3))
+    if not np.isfinite(vol).all():
+        raise ValueError("vertex_gradients: the volume holds non-finite values (NaN/inf sigma would give NaN vertices)")
+    inside = vol >= iso
+    out = []
+    for a in range(3):
+        lo = tuple(slice(0, -1) if d == a else slice(None) for d in range(3))
+        hi = tuple(slice(1, None) if d == a else slice(None) for d in range(3))
+        p0 = np.stack(np.nonzero(inside[lo] != inside[hi]), 1).astype(np.int64)
+        p1 = p0.copy()
+        p1[:, a] += 1
+        v0 = vol[tuple(p0.T)].astype(np.float64)
+        v1 = vol[tuple(p1.T)].astype(np.float64)
+        f = (iso - v0) / (v1 - v0)
+        f0 = 1.0 - f
+        out.append(np.stack([f0 * _point_gradient(vol, p0, b) + f * _point_gradient(vol, p1, b) for b in range(3)], 1))
+    return np.concatenate(out, 0)

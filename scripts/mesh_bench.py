@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Timing of the device meshing path against the host marching cubes it replaces, and of the tree-to-grid sampler.
 
-    python scripts/mesh_bench.py [--sizes 256 512] [--reps 5 3] [--tree_depth 8] [--json out.json]
+    python scripts/mesh_bench.py [--sizes 256 512] [--reps 5 3] [--tree_depth 8] [--attrs] [--json out.json]
 
 Field: "noise on a sphere", vol = 0.6 - |x| + 0.02 * N(0,1) on [-1,1]^3 (seeded, made on the GPU where gen_mesh's sigma grid
 lives), iso 0: a thick shell of cells that exercises every case.  Per size, alternating and warmed:
@@ -10,6 +10,9 @@ lives), iso 0: a thick shell of cells that exercises every case.  Per size, alte
   (b) host     the copy of the volume to the host + isosurface.marching_cubes
 and, with device events around the two library calls, pxo_mc_count and pxo_mc_emit on their own against the bytes they must
 move (computed from the shapes below).  The meshes of (a) and (b) are compared for equality at every size that is timed.
+--attrs adds, after each round's emit and outside its events, the two per-vertex stages on the mesh just emitted:
+pxo_mc_vertex_gradients, and pxo_shade_points with SH16 rows gathered at random from a 2^18-row table (a tree's leaves in place)
+along the normalised negative gradients.
 Then pxo_tree_sigma_grid at depth tree_depth + 1 on a tree of three fuzzy spheres refined from its 2^(tree_depth+1) mask (the
 scene of scripts/octree_bench.py).  Needs the GPU: there is nothing to time without one.
 """
@@ -53,7 +56,7 @@ def spread(xs):
     return {"min_ms": min(xs) * 1e3, "median_ms": statistics.median(xs) * 1e3, "max_ms": max(xs) * 1e3, "n": len(xs)}
 
 
-def bench_size(n, reps, dev):
+def bench_size(n, reps, dev, attrs=False):
     from plenoctree_amd import _lib, mesh_ops
     from plenoctree_amd.nerf_sh import isosurface
     from plenoctree_amd.ops import _f, _p, _stream
@@ -80,7 +83,11 @@ def bench_size(n, reps, dev):
     nbytes = mesh_ops.mc_workspace_bytes(n, n, n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     counts = (ctypes.c_int64 * 4)()
-    t_count, t_emit = [], []
+    t_count, t_emit, t_grad, t_shade = [], [], [], []
+    K, R = 16, 1 << 18
+    if attrs:
+        gen = torch.Generator(device=dev).manual_seed(1)
+        leaves = torch.randn(R, 3 * K + 1, device=dev, generator=gen)
     for i in range(reps + 1):
         e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         e[0].record()
@@ -96,6 +103,24 @@ def bench_size(n, reps, dev):
                    "pxo_mc_emit")
         e[3].record()
         torch.cuda.synchronize()
+        if attrs:                               # after the emit's events have been read off the stream
+            g = torch.empty(nv, 3, dtype=torch.float64, device=dev)
+            rows = torch.randint(0, R, (nv,), device=dev, generator=gen)
+            a = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            a[0].record()
+            _lib.check(lib.pxo_mc_vertex_gradients(_f(vol), n, n, n, 0.0, _p(ws), nbytes, counts, _p(ii), _p(g), _stream()),
+                       "pxo_mc_vertex_gradients")
+            a[1].record()
+            dirs = mesh_ops.shading_dirs(mesh_ops.unit_normals(g, [1.0] * 3))
+            rgb = torch.empty(nv, 3, device=dev)
+            a[2].record()
+            _lib.check(lib.pxo_shade_points(_f(leaves), 3 * K + 1, _p(rows), _f(dirs), nv, K, None, _f(rgb), _stream()),
+                       "pxo_shade_points")
+            a[3].record()
+            torch.cuda.synchronize()
+            if i:
+                t_grad.append(a[0].elapsed_time(a[1]) * 1e-3)
+                t_shade.append(a[2].elapsed_time(a[3]) * 1e-3)
         if i:                                   # the first round warms
             t_count.append(e[0].elapsed_time(e[1]) * 1e-3)
             t_emit.append(e[2].elapsed_time(e[3]) * 1e-3)
@@ -110,6 +135,13 @@ def bench_size(n, reps, dev):
         out[f"pxo_mc_{name}"] = dict(spread(ts), floor_bytes=fl[name], achieved_TB_per_s=fl[name] / med / 1e12,
                                      floor_ms_at_measured_peak=fl[name] / HBM_MEASURED * 1e3,
                                      share_of_measured_peak=fl[name] / med / HBM_MEASURED, share_of_spec_peak=fl[name] / med / HBM_SPEC)
+    if attrs:
+        # least traffic per vertex.  gradients: 8 B inside index + 1 B flag + 4 B id in, 24 B out (the float32 samples around the
+        # edge share lines with the neighbouring vertices: not counted).  shade: 8 B row + 12 B direction in, 12 B out, and the
+        # 3 K coefficients of a row picked at random (192 B; whole 32-byte sectors: 7 of them for a 196-byte row)
+        for name, ts, fb in (("pxo_mc_vertex_gradients", t_grad, 37 * len(dv)), ("pxo_shade_points_sh16", t_shade, (32 + 224) * len(dv))):
+            med = statistics.median(ts)
+            out[name] = dict(spread(ts), floor_bytes=fb, achieved_TB_per_s=fb / med / 1e12, share_of_measured_peak=fb / med / HBM_MEASURED)
     return out
 
 
@@ -158,6 +190,7 @@ def main(argv=None):
     p.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
     p.add_argument("--reps", type=int, nargs="+", default=[5, 3], help="timed repeats per size (the last value repeats)")
     p.add_argument("--tree_depth", type=int, default=8, help="0 skips the tree-to-grid timing")
+    p.add_argument("--attrs", action="store_true", help="also time pxo_mc_vertex_gradients and pxo_shade_points per size")
     p.add_argument("--json", type=str, default=None)
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
@@ -167,7 +200,7 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     out = {"marching_cubes": []}
     for i, n in enumerate(a.sizes):
-        r = bench_size(n, a.reps[min(i, len(a.reps) - 1)], dev)
+        r = bench_size(n, a.reps[min(i, len(a.reps) - 1)], dev, attrs=a.attrs)
         out["marching_cubes"].append(r)
         print(json.dumps(r), flush=True)
     if a.tree_depth:
