@@ -171,6 +171,16 @@ def init_from_env(backend=None, device=None):
     return Comm(world, rank, local_rank, backend)
 
 
+def open_cli(who):
+    """What a command-line entry point that runs one process per GPU starts with: (comm, this rank's device, say), `say` being
+    print on rank 0 and silent elsewhere.  `who` names the entry point in the refusal of a machine without a GPU."""
+    if not torch.cuda.is_available():
+        raise SystemExit(f"{who} needs a ROCm GPU; the HIP path has no CPU fallback")
+    comm = init_from_env()
+    torch.cuda.set_device(comm.local_rank)
+    return comm, torch.device("cuda", comm.local_rank), (print if comm.rank == 0 else (lambda *a, **k: None))
+
+
 def single_host(world=None):
     """Do all ranks of this job sit on ONE host?  torch.distributed.run exports LOCAL_WORLD_SIZE (ranks on this node): equal to
     WORLD_SIZE on one node.  Without a launcher (mp.spawn in tests) a loopback MASTER_ADDR says the same."""

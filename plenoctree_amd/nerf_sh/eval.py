@@ -5,10 +5,9 @@ import os
 import sys
 
 import numpy as np
-import torch
 
 from .. import dist
-from .nerf import llff, models, sg, utils, viewdirs
+from .nerf import families, llff, sg, utils, viewdirs
 
 
 def save_outputs(out_dir, idx, rgb, disp):
@@ -30,26 +29,10 @@ def main(argv=None):
     args = viewdirs.add_checkpoint_flags(utils.define_flags()).parse_args(argv)
     utils.update_flags(args)
     sg.apply_cli(args, argv)                     # --sg_dim K --sh_deg -1 on the command line win over the preset's sh_deg
-    if not torch.cuda.is_available():
-        raise SystemExit("nerf_sh.eval needs a ROCm GPU; the HIP path has no CPU fallback")
-    comm = dist.init_from_env()
-    torch.cuda.set_device(comm.local_rank)
-    device = torch.device("cuda", comm.local_rank)
-    if args.use_viewdirs:
-        # a view-dependent ("vanilla") NeRF: rendering opts in explicitly, like octree.extraction (training with this head is not
-        # built, so the generic check_flags keeps rejecting it)
-        viewdirs.check_render_dirs(args)
-    elif args.sg_dim > 0:
-        sg.check_dirs(args)          # a NeRF-SG (--sg_dim K --sh_deg -1): rendering opts in the same way
-    else:
-        utils.check_flags(args, world_size=comm.world)
+    comm, device, say = dist.open_cli("nerf_sh.eval")
+    families.check(args, "render", world_size=comm.world)
     dataset = llff.get_dataset("test", args, device)
-    if args.use_viewdirs:
-        model, state = viewdirs.restore_for_render(args, device, say=print if comm.rank == 0 else (lambda *a, **k: None))
-    elif args.sg_dim > 0:
-        model, state = sg.restore(args, device, say=print if comm.rank == 0 else (lambda *a, **k: None))
-    else:
-        model, state = models.get_model_state(args, device, restore=True)
+    model, state = families.restore(args, device, "render", say=say)
     # eval.py:63-65: a --render_path run (LLFF scenes) renders the dataset's camera path, which has no ground truth
     render_path = bool(args.render_path)
     out_dir = os.path.join(args.train_dir, "path_renders" if render_path else "test_preds")

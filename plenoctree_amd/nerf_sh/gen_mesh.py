@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import isosurface
-from .nerf import models, sg, utils
+from .nerf import families, sg, utils
 
 MC_CHOICES = ("device", "host")
 COLOR_CHOICES = ("none", "view")
@@ -137,16 +137,10 @@ def main(argv=None):
         raise SystemExit("nerf_sh.gen_mesh needs a ROCm GPU; the HIP path has no CPU fallback")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
     torch.cuda.set_device(device)
-    if args.sg_dim > 0 and not args.use_viewdirs:
-        sg.check_dirs(args, require_data=False)
-    else:
-        utils.check_flags(args, require_data=False)
+    families.check(args, "mesh", require_data=False)
     reso, c1, c2 = _triple(args.reso, int), _triple(args.c1, float), _triple(args.c2, float)
     print("* Creating model", flush=True)
-    if args.sg_dim > 0:        # a NeRF-SG (--sg_dim K --sh_deg -1): the same sigma head, lobes for --color view
-        model, state = sg.restore(args, device, require_data=False)
-    else:
-        model, state = models.get_model_state(args, device, restore=True)
+    model, state = families.restore(args, device, "mesh", require_data=False)
     print("* Eval reso", args.reso, "coarse?", args.coarse, flush=True)
     print("* Evaluating sigma @", reso[0] * reso[1] * reso[2], "points", flush=True)
 

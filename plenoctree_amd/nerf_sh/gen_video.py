@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import dist, ops
-from .nerf import llff, models, sg, utils, viewdirs
+from .nerf import families, llff, sg, utils, viewdirs
 
 
 def define_flags():
@@ -45,18 +45,8 @@ def main(argv=None):
     args = define_flags().parse_args(argv)
     utils.update_flags(args)
     sg.apply_cli(args, argv)                     # --sg_dim K --sh_deg -1 on the command line win over the preset's sh_deg
-    if not torch.cuda.is_available():
-        raise SystemExit("nerf_sh.gen_video needs a ROCm GPU; the HIP path has no CPU fallback")
-    comm = dist.init_from_env()
-    torch.cuda.set_device(comm.local_rank)
-    device = torch.device("cuda", comm.local_rank)
-    say = print if comm.rank == 0 else (lambda *a, **k: None)
-    if args.use_viewdirs:
-        viewdirs.check_render_dirs(args, require_data=False)
-    elif args.sg_dim > 0:
-        sg.check_dirs(args, require_data=False)
-    else:
-        utils.check_flags(args, require_data=False, world_size=comm.world)
+    comm, device, say = dist.open_cli("nerf_sh.gen_video")
+    families.check(args, "render", require_data=False, world_size=comm.world)
     path_ds = None
     if args.dataset == "llff":
         if not args.render_path or args.data_dir is None:
@@ -77,12 +67,7 @@ def main(argv=None):
         np.savetxt(args.write_poses, poses.reshape(-1, 4))
         print("Saved poses to", args.write_poses, flush=True)
     say("* Creating model", flush=True)
-    if args.use_viewdirs:      # a view-dependent ("vanilla") NeRF: opts in explicitly, like octree.extraction
-        model, state = viewdirs.restore_for_render(args, device, say=say, require_data=False)
-    elif args.sg_dim > 0:      # a NeRF-SG (--sg_dim K --sh_deg -1)
-        model, state = sg.restore(args, device, say=say, require_data=False)
-    else:
-        model, state = models.get_model_state(args, device, restore=True)
+    model, state = families.restore(args, device, "render", say=say, require_data=False)
     video_dir = os.path.join(args.train_dir, "video", "path" if path_ds is not None else "e{:03}".format(int(-args.elevation * 10)))
     frames_dir = os.path.join(video_dir, "frames")
     say(" Saving to", video_dir, flush=True)

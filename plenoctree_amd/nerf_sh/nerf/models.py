@@ -13,9 +13,21 @@ from ... import ops
 from . import utils
 
 
-class TrainState:
+class Workspace:
+    """The scratch buffer a state lends the kernels: grown when a call needs more, never shrunk."""
+    _ws = None
+
+    def workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.params.device)
+        return self._ws
+
+
+class TrainState(Workspace):
     """optimizer.target + Adam moments + step (utils.TrainState, nerf_sh/nerf/utils.py:38-41),
-    plus the MFMA-ordered weight images the kernels stream."""
+    plus the MFMA-ordered weight images the kernels stream, and the three library calls of train_step
+    that a state with more leaves (sg.SgState) replaces."""
 
     def __init__(self, cfg, params, step=0):
         self.cfg = cfg
@@ -33,7 +45,6 @@ class TrainState:
         self.bucket0 = self.reduce_buf[:self.n_mlp]
         self.bucket1 = self.reduce_buf[self.n_mlp:]
         self.packed = [None, None]
-        self._ws = None
         self.repack()
 
     def mlp_params(self, i):
@@ -46,11 +57,17 @@ class TrainState:
             f, b = self.packed[i] if self.packed[i] is not None else (None, None)
             self.packed[i] = ops.pack_weights(self.cfg, self.mlp_params(i), f, b, need_bwd=need_bwd)
 
-    def workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.params.device)
-        return self._ws
+    def train_workspace_bytes(self, cfg, B):
+        return ops.train_workspace_bytes(cfg, B)
+
+    def fwd_bwd(self, cfg, rays, pixels, ws, **kw):
+        """loss_fn + value_and_grad (pxo_train_fwd_bwd_bucketed) into the gradient arena and the stats."""
+        ops.train_fwd_bwd(cfg, self.params, self.packed, rays.origins, rays.directions, rays.viewdirs, pixels,
+                          self.grads, self.stats, ws, **kw)
+
+    def update(self, cfg, lr, grad_scale):
+        """Adam (train.py:119) and the refresh of the fragment-ordered weight images, one launch."""
+        ops.adam_pack_step(cfg, self.params, self.m, self.v, self.grads, lr, self.step, self.packed, grad_scale=grad_scale)
 
 
 def glorot_uniform_(w, fan_in, fan_out, gen):
@@ -58,9 +75,9 @@ def glorot_uniform_(w, fan_in, fan_out, gen):
     w.copy_((torch.rand(w.shape, generator=gen, dtype=torch.float64) * 2 - 1).mul_(lim).float())
 
 
-def init_params(cfg, seed=20200823):
-    """Glorot-uniform kernels, zero biases (nerf_sh/nerf/model_utils.py:63-65), host RNG."""
-    leaves, n = ops.param_layout(cfg)
+def glorot_arena(leaves, n, seed):
+    """Two MLPs of `leaves` (n floats each) in one flat arena: Glorot-uniform kernels, zero biases
+    (nerf_sh/nerf/model_utils.py:63-65), host RNG."""
     flat = torch.zeros(2 * n, dtype=torch.float32)
     gen = torch.Generator().manual_seed(seed)
     for mi in range(2):
@@ -68,6 +85,11 @@ def init_params(cfg, seed=20200823):
             if not is_bias:
                 glorot_uniform_(flat[mi * n + off: mi * n + off + rows * cols].view(rows, cols), rows, cols, gen)
     return flat
+
+
+def init_params(cfg, seed=20200823):
+    """Fresh parameters of the two MLPs of an SH model (or of a NeRF-SG with the same head width)."""
+    return glorot_arena(*ops.param_layout(cfg), seed)
 
 
 class NerfModel:
@@ -132,24 +154,22 @@ def train_step(model, state, batch, lr, randomized=True, t_rand=None, u=None, sp
 
     loss_fn + value_and_grad run in pxo_train_fwd_bwd_bucketed; `reducer` (dist.GradReducer: two RCCL sums over the ranks,
     MLP_0's half of the gradient arena under the fine level, MLP_1's half with the 6 stats in its tail at the end)
-    implements lax.pmean (train.py:117-118); Adam (train.py:119) and the re-pack of the weight images follow.  Returns
-    the device tensor stats[6] = (loss, psnr, loss_c, loss_sp, psnr_c, weight_l2); its values are only read by the
-    host when logging."""
+    implements lax.pmean (train.py:117-118); Adam (train.py:119) and the re-pack of the weight images follow.  The
+    library calls are the state's (TrainState; sg.SgState puts its own in their place), everything on the stream.
+    Returns the device tensor stats[6] = (loss, psnr, loss_c, loss_sp, psnr_c, weight_l2); its values are only read by
+    the host when logging."""
     cfg = model.cfg
     rays = batch["rays"]
-    B = rays.origins.shape[0]
-    ws = state.workspace(ops.train_workspace_bytes(cfg, B))
+    ws = state.workspace(state.train_workspace_bytes(cfg, rays.origins.shape[0]))
     ev = reducer.ready_event() if reducer is not None else None
-    ops.train_fwd_bwd(cfg, state.params, state.packed, rays.origins, rays.directions, rays.viewdirs, batch["pixels"],
-                      state.grads, state.stats, ws, randomized=randomized, t_rand=t_rand, u=u, sp_points=sp_points,
-                      seed=seed, grads0_ready=ev)
+    state.fwd_bwd(cfg, rays, batch["pixels"], ws, randomized=randomized, t_rand=t_rand, u=u, sp_points=sp_points, seed=seed,
+                  grads0_ready=ev)
     scale = 1.0
     if reducer is not None:
         reducer.reduce(state.bucket0, state.bucket1)
     if world_size > 1:
         state.stats.mul_(1.0 / world_size)
         scale = 1.0 / world_size
-    # Adam (train.py:119) and the refresh of the fragment-ordered weight images, one launch
-    ops.adam_pack_step(cfg, state.params, state.m, state.v, state.grads, lr, state.step, state.packed, grad_scale=scale)
+    state.update(cfg, lr, scale)
     state.step += 1
     return state.stats

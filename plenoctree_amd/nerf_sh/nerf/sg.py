@@ -9,11 +9,11 @@ A NeRF-SG is the SH network with 3 * sg_dim + 1 outputs.  For sg_dim in {1, 4, 9
 run for sh_deg = sqrt(sg_dim) - 1, so the model keeps a PxoCfg of that degree and shares packing, pxo_eval_points,
 pxo_grid_sigma and pxo_mean_over_samples with the SH path; only the shading differs (pxo_sg_render_fwd).  Lobes are one
 global set per model (the reference asserts a flag `sg_global` that it defines nowhere).  utils.check_supported keeps
-rejecting sg_dim > 0; nerf_sh.train, nerf_sh.eval, nerf_sh.gen_video and octree.extraction opt in through check_train_flags /
-check_render_flags / check_extraction_flags.
+rejecting sg_dim > 0; what nerf_sh.train, nerf_sh.eval, nerf_sh.gen_video, nerf_sh.gen_mesh and octree.extraction build of such
+a model, and which checkpoints they read, is the SG row of families.py.
 
-Training (train_step below; nerf_sh/nerf/models.py:107-117 puts sg_lambda and sg_mu_spher into the "params" collection, so
-train.py:101-119 differentiates, averages, decays and Adam-updates them like any other leaf): the raw parameters live on the
+Training (models.train_step with the SgState below; nerf_sh/nerf/models.py:107-117 puts sg_lambda and sg_mu_spher into the
+"params" collection, so train.py:101-119 differentiates, averages, decays and Adam-updates them like any other leaf): the raw parameters live on the
 device as one array sg_params [3K] = (sg_lambda [K], sg_mu_spher [K,2]) with their Adam moments; their gradient sits behind
 the two MLPs' in the state's reduce buffer, inside bucket 1, so the gradient exchange needs no collective of its own.
 pxo_sg_train_fwd_bwd derives the lobes from sg_params on the device, the update is pxo_adam_step on the 3K tail and pxo_sg_lobes
@@ -26,6 +26,7 @@ import math
 import numpy as np
 import torch
 
+from ... import ops
 from . import models
 
 SUPPORTED_DIMS = (1, 4, 9, 16, 25)
@@ -116,6 +117,23 @@ class SgState(models.TrainState):
                                 torch.as_tensor(a, dtype=torch.float32).reshape(3 * K).clone().to(dev) for a in (m, v))
         self.lobes = lobes_from_params(sg_lambda, sg_mu_spher).to(dev)
 
+    def train_workspace_bytes(self, cfg, B):
+        return ops.sg_train_workspace_bytes(cfg, B)
+
+    def fwd_bwd(self, cfg, rays, pixels, ws, **kw):
+        """pxo_sg_train_fwd_bwd_bucketed leaves the SG gradient behind the MLPs' in the reduce buffer (inside bucket 1, so the
+        step's reducer averages it with the rest)."""
+        ops.sg_train_fwd_bwd(cfg, self.params, self.sg_params, self.packed, rays.origins, rays.directions, rays.viewdirs, pixels,
+                             self.grads, self.sg_grads, self.stats, ws, **kw)
+
+    def update(self, cfg, lr, grad_scale):
+        """Adam over the two MLPs with the re-pack, Adam over the 3K SG tail at the same learning rate and step (train.py:119)
+        and the refresh of the lobes -- all on the stream; the host copies are stale from here on."""
+        super().update(cfg, lr, grad_scale)
+        ops.adam_step(self.sg_params, self.sg_m, self.sg_v, self.sg_grads, lr, self.step, grad_scale=grad_scale)
+        ops.sg_lobes(self.sg_params, self.sg_dim, self.lobes)
+        self._sg_stale = True
+
     def sg_moments(self):
         """((m of sg_lambda [K], m of sg_mu_spher [K,2]), (v ...)) on the host, for a checkpoint."""
         K = self.sg_dim
@@ -133,7 +151,6 @@ class SgModel(models.NerfModel):
         self.sg_dim = (cfg.sh_deg + 1) ** 2
 
     def apply(self, state, rays, randomized, t_rand=None, u=None, seed=0):
-        from ... import ops
         ws = state.workspace(ops.render_workspace_bytes(self.cfg, rays.origins.shape[0]))
         return ops.render_fwd(self.cfg, state.packed[0][0], state.packed[1][0], rays.origins, rays.directions, rays.viewdirs,
                               randomized=randomized, t_rand=t_rand, u=u, seed=seed, ws=ws, lobes=state.lobes)
@@ -159,68 +176,6 @@ def apply_cli(args, argv=None):
     return args
 
 
-def _unbuilt_flags(args):
-    """Names of the flags of an sg_dim > 0 model that the MI355X path does not build."""
-    bad = []
-    if args.sg_dim <= 0:
-        bad.append(f"sg_dim={args.sg_dim} (an SH model: the plain path)")
-    elif args.sg_dim not in SUPPORTED_DIMS:
-        bad.append(f"sg_dim={args.sg_dim} (need one of {SUPPORTED_DIMS}: the widths of the MLP head and the renderers)")
-    if args.sh_deg != -1:
-        bad.append(f"sh_deg={args.sh_deg} (need -1: you can only use up to one of SH or SG)")
-    if args.use_viewdirs:
-        bad.append("use_viewdirs=true (an SG model has no view-conditioned head)")
-    if (args.net_depth, args.net_width, args.skip_layer) != (8, 256, 4):
-        bad.append("net_depth/net_width/skip_layer != 8/256/4")
-    if (args.min_deg_point, args.max_deg_point) != (0, 10):
-        bad.append("min/max_deg_point != 0/10")
-    if args.num_rgb_channels != 3 or args.num_sigma_channels != 1:
-        bad.append("num_rgb_channels/num_sigma_channels != 3/1")
-    if args.noise_std is not None and args.noise_std < 0:
-        bad.append("noise_std < 0")
-    if getattr(args, "render_path", False) or getattr(args, "spherify", False):
-        bad.append("render_path / spherify (LLFF scenes)")
-    if getattr(args, "dataset", None) == "llff":
-        bad.append("dataset=llff (LLFF scenes: an SG model on a forward-facing scene is not built)")
-    if args.legacy_posenc_order:
-        bad.append("legacy_posenc_order")
-    if (args.net_activation.lower(), args.rgb_activation.lower(), args.sigma_activation.lower()) != ("relu", "sigmoid", "relu"):
-        bad.append("activations other than relu/sigmoid/relu")
-    return bad
-
-
-def check_train_flags(args):
-    """What nerf_sh.train builds of an sg_dim > 0 model; everything else is rejected by name."""
-    bad = _unbuilt_flags(args)
-    if bad:
-        raise NotImplementedError("training a NeRF-SG, not built on the MI355X path: " + "; ".join(bad))
-
-
-def check_render_flags(args):
-    """What nerf_sh.eval / gen_video build of an sg_dim > 0 model; everything else is rejected by name."""
-    bad = _unbuilt_flags(args)
-    if bad:
-        raise NotImplementedError("rendering a NeRF-SG, not built on the MI355X path: " + "; ".join(bad))
-
-
-def check_extraction_flags(args):
-    """What octree.extraction builds of an sg_dim > 0 model; everything else is rejected by name."""
-    bad = _unbuilt_flags(args)
-    if bad:
-        raise NotImplementedError("extraction of an SG PlenOctree, not built on the MI355X path: " + "; ".join(bad))
-
-
-def check_dirs(args, require_data=True, extraction=False, train=False, world_size=1):
-    """utils.check_flags' directory (and, for training, batch-size) checks, then the SG flag check."""
-    if args.train_dir is None:
-        raise ValueError("train_dir must be set. None set now.")
-    if require_data and args.data_dir is None and args.dataset != "synthetic":
-        raise ValueError("data_dir must be set. None set now.")
-    if train and args.batch_size % world_size != 0:
-        raise ValueError("Batch size must be divisible by the number of devices.")
-    (check_train_flags if train else check_extraction_flags if extraction else check_render_flags)(args)
-
-
 def make_cfg(args):
     """PxoCfg of the SH model with the same head width (sh_deg = sqrt(sg_dim) - 1); args is left as it is."""
     import copy
@@ -229,59 +184,12 @@ def make_cfg(args):
     return models.make_cfg(a)
 
 
-def get_model_state(args, device, extraction=False, train=False):
-    """Model + state with freshly initialised parameters (the caller restores a checkpoint)."""
-    (check_train_flags if train else check_extraction_flags if extraction else check_render_flags)(args)
+def get_model_state(args, device, purpose="render"):
+    """Model + state with freshly initialised parameters (the caller restores a checkpoint), after the flag check of the
+    `purpose` they are built for (families.SG)."""
+    from . import families
+    families.check_flags(families.SG, args, purpose)
     cfg = make_cfg(args)
     params = models.init_params(cfg, args.seed).to(device)
     lam, mu = init_lobe_params(args.sg_dim, args.seed)
     return SgModel(cfg), SgState(cfg, params, lam, mu)
-
-
-def restore(args, device, say=print, require_data=True, extraction=False):
-    """The --sg_dim K branch of nerf_sh.eval / gen_video / octree.extraction: flag checks, model + state, newest checkpoint of
-    train_dir in either of the reference's formats (extraction.load_nerf_checkpoint's choice)."""
-    from ...octree.extraction import load_nerf_checkpoint
-    check_dirs(args, require_data, extraction)
-    say(f"* Loading NeRF (SG{args.sg_dim})", flush=True)
-    model, state = get_model_state(args, device, extraction)
-    say(load_nerf_checkpoint(args, state), flush=True)
-    return model, state
-
-
-def get_train_state(args, device):
-    """models.get_model_state for nerf_sh.train with sg_dim > 0: fresh parameters, then the newest flax checkpoint of train_dir
-    if there is one (resume: parameters, SG leaves and all Adam moments)."""
-    from . import checkpoints
-    model, state = get_model_state(args, device, train=True)
-    if args.train_dir:
-        checkpoints.restore_checkpoint(args.train_dir, state)
-    return model, state
-
-
-def train_step(model, state, batch, lr, randomized=True, t_rand=None, u=None, sp_points=None, seed=0, world_size=1,
-               reducer=None):
-    """models.train_step for a NeRF-SG: pxo_sg_train_fwd_bwd_bucketed leaves the SG gradient behind the MLPs' in the reduce
-    buffer (inside bucket 1, so `reducer` averages it with the rest), then Adam over the two MLPs with the re-pack, Adam over
-    the 3K SG tail at the same learning rate and step (train.py:119) and the refresh of state.lobes -- all on the stream."""
-    from ... import ops
-    cfg = model.cfg
-    rays = batch["rays"]
-    B = rays.origins.shape[0]
-    ws = state.workspace(ops.sg_train_workspace_bytes(cfg, B))
-    ev = reducer.ready_event() if reducer is not None else None
-    ops.sg_train_fwd_bwd(cfg, state.params, state.sg_params, state.packed, rays.origins, rays.directions, rays.viewdirs,
-                         batch["pixels"], state.grads, state.sg_grads, state.stats, ws, randomized=randomized, t_rand=t_rand, u=u,
-                         sp_points=sp_points, seed=seed, grads0_ready=ev)
-    scale = 1.0
-    if reducer is not None:
-        reducer.reduce(state.bucket0, state.bucket1)
-    if world_size > 1:
-        state.stats.mul_(1.0 / world_size)
-        scale = 1.0 / world_size
-    ops.adam_pack_step(cfg, state.params, state.m, state.v, state.grads, lr, state.step, state.packed, grad_scale=scale)
-    ops.adam_step(state.sg_params, state.sg_m, state.sg_v, state.sg_grads, lr, state.step, grad_scale=scale)
-    ops.sg_lobes(state.sg_params, state.sg_dim, state.lobes)
-    state._sg_stale = True
-    state.step += 1
-    return state.stats

@@ -138,40 +138,53 @@ def update_flags(args):
     vars(args).update(configs)
 
 
-def check_flags(args, require_data=True, require_batch_size_div=False, world_size=1):
-    """utils.py:247-253, plus the restrictions of the MI355X path."""
+def check_dirs(args, require_data=True, require_batch_size_div=False, world_size=1):
+    """utils.py:247-253: the directory and batch-size checks every entry point starts with."""
     if args.train_dir is None:
         raise ValueError("train_dir must be set. None set now.")
     if require_data and args.data_dir is None and args.dataset != "synthetic":
         raise ValueError("data_dir must be set. None set now.")
     if require_batch_size_div and args.batch_size % world_size != 0:
         raise ValueError("Batch size must be divisible by the number of devices.")
+
+
+def check_flags(args, require_data=True, require_batch_size_div=False, world_size=1):
+    """utils.py:247-253, plus the restrictions of the MI355X path."""
+    check_dirs(args, require_data, require_batch_size_div, world_size)
     check_supported(args)
 
 
+# What no model family of the MI355X path builds, each clause written once: name -> (args -> its words, or nothing where the flag
+# is fine).  families.py lists, per family, these names among the clauses of its own, in the order its message names them.
+COMMON_CLAUSES = {
+    "trunk": lambda a: (a.net_depth, a.net_width, a.skip_layer) != (8, 256, 4) and "net_depth/net_width/skip_layer != 8/256/4",
+    "posenc": lambda a: (a.min_deg_point, a.max_deg_point) != (0, 10) and "min/max_deg_point != 0/10",
+    "channels": lambda a: (a.num_rgb_channels != 3 or a.num_sigma_channels != 1) and "num_rgb_channels/num_sigma_channels != 3/1",
+    "legacy_posenc_order": lambda a: a.legacy_posenc_order and "legacy_posenc_order",
+    "activations": lambda a: ((a.net_activation.lower(), a.rgb_activation.lower(), a.sigma_activation.lower())
+                              != ("relu", "sigmoid", "relu")) and "activations other than relu/sigmoid/relu",
+    "noise_std": lambda a: a.noise_std is not None and a.noise_std < 0 and "noise_std < 0",
+    "render_path": lambda a: ((getattr(a, "render_path", False) or getattr(a, "spherify", False))
+                              and "render_path / spherify (LLFF scenes)"),
+}
+
+
+def llff_clause(what):
+    """The clause of a family that is not built on forward-facing scenes; `what` names it in the sentence."""
+    return lambda a: (getattr(a, "dataset", None) == "llff"
+                      and f"dataset=llff (LLFF scenes: {what} on a forward-facing scene is not built)")
+
+
+def unbuilt_flags(args, clauses):
+    """What `args` asks for that `clauses` -- names in COMMON_CLAUSES, or functions like its values -- reject, in their order."""
+    found = ((COMMON_CLAUSES[c] if isinstance(c, str) else c)(args) for c in clauses)
+    return [words for words in found if words]
+
+
 def check_supported(args):
-    """The HIP path builds the SH configurations of config/blender.yaml, config/tt.yaml and config/llff.yaml."""
-    bad = []
-    if args.use_viewdirs:
-        bad.append("use_viewdirs=true (vanilla NeRF head)")
-    if args.sh_deg < 0 or args.sh_deg > 4:
-        bad.append(f"sh_deg={args.sh_deg} (need 0..4)")
-    if args.sg_dim > 0:
-        bad.append("sg_dim>0 (spherical gaussians)")
-    if (args.net_depth, args.net_width, args.skip_layer) != (8, 256, 4):
-        bad.append("net_depth/net_width/skip_layer != 8/256/4")
-    if (args.min_deg_point, args.max_deg_point) != (0, 10):
-        bad.append("min/max_deg_point != 0/10")
-    if args.noise_std is not None and args.noise_std < 0:
-        bad.append("noise_std < 0")
-    if (getattr(args, "render_path", False) or getattr(args, "spherify", False)) and args.dataset != "llff":
-        bad.append("render_path / spherify (LLFF scenes)")
-    if args.legacy_posenc_order:
-        bad.append("legacy_posenc_order")
-    if (args.net_activation.lower(), args.rgb_activation.lower(), args.sigma_activation.lower()) != ("relu", "sigmoid", "relu"):
-        bad.append("activations other than relu/sigmoid/relu")
-    if bad:
-        raise NotImplementedError("not built on the MI355X path: " + "; ".join(bad))
+    """The HIP path builds the SH configurations of config/blender.yaml, config/tt.yaml and config/llff.yaml (families.SH)."""
+    from . import families
+    families.check_flags(families.SH, args)
 
 
 def learning_rate_decay(step, lr_init, lr_final, max_steps, lr_delay_steps=0, lr_delay_mult=1):

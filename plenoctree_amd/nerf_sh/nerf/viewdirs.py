@@ -4,19 +4,20 @@ Host-side mirror of the torch twin with use_viewdirs=True (octree/nerf/models.py
 net_depth_condition 1, net_width_condition 128, deg_view 4): per MLP twelve dense layers in flax key order -- Dense_0..7 trunk,
 Dense_8 sigma, Dense_9 bottleneck, Dense_10 condition, Dense_11 rgb -- in one flat float32 arena (MLP_0 then MLP_1).  All
 arithmetic is done by libplenoctree_hip.so (csrc/viewdirs_kernels.hip) through plenoctree_amd.ops.  Training with this head is
-not built: nerf_sh.train keeps rejecting use_viewdirs=true (utils.check_supported); nerf_sh.eval and nerf_sh.gen_video opt in
-through check_render_flags.
+not built: nerf_sh.train keeps rejecting use_viewdirs=true (utils.check_supported); what nerf_sh.eval, nerf_sh.gen_video and
+octree.extraction build of such a model, and which checkpoints they read, is the view-conditioned row of families.py.
 """
 import math
 
 import torch
 
 from ... import ops
+from . import models
 
 DIRECTION_STREAM = 16        # Philox stream id of the projection's direction draw (0..4: the train step's draws)
 
 
-class ViewdirsState:
+class ViewdirsState(models.Workspace):
     """Parameters of the two MLPs and the images the kernels stream.  `packed[i][0]` starts with the forward image of an SH model
     of degree 0 (trunk + Dense_8), so the sigma-only consumers of a TrainState (extraction.grid_sigma) take this state as it is."""
 
@@ -25,7 +26,6 @@ class ViewdirsState:
         self.step = 0                # no optimiser state is restored: what eval names its per-step summary files with
         self.n_mlp = params.numel() // 2
         self.packed = [None, None]
-        self._ws = None
         self.repack()
 
     def mlp_params(self, i):
@@ -35,12 +35,6 @@ class ViewdirsState:
         for i in range(2):
             img = self.packed[i][0] if self.packed[i] is not None else None
             self.packed[i] = (ops.vd_pack_weights(self.mlp_params(i), img), None)
-
-    def workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.params.device)
-        return self._ws
 
 
 class ViewdirsModel:
@@ -88,102 +82,17 @@ class ViewdirsModel:
 
 def init_params(seed=20200823):
     """Glorot-uniform kernels, zero biases, host RNG (as nerf.models.init_params)."""
-    from .models import glorot_uniform_
-    leaves, n = ops.vd_param_layout()
-    flat = torch.zeros(2 * n, dtype=torch.float32)
-    gen = torch.Generator().manual_seed(seed)
-    for mi in range(2):
-        for layer, is_bias, off, rows, cols in leaves:
-            if not is_bias:
-                glorot_uniform_(flat[mi * n + off: mi * n + off + rows * cols].view(rows, cols), rows, cols, gen)
-    return flat
+    return models.glorot_arena(*ops.vd_param_layout(), seed)
 
 
-def _unbuilt_flags(args, projection):
-    """Names of the flags of a use_viewdirs=true model that the MI355X path does not build; `projection`: the clauses of the
-    SH projection (sh_deg, projection_samples) too."""
-    bad = []
-    if not args.use_viewdirs:
-        bad.append("use_viewdirs=false (an SH model: the plain path)")
-    if args.net_depth_condition != 1:
-        bad.append(f"net_depth_condition={args.net_depth_condition} (need 1)")
-    if args.net_width_condition != 128:
-        bad.append(f"net_width_condition={args.net_width_condition} (need 128)")
-    if args.deg_view != 4:
-        bad.append(f"deg_view={args.deg_view} (need 4)")
-    if projection and (args.sh_deg < 0 or args.sh_deg > 4):
-        bad.append(f"sh_deg={args.sh_deg} (the projection needs 0..4)")
-    if args.sg_dim > 0:
-        bad.append("sg_dim>0 (spherical gaussians)")
-    if args.legacy_posenc_order:
-        bad.append("legacy_posenc_order")
-    if (args.net_depth, args.net_width, args.skip_layer) != (8, 256, 4):
-        bad.append("net_depth/net_width/skip_layer != 8/256/4")
-    if (args.min_deg_point, args.max_deg_point) != (0, 10):
-        bad.append("min/max_deg_point != 0/10")
-    if args.num_rgb_channels != 3 or args.num_sigma_channels != 1:
-        bad.append("num_rgb_channels/num_sigma_channels != 3/1")
-    if getattr(args, "mlp_precision", "f32") != "f32":
-        bad.append(f"mlp_precision={args.mlp_precision} (the view-conditioned head is float32 only)")
-    if projection and getattr(args, "projection_samples", 1) < 1:
-        bad.append(f"projection_samples={args.projection_samples} (need >= 1)")
-    if getattr(args, "render_path", False) or getattr(args, "spherify", False):
-        bad.append("render_path / spherify (LLFF scenes)")
-    if getattr(args, "dataset", None) == "llff":
-        bad.append("dataset=llff (LLFF scenes: the view-conditioned head on a forward-facing scene is not built)")
-    if (args.net_activation.lower(), args.sigma_activation.lower()) != ("relu", "relu"):
-        bad.append("activations other than relu")
-    return bad
-
-
-def check_extraction_flags(args):
-    """What octree.extraction builds of a use_viewdirs=true model; everything else is rejected by name."""
-    bad = _unbuilt_flags(args, projection=True)
-    if bad:
-        raise NotImplementedError("SH projection of a view-dependent NeRF, not built on the MI355X path: " + "; ".join(bad))
-
-
-def check_render_flags(args):
-    """What nerf_sh.eval / gen_video build of a use_viewdirs=true model: check_extraction_flags without the projection's
-    clauses (the reference's rendering presets say sh_deg: -1), plus what the renderer itself reads."""
-    bad = _unbuilt_flags(args, projection=False)
-    if args.rgb_activation.lower() != "sigmoid":
-        bad.append("rgb_activation other than sigmoid")
-    if args.noise_std is not None and args.noise_std < 0:
-        bad.append("noise_std < 0")
-    if bad:
-        raise NotImplementedError("rendering a view-dependent NeRF, not built on the MI355X path: " + "; ".join(bad))
-
-
-def check_render_dirs(args, require_data=True):
-    """Flag check of the --use_viewdirs true branch of nerf_sh.eval / gen_video: utils.check_flags' directory checks, then
-    check_render_flags."""
-    if args.train_dir is None:
-        raise ValueError("train_dir must be set. None set now.")
-    if require_data and args.data_dir is None and args.dataset != "synthetic":
-        raise ValueError("data_dir must be set. None set now.")
-    check_render_flags(args)
-
-
-def get_model_state(args, device, render=False):
-    """Model + state with freshly initialised parameters (the caller restores a checkpoint).  render: the flag check of the ray
-    renderer instead of the projection's."""
-    (check_render_flags if render else check_extraction_flags)(args)
+def get_model_state(args, device, purpose="extract"):
+    """Model + state with freshly initialised parameters (the caller restores a checkpoint), after the flag check of the
+    `purpose` they are built for (families.VIEWDIRS): the SH projection's, or the ray renderer's."""
+    from . import families
+    families.check_flags(families.VIEWDIRS, args, purpose)
     model = ViewdirsModel(args.num_coarse_samples, args.num_fine_samples, near=args.near, far=args.far,
                           white_bkgd=args.white_bkgd, lindisp=args.lindisp, noise_std=args.noise_std)
     return model, ViewdirsState(init_params(args.seed).to(device))
-
-
-def restore_for_render(args, device, say=print, require_data=True):
-    """The --use_viewdirs true branch of nerf_sh.eval / gen_video, as octree.extraction's: flag checks, model + state, newest
-    checkpoint of train_dir (`*.ckpt` torch state dict, or flax msgpack with --is_jaxnerf_ckpt)."""
-    from . import checkpoints
-    check_render_dirs(args, require_data)
-    say("* Loading NeRF (view-conditioned head)", flush=True)
-    model, state = get_model_state(args, device, render=True)
-    say(checkpoints.restore_viewdirs_checkpoint(args.train_dir, state, bool(getattr(args, "is_jaxnerf_ckpt", False)),
-                                                bool(getattr(args, "trust_ckpt_pickle", False))), flush=True)
-    return model, state
 
 
 def add_checkpoint_flags(parser):

@@ -10,24 +10,15 @@ import numpy as np
 import torch
 
 from .. import dist
-from .nerf import checkpoints, llff, models, sg, utils
+from .nerf import checkpoints, families, llff, models, sg, utils
 
 
 def main(argv=None):
     args = utils.define_flags().parse_args(argv)
     utils.update_flags(args)
     sg.apply_cli(args, argv)                     # --sg_dim K --sh_deg -1 on the command line win over the preset's sh_deg
-    if not torch.cuda.is_available():
-        raise SystemExit("nerf_sh.train needs a ROCm GPU; the HIP path has no CPU fallback")
-    comm = dist.init_from_env()
-    torch.cuda.set_device(comm.local_rank)
-    device = torch.device("cuda", comm.local_rank)
-    if args.sg_dim > 0:
-        # a NeRF-SG (--sg_dim K --sh_deg -1) opts in with its own check, like eval and extraction do; the generic check_flags
-        # keeps rejecting sg_dim > 0
-        sg.check_dirs(args, train=True, world_size=comm.world)
-    else:
-        utils.check_flags(args, require_batch_size_div=True, world_size=comm.world)
+    comm, device, _ = dist.open_cli("nerf_sh.train")
+    families.check(args, "train", world_size=comm.world)
     if args.mlp_precision == "bf16x3":
         raise ValueError("--mlp_precision bf16x3 is an inference option (eval / gen_video / extraction); training runs in float32 "
                          "or in its float32-accurate emulation bf16x6")
@@ -56,15 +47,10 @@ def main(argv=None):
         # every rank its own host (np.random.seed(20201473 + jax.host_id()), train.py:128): its own image, its own pixels
         dataset = llff.get_dataset("train", args, device, batch_size=per_rank, seed=20201473 + comm.rank)
     test_dataset = llff.get_dataset("test", args, device)
-    if args.sg_dim > 0:
-        model, state = sg.get_train_state(args, device)
-        train_step = sg.train_step
-    else:
-        model, state = models.get_model_state(args, device, restore=True)
-        train_step = models.train_step
+    model, state = families.restore(args, device, "train")
     init_step = state.step + 1                                       # train.py:176
     if h0:
-        print(f"* {2 * state.n_mlp + (3 * args.sg_dim if args.sg_dim > 0 else 0)} parameters, resuming at step {init_step}, {comm.world} GPU(s), "
+        print(f"* {families.select(args).n_params(args, state)} parameters, resuming at step {init_step}, {comm.world} GPU(s), "
               f"{per_rank} rays/GPU", flush=True)
 
     reducer = dist.GradReducer(comm, device)
@@ -83,8 +69,8 @@ def main(argv=None):
         batch = next(dataset)
         lr = utils.learning_rate_decay(step, args.lr_init, args.lr_final, args.max_steps, args.lr_delay_steps,
                                        args.lr_delay_mult)
-        train_step(model, state, batch, lr, randomized=args.randomized, seed=(step << 8) | comm.rank,
-                   world_size=comm.world, reducer=reducer)
+        models.train_step(model, state, batch, lr, randomized=args.randomized, seed=(step << 8) | comm.rank,
+                          world_size=comm.world, reducer=reducer)
         stats_acc.add_(state.stats)
         acc_steps += 1
         if step % args.print_every == 0:                            # train.py:208-236

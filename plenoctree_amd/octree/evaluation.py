@@ -15,7 +15,6 @@ import os
 import sys
 
 import numpy as np
-import torch
 
 from .. import dist
 from ..nerf_sh.nerf import llff, utils
@@ -97,11 +96,7 @@ def main(argv=None):
     want_aux = args.write_aux is not None or args.write_points is not None
     if want_aux and args.points_stride < 1:
         raise ValueError(f"--points_stride {args.points_stride}: must be >= 1")
-    if not torch.cuda.is_available():
-        raise SystemExit("octree.evaluation needs a ROCm GPU; the HIP path has no CPU fallback")
-    comm = dist.init_from_env()
-    torch.cuda.set_device(comm.local_rank)
-    device = torch.device("cuda", comm.local_rank)
+    comm, device, _ = dist.open_cli("octree.evaluation")
     dataset = llff.get_dataset("test", args, device)
     if comm.rank == 0:
         print("N3Tree load", args.input, flush=True)

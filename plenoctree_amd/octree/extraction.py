@@ -26,7 +26,7 @@ import torch
 
 from .. import dist, ops
 from .. import octree_ops as oops
-from ..nerf_sh.nerf import llff, models, utils
+from ..nerf_sh.nerf import families, llff, sg, utils
 from .svox import N3Tree, NDCConfig, VolumeRenderer
 
 
@@ -325,72 +325,20 @@ def define_flags():
     return p
 
 
-def load_nerf_checkpoint(args, state):
-    """get_model_state(args, restore=True) of octree/nerf/models.py:38-49.  The reference reads one of two formats, chosen by
-    --is_jaxnerf_ckpt (:45): a flax-msgpack `checkpoint_<step>` of nerf_sh.train (restore_model_state_from_jaxnerf, :66-113) or
-    a torch state dict `*.ckpt` of its torch twin (restore_model_state, :52-63).  Both are read here.  Where the reference, with
-    no file of the chosen format in train_dir, silently goes on with the freshly initialised network, this raises -- except that
-    without the flag a train_dir holding only flax checkpoints (what nerf_sh.train here and the reference's JAX trainer write)
-    is read as such, and said so."""
-    from ..nerf_sh.nerf import checkpoints
-    if args.is_jaxnerf_ckpt:
-        path = checkpoints.restore_checkpoint(args.train_dir, state)
-        if path is None:
-            raise FileNotFoundError(f"--is_jaxnerf_ckpt: no flax checkpoint_<step> in {args.train_dir}")
-        return f"* restore ckpt from {path} (flax msgpack)"
-    path = checkpoints.restore_torch_checkpoint(args.train_dir, state, trust_pickle=bool(getattr(args, "trust_ckpt_pickle", False)))
-    if path is not None:
-        return f"* restore ckpt from {path}. (torch state dict)"
-    path = checkpoints.restore_checkpoint(args.train_dir, state)
-    if path is None:
-        raise FileNotFoundError(f"no *.ckpt (torch state dict) and no checkpoint_<step> (flax msgpack) in {args.train_dir}: "
-                                "nothing to extract from")
-    return f"* no *.ckpt in {args.train_dir}: restore ckpt from {path} (flax msgpack, as with --is_jaxnerf_ckpt)"
-
-
-def check_viewdirs_flags(args):
-    """Flag check of the --use_viewdirs true path: utils.check_flags' directory checks, then what the projection builds."""
-    from ..nerf_sh.nerf import viewdirs
-    if args.train_dir is None:
-        raise ValueError("train_dir must be set. None set now.")
-    if args.data_dir is None and args.dataset != "synthetic":
-        raise ValueError("data_dir must be set. None set now.")
-    viewdirs.check_extraction_flags(args)
+load_nerf_checkpoint = families.load_nerf_checkpoint      # the name scripts and tests know it by
 
 
 def main(argv=None, record_projection=False):
     """record_projection: keep the run's direction set and step-2 sample points on the returned tree (`projection_record`)."""
     args = define_flags().parse_args(argv)
     utils.update_flags(args)
-    from ..nerf_sh.nerf import sg
     sg.apply_cli(args, argv)                 # --sg_dim K --sh_deg -1 on the command line win over the preset's sh_deg
     args._record_projection = bool(record_projection)
     check_octree_flags(args, "octree.extraction")
-    if not torch.cuda.is_available():
-        raise SystemExit("octree.extraction needs a ROCm GPU; the HIP path has no CPU fallback")
-    comm = dist.init_from_env()
-    torch.cuda.set_device(comm.local_rank)
-    device = torch.device("cuda", comm.local_rank)
-    say = print if comm.rank == 0 else (lambda *a, **k: None)
-    dirs = None
-    if args.use_viewdirs:
-        # a view-dependent ("vanilla") NeRF: extraction opts in explicitly (training / rendering with this head are not built,
-        # so the generic check_flags keeps rejecting it) and projects its radiance onto SH of degree --sh_deg (:362-375)
-        from ..nerf_sh.nerf import checkpoints, viewdirs
-        check_viewdirs_flags(args)
-        say("* Loading NeRF (view-conditioned head)", flush=True)
-        model, state = viewdirs.get_model_state(args, device)
-        say(checkpoints.restore_viewdirs_checkpoint(args.train_dir, state, bool(args.is_jaxnerf_ckpt),
-                                                    bool(getattr(args, "trust_ckpt_pickle", False))), flush=True)
-        dirs = viewdirs.draw_directions(args.seed, args.projection_samples, device)
-    elif args.sg_dim > 0:
-        # a NeRF-SG (:436-442, :481-499): the SH steps with the head width of sg_dim, the tree takes the lobes as extra_data
-        model, state = sg.restore(args, device, say=say, extraction=True)
-    else:
-        utils.check_flags(args, require_data=True, world_size=comm.world)
-        say("* Loading NeRF", flush=True)
-        model, state = models.get_model_state(args, device, restore=False)
-        say(load_nerf_checkpoint(args, state), flush=True)
+    comm, device, say = dist.open_cli("octree.extraction")
+    family = families.select(args)
+    model, state = families.restore(args, device, "extract", say=say)
+    dirs = family.projection(args, device) if family.projection else None
     dataset = llff.get_dataset("train", args, device)      # `llff` is built there, every other name by the plain table
     if args.bbox_from_data:                                  # :447-451 (NSVF datasets carry bbox.txt)
         bbox = getattr(dataset, "bbox", None)
@@ -409,13 +357,9 @@ def main(argv=None, record_projection=False):
     radius = [r * args.bbox_scale for r in radius]
     if args.bbox_cube:
         radius = [max(radius)] * 3
-    basis_dim = args.sg_dim if args.sg_dim > 0 else (args.sh_deg + 1) ** 2
+    data_format, basis_dim, extra_data = family.tree(args, state)
     data_dim = 1 + args.num_rgb_channels * basis_dim
     say("data dim is", data_dim, flush=True)
-    if args.sg_dim > 0:
-        data_format, extra_data = f"SG{args.sg_dim}", state.lobes            # :437-442
-    else:
-        data_format, extra_data = f"SH{basis_dim}", None
     tree = N3Tree(N=args.tree_branch_n, data_dim=data_dim, init_refine=0, depth_limit=args.init_grid_depth,
                   radius=radius, center=center, data_format=data_format, extra_data=extra_data, map_location=device)
     reso = 2 ** (args.init_grid_depth + 1)

@@ -157,13 +157,8 @@ def main(argv=None):
     args = define_flags().parse_args(argv)
     utils.update_flags(args)
     extraction.check_octree_flags(args, "octree.optimization")
-    if not torch.cuda.is_available():
-        raise SystemExit("octree.optimization needs a ROCm GPU; the HIP path has no CPU fallback")
-    comm = dist.init_from_env()
-    torch.cuda.set_device(comm.local_rank)
-    device = torch.device("cuda", comm.local_rank)
+    comm, device, say = dist.open_cli("octree.optimization")
     torch.manual_seed(20200823)
-    say = print if comm.rank == 0 else (lambda *a, **k: None)
 
     def get_data(stage):
         ds = llff.get_dataset(stage, args, device)

@@ -155,3 +155,121 @@ def test_torch_state_dict_checkpoint_of_the_reference_twin(tmp_path, golden_dir)
     # a view-conditioned twin is rejected, not half-loaded
     with pytest.raises(ValueError, match="view-conditioned"):
         checkpoints.torch_state_dict_to_tree({"MLP_0.bottleneck_layer.weight": torch.zeros(1)})
+
+
+# ---- which checkpoint each family reads for which purpose (families.py) -------------------------------------------------------
+# What the loaders did before the policy became one table, recorded once by running them -- models.get_model_state's and
+# sg.get_train_state's restore_checkpoint, extraction.load_nerf_checkpoint, checkpoints.restore_viewdirs_checkpoint, as
+# train / eval / gen_video / gen_mesh / extraction called them -- on these directory contents: (content of train_dir,
+# --is_jaxnerf_ckpt) -> (the file that was read or "fresh", what was said) or ("raises", type, text); <dir> is train_dir.
+POLICY_OUTCOMES = {
+    "resume": {
+        ("ckpt", False): ("fresh", []), ("ckpt", True): ("fresh", []),
+        ("flax", False): ("flax", []), ("flax", True): ("flax", []),
+        ("both", False): ("flax", []), ("both", True): ("flax", []),
+        ("neither", False): ("fresh", []), ("neither", True): ("fresh", []),
+    },
+    "either": {
+        ("ckpt", False): ("torch", ["* restore ckpt from <dir>/model.ckpt. (torch state dict)"]),
+        ("ckpt", True): ("raises", "FileNotFoundError", "--is_jaxnerf_ckpt: no flax checkpoint_<step> in <dir>"),
+        ("flax", False): ("flax", ["* no *.ckpt in <dir>: restore ckpt from <dir>/checkpoint_5 (flax msgpack, as with "
+                                   "--is_jaxnerf_ckpt)"]),
+        ("flax", True): ("flax", ["* restore ckpt from <dir>/checkpoint_5 (flax msgpack)"]),
+        ("both", False): ("torch", ["* restore ckpt from <dir>/model.ckpt. (torch state dict)"]),
+        ("both", True): ("flax", ["* restore ckpt from <dir>/checkpoint_5 (flax msgpack)"]),
+        ("neither", False): ("raises", "FileNotFoundError", "no *.ckpt (torch state dict) and no checkpoint_<step> (flax msgpack) "
+                                                            "in <dir>: nothing to extract from"),
+        ("neither", True): ("raises", "FileNotFoundError", "--is_jaxnerf_ckpt: no flax checkpoint_<step> in <dir>"),
+    },
+    "either, view-conditioned": {
+        ("ckpt", False): ("torch", ["* restore ckpt from <dir>/model.ckpt (torch state dict, view-conditioned head)"]),
+        ("ckpt", True): ("raises", "FileNotFoundError", "no *.ckpt (torch state dict) and no checkpoint_<step> (flax msgpack) in "
+                                                        "<dir>"),
+        ("flax", False): ("flax", ["* restore ckpt from <dir>/checkpoint_5 (flax msgpack, view-conditioned head)"]),
+        ("flax", True): ("flax", ["* restore ckpt from <dir>/checkpoint_5 (flax msgpack, view-conditioned head)"]),
+        ("both", False): ("torch", ["* restore ckpt from <dir>/model.ckpt (torch state dict, view-conditioned head)"]),
+        ("both", True): ("flax", ["* restore ckpt from <dir>/checkpoint_5 (flax msgpack, view-conditioned head)"]),
+        ("neither", False): ("raises", "FileNotFoundError", "no *.ckpt (torch state dict) and no checkpoint_<step> (flax msgpack) "
+                                                            "in <dir>"),
+        ("neither", True): ("raises", "FileNotFoundError", "no *.ckpt (torch state dict) and no checkpoint_<step> (flax msgpack) "
+                                                           "in <dir>"),
+    },
+}
+POLICY_OF = {("sh", "train"): "resume", ("sh", "render"): "resume", ("sh", "mesh"): "resume", ("sh", "extract"): "either",
+             ("sg", "train"): "resume", ("sg", "render"): "either", ("sg", "mesh"): "either", ("sg", "extract"): "either",
+             ("viewdirs", "render"): "either, view-conditioned", ("viewdirs", "extract"): "either, view-conditioned"}
+CONTENTS = {"ckpt": ("torch",), "flax": ("flax",), "both": ("torch", "flax"), "neither": ()}
+
+
+def _fresh_state(family):
+    """A state of the family with all-zero parameters and no GPU kernels behind it."""
+    from plenoctree_amd import ops
+    from plenoctree_amd.nerf_sh.nerf import sg
+    if family == "viewdirs":
+        return types.SimpleNamespace(params=torch.zeros(2 * ops.vd_param_layout()[1]), repack=lambda: None)
+    cfg = _lib.make_cfg(sh_deg=1)
+    n = ops.param_layout(cfg)[1]
+    if family == "sh":
+        return _State(cfg, torch.zeros(2 * n))
+    st = object.__new__(sg.SgState)
+    st.cfg, st.params, st.step = cfg, torch.zeros(2 * n), 0
+    st.m, st.v = torch.zeros(2 * n), torch.zeros(2 * n)
+    st.repack = lambda *a, **k: None
+    st.set_lobe_params(torch.ones(4), torch.ones(4, 2))
+    return st
+
+
+@pytest.fixture(scope="module")
+def policy_dirs(tmp_path_factory):
+    """family -> content -> train_dir: the flax file holds parameters that are all 1, the torch file all 2."""
+    root = tmp_path_factory.mktemp("policy")
+    out = {}
+    for family in ("sh", "sg", "viewdirs"):
+        for content, kinds in CONTENTS.items():
+            d = root / family / content
+            d.mkdir(parents=True)
+            for kind in kinds:
+                st = _fresh_state(family)
+                st.params += {"flax": 1.0, "torch": 2.0}[kind]
+                if family == "viewdirs" and kind == "flax":
+                    tree = checkpoints.vd_arena_to_tree(st.params.numpy())
+                    (d / "checkpoint_5").write_bytes(checkpoints.msgpack_serialize({"optimizer": {"target": {"params": tree}}}))
+                elif family == "viewdirs":
+                    torch.save({"model": checkpoints.vd_state_dict_from_arena(st.params.numpy())}, str(d / "model.ckpt"))
+                elif kind == "flax":
+                    checkpoints.save_checkpoint(str(d), st, 5)
+                else:
+                    torch.save({"model": checkpoints.torch_state_dict_from_state(st)}, str(d / "model.ckpt"))
+            out[family, content] = str(d)
+    return out
+
+
+@pytest.mark.parametrize("family,purpose", sorted(POLICY_OF))
+def test_each_family_reads_for_each_purpose_what_it_read_before(policy_dirs, family, purpose):
+    from plenoctree_amd.nerf_sh.nerf import families
+    fam = {f.name: f for f in families.FAMILIES}[family]
+    assert {(f.name, p) for f in families.FAMILIES for p in f.checkpoint} == set(POLICY_OF)
+    expected = POLICY_OUTCOMES[POLICY_OF[family, purpose]]
+    policy = fam.checkpoint[purpose]
+    for (content, jax), want in expected.items():
+        d = policy_dirs[family, content]
+        args = types.SimpleNamespace(train_dir=d, is_jaxnerf_ckpt=jax, trust_ckpt_pickle=False)
+        st, said = _fresh_state(family), []
+        try:
+            families.load_checkpoint(fam, purpose, args, st, say=lambda *a, **k: said.append(" ".join(map(str, a))))
+            value = float(st.params[0])
+            assert bool((st.params == value).all())
+            got = ({0.0: "fresh", 1.0: "flax", 2.0: "torch"}[value], [s.replace(d, "<dir>") for s in said])
+        except FileNotFoundError as e:
+            assert not st.params.any() and not said
+            got = ("raises", type(e).__name__, str(e).replace(d, "<dir>"))
+        assert got == want, (content, jax)
+    # the table's own words agree with what it does: a policy that goes on with a fresh network says nothing, ever; one that
+    # raises reads both formats and always says what it read
+    absent = {want[0] for (content, _), want in expected.items() if content == "neither"}
+    assert absent == {"fresh" if policy.absent == "fresh" else "raises"}
+    assert (expected["ckpt", False][0] == "torch") == ("torch" in policy.formats) and "flax" in policy.formats
+    assert all((want[0] == "raises" or bool(want[1])) == (policy.absent == "raises") for want in expected.values())
+    if family == "sh" and purpose == "extract":
+        from plenoctree_amd.octree import extraction
+        assert extraction.load_nerf_checkpoint is policy.load

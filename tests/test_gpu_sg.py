@@ -251,7 +251,7 @@ def test_sg_pipeline_end_to_end(tmp_path):
     the SG basis (<= 1/K) weighs the leaf-averaged coefficients no more than the SH basis does; a dispatch that shades an SG
     tree with SH (or the reverse) changes the image by > 0.1 and falls far below."""
     dev = _gpu()
-    from plenoctree_amd.nerf_sh.nerf import checkpoints, datasets, models, sg, utils
+    from plenoctree_amd.nerf_sh.nerf import checkpoints, datasets, families, models, sg, utils
     from plenoctree_amd.octree import evaluation, extraction, optimization, svox
     fx = G.fixture()
     flat = make_params(O.Cfg(sh_deg=4), seed=11, bias_scale=0.2)
@@ -305,7 +305,7 @@ def test_sg_pipeline_end_to_end(tmp_path):
         # chunk boundaries reuse stream ids per `first`, so compare the first chunk only (as the SH pipeline test does)
         close("SG leaf data", tree.max_depth_data()[: 64 * 8], want[: 64 * 8], rtol=1e-5, atol=1e-6)
         # the flax file is read back by the CLI's own restore (both SG keys), and the evaluation CLI scores the tree
-        _, again = sg.restore(args, dev, say=lambda *a, **k: None, extraction=True)
+        _, again = families.restore(args, dev, "extract", say=lambda *a, **k: None)
         assert torch.equal(again.lobes, state.lobes) and torch.equal(again.params, state.params)
         ev = evaluation.main(common + ["--input", out, "--renderer_step_size", "1e-3"])
         assert np.isfinite(ev)

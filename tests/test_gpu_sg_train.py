@@ -1,6 +1,6 @@
 """-m gpu tests of NeRF-SG training (sg_dim > 0 on the HIP path): the fused shading kernel with the lobe gradient against the
 float64 twin (tests/_sg_train_oracle.py), pxo_sg_lobes against the host expression, the whole step against the reference's own
-train_step with the SG leaves (G1-SG: tests/golden/sg_train_grad.npz), the update wiring of sg.train_step, resume from a
+train_step with the SG leaves (G1-SG: tests/golden/sg_train_grad.npz), the update wiring of models.train_step on an SgState, resume from a
 checkpoint, nerf_sh.train end to end with eval and extraction on its checkpoint, and two ranks sharing the GPU."""
 import os
 import socket
@@ -324,18 +324,18 @@ def _fixture_state(ops, dev, prec=0):
 
 
 def test_train_step_moves_the_sg_parameters_and_refreshes_the_lobes():
-    """One sg.train_step from zero moments is Adam's first step: m_hat = g, v_hat = g^2, so every SG parameter moves by
-    lr g / (|g| + 1e-8) -- lr against the sign of its gradient, to the eps of the denominator (1 % at |g| = 1e-6, which is why
+    """One models.train_step on an SgState from zero moments is Adam's first step: m_hat = g, v_hat = g^2, so every SG parameter
+    moves by lr g / (|g| + 1e-8) -- lr against the sign of its gradient, to the eps of the denominator (1 % at |g| = 1e-6, which is why
     the expected move is written with it) -- checked to rtol 1e-3 wherever |g| > 1e-6; lr = 1e-2 keeps the float32 spacing of the
     parameters (<= 4.8e-7) below that tolerance.  Afterwards the device lobes are pxo_sg_lobes of the new parameters, and the
     host copies behind state.sg_lambda / sg_mu_spher are read back on demand."""
     ops = _ops(); dev = _gpu()
-    from plenoctree_amd.nerf_sh.nerf import sg
+    from plenoctree_amd.nerf_sh.nerf import models, sg
     model, state, batch, kw, sgp = _fixture_state(ops, dev)
     K, lr = state.sg_dim, 1e-2
     before, lobes_before = state.sg_params.clone(), state.lobes.clone()
     assert torch.equal(before.cpu(), sgp) and not state.sg_m.any() and not state.sg_v.any()
-    sg.train_step(model, state, batch, lr, **kw)
+    models.train_step(model, state, batch, lr, **kw)
     torch.cuda.synchronize()
     gr = state.sg_grads.cpu().double()
     moved = (state.sg_params.cpu().double() - before.cpu().double())
@@ -359,17 +359,17 @@ def test_resume_from_a_checkpoint_continues_bit_for_bit(tmp_path, prec_name, pre
     batches from the start of the sampler's stream again, as the reference's does, so the equality is stated here, at the
     step)."""
     ops = _ops(); dev = _gpu()
-    from plenoctree_amd.nerf_sh.nerf import checkpoints, sg
+    from plenoctree_amd.nerf_sh.nerf import checkpoints, models, sg
     model, live, batch, kw, _ = _fixture_state(ops, dev, prec)
     for _ in range(3):
-        sg.train_step(model, live, batch, 5e-4, **kw)
+        models.train_step(model, live, batch, 5e-4, **kw)
     checkpoints.save_checkpoint(str(tmp_path), live, step=live.step)
     _, back, _, _, _ = _fixture_state(ops, dev, prec)
     back.params.zero_()
     checkpoints.restore_checkpoint(str(tmp_path), back)
     assert back.step == 3 and float(back.sg_m.abs().max()) > 0
     for st in (live, back):
-        sg.train_step(model, st, batch, 5e-4, **kw)
+        models.train_step(model, st, batch, 5e-4, **kw)
     torch.cuda.synchronize()
     for name in ("params", "m", "v", "sg_params", "sg_m", "sg_v", "lobes", "stats", "sg_grads", "grads"):
         assert torch.equal(getattr(live, name), getattr(back, name)), name
@@ -444,13 +444,13 @@ def _free_port():
 
 def _rank_step(rank, world, comm, dev):
     from plenoctree_amd import dist, ops
-    from plenoctree_amd.nerf_sh.nerf import sg, utils
+    from plenoctree_amd.nerf_sh.nerf import models, sg, utils
     model, state, batch, kw, _ = _fixture_state(ops, dev)
     per = 24 // world
     sl = slice(rank * per, (rank + 1) * per)
     batch = {"rays": utils.Rays(*[r[sl].contiguous() for r in batch["rays"]]), "pixels": batch["pixels"][sl].contiguous()}
     reducer = dist.GradReducer(comm, dev) if world > 1 else None
-    sg.train_step(model, state, batch, 5e-4, t_rand=kw["t_rand"][sl].contiguous(), u=kw["u"][sl].contiguous(),
+    models.train_step(model, state, batch, 5e-4, t_rand=kw["t_rand"][sl].contiguous(), u=kw["u"][sl].contiguous(),
                   sp_points=kw["sp_points"], world_size=world, reducer=reducer)
     torch.cuda.synchronize()
     s = 1.0 / world

@@ -180,7 +180,7 @@ def test_error_paths(ctx):
 def test_eval_and_gen_video_cli(ctx, tmp_path):
     from plenoctree_amd import ops
     from plenoctree_amd.nerf_sh import eval as nerf_eval, gen_video
-    from plenoctree_amd.nerf_sh.nerf import datasets, utils
+    from plenoctree_amd.nerf_sh.nerf import datasets, families, utils
     from PIL import Image
     dev = ctx["dev"]
     torch.save({"model": ctx["sd"]}, os.path.join(str(tmp_path), "model.ckpt"))
@@ -197,7 +197,7 @@ def test_eval_and_gen_video_cli(ctx, tmp_path):
     # last chunk is shorter still): compared through the PNG's 8-bit quantisation of the same float32 values
     ex = dataset.get_image(0)
     H, W = ex["rays"].origins.shape[:2]
-    model, state = ctx["viewdirs"].restore_for_render(args, dev, say=lambda *a, **k: None)
+    model, state = families.restore(args, dev, "render", say=lambda *a, **k: None)
     flat = Rays(*[r.reshape(-1, 3).contiguous() for r in ex["rays"]])
     rgb = model.apply(state, flat, False)[-1][0].reshape(H, W, 3)
     chunked = utils.render_image(lambda r: model.apply(state, r, False), ex["rays"], chunk=1000)[0]

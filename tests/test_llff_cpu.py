@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from plenoctree_amd.nerf_sh.nerf import datasets, llff, sg, utils, viewdirs
+from plenoctree_amd.nerf_sh.nerf import datasets, families, llff, utils, viewdirs
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TINY = os.path.join(HERE, "golden", "llff_tiny")
@@ -244,16 +244,16 @@ def test_flags():
                 utils.check_flags(_args(dataset=name, **over))
     # SG models and the view-conditioned head stay refused on LLFF scenes, by name
     sg_args = _args(sg_dim=4, sh_deg=-1)
-    assert any("llff" in m for m in sg._unbuilt_flags(sg_args))
+    assert any("llff" in m for m in utils.unbuilt_flags(sg_args, families.SG.checks["train"][1]))
     with pytest.raises(NotImplementedError, match="LLFF"):
-        sg.check_dirs(sg_args, train=True)
+        families.check(sg_args, "train")
     with pytest.raises(NotImplementedError, match="LLFF"):
-        sg.check_dirs(_args(sg_dim=4, sh_deg=-1, dataset="blender", render_path=True))
+        families.check(_args(sg_dim=4, sh_deg=-1, dataset="blender", render_path=True), "render")
     vd_args = viewdirs.add_checkpoint_flags(utils.define_flags()).parse_args(["--config", "llff", "--train_dir", "x", "--data_dir", TINY])
     utils.update_flags(vd_args)
     vd_args.use_viewdirs, vd_args.sh_deg = True, -1
     with pytest.raises(NotImplementedError, match="LLFF"):
-        viewdirs.check_render_dirs(vd_args)
+        families.check(vd_args, "render")
     with pytest.raises(NotImplementedError, match="use_viewdirs"):
         utils.check_flags(_args(use_viewdirs=True))
     # the plain dataset table still refuses llff: the octree entry points, which call it, do not build these scenes

@@ -17,7 +17,7 @@ import _sg_train_cases as C
 import _sg_train_oracle as T
 from oracle import nerf_oracle as O
 from plenoctree_amd import _lib, build
-from plenoctree_amd.nerf_sh.nerf import checkpoints, models, sg, utils
+from plenoctree_amd.nerf_sh.nerf import checkpoints, families, models, sg, utils
 
 NEW_SYMBOLS = ("pxo_sg_lobes", "pxo_sg_shade_composite_train", "pxo_sg_train_workspace_bytes", "pxo_sg_train_fwd_bwd_bucketed",
                "pxo_sg_train_fwd_bwd")
@@ -91,8 +91,8 @@ def _sg_args(extra=()):
 
 def test_train_flag_check_accepts_the_preset_and_rejects_the_rest_by_name():
     a = _sg_args()
-    sg.check_train_flags(a)
-    sg.check_dirs(a, train=True, world_size=2)
+    families.check_flags(families.SG, a, "train")
+    families.check(a, "train", world_size=2)
     for mutate, word in ((dict(sg_dim=7), r"sg_dim=7 \(need one of \(1, 4, 9, 16, 25\)"),
                          (dict(sh_deg=3), r"sh_deg=3 \(need -1"),
                          (dict(use_viewdirs=True), "use_viewdirs=true"),
@@ -102,15 +102,16 @@ def test_train_flag_check_accepts_the_preset_and_rejects_the_rest_by_name():
         b = _sg_args()
         vars(b).update(mutate)
         with pytest.raises(NotImplementedError, match="training a NeRF-SG.*" + word):
-            sg.check_train_flags(b)
+            families.check_flags(families.SG, b, "train")
         with pytest.raises(NotImplementedError, match="training a NeRF-SG"):
-            sg.check_dirs(b, train=True)
+            utils.check_dirs(b, require_batch_size_div=True)          # the directory checks, then the SG row's own
+            families.check_flags(families.SG, b, "train")
     with pytest.raises(ValueError, match="Batch size must be divisible"):
         b = _sg_args(); b.batch_size = 1023
-        sg.check_dirs(b, train=True, world_size=2)
+        families.check(b, "train", world_size=2)
     with pytest.raises(ValueError, match="train_dir"):
         b = _sg_args(); b.train_dir = None
-        sg.check_dirs(b, train=True)
+        families.check(b, "train")
     # the generic check is what it was: it refuses the SG preset by name (nerf_sh.train routes around it for sg_dim > 0)
     with pytest.raises(NotImplementedError, match=r"sg_dim>0 \(spherical gaussians\)"):
         utils.check_flags(_sg_args(), require_batch_size_div=True)

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from plenoctree_amd import _lib, build, ops
-from plenoctree_amd.nerf_sh.nerf import checkpoints, utils, viewdirs
+from plenoctree_amd.nerf_sh.nerf import checkpoints, families, utils, viewdirs
 from plenoctree_amd.octree import extraction
 
 from _viewdirs_helpers import (EDGE_CROSS_N, EDGE_CROSS_R, EDGE_DIR_N, EDGE_DIR_R, EDGE_PER_POINT_N, EDGE_POINT_N, EDGE_POINT_R,
@@ -116,7 +116,7 @@ def _args(extra=()):
 
 
 def test_extraction_flag_check_accepts_the_built_combination_and_names_the_rest():
-    extraction.check_viewdirs_flags(_args())
+    families.check(_args(), "extract")
     for extra, word in ((["--net_depth_condition", "2"], "net_depth_condition=2"),
                         (["--net_width_condition", "256"], "net_width_condition=256"),
                         (["--deg_view", "3"], "deg_view=3"),
@@ -126,7 +126,7 @@ def test_extraction_flag_check_accepts_the_built_combination_and_names_the_rest(
                         (["--legacy_posenc_order", "true"], "legacy_posenc_order"),
                         (["--mlp_precision", "bf16x3"], "mlp_precision=bf16x3")):
         with pytest.raises(NotImplementedError, match=word):
-            extraction.check_viewdirs_flags(_args(extra))
+            families.check(_args(extra), "extract")
     # the generic check (training, NeRF rendering) keeps rejecting the head, with the reference's default flag values
     ref_defaults = utils.define_flags().parse_args(["--train_dir", "x", "--dataset", "synthetic"])
     assert ref_defaults.use_viewdirs is True

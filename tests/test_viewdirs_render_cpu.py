@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from plenoctree_amd import _lib, build
-from plenoctree_amd.nerf_sh.nerf import utils, viewdirs
+from plenoctree_amd.nerf_sh.nerf import families, utils, viewdirs
 from _viewdirs_render_helpers import check_level, fixture, fixture_rays, fixture_state_dict, host_render_f64, render_cfg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -97,9 +97,9 @@ def test_render_flag_check_accepts_the_references_presets_and_names_the_rest():
                "--sparsity_weight", "0.0"]                                   # config/misc/og_nerf.yaml: sh_deg stays -1
     proj = og_nerf[:-2] + ["--sh_deg", "4"]                                  # config/misc/proj.yaml
     assert _args(og_nerf).sh_deg == -1
-    viewdirs.check_render_flags(_args(og_nerf))
-    viewdirs.check_render_flags(_args(proj))
-    viewdirs.check_render_dirs(_args(og_nerf))
+    families.check_flags(families.VIEWDIRS, _args(og_nerf), "render")
+    families.check_flags(families.VIEWDIRS, _args(proj), "render")
+    families.check(_args(og_nerf), "render")
     for extra, word in ((["--net_width_condition", "256"], "net_width_condition=256"),
                         (["--deg_view", "3"], "deg_view=3"),
                         (["--sg_dim", "8"], "sg_dim>0"),
@@ -107,13 +107,13 @@ def test_render_flag_check_accepts_the_references_presets_and_names_the_rest():
                         (["--net_depth_condition", "2"], "net_depth_condition=2"),
                         (["--use_viewdirs", "false"], "use_viewdirs=false")):
         with pytest.raises(NotImplementedError, match=word):
-            viewdirs.check_render_flags(_args(og_nerf + extra))
+            families.check_flags(families.VIEWDIRS, _args(og_nerf + extra), "render")
     with pytest.raises(ValueError, match="train_dir"):
         a = _args(og_nerf); a.train_dir = None
-        viewdirs.check_render_dirs(a)
+        families.check(a, "render")
     # the projection keeps its own clauses, and the generic check (training, gen_mesh) keeps rejecting the head
     with pytest.raises(NotImplementedError, match="sh_deg=-1"):
-        viewdirs.check_extraction_flags(_args(og_nerf))
+        families.check_flags(families.VIEWDIRS, _args(og_nerf), "extract")
     with pytest.raises(NotImplementedError, match="use_viewdirs=true"):
         utils.check_flags(_args(og_nerf))
     with pytest.raises(NotImplementedError, match="use_viewdirs=true"):
