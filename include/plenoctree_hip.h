@@ -310,6 +310,59 @@ int pxo_sg_render_fwd(const PxoCfg* cfg, const float* lobes, const float* packed
                       const float* t_rand, const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c,
                       float* rgb_f, float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- occupancy grid: ray rendering that skips empty samples (entry points added without a change of PXO_ABI_VERSION: no
+ * existing struct and no existing call changes).  No reference counterpart: NerfModel.__call__ evaluates every sample of every
+ * ray (nerf_sh/nerf/models.py:242-264, :308-330).  Forward only, opt-in; the images are not the dense path's bit for bit unless
+ * every culled sample had relu(sigma) = 0 there.
+ *
+ * PxoOccGrid: one bit per cell of a reso^3 grid over the box a PlenOctree of the scene would span. */
+#define PXO_OCC_MAX_RESO 1024
+#define PXO_OCC_MAX_CHANNELS 4096
+typedef struct PxoOccGrid {
+  const uint32_t* bits;   /* device; reso^3 bits, linear cell index (x*reso + y)*reso + z, x slowest, as pxo_grid_sigma.  Bit i lives
+                             in word i>>5 at position i&31; the last word's unused bits are zero: (reso^3 + 31) / 32 words */
+  int32_t reso;           /* 1 .. PXO_OCC_MAX_RESO */
+  float offset[3];        /* as pxo_grid_sigma / N3Tree (octree/extraction.py:250-251): a world point p has grid coordinate */
+  float scale[3];         /*   t = p * scale + offset, inside the grid iff t in [0,1)^3 */
+  int32_t outside_live;   /* a sample outside [0,1)^3: 1 = evaluated, 0 = empty */
+} PxoOccGrid;
+
+/* sigma [reso^3] (device, pxo_grid_sigma's order) -> bits ((reso^3 + 31) / 32 words, every one written).  Cell c is occupied iff
+ * some cell c' INSIDE the grid at Chebyshev distance <= dilate (0 or 1) has !(sigma[c'] <= sigma_thresh): strictly above the
+ * threshold, or NaN. */
+int pxo_occ_pack(const float* sigma, int reso, float sigma_thresh, int dilate, uint32_t* bits, void* stream);
+
+/* Which of M points are worth evaluating, and their compaction.  Per point, in float32: t_a = fmaf(p_a, scale_a, offset_a); the
+ * point is inside iff 0 <= t_a < 1 on all three axes, its cell then (int)(t_a * reso) clamped to reso - 1.  LIVE iff inside and
+ * its bit is set, or outside and occ->outside_live, or any coordinate of p is not finite (a broken input still shows in the
+ * image).  slot[m] = number of live points before m if m is live, else -1; pts_live [n_live,3] (room for M rows) = the live
+ * points in their original order; *n_live_dev (device) = their number.  Count per block, scan, emit, no atomics: deterministic.
+ * M < 2^31.  ws: pxo_occ_cull_workspace_bytes(M) (M + ~M/64 bytes). */
+int pxo_occ_cull_workspace_bytes(int64_t M, size_t* bytes);
+int pxo_occ_cull(const PxoOccGrid* occ, const float* pts, int64_t M, float* pts_live, int32_t* slot, int64_t* n_live_dev, void* ws,
+                 size_t ws_bytes, void* stream);
+
+/* The way back: raw_rgb [M,C] / raw_sigma [M] row m = row slot[m] of raw_rgb_live / raw_sigma_live if slot[m] >= 0, else zeros
+ * (relu(0) = 0: density 0, alpha 0, weight 0).  A gather over the dense rows: every output element is written exactly once. */
+int pxo_occ_expand(const float* raw_rgb_live, const float* raw_sigma_live, const int32_t* slot, int64_t M, int C, float* raw_rgb,
+                   float* raw_sigma, void* stream);
+
+/* pxo_render_fwd (lobes == NULL) / pxo_sg_render_fwd (lobes [K,4]) with the MLP of each level run on the live samples only:
+ * per level the sampling launch, pxo_occ_cull, the SAME fused-MLP launch on pts_live with M = n_live (skipped when n_live = 0),
+ * pxo_occ_expand into the level's dense raw_rgb / raw_sigma, and the same shade + composite launch.  A sample's raw values do
+ * not depend on its position in an MLP launch, so with every sample live the six outputs are those of the dense call bit for
+ * bit.  n_live reaches the host through one 8-byte copy into pinned memory per level: the call synchronises `stream` once per
+ * level (twice per chunk) and is therefore NOT capturable into a graph.  live_rows (host, may be NULL): rows through MLP_0 /
+ * MLP_1.  Every mlp_precision; randomized with t_rand / u as pxo_render_fwd; cfg->noise_std > 0 with randomized:
+ * PXO_ERR_UNSUPPORTED (noise on a culled sample's zero sigma would resurrect it).  PXO_ERR_ARG: occ or occ->bits NULL, reso
+ * outside 1 .. PXO_OCC_MAX_RESO, a zero or non-finite scale.  ws: pxo_render_culled_workspace_bytes. */
+int pxo_render_culled_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes);
+int pxo_render_fwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float* lobes, const float* packed_fwd0,
+                          const float* packed_fwd1, const float* origins, const float* directions, const float* viewdirs, int64_t B,
+                          int randomized, const float* t_rand, const float* u, uint64_t seed, float* rgb_c, float* disp_c,
+                          float* acc_c, float* rgb_f, float* disp_f, float* acc_f, int64_t live_rows[2], void* ws, size_t ws_bytes,
+                          void* stream);
+
 /* ---- training a NeRF-SG (entry points added without a change of PXO_ABI_VERSION: no struct and no existing call changes) ----
  * The raw model-level parameters of a NeRF-SG (nerf_sh/nerf/models.py:107-117) travel as one device array
  * sg_params [3K] = sg_lambda [K] followed by sg_mu_spher [K,2] row-major (theta_0, phi_0, theta_1, ...), K = (cfg->sh_deg+1)^2.

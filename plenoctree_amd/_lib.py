@@ -87,6 +87,11 @@ class PxoQuantTree(Structure):
                 ("idx_stride", c_int32), ("ret_stride", c_int32), ("offset", c_float * 3), ("invradius", c_float * 3)]
 
 
+class PxoOccGrid(Structure):
+    _fields_ = [("bits", c_void_p), ("reso", c_int32), ("offset", c_float * 3), ("scale", c_float * 3), ("outside_live", c_int32)]
+
+
+OCC_MAX_RESO = 1024                 # PXO_OCC_MAX_RESO
 TREE_MAX_DEPTH = 10
 ABI_VERSION = 9                     # PXO_ABI_VERSION of include/plenoctree_hip.h
 SG_RAYS_PER_BLOCK = 4               # PXO_SG_RAYS_PER_BLOCK: rays per partial of pxo_sg_shade_composite_train's lobe_partials
@@ -136,6 +141,13 @@ SIGNATURES = {
                                c_size_t, P]),
     "pxo_sg_render_fwd": (c_int, [CFG, P, P, P, P, P, P, c_int64, c_int, P, P, c_uint64, P, P, P, P, P, P, P,
                                   c_size_t, P]),
+    "pxo_occ_pack": (c_int, [P, c_int, c_float, c_int, P, P]),
+    "pxo_occ_cull_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "pxo_occ_cull": (c_int, [POINTER(PxoOccGrid), P, c_int64, P, P, P, P, c_size_t, P]),
+    "pxo_occ_expand": (c_int, [P, P, P, c_int64, c_int, P, P, P]),
+    "pxo_render_culled_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
+    "pxo_render_fwd_culled": (c_int, [CFG, POINTER(PxoOccGrid), P, P, P, P, P, P, c_int64, c_int, P, P, c_uint64, P, P, P, P, P, P,
+                                      POINTER(c_int64), P, c_size_t, P]),
     "pxo_train_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
     "pxo_train_fwd_bwd": (c_int, [CFG, P, P, P, P, P, P, P, P, P, c_int64, c_int, P, P, P, c_uint64, P, P,
                                   P, c_size_t, P]),

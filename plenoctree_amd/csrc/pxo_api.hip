@@ -660,6 +660,121 @@ int pxo_sg_render_fwd(const PxoCfg* cfg, const float* lobes, const float* packed
                          disp_c, acc_c, rgb_f, disp_f, acc_f, ws, ws_bytes, stream, lobes, "pxo_sg_render_fwd");
 }
 
+}  // extern "C"
+
+namespace pxo {
+
+// What pxo_render_fwd_culled keeps behind the render workspace (whose layout stays pxo_render_fwd's): the compact point and
+// output rows of ONE level (the fine level's size; the coarse level uses their head), the slots, the two counts and the cull's scratch
+struct CullWs { float *pts_live, *rgb_live, *sigma_live; int32_t* slot; int64_t* n_live; void* cull; size_t total; };
+static void carve_cull(const PxoCfg* cfg, int64_t B, void* ws, size_t render_total, CullWs& k) {
+  Carver c(ws);
+  c.off = render_total;
+  const int64_t M = B * (cfg->num_coarse_samples + cfg->num_fine_samples);
+  k.pts_live = c.take<float>(M * 3);
+  k.rgb_live = c.take<float>(M * rgb_channels(cfg->sh_deg));
+  k.sigma_live = c.take<float>(M);
+  k.slot = c.take<int32_t>(M);
+  k.n_live = c.take<int64_t>(2);
+  k.cull = c.take<char>((int64_t)occ_cull_workspace_bytes(M));
+  k.total = (c.off + 255) & ~(size_t)255;
+}
+
+// the pinned words the two counts of a call land in: one pair per host thread, allocated on first use and kept for its life
+static int64_t* pinned_counts() {
+  static thread_local int64_t* p = nullptr;
+  if (!p && hipHostMalloc((void**)&p, 2 * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) p = nullptr;
+  return p;
+}
+
+// One level between its sampling launch and its shade + composite launch: cull, the MLP on the live rows, expand.  Synchronises.
+static int culled_mlp(const PxoCfg* cfg, const PxoOccGrid& occ, CullWs& k, int level, const float* packed, PassBuffers& p,
+                      int64_t* host_count, hipStream_t s) {
+  PXO_TRY(launch_occ_cull(occ, p.pts, p.M, k.pts_live, k.slot, k.n_live + level, k.cull, s));
+  if (hipMemcpyAsync(host_count, k.n_live + level, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    set_error("pxo_render_fwd_culled: reading the live-row count: %s", hipGetErrorString(hipGetLastError()));
+    return PXO_ERR_HIP;
+  }
+  const int64_t n_live = *host_count;
+  if (n_live < 0 || n_live > p.M) {
+    set_error("pxo_render_fwd_culled: live-row count %lld outside [0, %lld]", (long long)n_live, (long long)p.M);
+    return PXO_ERR_HIP;
+  }
+  if (n_live > 0)
+    PXO_TRY(launch_mlp_fwd(cfg, packed, k.pts_live, n_live, k.rgb_live, k.sigma_live, nullptr, nullptr, nullptr, s));
+  return launch_occ_expand(k.rgb_live, k.sigma_live, k.slot, p.M, rgb_channels(cfg->sh_deg), p.raw_rgb, p.raw_sigma, s);
+}
+
+}  // namespace pxo
+
+extern "C" {
+
+int pxo_render_culled_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
+  PXO_TRY(validate_cfg(cfg));
+  PXO_REQUIRE(bytes && B >= 0, "pxo_render_culled_workspace_bytes: bad arguments");
+  PXO_REQUIRE(B * (int64_t)(cfg->num_coarse_samples + cfg->num_fine_samples) < ((int64_t)1 << 31),
+              "pxo_render_culled_workspace_bytes: %lld rays x %d samples exceed 2^31 rows", (long long)B,
+              cfg->num_coarse_samples + cfg->num_fine_samples);
+  TrainWs t;
+  carve_train(cfg, B, nullptr, false, t);
+  CullWs k;
+  carve_cull(cfg, B, nullptr, t.total, k);
+  *bytes = k.total;
+  return PXO_OK;
+}
+
+int pxo_render_fwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float* lobes, const float* packed_fwd0,
+                          const float* packed_fwd1, const float* origins, const float* directions, const float* viewdirs, int64_t B,
+                          int randomized, const float* t_rand, const float* u, uint64_t seed, float* rgb_c, float* disp_c,
+                          float* acc_c, float* rgb_f, float* disp_f, float* acc_f, int64_t live_rows[2], void* ws, size_t ws_bytes,
+                          void* stream) {
+  const char* who = "pxo_render_fwd_culled";
+  PXO_TRY(validate_cfg(cfg));
+  PXO_TRY(occ_validate(occ, who));
+  if (randomized && cfg->noise_std > 0.f) {
+    set_error("%s: noise_std > 0 with randomized sampling (noise on a culled sample's zero sigma would resurrect it)", who);
+    return PXO_ERR_UNSUPPORTED;
+  }
+  if (live_rows) live_rows[0] = live_rows[1] = 0;
+  if (B == 0) return PXO_OK;
+  const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
+  PXO_REQUIRE(B >= 0 && B * (int64_t)(Nc + Nf) < ((int64_t)1 << 31), "%s: %lld rays x %d samples outside [0, 2^31) rows", who,
+              (long long)B, Nc + Nf);
+  PXO_REQUIRE(packed_fwd0 && origins && directions && viewdirs && rgb_c && disp_c && acc_c && ws, "%s: bad arguments", who);
+  if (Nf > 0) PXO_REQUIRE(packed_fwd1 && rgb_f && disp_f && acc_f, "%s: fine outputs/weights missing", who);
+  TrainWs t;
+  carve_train(cfg, B, ws, false, t);
+  CullWs k;
+  carve_cull(cfg, B, ws, t.total, k);
+  if (ws_bytes < k.total) {
+    set_error("%s: workspace %zu < %zu", who, ws_bytes, k.total);
+    return PXO_ERR_WORKSPACE;
+  }
+  int64_t* host = pinned_counts();
+  if (!host) {
+    set_error("%s: hipHostMalloc of the count words failed", who);
+    return PXO_ERR_HIP;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  Draws dr;
+  PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, nullptr, seed, s, dr));
+  // the launches of forward_coarse / forward_fine, with the MLP of each level between a cull and an expand
+  PXO_TRY(launch_sample_along_rays(origins, directions, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, t.c.z, t.c.pts, s));
+  PXO_TRY(culled_mlp(cfg, *occ, k, 0, packed_fwd0, t.c, host, s));
+  if (live_rows) live_rows[0] = host[0];
+  PXO_TRY(launch_shade_composite_fwd(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, directions, viewdirs, B, Nc, rgb_c, disp_c, acc_c,
+                                     t.c.weights, s, lobes));
+  if (Nf > 0) {
+    PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, origins, directions, B, Nc, Nf, dr.u, t.f.z, t.f.pts, s));
+    PXO_TRY(culled_mlp(cfg, *occ, k, 1, packed_fwd1, t.f, host + 1, s));
+    if (live_rows) live_rows[1] = host[1];
+    PXO_TRY(launch_shade_composite_fwd(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, directions, viewdirs, B, Nc + Nf, rgb_f, disp_f,
+                                       acc_f, t.f.weights, s, lobes));
+  }
+  return PXO_OK;
+}
+
 int pxo_train_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
   PXO_TRY(validate_cfg(cfg));
   PXO_REQUIRE(bytes && B >= 1, "pxo_train_workspace_bytes: bad arguments");

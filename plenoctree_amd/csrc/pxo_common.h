@@ -355,6 +355,13 @@ int launch_finalize_stats(const float* sse_f, const float* sse_c, const float* s
                           int64_t B, int64_t n_sp, float sp_weight, int64_t n_params, float* stats, hipStream_t s);
 int launch_adam_pack(const PxoCfg* cfg, float* p, float* m, float* v, const float* g, float lr, int64_t step,
                      float grad_scale, float* fwd0, float* bwd0, float* fwd1, float* bwd1, hipStream_t s);
+// occupancy_kernels.hip: the checks of a PxoOccGrid (`who` opens the message), and the cull / expand passes without them
+int occ_validate(const PxoOccGrid* occ, const char* who);
+size_t occ_cull_workspace_bytes(int64_t M);
+int launch_occ_cull(const PxoOccGrid& occ, const float* pts, int64_t M, float* pts_live, int32_t* slot, int64_t* n_live_dev,
+                    void* ws, hipStream_t s);
+int launch_occ_expand(const float* rgb_live, const float* sigma_live, const int32_t* slot, int64_t M, int C, float* raw_rgb,
+                      float* raw_sigma, hipStream_t s);
 int launch_fill(float* p, int64_t n, float v, hipStream_t s);
 int launch_axpy(float* y, const float* x, int64_t n, float a, hipStream_t s);
 

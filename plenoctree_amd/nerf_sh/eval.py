@@ -7,7 +7,7 @@ import sys
 import numpy as np
 
 from .. import dist
-from .nerf import families, llff, sg, utils, viewdirs
+from .nerf import families, llff, occupancy, sg, utils, viewdirs
 
 
 def save_outputs(out_dir, idx, rgb, disp):
@@ -39,12 +39,16 @@ def main(argv=None):
     if args.save_output and comm.rank == 0:
         os.makedirs(out_dir, exist_ok=True)
     psnrs, ssims = [], []
+    render_fn, live = occupancy.render_fn(args, model, state, comm, say)      # without --occupancy_reso: model.apply, as ever
     for idx in range(0, dataset.size, max(args.approx_eval_skip, 1)):
         ex = dataset.get_image(idx)
-        rgb, disp, acc = utils.render_image(lambda r: model.apply(state, r, False), ex["rays"],
+        rgb, disp, acc = utils.render_image(render_fn, ex["rays"],
                                             normalize_disp=(args.dataset == "llff"), chunk=args.chunk,      # eval.py:89
                                             world_size=comm.world, rank=comm.rank, gather=comm.all_gather_cat)
         disp = disp[..., 0] if disp.dim() == 3 else disp                        # eval.py:110: pred_disp[Ellipsis, 0]
+        if live is not None:
+            say(live.line(), flush=True)
+            live.reset()
         if render_path:
             if comm.rank == 0:
                 print(f"Rendered {idx + 1}/{dataset.size}", flush=True)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import dist, ops
-from .nerf import families, llff, sg, utils, viewdirs
+from .nerf import families, llff, occupancy, sg, utils, viewdirs
 
 
 def define_flags():
@@ -75,6 +75,7 @@ def main(argv=None):
         os.makedirs(frames_dir, exist_ok=True)
     c2w = None if path_ds is not None else torch.from_numpy(np.ascontiguousarray(poses[:, :3, :4])).to(device)
     frames = []
+    render_fn, live = occupancy.render_fn(args, model, state, comm, say)      # without --occupancy_reso: model.apply, as ever
     for i in range(args.num_views):
         say(f"** View {i + 1}/{args.num_views} = {i / args.num_views * 100}%", flush=True)
         if path_ds is not None:
@@ -82,9 +83,12 @@ def main(argv=None):
         else:
             rays = utils.Rays(*[r.reshape(args.height, args.width, 3)
                                 for r in ops.generate_rays(c2w[i], args.width, args.height, focal)])
-        rgb, disp, acc = utils.render_image(lambda r: model.apply(state, r, False), rays,
+        rgb, disp, acc = utils.render_image(render_fn, rays,
                                             normalize_disp=(args.dataset == "llff"), chunk=args.chunk,     # gen_video.py:158
                                             world_size=comm.world, rank=comm.rank, gather=comm.all_gather_cat)
+        if live is not None:
+            say(live.line(), flush=True)
+            live.reset()
         if comm.rank == 0:
             utils.save_img(rgb, os.path.join(frames_dir, f"{i:04}.png"))
             frames.append((np.clip(rgb.cpu().numpy(), 0.0, 1.0) * 255).astype(np.uint8))

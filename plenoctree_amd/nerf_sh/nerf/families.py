@@ -6,7 +6,7 @@ more purpose, is one entry here.
 """
 import collections
 
-from . import checkpoints, models, sg, utils, viewdirs
+from . import checkpoints, models, occupancy, sg, utils, viewdirs
 
 PURPOSES = ("train", "render", "extract", "mesh")      # nerf_sh.train | eval, gen_video | octree.extraction | nerf_sh.gen_mesh
 
@@ -86,6 +86,20 @@ def _sg_dim(a):
             and f"sg_dim={a.sg_dim} (need one of {sg.SUPPORTED_DIMS}: the widths of the MLP head and the renderers)")
 
 
+def _occupancy_render(a):
+    """--occupancy_reso R (nerf/occupancy.py) in nerf_sh.eval / nerf_sh.gen_video: what of it is not built."""
+    return "; ".join(occupancy.clauses(a))
+
+
+def _occupancy_elsewhere(a):
+    return occupancy.wanted(a) and ("occupancy_reso (the occupancy grid serves the renders of nerf_sh.eval and nerf_sh.gen_video: culling "
+                                    "inside training, its test renders, the extraction or meshing is not built)")
+
+
+def _with_occupancy(clauses, purpose):
+    return clauses + ((_occupancy_render if purpose == "render" else _occupancy_elsewhere),)
+
+
 _SH_CLAUSES = (lambda a: a.use_viewdirs and "use_viewdirs=true (vanilla NeRF head)",
                lambda a: (a.sh_deg < 0 or a.sh_deg > 4) and f"sh_deg={a.sh_deg} (need 0..4)",
                _no_sg, "trunk", "posenc", "noise_std", _render_path_off_llff, "legacy_posenc_order", "activations")
@@ -130,8 +144,8 @@ def _sh_tree(args, state):
 VIEWDIRS = Family(
     name="viewdirs",
     selects=lambda a: a.use_viewdirs,
-    checks={"render": ("rendering a view-dependent NeRF, ", _VD_RENDER),
-            "extract": ("SH projection of a view-dependent NeRF, ", _VD_PROJECTION)},
+    checks={"render": ("rendering a view-dependent NeRF, ", _with_occupancy(_VD_RENDER, "render")),
+            "extract": ("SH projection of a view-dependent NeRF, ", _with_occupancy(_VD_PROJECTION, "extract"))},
     instead={"train": ("sg", "sh"), "mesh": ("sh",)},
     construct=viewdirs.get_model_state,
     loading=lambda a: "* Loading NeRF (view-conditioned head)",
@@ -145,8 +159,10 @@ VIEWDIRS = Family(
 SG = Family(
     name="sg",
     selects=lambda a: a.sg_dim > 0,
-    checks={"train": ("training a NeRF-SG, ", _SG_CLAUSES), "render": ("rendering a NeRF-SG, ", _SG_CLAUSES),
-            "extract": ("extraction of an SG PlenOctree, ", _SG_CLAUSES), "mesh": ("rendering a NeRF-SG, ", _SG_CLAUSES)},
+    checks={"train": ("training a NeRF-SG, ", _with_occupancy(_SG_CLAUSES, "train")),
+            "render": ("rendering a NeRF-SG, ", _with_occupancy(_SG_CLAUSES, "render")),
+            "extract": ("extraction of an SG PlenOctree, ", _with_occupancy(_SG_CLAUSES, "extract")),
+            "mesh": ("rendering a NeRF-SG, ", _with_occupancy(_SG_CLAUSES, "mesh"))},
     instead={},
     construct=sg.get_model_state,
     loading=lambda a: f"* Loading NeRF (SG{a.sg_dim})",
@@ -158,7 +174,7 @@ SG = Family(
 SH = Family(
     name="sh",
     selects=lambda a: True,
-    checks=dict.fromkeys(PURPOSES, ("", _SH_CLAUSES)),
+    checks={purpose: ("", _with_occupancy(_SH_CLAUSES, purpose)) for purpose in PURPOSES},
     instead={},
     construct=lambda a, device, purpose: models.get_model_state(a, device, restore=False),
     loading=lambda a: "* Loading NeRF",

@@ -101,15 +101,24 @@ class NerfModel:
         self.num_fine_samples = cfg.num_fine_samples
         self.sh_deg = cfg.sh_deg
 
-    def apply(self, state, rays, randomized, t_rand=None, u=None, seed=0):
+    def apply(self, state, rays, randomized, t_rand=None, u=None, seed=0, occupancy=None, live_rows=None):
         """model.apply(variables, key_0, key_1, rays, randomized) (:216): returns
         [(rgb, disp, acc)_coarse, (rgb, disp, acc)_fine].  The jax keys are replaced by
-        explicit uniforms (t_rand [B,Nc], u [B,Nf]) or a Philox `seed`."""
+        explicit uniforms (t_rand [B,Nc], u [B,Nf]) or a Philox `seed`.  occupancy (an ops.OccupancyGrid, nerf/occupancy.py):
+        only the samples it calls live go through the MLPs (live_rows, a list, receives how many did per level)."""
+        if occupancy is not None:
+            return self._apply_culled(state, rays, randomized, t_rand, u, seed, occupancy, live_rows, None)
         ws = state.workspace(ops.render_workspace_bytes(self.cfg, rays.origins.shape[0]))
         return ops.render_fwd(self.cfg, state.packed[0][0], state.packed[1][0], rays.origins, rays.directions,
                               rays.viewdirs, randomized=randomized, t_rand=t_rand, u=u, seed=seed, ws=ws)
 
     __call__ = apply
+
+    def _apply_culled(self, state, rays, randomized, t_rand, u, seed, occupancy, live_rows, lobes):
+        ws = state.workspace(ops.render_culled_workspace_bytes(self.cfg, rays.origins.shape[0]))
+        return ops.render_fwd_culled(self.cfg, occupancy, state.packed[0][0], state.packed[1][0], rays.origins, rays.directions,
+                                     rays.viewdirs, randomized=randomized, t_rand=t_rand, u=u, seed=seed, ws=ws, lobes=lobes,
+                                     live_rows=live_rows)
 
     def eval_points_raw(self, state, points, viewdirs=None, coarse=False, want_rgb=True):
         """:143-181 / octree/nerf/models.py:211-252: raw SH coefficients [N,3K] and raw sigma [N,1]."""

@@ -150,7 +150,9 @@ class SgModel(models.NerfModel):
         super().__init__(cfg)
         self.sg_dim = (cfg.sh_deg + 1) ** 2
 
-    def apply(self, state, rays, randomized, t_rand=None, u=None, seed=0):
+    def apply(self, state, rays, randomized, t_rand=None, u=None, seed=0, occupancy=None, live_rows=None):
+        if occupancy is not None:
+            return self._apply_culled(state, rays, randomized, t_rand, u, seed, occupancy, live_rows, state.lobes)
         ws = state.workspace(ops.render_workspace_bytes(self.cfg, rays.origins.shape[0]))
         return ops.render_fwd(self.cfg, state.packed[0][0], state.packed[1][0], rays.origins, rays.directions, rays.viewdirs,
                               randomized=randomized, t_rand=t_rand, u=u, seed=seed, ws=ws, lobes=state.lobes)

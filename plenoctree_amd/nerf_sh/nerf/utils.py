@@ -118,6 +118,10 @@ def define_flags(parser=None):
     # reference's defaults so that its command lines and presets parse; check_supported rejects what would use them
     a("--net_depth_condition", type=int, default=1)        # :108
     a("--net_width_condition", type=int, default=128)      # :109
+    # no reference counterpart: the occupancy grid of nerf_sh.eval / nerf_sh.gen_video (nerf/occupancy.py); every other entry
+    # point refuses --occupancy_reso by name through the families table
+    from . import occupancy
+    occupancy.add_flags(p)
     return p
 
 

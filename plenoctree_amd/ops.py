@@ -679,3 +679,133 @@ def vd_composite_fwd(cfg, raw_rgb, raw_sigma, z_vals, directions):
     check(_lib.load().pxo_vd_composite_fwd(ctypes.byref(cfg), _f(raw_rgb), _f(raw_sigma), _f(z_vals), _f(directions), B, S,
                                            _f(comp), _f(disp), _f(acc), _f(w), _stream()), "pxo_vd_composite_fwd")
     return comp, disp, acc, w
+
+
+# ---- occupancy grid: ray rendering that skips empty samples (the pxo_occ_* entry points and pxo_render_fwd_culled) -----------
+def occ_words(reso):
+    """Words of the bit image of a reso^3 grid."""
+    return (int(reso) ** 3 + 31) // 32
+
+
+class OccupancyGrid:
+    """One bit per cell of a reso^3 grid over the box t = p * scale + offset in [0,1)^3 (PxoOccGrid): `bits` int32 [occ_words(reso)] on
+    the GPU, cell (x, y, z) at bit (x * reso + y) * reso + z.  outside_live: a sample outside the box is evaluated (True) or empty."""
+
+    def __init__(self, bits, reso, offset, scale, outside_live=False):
+        reso = int(reso)
+        offset = [float(v) for v in offset]
+        scale = [float(v) for v in scale]
+        if not 1 <= reso <= _lib.OCC_MAX_RESO:
+            raise PxoError(f"occupancy grid: reso {reso} outside [1, {_lib.OCC_MAX_RESO}]")
+        if len(offset) != 3 or len(scale) != 3:
+            raise PxoError("occupancy grid: offset and scale take three values each")
+        if any(s == 0.0 or s != s or s in (float("inf"), float("-inf")) for s in scale):
+            raise PxoError(f"occupancy grid: scale {scale} has a zero or non-finite entry")
+        if bits is None or bits.dtype != torch.int32 or bits.numel() != occ_words(reso) or not bits.is_contiguous():
+            raise PxoError(f"occupancy grid: bits must be a contiguous int32 tensor of {occ_words(reso)} words (reso {reso})")
+        self.bits, self.reso, self.offset, self.scale, self.outside_live = bits, reso, offset, scale, bool(outside_live)
+
+    def struct(self):
+        g = _lib.PxoOccGrid()
+        g.bits = self.bits.data_ptr()
+        g.reso = self.reso
+        g.offset = (ctypes.c_float * 3)(*self.offset)
+        g.scale = (ctypes.c_float * 3)(*self.scale)
+        g.outside_live = int(self.outside_live)
+        return g
+
+    def count_occupied(self):
+        b = self.bits.to(torch.int64) & 0xFFFFFFFF
+        n = 0
+        for shift in range(0, 32, 8):                      # popcount by bytes through a 256-entry table
+            n += int(_POPCOUNT8.to(b.device)[(b >> shift) & 0xFF].sum())
+        return n
+
+    def fraction_occupied(self):
+        return self.count_occupied() / float(self.reso ** 3)
+
+
+_POPCOUNT8 = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int64)
+
+
+def occ_pack(sigma, reso, sigma_thresh, dilate=1, bits=None):
+    """pxo_occ_pack: sigma [reso^3] (grid_sigma's order) -> the bit image (int32 [occ_words(reso)]); a cell is occupied iff a cell of
+    the grid within Chebyshev distance `dilate` has sigma > sigma_thresh (or NaN)."""
+    _require_gpu()
+    reso = int(reso)
+    if not 1 <= reso <= _lib.OCC_MAX_RESO:
+        raise PxoError(f"occ_pack: reso {reso} outside [1, {_lib.OCC_MAX_RESO}]")
+    if sigma.numel() != reso ** 3:
+        raise PxoError(f"occ_pack: sigma has {sigma.numel()} values, reso {reso} needs {reso ** 3}")
+    if bits is None:
+        bits = _new(occ_words(reso), device=sigma.device, dtype=torch.int32)
+    elif bits.numel() != occ_words(reso) or bits.dtype != torch.int32:
+        raise PxoError("occ_pack: `bits` has the wrong size or type")
+    check(_lib.load().pxo_occ_pack(_f(sigma), reso, float(sigma_thresh), int(dilate), _p(bits), _stream()), "pxo_occ_pack")
+    return bits
+
+
+def occ_cull(occ, pts):
+    """pxo_occ_cull: (pts_live [M,3] whose first n_live rows are the live points in order, slot int32 [M], n_live int64 [1] on the
+    device)."""
+    _require_gpu()
+    pts = pts.reshape(-1, 3)
+    M, dev = pts.shape[0], pts.device
+    pts_live = _new(M, 3, device=dev)
+    slot = _new(M, device=dev, dtype=torch.int32)
+    n_live = _new(1, device=dev, dtype=torch.int64)
+    n = ctypes.c_size_t(0)
+    lib = _lib.load()
+    check(lib.pxo_occ_cull_workspace_bytes(M, ctypes.byref(n)), "pxo_occ_cull_workspace_bytes")
+    ws = _new(max(n.value, 16), device=dev, dtype=torch.uint8)
+    g = occ.struct()
+    check(lib.pxo_occ_cull(ctypes.byref(g), _f(pts), M, _f(pts_live), _p(slot), _p(n_live), _p(ws), ws.numel(), _stream()),
+          "pxo_occ_cull")
+    return pts_live, slot, n_live
+
+
+def occ_expand(raw_rgb_live, raw_sigma_live, slot, C):
+    """pxo_occ_expand: dense raw_rgb [M,C] / raw_sigma [M] from the compact rows; a culled row is zero."""
+    _require_gpu()
+    if slot.dtype != torch.int32:
+        raise PxoError("occ_expand: slot must be int32")
+    M, dev = slot.numel(), slot.device
+    raw_rgb, raw_sigma = _new(M, C, device=dev), _new(M, device=dev)
+    check(_lib.load().pxo_occ_expand(_f(raw_rgb_live), _f(raw_sigma_live), _p(slot), M, int(C), _f(raw_rgb), _f(raw_sigma),
+                                     _stream()), "pxo_occ_expand")
+    return raw_rgb, raw_sigma
+
+
+def render_culled_workspace_bytes(cfg, B):
+    n = ctypes.c_size_t(0)
+    check(_lib.load().pxo_render_culled_workspace_bytes(ctypes.byref(cfg), B, ctypes.byref(n)), "pxo_render_culled_workspace_bytes")
+    return n.value
+
+
+def render_fwd_culled(cfg, occ, packed_fwd0, packed_fwd1, origins, directions, viewdirs, randomized=False, t_rand=None, u=None,
+                      seed=0, ws=None, lobes=None, live_rows=None):
+    """render_fwd with each level's MLP run only on the samples `occ` (an OccupancyGrid) calls live.  Returns render_fwd's list;
+    live_rows (a list, optional) receives the rows that went through MLP_0 and MLP_1.  Synchronises the stream twice."""
+    _require_gpu()
+    if not isinstance(occ, OccupancyGrid):
+        raise PxoError("render_fwd_culled: occ must be an ops.OccupancyGrid")
+    if lobes is not None:
+        K = (cfg.sh_deg + 1) ** 2
+        if lobes.dtype != torch.float32 or tuple(lobes.shape) != (K, 4) or not lobes.is_contiguous() or not lobes.is_cuda:
+            raise PxoError(f"SG lobes must be a contiguous float32 [{K}, 4] tensor on the GPU")
+    B, dev = origins.shape[0], origins.device
+    ws = _ws(ws, render_culled_workspace_bytes(cfg, B), dev)
+    outs = [(_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev))]
+    fine = cfg.num_fine_samples > 0
+    if fine:
+        outs.append((_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev)))
+    f = outs[1] if fine else (None, None, None)
+    rows = (ctypes.c_int64 * 2)(0, 0)
+    g = occ.struct()
+    check(_lib.load().pxo_render_fwd_culled(ctypes.byref(cfg), ctypes.byref(g), _f(lobes), _f(packed_fwd0), _f(packed_fwd1),
+                                            _f(origins), _f(directions), _f(viewdirs), B, int(randomized), _f(t_rand), _f(u), seed,
+                                            _f(outs[0][0]), _f(outs[0][1]), _f(outs[0][2]), _f(f[0]), _f(f[1]), _f(f[2]), rows,
+                                            _p(ws), ws.numel(), _stream()), "pxo_render_fwd_culled")
+    if live_rows is not None:
+        live_rows[:] = [rows[0], rows[1]]
+    return outs
