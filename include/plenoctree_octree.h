@@ -289,6 +289,52 @@ int pxo_octree_render_quant_aux_fwd(const PxoQuantTree* tree, const PxoCamera* c
                                     const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
                                     float* out_rgb, float* out_aux, void* stream);
 
+/* ---- float16 trees rendered in place  (the `data` array of the files N3Tree.save writes; svox writes the same) ----
+ *
+ * File array (D = data_dim = 3 basis_dim + 1, C = n_internal * 8 cells):
+ *   data  float16 [C, D]      rgb coefficients channel-major, last channel sigma, as in the float form
+ * Device layout made by pxo_octree_half_pack, one buffer:
+ *   data  float16 [C, row_stride]   logical index i of leaf r at half r * row_stride + i; row_stride = D rounded up to a
+ *                                   multiple of 4 (4, 16, 28, 52, 76 for basis_dim 1, 4, 9, 16, 25), so that a row starts 8-byte
+ *                                   aligned and every group of four logical indices that starts at a multiple of 4 is one
+ *                                   aligned 8-byte load; the padding (basis_dim 4 and 16: 3 halves) holds zeros
+ * Bytes per leaf: 2 row_stride (SH16: 104; float form 4 D = 196).  No load of the renderers leaves a row's row_stride halves. */
+
+/* Read-only view of a packed float16 tree for pxo_octree_render_half_fwd. */
+typedef struct PxoHalfTree {
+  const int32_t* child;
+  const void* data;             /* float16 [C, row_stride], 8-byte aligned */
+  int64_t n_internal;
+  int32_t data_dim;             /* 3*basis_dim + 1 */
+  int32_t basis_dim;            /* 1, 4, 9, 16 or 25 (SH<k> or SG<k>) */
+  int32_t row_stride;           /* halves per leaf: pxo_octree_half_pack_bytes */
+  float offset[3];
+  float invradius[3];
+} PxoHalfTree;
+
+/* Row stride (halves) and size (bytes) of the packed form of a tree of n_internal nodes with data_dim values per leaf
+ * (host only).  PXO_ERR_ARG unless data_dim is 3 k + 1 with k in {1, 4, 9, 16, 25}. */
+int pxo_octree_half_pack_bytes(int64_t n_internal, int data_dim, int32_t* row_stride, int64_t* bytes);
+/* Packs `src`, the file's data[:n_internal] uploaded as it is (device float16 [C, D]), into `packed` (`bytes` bytes, 8-byte
+ * aligned): the same halves at the row stride above, zeros in the padding. */
+int pxo_octree_half_pack(const void* src, int64_t n_internal, int data_dim, void* packed, size_t packed_bytes, void* stream);
+/* pxo_octree_render_fwd (lobes == NULL, ndc == NULL), pxo_octree_render_sg_fwd (lobes: the [basis_dim,4] lobes) or
+ * pxo_octree_render_ndc_fwd (ndc) on a float16 tree read in place: the same kernel with another load.  Rays, march, sample
+ * sequence, early stop, its rescale and the background are those of the float entry point, and so are, per lanes-per-ray
+ * setting (the forward value of pxo_octree_set_lanes_per_ray), the lane that owns a logical coefficient and the order of the
+ * multiply-adds; a coefficient is its half widened to float32 at the load, sigma the half at logical index data_dim - 1.
+ * Widening is exact, so out_rgb equals, bit for bit, what the float entry point returns for the tree whose data is the
+ * widened halves.  Argument checks of the float entry points, plus: row_stride must be that of pxo_octree_half_pack_bytes,
+ * data 8-byte aligned, and lobes together with ndc is PXO_ERR_ARG (SG trees have no NDC form).  Forward only. */
+int pxo_octree_render_half_fwd(const PxoHalfTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                               const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts,
+                               float* out_rgb, void* stream, const PxoNdc* ndc);
+/* pxo_octree_render_aux_fwd on a float16 tree (SH, world space): out_rgb and out_aux equal the float entry point's bit for
+ * bit.  Same argument checks as pxo_octree_render_half_fwd, plus those on surface_thresh and out_aux. */
+int pxo_octree_render_half_aux_fwd(const PxoHalfTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                   const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
+                                   float* out_rgb, float* out_aux, void* stream);
+
 /* ---- work counters of the marchers (roofline pass: scripts/octree_bench.py states each kernel's algorithmic bytes from
  *      these; nothing on the product path calls them) ----
  * One thread per ray repeats the renderer's / the weight mask's march -- same ray set-up, leaf lookup, step rule and early

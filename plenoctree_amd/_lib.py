@@ -87,6 +87,11 @@ class PxoQuantTree(Structure):
                 ("idx_stride", c_int32), ("ret_stride", c_int32), ("offset", c_float * 3), ("invradius", c_float * 3)]
 
 
+class PxoHalfTree(Structure):
+    _fields_ = [("child", c_void_p), ("data", c_void_p), ("n_internal", c_int64), ("data_dim", c_int32),
+                ("basis_dim", c_int32), ("row_stride", c_int32), ("offset", c_float * 3), ("invradius", c_float * 3)]
+
+
 class PxoOccGrid(Structure):
     _fields_ = [("bits", c_void_p), ("reso", c_int32), ("offset", c_float * 3), ("scale", c_float * 3), ("outside_live", c_int32)]
 
@@ -215,6 +220,12 @@ SIGNATURES = {
                                             POINTER(PxoRenderOpts), P, P]),
     "pxo_octree_render_quant_aux_fwd": (c_int, [POINTER(PxoQuantTree), POINTER(PxoCamera), P, P, P, c_int64,
                                                 POINTER(PxoRenderOpts), c_float, P, P, P]),
+    "pxo_octree_half_pack_bytes": (c_int, [c_int64, c_int, POINTER(c_int32), POINTER(c_int64)]),
+    "pxo_octree_half_pack": (c_int, [P, c_int64, c_int, P, c_size_t, P]),
+    "pxo_octree_render_half_fwd": (c_int, [POINTER(PxoHalfTree), P, POINTER(PxoCamera), P, P, P, c_int64,
+                                           POINTER(PxoRenderOpts), P, P, POINTER(PxoNdc)]),
+    "pxo_octree_render_half_aux_fwd": (c_int, [POINTER(PxoHalfTree), POINTER(PxoCamera), P, P, P, c_int64,
+                                               POINTER(PxoRenderOpts), c_float, P, P, P]),
     "pxo_octree_count_work": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), POINTER(PxoRenderOpts), P, P, P]),
     "pxo_grid_weight_count_work": (c_int, [P, c_int, P, c_int, c_float, c_float, c_int, c_int, POINTER(PxoRenderOpts),
                                            F3, F3, P, P, P]),

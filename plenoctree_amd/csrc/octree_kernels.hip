@@ -830,6 +830,49 @@ struct AuxOut {
   float surface_thresh;
 };
 struct RenderAuxArgs : RenderArgs, AuxOut {};
+// The argument block of a float16 tree (PxoHalfTree): RenderArgs member for member with the other tree view, so that the
+// forward kernel reads A.tree / A.opt / A.lobes / A.ndc of either.
+struct HalfRenderArgs {
+  PxoHalfTree tree;
+  PxoCamera cam;
+  int has_cam;
+  const float* origins;
+  const float* dirs;
+  const float* viewdirs;
+  int64_t B;
+  PxoRenderOpts opt;
+  const float* lobes;
+  PxoNdc ndc;
+};
+__device__ __forceinline__ void ray_basis(const HalfRenderArgs& A, int basis_dim, const float (&vdir)[3], float* Y) {
+  if (A.lobes) sg_basis_dyn(basis_dim, A.lobes, vdir[0], vdir[1], vdir[2], Y);
+  else sh_basis_dyn(basis_dim, vdir[0], vdir[1], vdir[2], Y);
+}
+struct HalfRenderAuxArgs : HalfRenderArgs, AuxOut {};
+// ST: what a leaf row stores, float (PxoTree) or _Float16 (PxoHalfTree)
+template <typename ST, bool AUX> struct FwdArgs { using type = std::conditional_t<AUX, RenderAuxArgs, RenderArgs>; };
+template <bool AUX> struct FwdArgs<_Float16, AUX> { using type = std::conditional_t<AUX, HalfRenderAuxArgs, HalfRenderArgs>; };
+
+// Four consecutive halves of a float16 leaf row, widened (exactly) to float32.  ALIGN: what is known at compile time of the
+// first half's index modulo 4 -- rows start 8-byte aligned (row_stride is a multiple of 4).  0: one 8-byte load; 2: two
+// 4-byte loads; 1 or 3: a half, an aligned pair, a half.  No piece reads outside [p, p + 4).
+typedef _Float16 f16x4a __attribute__((ext_vector_type(4), aligned(8)));
+typedef _Float16 f16x2a __attribute__((ext_vector_type(2), aligned(4)));
+template <int ALIGN>
+__device__ __forceinline__ f32x4u load_half4(const _Float16* __restrict__ p) {
+  f32x4u v;
+  if constexpr (ALIGN == 0) {
+    const f16x4a h = *reinterpret_cast<const f16x4a*>(p);
+    v[0] = (float)h[0]; v[1] = (float)h[1]; v[2] = (float)h[2]; v[3] = (float)h[3];
+  } else if constexpr (ALIGN == 2) {
+    const f16x2a a = *reinterpret_cast<const f16x2a*>(p), b = *reinterpret_cast<const f16x2a*>(p + 2);
+    v[0] = (float)a[0]; v[1] = (float)a[1]; v[2] = (float)b[0]; v[3] = (float)b[1];
+  } else {
+    const f16x2a m = *reinterpret_cast<const f16x2a*>(p + 1);
+    v[0] = (float)p[0]; v[1] = (float)m[0]; v[2] = (float)m[1]; v[3] = (float)p[3];
+  }
+  return v;
+}
 
 // Per-row marching state + the leaf lookup with path reuse.
 struct Marcher {
@@ -945,8 +988,12 @@ __device__ __forceinline__ RowId row_ray(const Args& A, int row, float (&origin)
 // sample distance, surface = distance of the sample at which the transmittance first falls to A.surface_thresh -- written to
 // A.out[ray*3 + c] by the lanes that write out_rgb.  A sample's distance is (t + delta / 2) delta_scale with the sample's OWN
 // t, kept in t_cur across the pipeline's advance of t.
-template <int MODE, int ROW, bool VEC = false, int KF = 0, bool AUX = false>
-__global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::conditional_t<AUX, RenderAuxArgs, RenderArgs> A,
+// ST = _Float16 (forward, VEC): the tree is a PxoHalfTree.  A leaf row is row_stride halves, logical index i at half i; a
+// coefficient and sigma are widened to float32 as they are loaded (load_half4 for the groups of four), and every lane owns
+// the logical indices, multiplies and adds in the order of the float instantiation with the same MODE, ROW, KF and AUX: the
+// two return the same bits for a tree whose float data is the widened halves.
+template <int MODE, int ROW, bool VEC = false, int KF = 0, bool AUX = false, typename ST = float>
+__global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(typename FwdArgs<ST, AUX>::type A,
                                                                         float* __restrict__ out_rgb,
                                                                         const float* __restrict__ fwd_rgb,
                                                                         const float* __restrict__ grad_out,
@@ -985,6 +1032,8 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
   __builtin_amdgcn_wave_barrier();
   static_assert(!VEC || MODE == 0, "vector loads: forward only (the gradient scatter wants contiguous dword rows)");
   static_assert(KF == 0 || (VEC && MODE == 0), "channel-aligned paths: forward, vector loads");
+  constexpr bool HALF = std::is_same_v<ST, _Float16>;
+  static_assert(std::is_same_v<ST, float> || (HALF && VEC && MODE == 0 && KF >= 0), "float16 rows: forward, vector loads, K known");
   const int Kc = KF > 0 ? KF : K;                    // compile-time when the launch is specialised for the tree's format
   constexpr int kChM = ((KF > 0 ? KF / 4 : 6) + ROW - 1) / ROW > 0 ? ((KF > 0 ? KF / 4 : 6) + ROW - 1) / ROW : 1;   // K <= 25: <= 6 whole groups
   const int chG = Kc >> 2, chR = Kc & 3;
@@ -1012,8 +1061,10 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
     b1[j] = ch == 1 ? bas : 0.0f;
     b2[j] = ch == 2 ? bas : 0.0f;
   }
-  const float* __restrict__ data = A.tree.data;
+  const ST* __restrict__ data = static_cast<const ST*>(A.tree.data);
   const int32_t* __restrict__ child = A.tree.child;
+  int row_elems = D;                           // from a leaf's row to the next, in elements of ST
+  if constexpr (HALF) row_elems = A.tree.row_stride;
 
   float g[3] = {0.f, 0.f, 0.f};
   if (MODE == 1) {
@@ -1046,10 +1097,10 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
     bool more = t < r.tmax;
     if (more) locate(t, leaf, delta_t);
     while (more) {
-      const float* __restrict__ val = data + leaf * D;
-      const float sg = val[D - 1];
+      const ST* __restrict__ val = data + leaf * row_elems;
+      const float sg = (float)val[D - 1];
       const float tn = t + delta_t;
-      more = tn > t && tn < r.tmax;              // !(tn > t): step below the resolution of t, stop rather than spin
+      more = tn > t && tn < r.tmax;           // !(tn > t): step below the resolution of t, stop rather than spin
       const int64_t leaf_cur = leaf;
       const float delta_cur = delta_t;
       const float t_cur = t;
@@ -1065,9 +1116,16 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
           for (int m = 0; m < kChM; ++m) {
             const int g = l + kRow * m;
             if (g < chG) {
-              const f32x4u c0 = *reinterpret_cast<const f32x4u*>(val + 4 * g);
-              const f32x4u c1 = *reinterpret_cast<const f32x4u*>(val + Kc + 4 * g);
-              const f32x4u c2 = *reinterpret_cast<const f32x4u*>(val + 2 * Kc + 4 * g);
+              f32x4u c0, c1, c2;
+              if constexpr (HALF) {                // channel c starts at half c K: its alignment is that of c KF modulo 4
+                c0 = load_half4<0>(val + 4 * g);
+                c1 = load_half4<KF % 4>(val + Kc + 4 * g);
+                c2 = load_half4<2 * KF % 4>(val + 2 * Kc + 4 * g);
+              } else {
+                c0 = *reinterpret_cast<const f32x4u*>(val + 4 * g);
+                c1 = *reinterpret_cast<const f32x4u*>(val + Kc + 4 * g);
+                c2 = *reinterpret_cast<const f32x4u*>(val + 2 * Kc + 4 * g);
+              }
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 p0 += c0[e] * bk[4 * m + e];
@@ -1078,19 +1136,21 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
           }
           if (l < chR) {
             const int k = 4 * chG + l;
-            p0 += val[k] * bk_r;
-            p1 += val[Kc + k] * bk_r;
-            p2 += val[2 * Kc + k] * bk_r;
+            p0 += (float)val[k] * bk_r;
+            p1 += (float)val[Kc + k] * bk_r;
+            p2 += (float)val[2 * Kc + k] * bk_r;
           }
         } else if (VEC) {
 #pragma unroll
           for (int j = 0; j < G::kMaxGroups; ++j) {
             const int g4 = 4 * (l + kRow * j);
             if (j < nload && g4 < D - 1) {
-              const f32x4u v4 = *reinterpret_cast<const f32x4u*>(val + g4);
+              f32x4u v4;
+              if constexpr (HALF) v4 = load_half4<0>(val + g4);         // g4 + 3 < row_stride: inside the row's padding at most
+              else v4 = *reinterpret_cast<const f32x4u*>(val + g4);
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                const float v = g4 + e < D - 1 ? v4[e] : 0.0f;          // the row's last float is sigma, not a coefficient
+                const float v = g4 + e < D - 1 ? v4[e] : 0.0f;         // the row's last float is sigma, not a coefficient
                 p0 += v * b0[4 * j + e];
                 p1 += v * b1[4 * j + e];
                 p2 += v * b2[4 * j + e];
@@ -1102,7 +1162,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(std::cond
           for (int j = 0; j < kMaxLoads; ++j) {
             if (j < nload) {
               const int idx = l + kRow * j;
-              const float v = idx < D - 1 ? val[idx] : 0.0f;
+              const float v = idx < D - 1 ? (float)val[idx] : 0.0f;
               p0 += v * b0[j];
               p1 += v * b1[j];
               p2 += v * b2[j];
@@ -1650,6 +1710,17 @@ __global__ void quant_pack_sigma_kernel(const T* __restrict__ src, int64_t cells
   if (i < cells) dst[i] = (float)src[i];
 }
 
+// float16 trees (PxoHalfTree): the file's [cells, D] rows at a stride of row_stride halves, zeros in the padding.  One thread
+// per packed half.
+__global__ void half_pack_kernel(const _Float16* __restrict__ src, int64_t cells, int D, int row_stride,
+                                 _Float16* __restrict__ dst) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= cells * row_stride) return;
+  const int64_t r = i / row_stride;
+  const int e = (int)(i - r * row_stride);
+  dst[i] = e < D ? src[r * D + e] : (_Float16)0.0f;
+}
+
 struct QuantRenderArgs {
   PxoQuantTree tree;
   PxoCamera cam;
@@ -1990,6 +2061,25 @@ static void launch_render_fwd(const std::conditional_t<AUX, RenderAuxArgs, Rende
       case 16: kernel = octree_render_kernel<0, 4, true, 16, AUX>; break;
       case 25: kernel = octree_render_kernel<0, 4, true, 25, AUX>; break;
       default: kernel = octree_render_kernel<0, 4, true, -1, AUX>; break;
+    }
+  }
+  const float* none = nullptr;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr);
+}
+
+// Forward launch of a float16 tree: launch_render_fwd's choice of instantiation, with float16 rows.  The caller has checked
+// basis_dim (check_format), so there is no run-time-K variant.
+template <bool AUX>
+static void launch_half_fwd(const std::conditional_t<AUX, HalfRenderAuxArgs, HalfRenderArgs>& A, int row, unsigned grid,
+                            float* out_rgb, void* stream) {
+  auto kernel = row == 8 ? octree_render_kernel<0, 8, true, 0, AUX, _Float16> : octree_render_kernel<0, 16, true, 0, AUX, _Float16>;
+  if (row == 4) {
+    switch (A.tree.basis_dim) {
+      case 1: kernel = octree_render_kernel<0, 4, true, 1, AUX, _Float16>; break;
+      case 4: kernel = octree_render_kernel<0, 4, true, 4, AUX, _Float16>; break;
+      case 9: kernel = octree_render_kernel<0, 4, true, 9, AUX, _Float16>; break;
+      case 16: kernel = octree_render_kernel<0, 4, true, 16, AUX, _Float16>; break;
+      default: kernel = octree_render_kernel<0, 4, true, 25, AUX, _Float16>; break;
     }
   }
   const float* none = nullptr;
@@ -2566,6 +2656,92 @@ int pxo_octree_render_quant_aux_fwd(const PxoQuantTree* tree, const PxoCamera* c
   A.surface_thresh = surface_thresh;
   launch_quant_fwd<true>(A, row, grid, out_rgb, stream);
   return check_launch("octree_render_quant_aux_fwd");
+}
+
+// ---- float16 trees rendered in place (the data array of the files N3Tree.save writes) ----
+static int half_format_ok(int64_t n_internal, int data_dim, const char* who) {
+  PXO_REQUIRE(data_dim >= 4 && (data_dim - 1) % 3 == 0, "%s: data_dim %d is not 3*basis_dim+1", who, data_dim);
+  if (int rc = check_format((data_dim - 1) / 3, data_dim, "SH", who)) return rc;
+  PXO_REQUIRE(n_internal >= 1 && n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
+  return PXO_OK;
+}
+
+int pxo_octree_half_pack_bytes(int64_t n_internal, int data_dim, int32_t* row_stride, int64_t* bytes) {
+  if (int rc = half_format_ok(n_internal, data_dim, "pxo_octree_half_pack_bytes")) return rc;
+  PXO_REQUIRE(row_stride && bytes, "pxo_octree_half_pack_bytes: null output");
+  *row_stride = (data_dim + 3) & ~3;
+  *bytes = n_internal * 8 * *row_stride * 2;
+  return PXO_OK;
+}
+
+int pxo_octree_half_pack(const void* src, int64_t n_internal, int data_dim, void* packed, size_t packed_bytes, void* stream) {
+  int32_t row_stride;
+  int64_t bytes;
+  if (int rc = pxo_octree_half_pack_bytes(n_internal, data_dim, &row_stride, &bytes)) return rc;
+  PXO_REQUIRE(src && packed, "pxo_octree_half_pack: null pointer");
+  PXO_REQUIRE(((uintptr_t)packed & 7) == 0, "pxo_octree_half_pack: packed buffer must be 8-byte aligned");
+  if (packed_bytes < (size_t)bytes) {
+    set_error("pxo_octree_half_pack: buffer %zu < %lld", packed_bytes, (long long)bytes);
+    return PXO_ERR_WORKSPACE;
+  }
+  const int64_t cells = n_internal * 8;          // < 2^31 cells x at most 76 halves: fewer than 2^31 blocks of 256
+  hipLaunchKernelGGL(half_pack_kernel, dim3((unsigned)blocks_for(cells * row_stride, 256)), dim3(256), 0, (hipStream_t)stream,
+                     static_cast<const _Float16*>(src), cells, data_dim, (int)row_stride, static_cast<_Float16*>(packed));
+  return check_launch("octree_half_pack");
+}
+
+// the argument checks and the launch shape of the float16 renderers: those of render_args, plus row_stride and alignment
+static int half_render_args(const PxoHalfTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                            const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const char* who,
+                            HalfRenderArgs& A, unsigned& grid, int& row) {
+  if (int rc = check_opts(opts, who)) return rc;
+  PXO_REQUIRE(tree && tree->child && tree->data, "%s: null tree", who);
+  if (int rc = check_format(tree->basis_dim, tree->data_dim, lobes ? "SG" : "SH", who)) return rc;
+  PXO_REQUIRE(tree->n_internal >= 1 && tree->n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
+  PXO_REQUIRE(tree->row_stride == ((tree->data_dim + 3) & ~3), "%s: row_stride %d is not that of pxo_octree_half_pack_bytes (%d)",
+              who, tree->row_stride, (tree->data_dim + 3) & ~3);
+  PXO_REQUIRE(((uintptr_t)tree->data & 7) == 0, "%s: data must be 8-byte aligned", who);
+  row = render_row(false);
+  A.tree = *tree;
+  A.opt = *opts;
+  A.lobes = lobes;
+  A.ndc = kNoNdc;
+  return launch_shape(cam, origins, dirs, viewdirs, B, row, who, A, grid);
+}
+
+int pxo_octree_render_half_fwd(const PxoHalfTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                               const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb,
+                               void* stream, const PxoNdc* ndc) {
+  const char* who = "pxo_octree_render_half_fwd";
+  PXO_REQUIRE(!(lobes && ndc), "%s: SG trees have no NDC form (lobes and ndc are both set)", who);
+  if (ndc)
+    if (int rc = check_ndc(ndc, who)) return rc;
+  HalfRenderArgs A;
+  unsigned grid;
+  int row;
+  if (int rc = half_render_args(tree, lobes, cam, origins, dirs, viewdirs, B, opts, who, A, grid, row)) return rc;
+  if (ndc) A.ndc = *ndc;
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(out_rgb, "%s: null output", who);
+  launch_half_fwd<false>(A, row, grid, out_rgb, stream);
+  return check_launch("octree_render_half_fwd");
+}
+
+int pxo_octree_render_half_aux_fwd(const PxoHalfTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                   const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
+                                   float* out_rgb, float* out_aux, void* stream) {
+  const char* who = "pxo_octree_render_half_aux_fwd";
+  HalfRenderAuxArgs A;
+  unsigned grid;
+  int row;
+  if (int rc = half_render_args(tree, nullptr, cam, origins, dirs, viewdirs, B, opts, who, A, grid, row)) return rc;
+  if (int rc = check_surface_thresh(opts, surface_thresh, who)) return rc;
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(out_rgb && out_aux, "%s: null output", who);
+  A.out = out_aux;
+  A.surface_thresh = surface_thresh;
+  launch_half_fwd<true>(A, row, grid, out_rgb, stream);
+  return check_launch("octree_render_half_aux_fwd");
 }
 
 int pxo_octree_count_work(const PxoTree* tree, const PxoCamera* cam, const PxoRenderOpts* opts, unsigned long long* counts,

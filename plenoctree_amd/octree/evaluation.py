@@ -3,6 +3,8 @@ mean PSNR of its renders of the test split; test images are sharded over the GPU
 
     python -m plenoctree_amd.octree.evaluation --input tree_opt.npz --config blender --data_dir ... [--write_images DIR]
         [--keep_compressed]     (a tree written by octree.compression is rendered from its palette form, in place)
+        [--keep_half]           (an uncompressed tree is rendered from the float16 data of its file, in place: the images of
+                                 the float tree bit for bit; SH, SG and NDC scenes, --write_aux / --write_points on SH trees)
         [--write_aux DIR]       (per view NNN_rgba.png, the render with its opacity as the alpha channel, and NNN_depth.npz
                                  with float32 depth / surface / alpha; distances are Euclidean, from the camera origin)
         [--write_points F.ply]  (every --points_stride-th pixel of every view whose transmittance falls to --surface_thresh,
@@ -32,6 +34,9 @@ def define_flags():
     a("--no_early_stop", action="store_true")
     a("--keep_compressed", action="store_true",
       help="evaluate a compressed tree (octree.compression) in its palette form instead of re-inflating it to float32")
+    a("--keep_half", action="store_true",
+      help="evaluate an uncompressed tree from the float16 data of its file, in place, instead of widening it to float32 "
+           "(the same images bit for bit, half the device memory)")
     # not reference flags: the renderer's opacity / distance outputs (VolumeRenderer.render_persp_aux)
     a("--write_aux", type=str, default=None, help="directory for NNN_rgba.png and NNN_depth.npz of every test view")
     a("--write_points", type=str, default=None, help="binary PLY of the back-projected surface points of all test views")
@@ -90,6 +95,9 @@ def main(argv=None):
         # checked BEFORE anything is rendered: imageio / ffmpeg are not installed, so only the animated GIF writer is built
         raise ValueError(f"--write_vid {args.write_vid}: only animated GIF output is built (no imageio/ffmpeg here); "
                          "give a .gif path")
+    if args.keep_half and args.keep_compressed:
+        raise ValueError("--keep_half together with --keep_compressed: a file holds either float16 data or the palette form; "
+                         "give the flag that matches --input")
     extraction.check_octree_flags(args, "octree.evaluation", (("--keep_compressed", args.keep_compressed),
                                                               ("--write_aux", args.write_aux is not None),
                                                               ("--write_points", args.write_points is not None)))
@@ -101,9 +109,13 @@ def main(argv=None):
     if comm.rank == 0:
         print("N3Tree load", args.input, flush=True)
     check_sg_flags(args)
-    tree = N3Tree.load(args.input, map_location=device, keep_quantized=args.keep_compressed)   # not compressed + flag: ValueError
+    tree = N3Tree.load(args.input, map_location=device, keep_quantized=args.keep_compressed,   # not compressed + flag: ValueError
+                       keep_half=args.keep_half)                                               # compressed + flag: ValueError
     if args.keep_compressed and comm.rank == 0:
         print(f"compressed tree kept in place: {tree.nbytes / 2 ** 20:.1f} MB on the device "
+              f"(float form: {tree.float_nbytes / 2 ** 20:.1f} MB)", flush=True)
+    if args.keep_half and comm.rank == 0:
+        print(f"float16 tree kept in place: {tree.nbytes / 2 ** 20:.1f} MB on the device "
               f"(float form: {tree.float_nbytes / 2 ** 20:.1f} MB)", flush=True)
     want_frames = args.write_images is not None or args.write_vid is not None
     if want_aux:

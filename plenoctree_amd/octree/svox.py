@@ -456,11 +456,25 @@ class N3Tree:
         (np.savez_compressed if compress else np.savez)(path, **z)
 
     @classmethod
-    def load(cls, path, device="cpu", map_location=None, keep_quantized=False):
+    def load(cls, path, device="cpu", map_location=None, keep_quantized=False, keep_half=False):
         """svox N3Tree.load.  A compressed file (octree/compression.py) is re-inflated to float32 `data`, unless
-        `keep_quantized`: then the palette form is kept as it is and a read-only QuantizedN3Tree comes back."""
+        `keep_quantized`: then the palette form is kept as it is and a read-only QuantizedN3Tree comes back.
+        `keep_half`: the float16 `data` of an uncompressed file is kept as it is (SH or SG) and a read-only HalfN3Tree comes
+        back, which renders exactly what the float tree of the same file renders."""
         dev = torch.device(map_location if map_location is not None else device)
+        if keep_half and keep_quantized:
+            raise ValueError(f"{path}: keep_half=True together with keep_quantized=True: a file holds either float16 data or the "
+                             "palette form; choose one")
         z = np.load(path)
+        if keep_half:
+            if "data" not in z.files:
+                what = "a compressed tree (the palette form): load it with keep_quantized=True" if "quant_colors" in z.files \
+                    else "no data array"
+                raise ValueError(f"{path}: keep_half=True needs the float16 data of an uncompressed tree; the file has {what}")
+            data = z["data"]
+            if data.dtype != np.float16:
+                raise ValueError(f"{path}: keep_half=True needs float16 data; the file's data is {data.dtype}")
+            return HalfN3Tree(z, data, dev)
         if keep_quantized:
             if "quant_colors" not in z.files:
                 raise ValueError(f"{path}: keep_quantized=True needs a compressed tree (no quant_colors in the file)")
@@ -726,6 +740,111 @@ class QuantizedN3Tree:
         self._read_only("save")
 
 
+class HalfN3Tree:
+    """An uncompressed tree kept in the float16 of its file: `N3Tree.load(path, keep_half=True)`.
+
+    Read-only.  It has the geometry of an N3Tree (child, parent_depth, offset, invradius, depth_limit, data_format,
+    extra_data for an SG file, n_internal, max_depth, device) and is rendered in place by VolumeRenderer, bit for bit as the
+    float tree of the same file: on a GPU device the file's data is uploaded as it is and laid out there at the row stride
+    of include/plenoctree_octree.h (PxoHalfTree).  There is no float `data`: everything that needs or edits float leaf values
+    goes through `to_float()`."""
+
+    def __init__(self, z, data, dev):
+        n = _load_geometry(self, z, dev)
+        if data.ndim != 5 or data.shape[0] < n or data.shape[1:] != (2, 2, 2, self.data_dim):
+            raise ValueError(f"data: shape {data.shape} does not hold [{n}, 2, 2, 2, {self.data_dim}] leaves like child")
+        self.row_stride, self._packed_bytes = oops.half_layout(n, self.data_dim)
+        half = torch.from_numpy(np.ascontiguousarray(data[:n]))
+        self._half, self._packed = None, None
+        if dev.type == "cuda":
+            self._packed, _ = oops.half_pack(half.to(dev), n)        # the upload is dropped once it is laid out
+        else:
+            self._half = half
+
+    basis_dim = N3Tree.basis_dim
+    data_dim = N3Tree.data_dim
+    n_internal = N3Tree.n_internal
+    n_leaves = N3Tree.n_leaves
+    max_depth = N3Tree.max_depth
+    basis_kwargs = N3Tree.basis_kwargs
+
+    @property
+    def device(self):
+        return self.child.device
+
+    @property
+    def nbytes(self):
+        """Device bytes of this form: the float16 rows at their stride + child + parent_depth."""
+        return int(self._packed_bytes) + 4 * (self.child.numel() + self.parent_depth.numel())
+
+    @property
+    def float_nbytes(self):
+        """Device bytes the float form (`to_float()`, what N3Tree.load makes of the same file) takes."""
+        return 4 * self.n_internal * 8 * self.data_dim + 4 * (self.child.numel() + self.parent_depth.numel())
+
+    def half_view(self):
+        if self._packed is None:
+            raise PxoError("a HalfN3Tree renders on a ROCm device only (there is no CPU fallback): load it with map_location='cuda'")
+        return oops.half_tree_view(self.child, self._packed, self.data_dim, self.offset, self.invradius)
+
+    def to_float(self):
+        """The float N3Tree that `N3Tree.load(path)` makes of the same file, on this tree's device."""
+        n, D = self.n_internal, self.data_dim
+        half = self._half if self._packed is None else self._packed[:, :D].reshape(n, 2, 2, 2, D)
+        t = object.__new__(N3Tree)
+        t.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("row_stride", "_packed_bytes", "_half", "_packed")})
+        t.child, t.parent_depth = self.child.clone(), self.parent_depth.clone()
+        t.invradius, t.offset = self.invradius.clone(), self.offset.clone()
+        t.extra_data = None if self.extra_data is None else self.extra_data.clone()
+        t.level_nodes = list(self.level_nodes)
+        t.data = torch.nn.Parameter(half.float().contiguous())
+        return t
+
+    def __repr__(self):
+        return (f"svox.HalfN3Tree(N=2, data_format:{self.data_format}, n_internal:{self.n_internal}, row_stride:{self.row_stride}, "
+                f"{self.nbytes / 2 ** 20:.1f} MB on the device, float form {self.float_nbytes / 2 ** 20:.1f} MB)")
+
+    def _read_only(self, what):
+        raise PxoError(f"{what}: a HalfN3Tree is read-only and has no float leaf data; call to_float() for an N3Tree")
+
+    @property
+    def data(self):
+        self._read_only("tree.data")
+
+    def parameters(self):
+        self._read_only("tree.parameters()")
+
+    def __getitem__(self, key):
+        self._read_only("tree[...]")
+
+    def __setitem__(self, key, value):
+        self._read_only("tree[...] = value")
+
+    def refine(self, *args, **kwargs):
+        self._read_only("refine")
+
+    def refine_from_mask(self, mask):
+        self._read_only("refine_from_mask")
+
+    def relu_sigma_(self):
+        self._read_only("relu_sigma_")
+
+    def accumulate_weights(self, op="sum"):
+        self._read_only("accumulate_weights")
+
+    def prune_(self, keep, collapse=True):
+        self._read_only("prune_")
+
+    def refine_leaves(self, mask):
+        self._read_only("refine_leaves")
+
+    def view(self):
+        self._read_only("view()")
+
+    def save(self, path, shrink=True, compress=True):
+        self._read_only("save")
+
+
 def parent_depth_from_child(child):
     """Rebuilds parent_depth [n,2] from the child offsets (compressed npz files drop it, compression.py:77)."""
     n = child.shape[0]
@@ -771,7 +890,11 @@ class VolumeRenderer:
     given in world space; every ray is converted as include/plenoctree_octree.h ("forward-facing scenes") and DESIGN section 13
     define: the SH basis on the world-space direction, convert_to_ndc, a unit NDC direction, then the unchanged march (step
     lengths are NDC lengths, what the NeRF integrated sigma over).  svox's own NDC kernel could not be compared.  Float SH
-    trees only: a QuantizedN3Tree, an SG tree and the alpha / depth / surface outputs are refused by name."""
+    trees only: a QuantizedN3Tree, an SG tree and the alpha / depth / surface outputs are refused by name.
+
+    A HalfN3Tree renders wherever the float tree of the same file does (SH and SG in world space, SH with ndc, the alpha /
+    depth / surface outputs on SH in world space), the same values bit for bit, and is refused where that tree is, in the same
+    words.  It is never differentiable."""
 
     def __init__(self, tree, step_size=1e-3, background_brightness=1.0, ndc=None):
         if ndc is not None:
@@ -816,6 +939,10 @@ class VolumeRenderer:
         if isinstance(self.tree, QuantizedN3Tree):
             # nothing in a compressed tree requires grad: rendered directly, with grad mode on as well, `fast` both ways
             return oops.octree_render_quant_persp(self.tree.quant_view(), c2w, width, height, fx, self._opts(fast), fy)
+        if isinstance(self.tree, HalfN3Tree):
+            # read-only as well: the float tree's launch on the file's float16 rows, the same image bit for bit
+            return oops.octree_render_half_persp(self.tree.half_view(), c2w, width, height, fx, self._opts(fast), fy,
+                                                 **self._basis_kwargs())
         data = self.tree.data
         differentiable = torch.is_grad_enabled() and data.requires_grad
         accum = self.tree._weight_accum
@@ -838,6 +965,9 @@ class VolumeRenderer:
         (world space) shade them."""
         if isinstance(self.tree, QuantizedN3Tree):
             return oops.octree_render_quant_rays(self.tree.quant_view(), origins, dirs, viewdirs, self._opts(fast))
+        if isinstance(self.tree, HalfN3Tree):
+            return oops.octree_render_half_rays(self.tree.half_view(), origins, dirs, viewdirs, self._opts(fast),
+                                                **self._basis_kwargs())
         accum = self.tree._weight_accum
         if accum is not None:
             oops.octree_weight_accum_rays(self.tree.view(), origins, dirs, self._opts(fast), accum.op, accum._buffer(),
@@ -856,6 +986,8 @@ class VolumeRenderer:
                                       "trees only")
         if isinstance(self.tree, QuantizedN3Tree):
             return self.tree.quant_view()
+        if isinstance(self.tree, HalfN3Tree):
+            return self.tree.half_view()
         if torch.is_grad_enabled() and self.tree.data.requires_grad:
             raise oops.PxoError(f"{what} is not differentiable (alpha, depth and surface have no gradient kernel): call it "
                                 "under torch.no_grad()")

@@ -426,13 +426,100 @@ def octree_render_quant_rays(qtree, origins, dirs, viewdirs, opts):
     return out
 
 
+# ---- float16 trees rendered in place (the data array of the files N3Tree.save writes) ----
+def half_layout(n_internal, data_dim):
+    """(row_stride in halves, bytes) of the packed form (host only: no GPU needed)."""
+    stride, nbytes = ctypes.c_int32(0), ctypes.c_int64(0)
+    check(_lib.load().pxo_octree_half_pack_bytes(int(n_internal), int(data_dim), ctypes.byref(stride), ctypes.byref(nbytes)),
+          "pxo_octree_half_pack_bytes")
+    return stride.value, nbytes.value
+
+
+def half_pack(data, n_internal):
+    """The file's data[:n_internal], uploaded as it is (float16 [n, 2,2,2, D] or [n*8, D]) -> (the packed float16 buffer
+    [n*8, row_stride], row_stride)."""
+    _require_gpu()
+    if data.dtype != torch.float16 or not data.is_contiguous():
+        raise PxoError("half_pack: data must be a contiguous float16 tensor")
+    data_dim = data.shape[-1]
+    if data.numel() != n_internal * 8 * data_dim:
+        raise PxoError("half_pack: array size does not match (n_internal, data_dim)")
+    stride, nbytes = half_layout(n_internal, data_dim)
+    packed = torch.empty(n_internal * 8, stride, dtype=torch.float16, device=data.device)
+    check(_lib.load().pxo_octree_half_pack(_p(data), n_internal, data_dim, _p(packed), nbytes, _stream()),
+          "pxo_octree_half_pack")
+    return packed, stride
+
+
+def half_tree_view(child, packed, data_dim, offset, invradius):
+    """PxoHalfTree struct over torch storage (keeps no reference: the caller owns the tensors)."""
+    if child.dtype != torch.int32:
+        raise PxoError("child must be int32")
+    stride, nbytes = half_layout(child.shape[0], data_dim)
+    if packed.dtype != torch.float16 or not packed.is_contiguous() or packed.numel() * 2 < nbytes:
+        raise PxoError("packed buffer is smaller than its layout")
+    t = _lib.PxoHalfTree()
+    t.child = _p(child).value
+    t.data = _p(packed).value
+    t.n_internal = child.shape[0]
+    t.data_dim = int(data_dim)
+    t.basis_dim = (int(data_dim) - 1) // 3
+    t.row_stride = stride
+    t.offset = _vec3(offset)
+    t.invradius = _vec3(invradius)
+    return t
+
+
+def _render_half_fwd(htree, lobes, rays, opts, out, ndc):
+    _no_sg_ndc(lobes, ndc)
+    check(_lib.load().pxo_octree_render_half_fwd(ctypes.byref(htree), None if lobes is None else _lobes(lobes, htree), *rays,
+                                                 ctypes.byref(opts), _f(out), _stream(),
+                                                 None if ndc is None else ctypes.byref(_ndc(ndc))),
+          "pxo_octree_render_half_fwd")
+    return out
+
+
+def octree_render_half_persp(htree, c2w, width, height, fx, opts, fy=None, lobes=None, ndc=None):
+    """octree_render_persp on a PxoHalfTree: bit for bit the image of the float tree with the widened data."""
+    _require_gpu()
+    cam, keep = _camera(c2w, width, height, fx, fy)
+    out = _new(height, width, 3, device=keep.device)
+    return _render_half_fwd(htree, lobes, _rays(cam), opts, out, ndc)
+
+
+def octree_render_half_rays(htree, origins, dirs, viewdirs, opts, lobes=None, ndc=None):
+    """octree_render_rays on a PxoHalfTree."""
+    _require_gpu()
+    out = _new(origins.shape[0], 3, device=origins.device)
+    return _render_half_fwd(htree, lobes, _rays(None, origins, dirs, viewdirs), opts, out, ndc)
+
+
+def _half_only(htree):
+    if not isinstance(htree, _lib.PxoHalfTree):
+        raise PxoError(f"expected a PxoHalfTree, got {type(htree).__name__}")
+
+
+def octree_render_half_aux_persp(htree, c2w, width, height, fx, opts, fy=None, surface_thresh=0.5):
+    """octree_render_aux_persp on a PxoHalfTree (SH, world space): rgb and aux bit for bit those of the float tree."""
+    _half_only(htree)
+    return octree_render_aux_persp(htree, c2w, width, height, fx, opts, fy, surface_thresh)
+
+
+def octree_render_half_aux_rays(htree, origins, dirs, viewdirs, opts, surface_thresh=0.5):
+    """octree_render_aux_rays on a PxoHalfTree (SH, world space)."""
+    _half_only(htree)
+    return octree_render_aux_rays(htree, origins, dirs, viewdirs, opts, surface_thresh)
+
+
 def _aux_entry(tree):
-    """(entry point, its name) of the renderer with the extra outputs for a PxoTree or a PxoQuantTree."""
+    """(entry point, its name) of the renderer with the extra outputs for a PxoTree, a PxoQuantTree or a PxoHalfTree."""
     if isinstance(tree, _lib.PxoQuantTree):
         return _lib.load().pxo_octree_render_quant_aux_fwd, "pxo_octree_render_quant_aux_fwd"
+    if isinstance(tree, _lib.PxoHalfTree):
+        return _lib.load().pxo_octree_render_half_aux_fwd, "pxo_octree_render_half_aux_fwd"
     if isinstance(tree, _lib.PxoTree):
         return _lib.load().pxo_octree_render_aux_fwd, "pxo_octree_render_aux_fwd"
-    raise PxoError(f"expected a PxoTree or a PxoQuantTree, got {type(tree).__name__}")
+    raise PxoError(f"expected a PxoTree, a PxoQuantTree or a PxoHalfTree, got {type(tree).__name__}")
 
 
 def octree_render_aux_persp(tree, c2w, width, height, fx, opts, fy=None, surface_thresh=0.5):
