@@ -363,6 +363,37 @@ int pxo_render_fwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float*
                           float* acc_c, float* rgb_f, float* disp_f, float* acc_f, int64_t live_rows[2], void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ---- training through the occupancy grid (entry points added without a change of PXO_ABI_VERSION) ----
+ * The inverse of pxo_occ_expand, for the reverse pass: dense row m of d_raw_rgb [M,C] / d_raw_sigma [M] with slot[m] >= 0 is
+ * copied to row slot[m] of d_rgb_live / d_sigma_live (room for M rows each); a row with slot[m] < 0 is dropped (a culled sample
+ * is the constant 0 and carries no gradient).  The slots of the live rows are distinct, so every compact element is written
+ * exactly once, by a plain store: no atomics, no memset, two calls give the same bits; compact rows no slot names are left
+ * untouched.  A slot >= M (outside the compact arrays) is dropped as well.  M < 2^31, 1 <= C <= PXO_OCC_MAX_CHANNELS. */
+int pxo_occ_gather(const float* d_raw_rgb, const float* d_raw_sigma, const int32_t* slot, int64_t M, int C, float* d_rgb_live,
+                   float* d_sigma_live, void* stream);
+
+/* pxo_train_fwd_bwd_bucketed of an SH model with both levels' MLPs -- forward AND reverse -- run on the live samples only.  Per
+ * level: the sampling launch, pxo_occ_cull, the fused-MLP forward on the compact points (acts / enc / relu mask in compact
+ * order), pxo_occ_expand, the dense shade + composite + loss launch, pxo_occ_gather of its d_raw_*, then backward(data) and
+ * the weight gradients with M = n_live (+ the sparsity points of the last level, which are always live and follow the live
+ * sample rows in the compact order).  A culled sample's raw outputs are the constants 0: the loss is that of the dense step
+ * with those rows replaced, and the gradient is the exact gradient of that loss.  With every sample live, grads and stats are
+ * pxo_train_fwd_bwd_bucketed's bit for bit.  A level without a live row launches no MLP kernel: its gradient is zero plus the
+ * weight-decay term.  The weight-gradient split is that of the compact M; skip_zero_rows, the tile schedule knob, weight decay,
+ * stats and grads0_ready (recorded after the coarse weight gradients) work as in the dense step;
+ * PXO_TUNE_COARSE_REVERSE_STREAM is ignored (everything runs on `stream`).  n_live reaches the host through one pinned 8-byte
+ * copy per level: the call synchronises `stream` twice and is not capturable into a graph.  live_rows (host, may be NULL):
+ * live SAMPLE rows of the two levels (sparsity points not counted).  PXO_ERR_UNSUPPORTED: mlp_precision bf16x3; noise_std > 0
+ * with randomized (as pxo_render_fwd_culled).  PXO_ERR_ARG: a NULL or broken grid.  The workspace is the pxo_train_fwd_bwd block
+ * with the compact arrays behind it: pxo_train_culled_workspace_bytes.  pxo_train_backward_work refuses a workspace whose last
+ * step was this one. */
+int pxo_train_culled_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes);
+int pxo_train_fwd_bwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float* params, const float* packed_fwd0,
+                             const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1, const float* origins,
+                             const float* directions, const float* viewdirs, const float* pixels, int64_t B, int randomized,
+                             const float* t_rand, const float* u, const float* sp_points, uint64_t seed, float* grads,
+                             float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream, int64_t live_rows[2]);
+
 /* ---- training a NeRF-SG (entry points added without a change of PXO_ABI_VERSION: no struct and no existing call changes) ----
  * The raw model-level parameters of a NeRF-SG (nerf_sh/nerf/models.py:107-117) travel as one device array
  * sg_params [3K] = sg_lambda [K] followed by sg_mu_spher [K,2] row-major (theta_0, phi_0, theta_1, ...), K = (cfg->sh_deg+1)^2.

@@ -153,6 +153,10 @@ SIGNATURES = {
     "pxo_render_culled_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
     "pxo_render_fwd_culled": (c_int, [CFG, POINTER(PxoOccGrid), P, P, P, P, P, P, c_int64, c_int, P, P, c_uint64, P, P, P, P, P, P,
                                       POINTER(c_int64), P, c_size_t, P]),
+    "pxo_occ_gather": (c_int, [P, P, P, c_int64, c_int, P, P, P]),
+    "pxo_train_culled_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
+    "pxo_train_fwd_bwd_culled": (c_int, [CFG, POINTER(PxoOccGrid), P, P, P, P, P, P, P, P, P, c_int64, c_int, P, P, P, c_uint64, P,
+                                         P, P, c_size_t, P, P, POINTER(c_int64)]),
     "pxo_train_workspace_bytes": (c_int, [CFG, c_int64, POINTER(c_size_t)]),
     "pxo_train_fwd_bwd": (c_int, [CFG, P, P, P, P, P, P, P, P, P, c_int64, c_int, P, P, P, c_uint64, P, P,
                                   P, c_size_t, P]),

@@ -9,6 +9,7 @@
 //            LDS, block offset from the scan): slot[] and the live points in their original order.  No atomics: two calls give
 //            the same bits.  The structure is that of the marching cubes' count / emit passes (mesh_kernels.hip).
 //   expand   the gather that puts the MLP's compact rows back: dense row m copies compact row slot[m], or is zero
+//   gather   its inverse for the reverse pass of pxo_train_fwd_bwd_culled: dense row m goes to compact row slot[m], or is dropped
 #include "pxo_common.h"
 
 namespace pxo {
@@ -250,6 +251,38 @@ __global__ __launch_bounds__(256) void occ_expand_kernel(const float* __restrict
   }
 }
 
+// ---- gather ----------------------------------------------------------------------------------------------------------------
+// occ_expand_kernel's shape the other way round: a lane per element of the DENSE d_raw_rgb [M,C] (consecutive lanes, consecutive
+// addresses on the read side, and on the write side inside every run of live rows, whose slots are consecutive); the element
+// of a live row goes to compact row slot[m], the lane of a row's first channel also moves the row's d_sigma.  The live rows'
+// slots are distinct: every compact element has one writer.  A slot outside [0, M) is dropped (the compact arrays hold M rows).
+template <int CT>
+__global__ __launch_bounds__(256) void occ_gather_kernel(const float* __restrict__ d_rgb, const float* __restrict__ d_sigma,
+                                                         const int32_t* __restrict__ slot, int64_t M, uint32_t c_runtime,
+                                                         float* __restrict__ d_rgb_live, float* __restrict__ d_sigma_live) {
+  const uint32_t C = CT > 0 ? (uint32_t)CT : c_runtime;
+  const int64_t e0 = blockIdx.x * (int64_t)kExpandPerBlock;
+  const int64_t m0 = e0 / C;
+  const uint32_t l0 = (uint32_t)(e0 - m0 * C) + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kExpandPerBlock / 256; ++k) {
+    const uint32_t l = l0 + 256u * k;
+    const uint32_t dm = l / C, c = l - dm * C;
+    const int64_t m = m0 + dm;
+    if (m >= M) return;                               // rows only grow with k
+    const int32_t s = slot[m];
+    if (s < 0 || (int64_t)s >= M) continue;
+    d_rgb_live[(int64_t)s * C + c] = d_rgb[m * C + c];
+    if (c == 0) d_sigma_live[s] = d_sigma[m];
+  }
+}
+
+// slot[i] = first + i for the n rows that are live whatever the grid says (the sparsity points behind the last level's samples)
+__global__ __launch_bounds__(256) void occ_tail_slots_kernel(int32_t* __restrict__ slot, int64_t n, int32_t first) {
+  const int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x;
+  if (i < n) slot[i] = first + (int32_t)i;
+}
+
 // ---- launchers (also used by pxo_render_fwd_culled) ------------------------------------------------------------------------
 int launch_occ_cull(const PxoOccGrid& occ, const float* pts, int64_t M, float* pts_live, int32_t* slot, int64_t* n_live_dev,
                     void* ws, hipStream_t s) {
@@ -280,6 +313,26 @@ int launch_occ_expand(const float* rgb_live, const float* sigma_live, const int3
     default: hipLaunchKernelGGL(occ_expand_kernel<0>, grid, block, 0, s, rgb_live, sigma_live, slot, M, (uint32_t)C, raw_rgb, raw_sigma);
   }
   return check_launch("occ_expand");
+}
+
+int launch_occ_gather(const float* d_rgb, const float* d_sigma, const int32_t* slot, int64_t M, int C, float* d_rgb_live,
+                      float* d_sigma_live, hipStream_t s) {
+  const int64_t blocks = (M * C + kExpandPerBlock - 1) / kExpandPerBlock;
+  const dim3 grid((unsigned)blocks), block(256);
+  switch (C) {
+#define PXO_GATHER_CASE(CT)                                                                                                       \
+    case CT: hipLaunchKernelGGL(occ_gather_kernel<CT>, grid, block, 0, s, d_rgb, d_sigma, slot, M, (uint32_t)C, d_rgb_live, d_sigma_live); \
+      break;
+    PXO_GATHER_CASE(3) PXO_GATHER_CASE(12) PXO_GATHER_CASE(27) PXO_GATHER_CASE(48) PXO_GATHER_CASE(75)
+#undef PXO_GATHER_CASE
+    default: hipLaunchKernelGGL(occ_gather_kernel<0>, grid, block, 0, s, d_rgb, d_sigma, slot, M, (uint32_t)C, d_rgb_live, d_sigma_live);
+  }
+  return check_launch("occ_gather");
+}
+
+int launch_occ_tail_slots(int32_t* slot, int64_t n, int64_t first, hipStream_t s) {
+  hipLaunchKernelGGL(occ_tail_slots_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slot, n, (int32_t)first);
+  return check_launch("occ_tail_slots");
 }
 
 }  // namespace pxo
@@ -336,6 +389,15 @@ int pxo_occ_expand(const float* raw_rgb_live, const float* raw_sigma_live, const
   // the compact arrays may be NULL when no row is live (every slot is -1: they are never read)
   PXO_REQUIRE(slot && raw_rgb && raw_sigma, "pxo_occ_expand: null pointer");
   return launch_occ_expand(raw_rgb_live, raw_sigma_live, slot, M, C, raw_rgb, raw_sigma, (hipStream_t)stream);
+}
+
+int pxo_occ_gather(const float* d_raw_rgb, const float* d_raw_sigma, const int32_t* slot, int64_t M, int C, float* d_rgb_live,
+                   float* d_sigma_live, void* stream) {
+  PXO_REQUIRE(M >= 0 && M < ((int64_t)1 << 31), "pxo_occ_gather: %lld rows outside [0, 2^31)", (long long)M);
+  PXO_REQUIRE(C >= 1 && C <= PXO_OCC_MAX_CHANNELS, "pxo_occ_gather: C = %d outside [1,%d]", C, PXO_OCC_MAX_CHANNELS);
+  if (M == 0) return PXO_OK;
+  PXO_REQUIRE(d_raw_rgb && d_raw_sigma && slot && d_rgb_live && d_sigma_live, "pxo_occ_gather: null pointer");
+  return launch_occ_gather(d_raw_rgb, d_raw_sigma, slot, M, C, d_rgb_live, d_sigma_live, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -966,6 +966,190 @@ int pxo_train_fwd_bwd(const PxoCfg* cfg, const float* params, const float* packe
                                     nullptr, stream);
 }
 
+}  // extern "C"
+
+namespace pxo {
+
+// The record of a culled step (pxo_train_fwd_bwd_culled) in the step words: not kStepRecord, so that pxo_train_backward_work,
+// whose chunk totals are those of the dense row count, refuses such a workspace by name.
+constexpr unsigned int kStepRecordCulled = 0x5E7DC000u;
+
+// What pxo_train_fwd_bwd_culled keeps behind the TrainWs block (whose layout stays pxo_train_fwd_bwd's), after carve_cull: the
+// compact points, raw rows and upstream gradient of ONE level (the last level's size, sparsity points included; the coarse
+// level uses their head), the slots, the two counts and the cull's scratch
+struct TrainCullWs {
+  float *pts_live, *rgb_live, *sigma_live, *d_rgb_live, *d_sigma_live;
+  int32_t* slot;
+  int64_t* n_live;
+  void* cull;
+  size_t total;
+};
+static void carve_train_cull(const PxoCfg* cfg, int64_t B, void* ws, const TrainWs& t, TrainCullWs& k) {
+  Carver c(ws);
+  c.off = t.total;
+  const int C = rgb_channels(cfg->sh_deg);
+  const int64_t rows = B * (cfg->num_coarse_samples + cfg->num_fine_samples), M = rows + t.n_sp;
+  k.pts_live = c.take<float>(M * 3);
+  k.rgb_live = c.take<float>(M * C);
+  k.sigma_live = c.take<float>(M);
+  k.d_rgb_live = c.take<float>(M * C);
+  k.d_sigma_live = c.take<float>(M);
+  k.slot = c.take<int32_t>(M);
+  k.n_live = c.take<int64_t>(2);
+  k.cull = c.take<char>((int64_t)occ_cull_workspace_bytes(rows));
+  k.total = (c.off + 255) & ~(size_t)255;
+}
+
+// One level of the culled step between its sampling launch and its shade + composite launch: cull the B * p.S sample rows, read
+// n_live (synchronises), append the always-live rows behind the samples (the sparsity points of the last level: p.M - B * p.S
+// of them), the training forward on the compact rows -- acts / enc / mask in compact order -- and expand.  *M_live: the rows
+// the level's MLP launches run on.
+static int culled_train_forward(const PxoCfg* cfg, const PxoOccGrid& occ, TrainCullWs& k, int level, const float* packed_fwd,
+                                PassBuffers& p, int64_t B, int64_t* host_count, unsigned int* tile_counter, hipStream_t s,
+                                int64_t* M_live) {
+  const char* who = "pxo_train_fwd_bwd_culled";
+  const int64_t rows = B * p.S, extra = p.M - rows;
+  PXO_TRY(launch_occ_cull(occ, p.pts, rows, k.pts_live, k.slot, k.n_live + level, k.cull, s));
+  if (hipMemcpyAsync(host_count, k.n_live + level, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    set_error("%s: reading the live-row count: %s", who, hipGetErrorString(hipGetLastError()));
+    return PXO_ERR_HIP;
+  }
+  const int64_t n_live = *host_count;
+  if (n_live < 0 || n_live > rows) {
+    set_error("%s: live-row count %lld outside [0, %lld]", who, (long long)n_live, (long long)rows);
+    return PXO_ERR_HIP;
+  }
+  if (extra > 0) {                                    // slot[rows + j] = n_live + j <= p.M - 1: inside the compact arrays
+    if (hipMemcpyAsync(k.pts_live + 3 * n_live, p.pts + 3 * rows, (size_t)extra * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) !=
+        hipSuccess) {
+      set_error("%s: hipMemcpyAsync(sparsity points) failed", who);
+      return PXO_ERR_HIP;
+    }
+    PXO_TRY(launch_occ_tail_slots(k.slot + rows, extra, n_live, s));
+  }
+  *M_live = n_live + extra;
+  if (*M_live > 0)
+    PXO_TRY(launch_mlp_fwd(cfg, packed_fwd, k.pts_live, *M_live, k.rgb_live, k.sigma_live, p.acts, p.enc, p.mask, s, tile_counter));
+  return launch_occ_expand(k.rgb_live, k.sigma_live, k.slot, p.M, rgb_channels(cfg->sh_deg), p.raw_rgb, p.raw_sigma, s);
+}
+
+// The reverse of that level: the dense d_raw_* of the shade launch gathered to compact order, then the existing backward(data)
+// and weight-gradient launches on M_live rows, with the split of that M.  No live row: no MLP launch, a zero gradient.
+static int culled_train_reverse(const PxoCfg* cfg, TrainWs& t, TrainCullWs& k, const float* packed_bwd, PassBuffers& p,
+                                int64_t M_live, float* grads, int64_t n_mlp, const StepPlan& plan, const Tuning& tu,
+                                unsigned int* tile_counter, hipStream_t s) {
+  if (M_live == 0) return launch_fill(grads, n_mlp, 0.f, s);
+  PXO_TRY(launch_occ_gather(p.d_raw_rgb, p.d_raw_sigma, k.slot, p.M, rgb_channels(cfg->sh_deg), k.d_rgb_live, k.d_sigma_live, s));
+  uint8_t* const live = plan.skip ? p.live : nullptr;
+  PXO_TRY(launch_mlp_bwd_data(cfg, packed_bwd, k.d_rgb_live, k.d_sigma_live, p.mask, M_live, p.dz, p.dbias, live, tile_counter, s,
+                              plan.bias_from_wgrad));
+  return launch_mlp_bwd_weights(cfg, p.acts, p.enc, p.dz, k.d_rgb_live, k.d_sigma_live, p.dbias, M_live, grads, t.wgrad_ws,
+                                t.wgrad_bytes, live, s, wgrad_split(M_live, num_cus(), tu), plan.x6_main, plan.bias_from_wgrad);
+}
+
+}  // namespace pxo
+
+extern "C" {
+
+int pxo_train_culled_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
+  PXO_TRY(validate_cfg(cfg));
+  PXO_REQUIRE(bytes && B >= 1, "pxo_train_culled_workspace_bytes: bad arguments");
+  TrainWs t;
+  carve_train(cfg, B, nullptr, true, t);
+  PXO_REQUIRE(B * (int64_t)(cfg->num_coarse_samples + cfg->num_fine_samples) + t.n_sp < ((int64_t)1 << 31),
+              "pxo_train_culled_workspace_bytes: %lld rays x %d samples exceed 2^31 rows", (long long)B,
+              cfg->num_coarse_samples + cfg->num_fine_samples);
+  TrainCullWs k;
+  carve_train_cull(cfg, B, nullptr, t, k);
+  *bytes = k.total;
+  return PXO_OK;
+}
+
+int pxo_train_fwd_bwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float* params, const float* packed_fwd0,
+                             const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1, const float* origins,
+                             const float* directions, const float* viewdirs, const float* pixels, int64_t B, int randomized,
+                             const float* t_rand, const float* u, const float* sp_points, uint64_t seed, float* grads,
+                             float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream, int64_t live_rows[2]) {
+  const char* who = "pxo_train_fwd_bwd_culled";
+  PXO_TRY(validate_cfg(cfg));
+  PXO_TRY(occ_validate(occ, who));
+  if (cfg->mlp_precision != PXO_MLP_F32 && cfg->mlp_precision != PXO_MLP_BF16X6) {
+    set_error("%s: training runs in float32 or its float32-accurate bf16x6 emulation only (mlp_precision bf16x3 is an inference option)", who);
+    return PXO_ERR_UNSUPPORTED;
+  }
+  if (randomized && cfg->noise_std > 0.f) {
+    set_error("%s: noise_std > 0 with randomized sampling (noise on a culled sample's zero sigma would resurrect it)", who);
+    return PXO_ERR_UNSUPPORTED;
+  }
+  if (live_rows) live_rows[0] = live_rows[1] = 0;
+  const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
+  PXO_REQUIRE(B >= 1 && params && packed_fwd0 && packed_bwd0 && origins && directions && viewdirs && pixels && grads && stats && ws,
+              "%s: bad arguments", who);
+  if (Nf > 0) PXO_REQUIRE(packed_fwd1 && packed_bwd1, "%s: MLP_1 images missing", who);
+  hipStream_t s = (hipStream_t)stream;
+  TrainWs t;
+  carve_train(cfg, B, ws, true, t);
+  PXO_REQUIRE(B * (int64_t)(Nc + Nf) + t.n_sp < ((int64_t)1 << 31), "%s: %lld rays x %d samples exceed 2^31 rows", who, (long long)B,
+              Nc + Nf);
+  TrainCullWs k;
+  carve_train_cull(cfg, B, ws, t, k);
+  if (ws_bytes < k.total) {
+    set_error("%s: workspace %zu < %zu", who, ws_bytes, k.total);
+    return PXO_ERR_WORKSPACE;
+  }
+  int64_t* host = pinned_counts();
+  if (!host) {
+    set_error("%s: hipHostMalloc of the count words failed", who);
+    return PXO_ERR_HIP;
+  }
+  const int64_t n_mlp = mlp_param_count(cfg->sh_deg);
+  const int64_t n_all = 2 * n_mlp;
+  const float wd_coef = 2.f * cfg->weight_decay_mult / (float)n_all;
+  // the dense step's decisions (one snapshot of the knobs), but for the weight-gradient splits, which follow the compact M of
+  // each level (a compact pass is no longer than the dense one: a dense split that fits the live lists stays fitting)
+  const Tuning tu = tuning_snapshot();
+  const StepPlan plan = plan_step(*cfg, t.c.M, Nf > 0 ? t.f.M : 0, num_cus(), tu);
+  float* const sumsq_partial = t.scalars;
+  unsigned int* const step_words = reinterpret_cast<unsigned int*>(t.scalars + kStepWordsAt);
+  unsigned int* const counters = step_words + 2;
+  unsigned int* const cnt_fwd_c = plan.dyn ? counters + 0 : nullptr;
+  unsigned int* const cnt_fwd_f = plan.dyn ? counters + 2 : nullptr;
+  unsigned int* const cnt_bwd_c = (plan.dyn || cfg->skip_zero_rows) ? counters + 1 : nullptr;
+  unsigned int* const cnt_bwd_f = (plan.dyn || cfg->skip_zero_rows) ? counters + 3 : nullptr;
+  Draws dr;
+  PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, sp_points, seed, s, dr, params, 2 * n_mlp, sumsq_partial, step_words,
+                        kStepWords, kStepRecordCulled));
+  // coarse level
+  int64_t M_c = 0, M_f = 0;
+  PXO_TRY(launch_sample_along_rays(origins, directions, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, t.c.z, t.c.pts, s));
+  PXO_TRY(culled_train_forward(cfg, *occ, k, 0, packed_fwd0, t.c, B, host, cnt_fwd_c, s, &M_c));
+  if (live_rows) live_rows[0] = host[0];
+  PXO_TRY(launch_shade_composite_train(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, directions, viewdirs, pixels, B, Nc, nullptr,
+                                       Nf > 0 ? t.c.weights : nullptr, t.c.ray_sse, t.c.d_raw_rgb, t.c.d_raw_sigma,
+                                       Nf > 0 ? 0 : t.n_sp, t.sp_exp, nullptr, nullptr, s));
+  PXO_TRY(culled_train_reverse(cfg, t, k, packed_bwd0, t.c, M_c, grads, n_mlp, plan, tu, cnt_bwd_c, s));
+  if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads, params, n_mlp, wd_coef, s));
+  if (grads0_ready && hipEventRecord((hipEvent_t)grads0_ready, s) != hipSuccess) {
+    set_error("%s: hipEventRecord(grads0_ready) failed", who);
+    return PXO_ERR_HIP;
+  }
+  if (Nf > 0) {
+    PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, origins, directions, B, Nc, Nf, dr.u, t.f.z, t.f.pts, s));
+    PXO_TRY(culled_train_forward(cfg, *occ, k, 1, packed_fwd1, t.f, B, host + 1, cnt_fwd_f, s, &M_f));
+    if (live_rows) live_rows[1] = host[1];
+    PXO_TRY(launch_shade_composite_train(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, directions, viewdirs, pixels, B, Nc + Nf, nullptr,
+                                         nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp, nullptr, nullptr,
+                                         s));
+    PXO_TRY(culled_train_reverse(cfg, t, k, packed_bwd1, t.f, M_f, grads + n_mlp, n_mlp, plan, tu, cnt_bwd_f, s));
+  } else {
+    PXO_TRY(launch_fill(grads + n_mlp, n_mlp, 0.f, s));
+  }
+  if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads + n_mlp, params + n_mlp, n_mlp, wd_coef, s));
+  return launch_finalize_stats(Nf > 0 ? t.f.ray_sse : nullptr, t.c.ray_sse, t.n_sp > 0 ? t.sp_exp : nullptr, sumsq_partial, B,
+                               t.n_sp, cfg->sparsity_weight, n_all, stats, s);
+}
+
 int pxo_train_backward_work(const PxoCfg* cfg, int64_t B, void* ws, size_t ws_bytes, int64_t* live_chunks,
                             int64_t* total_chunks, void* stream) {
   PXO_TRY(validate_cfg(cfg));
@@ -983,6 +1167,11 @@ int pxo_train_backward_work(const PxoCfg* cfg, int64_t B, void* ws, size_t ws_by
       hipStreamSynchronize(s) != hipSuccess) {
     set_error("pxo_train_backward_work: copy back failed");
     return PXO_ERR_HIP;
+  }
+  if (record == kStepRecordCulled) {
+    set_error("pxo_train_backward_work: the last step on this workspace was pxo_train_fwd_bwd_culled, whose reverse pass ran on the "
+              "live rows only (the chunk totals of the dense row count do not describe it; see its live_rows)");
+    return PXO_ERR_ARG;
   }
   if ((record & ~1u) != kStepRecord) { set_error("pxo_train_backward_work: no pxo_train_fwd_bwd call has used this workspace"); return PXO_ERR_ARG; }
   if (!(record & 1u)) {

@@ -362,6 +362,10 @@ int launch_occ_cull(const PxoOccGrid& occ, const float* pts, int64_t M, float* p
                     void* ws, hipStream_t s);
 int launch_occ_expand(const float* rgb_live, const float* sigma_live, const int32_t* slot, int64_t M, int C, float* raw_rgb,
                       float* raw_sigma, hipStream_t s);
+// the reverse of launch_occ_expand (rows with slot < 0 dropped), and slot[i] = first + i for rows that are always live
+int launch_occ_gather(const float* d_rgb, const float* d_sigma, const int32_t* slot, int64_t M, int C, float* d_rgb_live,
+                      float* d_sigma_live, hipStream_t s);
+int launch_occ_tail_slots(int32_t* slot, int64_t n, int64_t first, hipStream_t s);
 int launch_fill(float* p, int64_t n, float v, hipStream_t s);
 int launch_axpy(float* y, const float* x, int64_t n, float a, hipStream_t s);
 

@@ -92,12 +92,29 @@ def _occupancy_render(a):
 
 
 def _occupancy_elsewhere(a):
-    return occupancy.wanted(a) and ("occupancy_reso (the occupancy grid serves the renders of nerf_sh.eval and nerf_sh.gen_video: culling "
-                                    "inside training, its test renders, the extraction or meshing is not built)")
+    return occupancy.wanted(a) and ("occupancy_reso (the grid of --occupancy_reso serves the renders of nerf_sh.eval and "
+                                    "nerf_sh.gen_video: culling inside training and its test renders is --cull_reso of nerf_sh.train, "
+                                    "culling in the extraction or meshing is not built)")
 
 
-def _with_occupancy(clauses, purpose):
-    return clauses + ((_occupancy_render if purpose == "render" else _occupancy_elsewhere),)
+def _cull_train(a):
+    """--cull_reso R (nerf/occupancy.py TrainingGrid) in nerf_sh.train with an SH model: what of it is not built."""
+    return "; ".join(occupancy.cull_clauses(a))
+
+
+def _cull_train_sg(a):
+    return occupancy.cull_wanted(a) and "cull_reso with sg_dim>0 (training a NeRF-SG through the occupancy grid is not built)"
+
+
+def _cull_elsewhere(a):
+    return occupancy.cull_wanted(a) and ("cull_reso (the grid that follows a model is nerf_sh.train's: eval and gen_video take "
+                                         "--occupancy_reso, culling in the extraction or meshing is not built)")
+
+
+def _with_occupancy(clauses, purpose, cull_train=_cull_train):
+    """`clauses` plus the family's answer to the two grids: --occupancy_reso is the renderers', --cull_reso is nerf_sh.train's."""
+    return clauses + ((_occupancy_render if purpose == "render" else _occupancy_elsewhere),
+                      (cull_train if purpose == "train" else _cull_elsewhere))
 
 
 _SH_CLAUSES = (lambda a: a.use_viewdirs and "use_viewdirs=true (vanilla NeRF head)",
@@ -159,7 +176,7 @@ VIEWDIRS = Family(
 SG = Family(
     name="sg",
     selects=lambda a: a.sg_dim > 0,
-    checks={"train": ("training a NeRF-SG, ", _with_occupancy(_SG_CLAUSES, "train")),
+    checks={"train": ("training a NeRF-SG, ", _with_occupancy(_SG_CLAUSES, "train", _cull_train_sg)),
             "render": ("rendering a NeRF-SG, ", _with_occupancy(_SG_CLAUSES, "render")),
             "extract": ("extraction of an SG PlenOctree, ", _with_occupancy(_SG_CLAUSES, "extract")),
             "mesh": ("rendering a NeRF-SG, ", _with_occupancy(_SG_CLAUSES, "mesh"))},
@@ -176,7 +193,7 @@ SH = Family(
     selects=lambda a: True,
     checks={purpose: ("", _with_occupancy(_SH_CLAUSES, purpose)) for purpose in PURPOSES},
     instead={},
-    construct=lambda a, device, purpose: models.get_model_state(a, device, restore=False),
+    construct=lambda a, device, purpose: models.get_model_state(a, device, restore=False, purpose=purpose),
     loading=lambda a: "* Loading NeRF",
     checkpoint={"train": RESUME, "render": RESUME, "extract": EITHER, "mesh": RESUME},
     n_params=lambda a, state: 2 * state.n_mlp,

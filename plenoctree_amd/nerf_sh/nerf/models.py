@@ -60,8 +60,16 @@ class TrainState(Workspace):
     def train_workspace_bytes(self, cfg, B):
         return ops.train_workspace_bytes(cfg, B)
 
-    def fwd_bwd(self, cfg, rays, pixels, ws, **kw):
-        """loss_fn + value_and_grad (pxo_train_fwd_bwd_bucketed) into the gradient arena and the stats."""
+    def train_culled_workspace_bytes(self, cfg, B):
+        return ops.train_culled_workspace_bytes(cfg, B)
+
+    def fwd_bwd(self, cfg, rays, pixels, ws, occupancy=None, live_rows=None, **kw):
+        """loss_fn + value_and_grad (pxo_train_fwd_bwd_bucketed) into the gradient arena and the stats.  occupancy (an
+        ops.OccupancyGrid): the step runs both levels' MLPs, forward and reverse, on the samples it calls live only
+        (pxo_train_fwd_bwd_culled; ws of train_culled_workspace_bytes; live_rows, a list, receives the live rows per level)."""
+        if occupancy is not None:
+            return ops.train_fwd_bwd_culled(cfg, occupancy, self.params, self.packed, rays.origins, rays.directions, rays.viewdirs,
+                                            pixels, self.grads, self.stats, ws, live_rows=live_rows, **kw)
         ops.train_fwd_bwd(cfg, self.params, self.packed, rays.origins, rays.directions, rays.viewdirs, pixels,
                           self.grads, self.stats, ws, **kw)
 
@@ -139,18 +147,18 @@ def make_cfg(args):
                         skip_zero_rows=int(bool(getattr(args, "skip_zero_rows", False))))
 
 
-def construct_nerf(args, device, seed=None):
-    """construct_nerf (:351-428): validates the configuration and initialises the parameters."""
-    utils.check_supported(args)
+def construct_nerf(args, device, seed=None, purpose="render"):
+    """construct_nerf (:351-428): validates the configuration (for the entry point `purpose`) and initialises the parameters."""
+    utils.check_supported(args, purpose)
     cfg = make_cfg(args)
     params = init_params(cfg, args.seed if seed is None else seed).to(device)
     return NerfModel(cfg), params
 
 
-def get_model_state(args, device, restore=True):
+def get_model_state(args, device, restore=True, purpose="render"):
     """get_model_state (:38-49): model + TrainState, restoring the newest checkpoint if any."""
     from . import checkpoints
-    model, params = construct_nerf(args, device)
+    model, params = construct_nerf(args, device, purpose=purpose)
     state = TrainState(model.cfg, params)
     if restore and args.train_dir:
         checkpoints.restore_checkpoint(args.train_dir, state)
@@ -158,7 +166,7 @@ def get_model_state(args, device, restore=True):
 
 
 def train_step(model, state, batch, lr, randomized=True, t_rand=None, u=None, sp_points=None, seed=0,
-               world_size=1, reducer=None):
+               world_size=1, reducer=None, occupancy=None, live_rows=None):
     """One optimisation step (nerf_sh/train.py:51-121) on this rank's shard of the batch.
 
     loss_fn + value_and_grad run in pxo_train_fwd_bwd_bucketed; `reducer` (dist.GradReducer: two RCCL sums over the ranks,
@@ -166,13 +174,20 @@ def train_step(model, state, batch, lr, randomized=True, t_rand=None, u=None, sp
     implements lax.pmean (train.py:117-118); Adam (train.py:119) and the re-pack of the weight images follow.  The
     library calls are the state's (TrainState; sg.SgState puts its own in their place), everything on the stream.
     Returns the device tensor stats[6] = (loss, psnr, loss_c, loss_sp, psnr_c, weight_l2); its values are only read by
-    the host when logging."""
+    the host when logging.  occupancy (an ops.OccupancyGrid, e.g. occupancy.TrainingGrid.before_step): the step through the
+    grid (pxo_train_fwd_bwd_culled), live_rows (a list) receiving the live sample rows of the two levels; without it the
+    dense call, with the arguments it always had."""
     cfg = model.cfg
     rays = batch["rays"]
-    ws = state.workspace(state.train_workspace_bytes(cfg, rays.origins.shape[0]))
     ev = reducer.ready_event() if reducer is not None else None
-    state.fwd_bwd(cfg, rays, batch["pixels"], ws, randomized=randomized, t_rand=t_rand, u=u, sp_points=sp_points, seed=seed,
-                  grads0_ready=ev)
+    if occupancy is not None:
+        ws = state.workspace(state.train_culled_workspace_bytes(cfg, rays.origins.shape[0]))
+        state.fwd_bwd(cfg, rays, batch["pixels"], ws, randomized=randomized, t_rand=t_rand, u=u, sp_points=sp_points, seed=seed,
+                      grads0_ready=ev, occupancy=occupancy, live_rows=live_rows)
+    else:
+        ws = state.workspace(state.train_workspace_bytes(cfg, rays.origins.shape[0]))
+        state.fwd_bwd(cfg, rays, batch["pixels"], ws, randomized=randomized, t_rand=t_rand, u=u, sp_points=sp_points, seed=seed,
+                      grads0_ready=ev)
     scale = 1.0
     if reducer is not None:
         reducer.reduce(state.bucket0, state.bucket1)

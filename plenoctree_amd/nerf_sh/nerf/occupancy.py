@@ -10,8 +10,11 @@ only the samples in occupied cells (ops.render_fwd_culled); the others get raw s
   from_tree   a finished float SH or SG tree sampled at 2^depth cells per axis (pxo_tree_sigma_grid), occupied iff sigma > 0, over
               the tree's own box
 
-Forward-only and opt-in (nerf_sh.eval / nerf_sh.gen_video --occupancy_reso R); not built: culling inside training or its test
-renders, the view-conditioned head, NDC scenes, a grid that follows a model while it trains.
+Rendering: opt-in, nerf_sh.eval / nerf_sh.gen_video --occupancy_reso R.  Training: opt-in, nerf_sh.train --cull_reso R -- a
+TrainingGrid follows the model (rebuilt from the fine MLP every --cull_update_every steps after --cull_warmup_steps dense steps),
+models.train_step(..., occupancy=grid) runs both levels' MLPs, forward and reverse, on the live samples only
+(ops.train_fwd_bwd_culled), and the periodic test render goes through the same grid.  Not built: SG and view-conditioned training
+through the grid, NDC scenes, culling in extraction and meshing, a device-side row count.
 """
 import math
 import time
@@ -111,6 +114,20 @@ def add_flags(parser):
     a("--occupancy_outside", choices=OUTSIDE, default="empty", help="samples outside the grid's box: skipped, or evaluated")
     a("--occupancy_tree", type=str, default="", help="take the grid from this float PlenOctree (npz) instead of the model; "
                                                       "--occupancy_reso must then be a power of two")
+    # nerf_sh.train: the grid that follows the model while it trains (TrainingGrid)
+    a("--cull_reso", type=int, default=0,
+      help="nerf_sh.train: cells per axis of an occupancy grid rebuilt from the fine MLP while training; the train step and the test "
+           "renders then run the MLPs on the samples in occupied cells only; 0 = off (every sample is evaluated)")
+    a("--cull_center", type=_floats(3), default=[0.0, 0.0, 0.0], help='centre of the training grid\'s box, "x y z"')
+    a("--cull_radius", type=_floats(3), default=[1.5, 1.5, 1.5], help='half side of the training grid\'s box, "r" or "rx ry rz"')
+    a("--cull_alpha_thresh", type=float, default=0.01,
+      help="a cell of the training grid is occupied if its alpha over one cell side exceeds this; 0: sigma > 0")
+    a("--cull_dilate", type=int, choices=(0, 1), default=1, help="also occupy the cells next to an occupied one")
+    a("--cull_warmup_steps", type=int, default=500, help="steps that run dense before the first grid is built")
+    a("--cull_update_every", type=int, default=32,
+      help="the grid is rebuilt from scratch before every step s > cull_warmup_steps with (s - 1) %% cull_update_every == 0 (and "
+           "whenever there is none: at the first culled step and after a resume).  The schedule depends on the step alone: a run "
+           "resumed from a checkpoint whose step is a multiple of cull_update_every continues bit for bit")
     return parser
 
 
@@ -143,6 +160,120 @@ def clauses(args):
     if min(radius) <= 0.0:
         bad.append(f"occupancy_radius={radius} (need > 0)")
     return bad
+
+
+# ---- nerf_sh.train --cull_reso: the grid that follows the model ------------------------------------------------------------------
+def cull_wanted(args):
+    return int(getattr(args, "cull_reso", 0) or 0) != 0
+
+
+def cull_clauses(args):
+    """What the --cull_* flags ask of nerf_sh.train that is not built, in words (the SH family's `train` clauses call this)."""
+    if not cull_wanted(args):
+        return []
+    bad = []
+    reso = int(args.cull_reso)
+    if not 1 <= reso <= ops._lib.OCC_MAX_RESO:
+        bad.append(f"cull_reso={reso} (need 1..{ops._lib.OCC_MAX_RESO}, or 0 = off)")
+    if getattr(args, "use_viewdirs", False):
+        bad.append("cull_reso with use_viewdirs=true (training through the occupancy grid is not built for the view-conditioned head)")
+    if getattr(args, "dataset", None) == "llff" and not getattr(args, "spherify", False):
+        bad.append("cull_reso on a forward-facing scene without --spherify (NDC: the grid is not built for NDC rays)")
+    if getattr(args, "noise_std", None) and getattr(args, "randomized", False):
+        bad.append("cull_reso with noise_std and randomized sampling (noise on a culled sample's zero sigma would resurrect it)")
+    alpha = float(getattr(args, "cull_alpha_thresh", 0.01))
+    if not 0.0 <= alpha < 1.0:
+        bad.append(f"cull_alpha_thresh={alpha:g} (need 0 <= a < 1)")
+    if min(getattr(args, "cull_radius", [1.5])) <= 0.0:
+        bad.append(f"cull_radius={args.cull_radius} (need > 0)")
+    if int(getattr(args, "cull_warmup_steps", 0)) < 0:
+        bad.append(f"cull_warmup_steps={args.cull_warmup_steps} (need >= 0)")
+    if int(getattr(args, "cull_update_every", 1)) < 1:
+        bad.append(f"cull_update_every={args.cull_update_every} (need >= 1)")
+    return bad
+
+
+class TrainingGrid:
+    """The occupancy grid of a training run.  before_step(step, model, state) gives the grid step `step` runs through, or None
+    for a dense step:
+
+      * the first `warmup_steps` steps run dense;
+      * from then on the grid is rebuilt before every step s with (s - 1) % update_every == 0, and whenever there is none (the
+        first culled step; the first step after a resume) -- from scratch, never as a running maximum: `build` evaluates the
+        fine MLP in EVERY cell, so density that grows into a culled cell by the network's continuity turns the cell back on;
+      * between rebuilds the grid is reused;
+      * a rebuild that finds no occupied cell makes the steps up to the next rebuild dense, and says so once.
+
+    The schedule is a function of the step alone, and every rank builds the same grid from the same parameters (no
+    communication; the ranks' live-row counts differ, the gradient all-reduces do not change).  build(model, state) -> a grid
+    with fraction_occupied(); the default is from_model over the box (center, radius)."""
+
+    def __init__(self, reso, center=(0.0, 0.0, 0.0), radius=1.5, alpha_thresh=0.01, dilate=1, warmup_steps=500, update_every=32,
+                 build=None, say=print):
+        check_grid_args(reso, dilate, "empty")
+        if int(update_every) < 1 or int(warmup_steps) < 0:
+            raise ValueError(f"TrainingGrid: update_every {update_every} < 1 or warmup_steps {warmup_steps} < 0")
+        self.reso, self.warmup_steps, self.update_every = int(reso), int(warmup_steps), int(update_every)
+        self.build = build or (lambda model, state: from_model(model, state, reso, center, radius, alpha_thresh, dilate, "empty"))
+        self.say = say
+        self.grid = None                  # the grid in use (None: none built yet, or the last build was empty)
+        self.built_at = None              # the step before which the last rebuild ran
+        self.rebuilds = []                # every such step, in order
+        self.fraction = None              # the last build's occupied fraction
+        self.rebuild_seconds = 0.0        # and its time
+        self.live = None                  # LiveRows since the last line()
+        self._said_empty = False
+
+    @classmethod
+    def from_args(cls, args, say=print):
+        """The TrainingGrid of the --cull_* flags, or None without --cull_reso."""
+        if not cull_wanted(args):
+            return None
+        return cls(args.cull_reso, args.cull_center, args.cull_radius, args.cull_alpha_thresh, args.cull_dilate,
+                   args.cull_warmup_steps, args.cull_update_every, say=say)
+
+    def due(self, step):
+        """Whether a rebuild runs before step `step` (1-based, the step about to be taken)."""
+        if step <= self.warmup_steps:
+            return False
+        return self.built_at is None or (step - 1) % self.update_every == 0
+
+    def before_step(self, step, model, state):
+        if step <= self.warmup_steps:
+            return None
+        if self.due(step) and self.built_at != step:
+            import torch
+            t0 = time.time()
+            grid = self.build(model, state)
+            self.fraction = float(grid.fraction_occupied())              # reads the bits back: the build is complete
+            if torch.cuda.is_available():
+                torch.cuda.synchronize()
+            self.rebuild_seconds = time.time() - t0
+            self.built_at = step
+            self.rebuilds.append(step)
+            self.grid = grid if self.fraction > 0.0 else None
+            if self.grid is None and not self._said_empty:
+                self._said_empty = True
+                self.say(f"* training grid {self.reso}^3 rebuilt before step {step}: no occupied cell -- the steps run dense until a "
+                         "rebuild finds one", flush=True)
+        return self.grid
+
+    def count(self, cfg, rows, n_rays):
+        """Add one culled step's live rows (train_step's live_rows) to the fractions of the next line()."""
+        if self.live is None:
+            self.live = LiveRows(cfg)
+        self.live.add(rows, n_rays)
+
+    def line(self):
+        """What the progress line gains: the live-row fractions since the last call and the last rebuild's time."""
+        if self.built_at is None:
+            return f"cull: dense until step {self.warmup_steps + 1}"
+        if self.live is None or not self.live.total[0]:
+            return f"cull: dense (grid {100.0 * (self.fraction or 0.0):.2f} % occupied)"
+        text = (f"{self.live.line()}, grid {100.0 * self.fraction:.2f} % occupied, rebuilt before step {self.built_at} in "
+                f"{self.rebuild_seconds:.3f} s")
+        self.live.reset()
+        return text
 
 
 def from_args(args, model, state, comm=None, say=print):

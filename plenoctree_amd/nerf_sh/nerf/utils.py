@@ -118,8 +118,8 @@ def define_flags(parser=None):
     # reference's defaults so that its command lines and presets parse; check_supported rejects what would use them
     a("--net_depth_condition", type=int, default=1)        # :108
     a("--net_width_condition", type=int, default=128)      # :109
-    # no reference counterpart: the occupancy grid of nerf_sh.eval / nerf_sh.gen_video (nerf/occupancy.py); every other entry
-    # point refuses --occupancy_reso by name through the families table
+    # no reference counterpart: the occupancy grid of nerf_sh.eval / nerf_sh.gen_video (--occupancy_*) and the one that follows a
+    # model in nerf_sh.train (--cull_*), nerf/occupancy.py; every other entry point refuses either by name through the families table
     from . import occupancy
     occupancy.add_flags(p)
     return p
@@ -185,10 +185,11 @@ def unbuilt_flags(args, clauses):
     return [words for words in found if words]
 
 
-def check_supported(args):
-    """The HIP path builds the SH configurations of config/blender.yaml, config/tt.yaml and config/llff.yaml (families.SH)."""
+def check_supported(args, purpose="render"):
+    """The HIP path builds the SH configurations of config/blender.yaml, config/tt.yaml and config/llff.yaml (families.SH);
+    purpose: the entry point's (what only one of them builds, such as nerf_sh.train's --cull_reso, is judged by it)."""
     from . import families
-    families.check_flags(families.SH, args)
+    families.check_flags(families.SH, args, purpose)
 
 
 def learning_rate_decay(step, lr_init, lr_final, max_steps, lr_delay_steps=0, lr_delay_mult=1):

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .. import dist
-from .nerf import checkpoints, families, llff, models, sg, utils
+from .nerf import checkpoints, families, llff, models, occupancy, sg, utils
 
 
 def main(argv=None):
@@ -54,6 +54,9 @@ def main(argv=None):
               f"{per_rank} rays/GPU", flush=True)
 
     reducer = dist.GradReducer(comm, device)
+    # --cull_reso R: the occupancy grid that follows the model (None without the flag: the loop below then makes the calls it
+    # always made)
+    cull = occupancy.TrainingGrid.from_args(args, say=print if h0 else (lambda *a, **k: None))
     t_loop_start = time.time()
     stats_trace = []
     # the reference averages loss / psnr over EVERY step since the last print (stats_trace, train.py:199-200,216-218); here the
@@ -69,8 +72,15 @@ def main(argv=None):
         batch = next(dataset)
         lr = utils.learning_rate_decay(step, args.lr_init, args.lr_final, args.max_steps, args.lr_delay_steps,
                                        args.lr_delay_mult)
-        models.train_step(model, state, batch, lr, randomized=args.randomized, seed=(step << 8) | comm.rank,
-                          world_size=comm.world, reducer=reducer)
+        if cull is None:
+            models.train_step(model, state, batch, lr, randomized=args.randomized, seed=(step << 8) | comm.rank,
+                              world_size=comm.world, reducer=reducer)
+        else:
+            grid, rows = cull.before_step(step, model, state), []
+            models.train_step(model, state, batch, lr, randomized=args.randomized, seed=(step << 8) | comm.rank,
+                              world_size=comm.world, reducer=reducer, occupancy=grid, live_rows=rows)
+            if grid is not None:
+                cull.count(model.cfg, rows, per_rank)
         stats_acc.add_(state.stats)
         acc_steps += 1
         if step % args.print_every == 0:                            # train.py:208-236
@@ -86,15 +96,18 @@ def main(argv=None):
                 precision = int(np.ceil(np.log10(args.max_steps))) + 1
                 print(("{:" + "{:d}".format(precision) + "d}").format(step) + f"/{args.max_steps:d}: "
                       + f"i_loss={s.loss:0.4f}, avg_loss={avg.loss:0.4f}, weight_l2={s.weight_l2:0.2e}, lr={lr:0.2e}, "
-                      + f"{rays_per_sec:0.0f} rays/sec", flush=True)
+                      + f"{rays_per_sec:0.0f} rays/sec" + (f", {cull.line()}" if cull is not None else ""), flush=True)
                 stats_trace.append((step, s.loss, s.psnr, rays_per_sec, avg.loss, avg.psnr))
         if step % args.save_every == 0 and h0:                      # train.py:237-242
             checkpoints.save_checkpoint(args.train_dir, state, step, keep=200)
         if args.render_every > 0 and step % args.render_every == 0:  # train.py:245-296 (PSNR only)
             ex = next(test_dataset)
             t0 = time.time()
+            # with --cull_reso the test render goes through the grid the steps use, once one exists
+            grid = cull.grid if cull is not None else None
             rgb, disp, acc = utils.render_image(
-                lambda r: model.apply(state, r, args.randomized, seed=step), ex["rays"],
+                (lambda r: model.apply(state, r, args.randomized, seed=step)) if grid is None else
+                (lambda r: model.apply(state, r, args.randomized, seed=step, occupancy=grid)), ex["rays"],
                 normalize_disp=(args.dataset == "llff"), chunk=args.chunk,          # train.py:259
                 world_size=comm.world, rank=comm.rank, gather=comm.all_gather_cat)
             torch.cuda.synchronize()

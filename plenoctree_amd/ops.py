@@ -809,3 +809,55 @@ def render_fwd_culled(cfg, occ, packed_fwd0, packed_fwd1, origins, directions, v
     if live_rows is not None:
         live_rows[:] = [rows[0], rows[1]]
     return outs
+
+
+# ---- training through the occupancy grid ---------------------------------------------------------------------------------------
+def occ_gather(d_raw_rgb, d_raw_sigma, slot, d_rgb_live=None, d_sigma_live=None):
+    """pxo_occ_gather, the inverse of occ_expand: dense row m of d_raw_rgb [M,C] / d_raw_sigma [M] with slot[m] >= 0 goes to row
+    slot[m] of (d_rgb_live [M,C], d_sigma_live [M]); rows with slot[m] < 0 are dropped, compact rows no slot names are left as
+    they were (the outputs are allocated uninitialised unless given)."""
+    _require_gpu()
+    if slot.dtype != torch.int32:
+        raise PxoError("occ_gather: slot must be int32")
+    M, dev = slot.numel(), slot.device
+    d_raw_rgb = d_raw_rgb.reshape(M, -1) if M else d_raw_rgb.reshape(0, max(d_raw_rgb.shape[-1], 1))
+    C = d_raw_rgb.shape[1]
+    if d_raw_sigma.numel() != M:
+        raise PxoError(f"occ_gather: d_raw_sigma has {d_raw_sigma.numel()} rows, slot {M}")
+    if d_rgb_live is None:
+        d_rgb_live = _new(M, C, device=dev)
+    if d_sigma_live is None:
+        d_sigma_live = _new(M, device=dev)
+    if d_rgb_live.numel() != M * C or d_sigma_live.numel() != M:
+        raise PxoError("occ_gather: the compact outputs must have room for all M rows")
+    check(_lib.load().pxo_occ_gather(_f(d_raw_rgb), _f(d_raw_sigma), _p(slot), M, int(C), _f(d_rgb_live), _f(d_sigma_live),
+                                     _stream()), "pxo_occ_gather")
+    return d_rgb_live, d_sigma_live
+
+
+def train_culled_workspace_bytes(cfg, B):
+    n = ctypes.c_size_t(0)
+    check(_lib.load().pxo_train_culled_workspace_bytes(ctypes.byref(cfg), B, ctypes.byref(n)), "pxo_train_culled_workspace_bytes")
+    return n.value
+
+
+def train_fwd_bwd_culled(cfg, occ, params, packed, origins, directions, viewdirs, pixels, grads, stats, ws, randomized=True,
+                         t_rand=None, u=None, sp_points=None, seed=0, grads0_ready=None, live_rows=None):
+    """train_fwd_bwd with both levels' MLPs, forward and reverse, run only on the samples `occ` (an OccupancyGrid; None is refused
+    by the library) calls live; ws of train_culled_workspace_bytes.  live_rows (a list, optional) receives the live sample rows
+    of the two levels.  Synchronises the stream twice."""
+    _require_gpu()
+    if occ is not None and not isinstance(occ, OccupancyGrid):
+        raise PxoError("train_fwd_bwd_culled: occ must be an ops.OccupancyGrid")
+    lib = _lib.load()
+    (f0, b0), (f1, b1) = packed
+    B = origins.shape[0]
+    rows = (ctypes.c_int64 * 2)(0, 0)
+    g = occ.struct() if occ is not None else None
+    check(lib.pxo_train_fwd_bwd_culled(ctypes.byref(cfg), ctypes.byref(g) if g is not None else None, _f(params), _f(f0), _f(b0),
+                                       _f(f1), _f(b1), _f(origins), _f(directions), _f(viewdirs), _f(pixels), B, int(randomized),
+                                       _f(t_rand), _f(u), _f(sp_points), seed, _f(grads), _f(stats), _p(ws), ws.numel(),
+                                       grads0_ready.handle if grads0_ready is not None else None, _stream(), rows),
+          "pxo_train_fwd_bwd_culled")
+    if live_rows is not None:
+        live_rows[:] = [rows[0], rows[1]]
