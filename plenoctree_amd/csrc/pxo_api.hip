@@ -1,6 +1,9 @@
 // C ABI of the gfx950 NeRF-SH hot path (see include/plenoctree_hip.h).  Host-side glue only:
 // argument checks, workspace carving and the kernel sequences of NerfModel.__call__
 // (nerf_sh/nerf/models.py:216-348) and loss_fn/value_and_grad (nerf_sh/train.py:66-116).
+// Each sequence is written once: lay_out carves every workspace, level_forward / level_reverse launch one level of NeRF,
+// render_fwd_impl / train_fwd_bwd_impl order them.  The SH, NeRF-SG and culled entry points are thin callers that differ in what
+// they pass: SG lobes, an occupancy grid (the cull context), both or neither.
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -205,6 +208,9 @@ static void carve_pass(Carver& c, PassBuffers& p, int64_t B, int S, int64_t extr
 constexpr int kStepWordsAt = 98;
 constexpr int kStepWords = 6;
 constexpr unsigned int kStepRecord = 0x5E7D5700u;
+// The record of a culled step (pxo_train_fwd_bwd_culled): not kStepRecord, so that pxo_train_backward_work, whose chunk totals
+// are those of the dense row count, refuses such a workspace by name.
+constexpr unsigned int kStepRecordCulled = 0x5E7DC000u;
 
 struct TrainWs {
   PassBuffers c, f;
@@ -255,16 +261,101 @@ static void carve_sg(const PxoCfg* cfg, int64_t B, void* ws, size_t train_total,
   g.total = (c.off + 255) & ~(size_t)255;
 }
 
+// What a culled sequence keeps behind the TrainWs block (whose layout stays the dense sequence's): the compact points and raw
+// rows of ONE level (the last level's size, sparsity points included -- t.n_sp is 0 in a render workspace; the coarse level uses
+// their head), with `train` the compact upstream gradient as well, then the slots, the two counts and the cull's scratch
+struct CullWs {
+  float *pts_live, *rgb_live, *sigma_live, *d_rgb_live, *d_sigma_live;
+  int32_t* slot;
+  int64_t* n_live;
+  void* cull;
+  size_t total;
+};
+static void carve_cull(const PxoCfg* cfg, int64_t B, void* ws, const TrainWs& t, bool train, CullWs& k) {
+  Carver c(ws);
+  c.off = t.total;
+  const int C = rgb_channels(cfg->sh_deg);
+  const int64_t rows = B * (cfg->num_coarse_samples + cfg->num_fine_samples), M = rows + t.n_sp;
+  k.pts_live = c.take<float>(M * 3);
+  k.rgb_live = c.take<float>(M * C);
+  k.sigma_live = c.take<float>(M);
+  k.d_rgb_live = train ? c.take<float>(M * C) : nullptr;
+  k.d_sigma_live = train ? c.take<float>(M) : nullptr;
+  k.slot = c.take<int32_t>(M);
+  k.n_live = c.take<int64_t>(2);
+  k.cull = c.take<char>((int64_t)occ_cull_workspace_bytes(rows));
+  k.total = (c.off + 255) & ~(size_t)255;
+}
+
 #define PXO_TRY(expr)            \
   do {                           \
     int _rc = (expr);            \
     if (_rc != PXO_OK) return _rc; \
   } while (0)
 
-// NerfModel.__call__ (nerf_sh/nerf/models.py:216-348) in three pieces, so that the training sequence can put the reverse of
-// the coarse level between the levels.  pixels != nullptr selects the training form: compositing, the pixel loss and its
-// reverse in one kernel per pass (d_raw_* and ray_sse are written, the rgb/disp/acc outputs are not), with the sparsity
-// rows of the last pass served by the same launch.
+// Every workspace of the render and train sequences, and its size, in one place: the TrainWs block, then what a NeRF-SG step
+// (`sg`) or a culled sequence (`cull`) keeps behind it.  ws == nullptr only measures (the *_workspace_bytes entry points);
+// otherwise ws_bytes must hold the whole layout.  `who` names the entry point in messages.
+struct Layout { TrainWs t; SgWs g; CullWs k; size_t total; };
+static int lay_out(const PxoCfg* cfg, int64_t B, void* ws, size_t ws_bytes, bool train, bool sg, bool cull, const char* who,
+                   Layout& L) {
+  carve_train(cfg, B, ws, train, L.t);
+  L.total = L.t.total;
+  L.g = SgWs{nullptr, nullptr, nullptr, 0, L.total};
+  if (sg) { carve_sg(cfg, B, ws, L.total, L.g); L.total = L.g.total; }
+  if (cull) {                                          // the slots are int32
+    const int S = cfg->num_coarse_samples + cfg->num_fine_samples;
+    PXO_REQUIRE(B * (int64_t)S + L.t.n_sp < ((int64_t)1 << 31), "%s: %lld rays x %d samples exceed 2^31 rows", who, (long long)B, S);
+    carve_cull(cfg, B, ws, L.t, train, L.k);
+    L.total = L.k.total;
+  }
+  if (ws && ws_bytes < L.total) {
+    set_error("%s: workspace %zu < %zu", who, ws_bytes, L.total);
+    return PXO_ERR_WORKSPACE;
+  }
+  return PXO_OK;
+}
+static int workspace_bytes(const PxoCfg* cfg, int64_t B, bool train, bool sg, bool cull, const char* who, size_t* bytes) {
+  PXO_TRY(validate_cfg(cfg));
+  PXO_REQUIRE(bytes && B >= (train ? 1 : 0), "%s: bad arguments", who);
+  Layout L;
+  PXO_TRY(lay_out(cfg, B, nullptr, 0, train, sg, cull, who, L));
+  *bytes = L.total;
+  return PXO_OK;
+}
+
+// The cull context of a sequence (optional): the grid that calls a sample live, its block of the workspace, the pinned words
+// the two counts of a call land in (one pair per host thread, allocated on first use and kept for its life) and the caller's
+// live_rows[2] or nullptr
+struct CullCtx { const PxoOccGrid* occ; CullWs* k; int64_t* host; int64_t* live_rows; };
+static int open_cull(const PxoOccGrid* occ, CullWs& k, int64_t* live_rows, const char* who, CullCtx& cx) {
+  static thread_local int64_t* pinned = nullptr;
+  if (!pinned && hipHostMalloc((void**)&pinned, 2 * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) pinned = nullptr;
+  if (!pinned) {
+    set_error("%s: hipHostMalloc of the count words failed", who);
+    return PXO_ERR_HIP;
+  }
+  cx = CullCtx{occ, &k, pinned, live_rows};
+  return PXO_OK;
+}
+// both culled sequences refuse density noise
+static int refuse_noise(const PxoCfg* cfg, int randomized, const char* who) {
+  if (randomized && cfg->noise_std > 0.f) {
+    set_error("%s: noise_std > 0 with randomized sampling (noise on a culled sample's zero sigma would resurrect it)", who);
+    return PXO_ERR_UNSUPPORTED;
+  }
+  return PXO_OK;
+}
+static int require_train_precision(const PxoCfg* cfg, const char* who) {
+  if (cfg->mlp_precision != PXO_MLP_F32 && cfg->mlp_precision != PXO_MLP_BF16X6) {
+    set_error("%s: training runs in float32 or its float32-accurate bf16x6 emulation only (mlp_precision bf16x3 is an inference option)", who);
+    return PXO_ERR_UNSUPPORTED;
+  }
+  return PXO_OK;
+}
+
+// NerfModel.__call__ (nerf_sh/nerf/models.py:216-348) in pieces, so that the training sequence can put the reverse of the
+// coarse level between the levels: the draws of the step, then level_forward / level_reverse per level.
 struct Draws { const float* t_rand; const float* u; bool noisy; uint64_t seed; };
 
 // every uniform draw of the step in one launch (jax.random.uniform call sites model_utils.py:135,262, train.py:79)
@@ -296,36 +387,87 @@ static int prepare_draws(const PxoCfg* cfg, TrainWs& t, int64_t B, int randomize
   return launch_uniform_jobs(seed, jobs, nj, s, params, n_params, sumsq_partial, step_words, n_words, first_word);
 }
 
-static int forward_coarse(const PxoCfg* cfg, TrainWs& t, const float* pk0, const float* o, const float* d, const float* v,
-                          int64_t B, const Draws& dr, const float* pixels, float* rgb_c, float* disp_c, float* acc_c,
-                          hipStream_t s, unsigned int* tile_counter = nullptr, const float* lobes = nullptr,
-                          float* lobe_partials = nullptr) {
+// One level of NeRF, forward: the sampling launch of the level (0 coarse, 1 fine), the MLP stage, the density noise when
+// dr.noisy (models.py:258-264 / :318-324), and the training (pixels != nullptr) or inference shade + composite launch.  What
+// differs between the levels is data: the level's buffers, the noise stream (3 / 4), whether a next level needs its weights,
+// and whether the sparsity rows ride along (they do with the last level, eval_points_raw uses its MLP).
+// The MLP stage is the fused forward on p.pts, or with a cull context: cull the B * p.S sample rows, read the live count
+// (synchronises), append the always-live rows behind the live samples (the sparsity points: p.M - B * p.S of them), the same
+// forward on the compact rows -- acts / enc / mask in compact order when the pass saves them -- and expand.  *M_run: the rows
+// the level's MLP launches ran on.  With lobes (NeRF-SG): the lobe basis, and the partials of the lobe gradient.
+static int level_forward(const PxoCfg* cfg, TrainWs& t, int level, const float* packed_fwd, const float* o, const float* d,
+                         const float* v, int64_t B, const Draws& dr, const float* pixels, float* rgb, float* disp, float* acc,
+                         hipStream_t s, unsigned int* tile_counter, const float* lobes, float* lobe_partials, const CullCtx* cx,
+                         const char* who, int64_t* M_run = nullptr) {
   const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
-  PXO_TRY(launch_sample_along_rays(o, d, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, t.c.z, t.c.pts, s));
-  PXO_TRY(launch_mlp_fwd(cfg, pk0, t.c.pts, t.c.M, t.c.raw_rgb, t.c.raw_sigma, t.c.acts, t.c.enc, t.c.mask, s, tile_counter));
-  if (dr.noisy) PXO_TRY(launch_add_noise(t.c.raw_sigma, B * Nc, cfg->noise_std, nullptr, dr.seed, 3, s));   // models.py:258-264
-  if (pixels)               // with lobes (NeRF-SG): the lobe basis, and the partials of the lobe gradient
-    return launch_shade_composite_train(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, d, v, pixels, B, Nc, nullptr,
-                                        Nf > 0 ? t.c.weights : nullptr, t.c.ray_sse, t.c.d_raw_rgb, t.c.d_raw_sigma,
-                                        Nf > 0 ? 0 : t.n_sp, t.sp_exp, lobes, lobe_partials, s);
-  return launch_shade_composite_fwd(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, d, v, B, Nc, rgb_c, disp_c, acc_c,
-                                    t.c.weights, s, lobes);
+  const bool last = level == 1 || Nf == 0;
+  PassBuffers& p = level == 0 ? t.c : t.f;
+  if (level == 0)
+    PXO_TRY(launch_sample_along_rays(o, d, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, p.z, p.pts, s));
+  else
+    PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, o, d, B, Nc, Nf, dr.u, p.z, p.pts, s));
+  int64_t M = p.M;
+  if (!cx) {
+    PXO_TRY(launch_mlp_fwd(cfg, packed_fwd, p.pts, M, p.raw_rgb, p.raw_sigma, p.acts, p.enc, p.mask, s, tile_counter));
+  } else {
+    CullWs& k = *cx->k;
+    const int64_t rows = B * p.S, extra = p.M - rows;
+    PXO_TRY(launch_occ_cull(*cx->occ, p.pts, rows, k.pts_live, k.slot, k.n_live + level, k.cull, s));
+    if (hipMemcpyAsync(cx->host + level, k.n_live + level, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+      set_error("%s: reading the live-row count: %s", who, hipGetErrorString(hipGetLastError()));
+      return PXO_ERR_HIP;
+    }
+    const int64_t n_live = cx->host[level];
+    if (n_live < 0 || n_live > rows) {
+      set_error("%s: live-row count %lld outside [0, %lld]", who, (long long)n_live, (long long)rows);
+      return PXO_ERR_HIP;
+    }
+    if (extra > 0) {                                    // slot[rows + j] = n_live + j <= p.M - 1: inside the compact arrays
+      if (hipMemcpyAsync(k.pts_live + 3 * n_live, p.pts + 3 * rows, (size_t)extra * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) !=
+          hipSuccess) {
+        set_error("%s: hipMemcpyAsync(sparsity points) failed", who);
+        return PXO_ERR_HIP;
+      }
+      PXO_TRY(launch_occ_tail_slots(k.slot + rows, extra, n_live, s));
+    }
+    M = n_live + extra;
+    if (M > 0) PXO_TRY(launch_mlp_fwd(cfg, packed_fwd, k.pts_live, M, k.rgb_live, k.sigma_live, p.acts, p.enc, p.mask, s, tile_counter));
+    PXO_TRY(launch_occ_expand(k.rgb_live, k.sigma_live, k.slot, p.M, rgb_channels(cfg->sh_deg), p.raw_rgb, p.raw_sigma, s));
+    if (cx->live_rows) cx->live_rows[level] = n_live;
+  }
+  if (M_run) *M_run = M;
+  if (dr.noisy) PXO_TRY(launch_add_noise(p.raw_sigma, B * p.S, cfg->noise_std, nullptr, dr.seed, 3 + level, s));
+  if (pixels)
+    return launch_shade_composite_train(cfg, p.raw_rgb, p.raw_sigma, p.z, d, v, pixels, B, p.S, nullptr, last ? nullptr : p.weights,
+                                        p.ray_sse, p.d_raw_rgb, p.d_raw_sigma, last ? t.n_sp : 0, t.sp_exp, lobes, lobe_partials, s);
+  return launch_shade_composite_fwd(cfg, p.raw_rgb, p.raw_sigma, p.z, d, v, B, p.S, rgb, disp, acc, p.weights, s, lobes);
 }
 
-static int forward_fine(const PxoCfg* cfg, TrainWs& t, const float* pk1, const float* o, const float* d, const float* v,
-                        int64_t B, const Draws& dr, const float* pixels, float* rgb_f, float* disp_f, float* acc_f,
-                        hipStream_t s, unsigned int* tile_counter = nullptr, const float* lobes = nullptr,
-                        float* lobe_partials = nullptr) {
-  const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
-  PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, o, d, B, Nc, Nf, dr.u, t.f.z, t.f.pts, s));
-  PXO_TRY(launch_mlp_fwd(cfg, pk1, t.f.pts, t.f.M, t.f.raw_rgb, t.f.raw_sigma, t.f.acts, t.f.enc, t.f.mask, s, tile_counter));
-  if (dr.noisy) PXO_TRY(launch_add_noise(t.f.raw_sigma, B * (Nc + Nf), cfg->noise_std, nullptr, dr.seed, 4, s));   // :318-324
-  if (pixels)
-    return launch_shade_composite_train(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, pixels, B, Nc + Nf, nullptr,
-                                        nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp, lobes,
-                                        lobe_partials, s);
-  return launch_shade_composite_fwd(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, d, v, B, Nc + Nf, rgb_f, disp_f, acc_f,
-                                    t.f.weights, s, lobes);
+// One level of NeRF, reverse: backward(data), then the weight gradients into `grads` (the level's MLP's), of the M rows the
+// level's MLP ran on, on stream `s`.  Dense: M = p.M and the upstream gradient is the shade launch's d_raw_*.  Culled (k): that
+// gradient gathered to compact order first; no live row, no MLP launch and a zero gradient.  The weight gradients wait for
+// `join` (the fine level's: the slabs are the forked coarse pass's until then).
+// The split is that of the M the launches run on; for the dense M it is plan.split_c / plan.split_f, which plan_step derives
+// from the same call.  skip_zero_rows (plan.skip): rows with an exactly zero upstream gradient are left out (bit-identical).
+static int level_reverse(const PxoCfg* cfg, TrainWs& t, PassBuffers& p, const float* packed_bwd, int64_t M, float* grads,
+                         const StepPlan& plan, const Tuning& tu, unsigned int* tile_counter, hipStream_t s, const CullWs* k,
+                         SideFork* join, const char* who) {
+  const float *d_rgb = p.d_raw_rgb, *d_sigma = p.d_raw_sigma;
+  if (k) {
+    if (M == 0) return launch_fill(grads, mlp_param_count(cfg->sh_deg), 0.f, s);
+    PXO_TRY(launch_occ_gather(d_rgb, d_sigma, k->slot, p.M, rgb_channels(cfg->sh_deg), k->d_rgb_live, k->d_sigma_live, s));
+    d_rgb = k->d_rgb_live;
+    d_sigma = k->d_sigma_live;
+  }
+  uint8_t* const live = plan.skip ? p.live : nullptr;
+  PXO_TRY(launch_mlp_bwd_data(cfg, packed_bwd, d_rgb, d_sigma, p.mask, M, p.dz, p.dbias, live, tile_counter, s, plan.bias_from_wgrad));
+  if (join && !join->join()) {
+    set_error("%s: join of the side stream failed", who);
+    return PXO_ERR_HIP;
+  }
+  return launch_mlp_bwd_weights(cfg, p.acts, p.enc, p.dz, d_rgb, d_sigma, p.dbias, M, grads, t.wgrad_ws, t.wgrad_bytes, live, s,
+                                wgrad_split(M, num_cus(), tu), plan.x6_main, plan.bias_from_wgrad);
 }
 
 // diagnostic: `blocks` workgroups of `threads` threads that do nothing for `micros` microseconds of the device's
@@ -606,38 +748,38 @@ int pxo_adam_step(float* params, float* m, float* v, const float* grads, int64_t
 }
 
 int pxo_render_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
-  PXO_TRY(validate_cfg(cfg));
-  PXO_REQUIRE(bytes && B >= 0, "pxo_render_workspace_bytes: bad arguments");
-  TrainWs t;
-  carve_train(cfg, B, nullptr, false, t);
-  *bytes = t.total;
-  return PXO_OK;
+  return workspace_bytes(cfg, B, false, false, false, "pxo_render_workspace_bytes", bytes);
+}
+int pxo_render_culled_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
+  return workspace_bytes(cfg, B, false, false, true, "pxo_render_culled_workspace_bytes", bytes);
 }
 
-// lobes != NULL: the NeRF-SG form (pxo_sg_render_fwd); only the shade/composite launches differ
+// The render sequence.  lobes != NULL: the NeRF-SG form (pxo_sg_render_fwd), only the shade/composite launches differ;
+// occ != NULL: the culled form (pxo_render_fwd_culled), each level's MLP between a cull and an expand, two synchronisations
 static int render_fwd_impl(const PxoCfg* cfg, const float* packed_fwd0, const float* packed_fwd1, const float* origins,
                            const float* directions, const float* viewdirs, int64_t B, int randomized, const float* t_rand,
                            const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f,
                            float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream, const float* lobes,
-                           const char* who) {
+                           const PxoOccGrid* occ, int64_t* live_rows, const char* who) {
   PXO_TRY(validate_cfg(cfg));
   if (B == 0) return PXO_OK;                   // an empty batch has no buffers to check
   PXO_REQUIRE(B >= 0 && packed_fwd0 && origins && directions && viewdirs && rgb_c && disp_c && acc_c && ws,
               "%s: bad arguments", who);
   if (cfg->num_fine_samples > 0)
     PXO_REQUIRE(packed_fwd1 && rgb_f && disp_f && acc_f, "%s: fine outputs/weights missing", who);
-  TrainWs t;
-  carve_train(cfg, B, ws, false, t);
-  if (ws_bytes < t.total) {
-    set_error("%s: workspace %zu < %zu", who, ws_bytes, t.total);
-    return PXO_ERR_WORKSPACE;
-  }
+  Layout L;
+  PXO_TRY(lay_out(cfg, B, ws, ws_bytes, false, false, occ != nullptr, who, L));
+  CullCtx cull;
+  if (occ) PXO_TRY(open_cull(occ, L.k, live_rows, who, cull));
+  const CullCtx* cx = occ ? &cull : nullptr;
   hipStream_t s = (hipStream_t)stream;
   Draws dr;
-  PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, nullptr, seed, s, dr));
-  PXO_TRY(forward_coarse(cfg, t, packed_fwd0, origins, directions, viewdirs, B, dr, nullptr, rgb_c, disp_c, acc_c, s, nullptr, lobes));
+  PXO_TRY(prepare_draws(cfg, L.t, B, randomized, t_rand, u, nullptr, seed, s, dr));
+  PXO_TRY(level_forward(cfg, L.t, 0, packed_fwd0, origins, directions, viewdirs, B, dr, nullptr, rgb_c, disp_c, acc_c, s, nullptr,
+                        lobes, nullptr, cx, who));
   if (cfg->num_fine_samples > 0)
-    PXO_TRY(forward_fine(cfg, t, packed_fwd1, origins, directions, viewdirs, B, dr, nullptr, rgb_f, disp_f, acc_f, s, nullptr, lobes));
+    PXO_TRY(level_forward(cfg, L.t, 1, packed_fwd1, origins, directions, viewdirs, B, dr, nullptr, rgb_f, disp_f, acc_f, s, nullptr,
+                          lobes, nullptr, cx, who));
   return PXO_OK;
 }
 
@@ -646,7 +788,7 @@ int pxo_render_fwd(const PxoCfg* cfg, const float* packed_fwd0, const float* pac
                    const float* u, uint64_t seed, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f,
                    float* disp_f, float* acc_f, void* ws, size_t ws_bytes, void* stream) {
   return render_fwd_impl(cfg, packed_fwd0, packed_fwd1, origins, directions, viewdirs, B, randomized, t_rand, u, seed, rgb_c,
-                         disp_c, acc_c, rgb_f, disp_f, acc_f, ws, ws_bytes, stream, nullptr, "pxo_render_fwd");
+                         disp_c, acc_c, rgb_f, disp_f, acc_f, ws, ws_bytes, stream, nullptr, nullptr, nullptr, "pxo_render_fwd");
 }
 
 int pxo_sg_render_fwd(const PxoCfg* cfg, const float* lobes, const float* packed_fwd0, const float* packed_fwd1,
@@ -657,71 +799,7 @@ int pxo_sg_render_fwd(const PxoCfg* cfg, const float* lobes, const float* packed
   PXO_REQUIRE(lobes, "pxo_sg_render_fwd: null lobes ([sg_dim,4] with sg_dim = (sh_deg+1)^2 = %d)",
               (cfg->sh_deg + 1) * (cfg->sh_deg + 1));
   return render_fwd_impl(cfg, packed_fwd0, packed_fwd1, origins, directions, viewdirs, B, randomized, t_rand, u, seed, rgb_c,
-                         disp_c, acc_c, rgb_f, disp_f, acc_f, ws, ws_bytes, stream, lobes, "pxo_sg_render_fwd");
-}
-
-}  // extern "C"
-
-namespace pxo {
-
-// What pxo_render_fwd_culled keeps behind the render workspace (whose layout stays pxo_render_fwd's): the compact point and
-// output rows of ONE level (the fine level's size; the coarse level uses their head), the slots, the two counts and the cull's scratch
-struct CullWs { float *pts_live, *rgb_live, *sigma_live; int32_t* slot; int64_t* n_live; void* cull; size_t total; };
-static void carve_cull(const PxoCfg* cfg, int64_t B, void* ws, size_t render_total, CullWs& k) {
-  Carver c(ws);
-  c.off = render_total;
-  const int64_t M = B * (cfg->num_coarse_samples + cfg->num_fine_samples);
-  k.pts_live = c.take<float>(M * 3);
-  k.rgb_live = c.take<float>(M * rgb_channels(cfg->sh_deg));
-  k.sigma_live = c.take<float>(M);
-  k.slot = c.take<int32_t>(M);
-  k.n_live = c.take<int64_t>(2);
-  k.cull = c.take<char>((int64_t)occ_cull_workspace_bytes(M));
-  k.total = (c.off + 255) & ~(size_t)255;
-}
-
-// the pinned words the two counts of a call land in: one pair per host thread, allocated on first use and kept for its life
-static int64_t* pinned_counts() {
-  static thread_local int64_t* p = nullptr;
-  if (!p && hipHostMalloc((void**)&p, 2 * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) p = nullptr;
-  return p;
-}
-
-// One level between its sampling launch and its shade + composite launch: cull, the MLP on the live rows, expand.  Synchronises.
-static int culled_mlp(const PxoCfg* cfg, const PxoOccGrid& occ, CullWs& k, int level, const float* packed, PassBuffers& p,
-                      int64_t* host_count, hipStream_t s) {
-  PXO_TRY(launch_occ_cull(occ, p.pts, p.M, k.pts_live, k.slot, k.n_live + level, k.cull, s));
-  if (hipMemcpyAsync(host_count, k.n_live + level, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    set_error("pxo_render_fwd_culled: reading the live-row count: %s", hipGetErrorString(hipGetLastError()));
-    return PXO_ERR_HIP;
-  }
-  const int64_t n_live = *host_count;
-  if (n_live < 0 || n_live > p.M) {
-    set_error("pxo_render_fwd_culled: live-row count %lld outside [0, %lld]", (long long)n_live, (long long)p.M);
-    return PXO_ERR_HIP;
-  }
-  if (n_live > 0)
-    PXO_TRY(launch_mlp_fwd(cfg, packed, k.pts_live, n_live, k.rgb_live, k.sigma_live, nullptr, nullptr, nullptr, s));
-  return launch_occ_expand(k.rgb_live, k.sigma_live, k.slot, p.M, rgb_channels(cfg->sh_deg), p.raw_rgb, p.raw_sigma, s);
-}
-
-}  // namespace pxo
-
-extern "C" {
-
-int pxo_render_culled_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
-  PXO_TRY(validate_cfg(cfg));
-  PXO_REQUIRE(bytes && B >= 0, "pxo_render_culled_workspace_bytes: bad arguments");
-  PXO_REQUIRE(B * (int64_t)(cfg->num_coarse_samples + cfg->num_fine_samples) < ((int64_t)1 << 31),
-              "pxo_render_culled_workspace_bytes: %lld rays x %d samples exceed 2^31 rows", (long long)B,
-              cfg->num_coarse_samples + cfg->num_fine_samples);
-  TrainWs t;
-  carve_train(cfg, B, nullptr, false, t);
-  CullWs k;
-  carve_cull(cfg, B, nullptr, t.total, k);
-  *bytes = k.total;
-  return PXO_OK;
+                         disp_c, acc_c, rgb_f, disp_f, acc_f, ws, ws_bytes, stream, lobes, nullptr, nullptr, "pxo_sg_render_fwd");
 }
 
 int pxo_render_fwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float* lobes, const float* packed_fwd0,
@@ -732,94 +810,60 @@ int pxo_render_fwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float*
   const char* who = "pxo_render_fwd_culled";
   PXO_TRY(validate_cfg(cfg));
   PXO_TRY(occ_validate(occ, who));
-  if (randomized && cfg->noise_std > 0.f) {
-    set_error("%s: noise_std > 0 with randomized sampling (noise on a culled sample's zero sigma would resurrect it)", who);
-    return PXO_ERR_UNSUPPORTED;
-  }
+  PXO_TRY(refuse_noise(cfg, randomized, who));
   if (live_rows) live_rows[0] = live_rows[1] = 0;
-  if (B == 0) return PXO_OK;
-  const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
-  PXO_REQUIRE(B >= 0 && B * (int64_t)(Nc + Nf) < ((int64_t)1 << 31), "%s: %lld rays x %d samples outside [0, 2^31) rows", who,
-              (long long)B, Nc + Nf);
-  PXO_REQUIRE(packed_fwd0 && origins && directions && viewdirs && rgb_c && disp_c && acc_c && ws, "%s: bad arguments", who);
-  if (Nf > 0) PXO_REQUIRE(packed_fwd1 && rgb_f && disp_f && acc_f, "%s: fine outputs/weights missing", who);
-  TrainWs t;
-  carve_train(cfg, B, ws, false, t);
-  CullWs k;
-  carve_cull(cfg, B, ws, t.total, k);
-  if (ws_bytes < k.total) {
-    set_error("%s: workspace %zu < %zu", who, ws_bytes, k.total);
-    return PXO_ERR_WORKSPACE;
-  }
-  int64_t* host = pinned_counts();
-  if (!host) {
-    set_error("%s: hipHostMalloc of the count words failed", who);
-    return PXO_ERR_HIP;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  Draws dr;
-  PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, nullptr, seed, s, dr));
-  // the launches of forward_coarse / forward_fine, with the MLP of each level between a cull and an expand
-  PXO_TRY(launch_sample_along_rays(origins, directions, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, t.c.z, t.c.pts, s));
-  PXO_TRY(culled_mlp(cfg, *occ, k, 0, packed_fwd0, t.c, host, s));
-  if (live_rows) live_rows[0] = host[0];
-  PXO_TRY(launch_shade_composite_fwd(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, directions, viewdirs, B, Nc, rgb_c, disp_c, acc_c,
-                                     t.c.weights, s, lobes));
-  if (Nf > 0) {
-    PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, origins, directions, B, Nc, Nf, dr.u, t.f.z, t.f.pts, s));
-    PXO_TRY(culled_mlp(cfg, *occ, k, 1, packed_fwd1, t.f, host + 1, s));
-    if (live_rows) live_rows[1] = host[1];
-    PXO_TRY(launch_shade_composite_fwd(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, directions, viewdirs, B, Nc + Nf, rgb_f, disp_f,
-                                       acc_f, t.f.weights, s, lobes));
-  }
-  return PXO_OK;
+  return render_fwd_impl(cfg, packed_fwd0, packed_fwd1, origins, directions, viewdirs, B, randomized, t_rand, u, seed, rgb_c,
+                         disp_c, acc_c, rgb_f, disp_f, acc_f, ws, ws_bytes, stream, lobes, occ, live_rows, who);
 }
 
 int pxo_train_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
-  PXO_TRY(validate_cfg(cfg));
-  PXO_REQUIRE(bytes && B >= 1, "pxo_train_workspace_bytes: bad arguments");
-  TrainWs t;
-  carve_train(cfg, B, nullptr, true, t);
-  *bytes = t.total;
-  return PXO_OK;
+  return workspace_bytes(cfg, B, true, false, false, "pxo_train_workspace_bytes", bytes);
+}
+int pxo_sg_train_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
+  return workspace_bytes(cfg, B, true, true, false, "pxo_sg_train_workspace_bytes", bytes);
+}
+int pxo_train_culled_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
+  return workspace_bytes(cfg, B, true, false, true, "pxo_train_culled_workspace_bytes", bytes);
 }
 
+// The train sequence; `who` names the entry point in messages.
 // sg_params != nullptr: the NeRF-SG step (pxo_sg_train_fwd_bwd_bucketed) -- the shade launches take the lobe basis and leave the
-// partials of the lobe gradient, sg_grads is filled at the end, and weight_l2 counts the 3K SG entries; `who` names the entry
-// point in messages
+// partials of the lobe gradient, sg_grads is filled at the end, and weight_l2 counts the 3K SG entries.
+// occ != nullptr: the culled step (pxo_train_fwd_bwd_culled) -- both levels' MLPs, forward and reverse, run on the live rows
+// only, the step's record is kStepRecordCulled, and nothing is forked (the count read-back of each level synchronises).
 static int train_fwd_bwd_impl(const PxoCfg* cfg, const float* params, const float* packed_fwd0, const float* packed_bwd0,
                               const float* packed_fwd1, const float* packed_bwd1, const float* origins,
                               const float* directions, const float* viewdirs, const float* pixels, int64_t B,
                               int randomized, const float* t_rand, const float* u, const float* sp_points, uint64_t seed,
                               float* grads, float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream,
-                              const float* sg_params, float* sg_grads, const char* who) {
+                              const float* sg_params, float* sg_grads, const PxoOccGrid* occ, int64_t* live_rows,
+                              const char* who) {
   PXO_TRY(validate_cfg(cfg));
   PXO_REQUIRE(B >= 1 && params && packed_fwd0 && packed_bwd0 && origins && directions && viewdirs && pixels && grads &&
                   stats && ws,
               "%s: bad arguments", who);
-  if (cfg->mlp_precision != PXO_MLP_F32 && cfg->mlp_precision != PXO_MLP_BF16X6) {
-    set_error("%s: training runs in float32 or its float32-accurate bf16x6 emulation only (mlp_precision bf16x3 is an inference option)", who);
-    return PXO_ERR_UNSUPPORTED;
-  }
+  PXO_TRY(require_train_precision(cfg, who));
   if (cfg->num_fine_samples > 0) PXO_REQUIRE(packed_fwd1 && packed_bwd1, "%s: MLP_1 images missing", who);
   hipStream_t s = (hipStream_t)stream;
-  TrainWs t;
-  carve_train(cfg, B, ws, true, t);
   const bool sg = sg_params != nullptr;
-  SgWs g{nullptr, nullptr, nullptr, 0, t.total};
-  if (sg) carve_sg(cfg, B, ws, t.total, g);
-  if (ws_bytes < g.total) {
-    set_error("%s: workspace %zu < %zu", who, ws_bytes, g.total);
-    return PXO_ERR_WORKSPACE;
-  }
+  Layout L;
+  PXO_TRY(lay_out(cfg, B, ws, ws_bytes, true, sg, occ != nullptr, who, L));
+  TrainWs& t = L.t;
+  const SgWs& g = L.g;
+  CullCtx cull;
+  if (occ) PXO_TRY(open_cull(occ, L.k, live_rows, who, cull));
+  const CullCtx* cx = occ ? &cull : nullptr;
+  const CullWs* k = occ ? &L.k : nullptr;
   const int deg = cfg->sh_deg;
   const int64_t n_mlp = mlp_param_count(deg);
   const int sgK = sh_dim(deg);
   const int64_t n_all = 2 * n_mlp + (sg ? 3 * sgK : 0);                     // the SG leaves are counted (train.py:101-108)
   const float wd_coef = 2.f * cfg->weight_decay_mult / (float)n_all;   // d/dp of weight_decay_mult * sum(p^2)/n (train.py:101-114)
   const int Nf = cfg->num_fine_samples;
-  // everything the step decides, from one snapshot of the tuning knobs, before its first launch
-  const StepPlan plan = plan_step(*cfg, t.c.M, Nf > 0 ? t.f.M : 0, num_cus(), tuning_snapshot());
+  // everything the step decides, from one snapshot of the tuning knobs, before its first launch (a culled step takes the dense
+  // step's decisions: a compact pass is no longer than the dense one, so a dense split that fits the live lists stays fitting)
+  const Tuning tu = tuning_snapshot();
+  const StepPlan plan = plan_step(*cfg, t.c.M, Nf > 0 ? t.f.M : 0, num_cus(), tu);
   // weight_l2 = sum(p^2) / n (train.py:101-108) depends on the parameters only: its partial sums ride in the step's first
   // launch, together with every uniform draw and the step words: the step's record (what pxo_train_backward_work reports)
   // and the tile counters of its four persistent MLP launches (forward / backward(data) of each level), zeroed -- the dense
@@ -833,42 +877,28 @@ static int train_fwd_bwd_impl(const PxoCfg* cfg, const float* params, const floa
   unsigned int* const cnt_bwd_f = (plan.dyn || cfg->skip_zero_rows) ? counters + 3 : nullptr;
   Draws dr;
   PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, sp_points, seed, s, dr, params, 2 * n_mlp, sumsq_partial, step_words,
-                        kStepWords, kStepRecord | (plan.skip ? 1u : 0u)));
+                        kStepWords, cx ? kStepRecordCulled : kStepRecord | (plan.skip ? 1u : 0u)));
   if (sg) PXO_TRY(launch_sg_lobes(sg_params, sgK, g.lobes, s));
   // coarse level: forward, losses (train.py:77-98), reverse of the compositing, reverse through MLP_0.  Nothing of the fine
   // level feeds MLP_0's gradient (the fine sample positions carry no gradient, model_utils.py:286), so it is complete here
   // -- a quarter into the step -- and its all-reduce can ride under the fine level.
-  PXO_TRY(forward_coarse(cfg, t, packed_fwd0, origins, directions, viewdirs, B, dr, pixels, nullptr, nullptr, nullptr, s,
-                         cnt_fwd_c, g.lobes, g.part_c));
-  // skip_zero_rows: rows with an exactly zero upstream gradient are left out of the reverse pass (bit-identical gradients)
-  uint8_t* const live_c = plan.skip ? t.c.live : nullptr;
-  uint8_t* const live_f = plan.skip ? t.f.live : nullptr;
+  int64_t M_c = 0, M_f = 0;
+  PXO_TRY(level_forward(cfg, t, 0, packed_fwd0, origins, directions, viewdirs, B, dr, pixels, nullptr, nullptr, nullptr, s,
+                        cnt_fwd_c, g.lobes, g.part_c, cx, who, &M_c));
   // The coarse reverse pass touches nothing the fine forward reads or writes (its own workspace slices, the MLP_0 half of
   // `grads`; the weight-gradient slabs are shared with the fine pass, which therefore waits for it): with plan.fork it runs
   // on the side stream, beside sample_pdf / the fine forward, and joins before the fine weight gradients.
-  SideFork fk(s, plan.fork);
-  PXO_TRY(launch_mlp_bwd_data(cfg, packed_bwd0, t.c.d_raw_rgb, t.c.d_raw_sigma, t.c.mask, t.c.M, t.c.dz, t.c.dbias, live_c,
-                              cnt_bwd_c, fk.sc, plan.bias_from_wgrad));
-  PXO_TRY(launch_mlp_bwd_weights(cfg, t.c.acts, t.c.enc, t.c.dz, t.c.d_raw_rgb, t.c.d_raw_sigma, t.c.dbias, t.c.M,
-                                 grads, t.wgrad_ws, t.wgrad_bytes, live_c, fk.sc, plan.split_c, plan.x6_main,
-                                 plan.bias_from_wgrad));
+  SideFork fk(s, plan.fork && !cx);
+  PXO_TRY(level_reverse(cfg, t, t.c, packed_bwd0, M_c, grads, plan, tu, cnt_bwd_c, fk.sc, k, nullptr, who));
   if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads, params, n_mlp, wd_coef, fk.sc));
   if (grads0_ready && hipEventRecord((hipEvent_t)grads0_ready, fk.sc) != hipSuccess) {
     set_error("%s: hipEventRecord(grads0_ready) failed", who);
     return PXO_ERR_HIP;
   }
   if (Nf > 0) {
-    PXO_TRY(forward_fine(cfg, t, packed_fwd1, origins, directions, viewdirs, B, dr, pixels, nullptr, nullptr, nullptr, s,
-                         cnt_fwd_f, g.lobes, g.part_f));
-    PXO_TRY(launch_mlp_bwd_data(cfg, packed_bwd1, t.f.d_raw_rgb, t.f.d_raw_sigma, t.f.mask, t.f.M, t.f.dz, t.f.dbias, live_f,
-                                cnt_bwd_f, s, plan.bias_from_wgrad));
-    if (!fk.join()) {                                         // the slabs are the coarse pass's until here
-      set_error("%s: join of the side stream failed", who);
-      return PXO_ERR_HIP;
-    }
-    PXO_TRY(launch_mlp_bwd_weights(cfg, t.f.acts, t.f.enc, t.f.dz, t.f.d_raw_rgb, t.f.d_raw_sigma, t.f.dbias, t.f.M,
-                                   grads + n_mlp, t.wgrad_ws, t.wgrad_bytes, live_f, s, plan.split_f, plan.x6_main,
-                                   plan.bias_from_wgrad));
+    PXO_TRY(level_forward(cfg, t, 1, packed_fwd1, origins, directions, viewdirs, B, dr, pixels, nullptr, nullptr, nullptr, s,
+                          cnt_fwd_f, g.lobes, g.part_f, cx, who, &M_f));
+    PXO_TRY(level_reverse(cfg, t, t.f, packed_bwd1, M_f, grads + n_mlp, plan, tu, cnt_bwd_f, s, k, &fk, who));
   } else {
     PXO_TRY(launch_fill(grads + n_mlp, n_mlp, 0.f, s));
   }
@@ -890,7 +920,24 @@ int pxo_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const flo
                                float* grads, float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream) {
   return train_fwd_bwd_impl(cfg, params, packed_fwd0, packed_bwd0, packed_fwd1, packed_bwd1, origins, directions, viewdirs,
                             pixels, B, randomized, t_rand, u, sp_points, seed, grads, stats, ws, ws_bytes, grads0_ready, stream,
-                            nullptr, nullptr, "pxo_train_fwd_bwd");
+                            nullptr, nullptr, nullptr, nullptr, "pxo_train_fwd_bwd");
+}
+
+// (no sg_params: a culled NeRF-SG step is not built, and the families table refuses it before this is reached)
+int pxo_train_fwd_bwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float* params, const float* packed_fwd0,
+                             const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1, const float* origins,
+                             const float* directions, const float* viewdirs, const float* pixels, int64_t B, int randomized,
+                             const float* t_rand, const float* u, const float* sp_points, uint64_t seed, float* grads,
+                             float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream, int64_t live_rows[2]) {
+  const char* who = "pxo_train_fwd_bwd_culled";
+  PXO_TRY(validate_cfg(cfg));
+  PXO_TRY(occ_validate(occ, who));
+  PXO_TRY(require_train_precision(cfg, who));
+  PXO_TRY(refuse_noise(cfg, randomized, who));
+  if (live_rows) live_rows[0] = live_rows[1] = 0;
+  return train_fwd_bwd_impl(cfg, params, packed_fwd0, packed_bwd0, packed_fwd1, packed_bwd1, origins, directions, viewdirs,
+                            pixels, B, randomized, t_rand, u, sp_points, seed, grads, stats, ws, ws_bytes, grads0_ready, stream,
+                            nullptr, nullptr, occ, live_rows, who);
 }
 
 int pxo_sg_lobes(const float* sg_params, int K, float* lobes, void* stream) {
@@ -922,17 +969,6 @@ int pxo_sg_shade_composite_train(const PxoCfg* cfg, const float* lobes, const fl
   return launch_sg_lobe_grad(lobe_partials, sg_ray_blocks(B), nullptr, 0, K, nullptr, 0.f, d_lobes, nullptr, nullptr, s);
 }
 
-int pxo_sg_train_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
-  PXO_TRY(validate_cfg(cfg));
-  PXO_REQUIRE(bytes && B >= 1, "pxo_sg_train_workspace_bytes: bad arguments");
-  TrainWs t;
-  carve_train(cfg, B, nullptr, true, t);
-  SgWs g;
-  carve_sg(cfg, B, nullptr, t.total, g);
-  *bytes = g.total;
-  return PXO_OK;
-}
-
 int pxo_sg_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const float* sg_params, const float* packed_fwd0,
                                   const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1,
                                   const float* origins, const float* directions, const float* viewdirs, const float* pixels,
@@ -943,7 +979,7 @@ int pxo_sg_train_fwd_bwd_bucketed(const PxoCfg* cfg, const float* params, const 
   PXO_REQUIRE(sg_grads != nullptr, "pxo_sg_train_fwd_bwd: null sg_grads ([3K])");
   return train_fwd_bwd_impl(cfg, params, packed_fwd0, packed_bwd0, packed_fwd1, packed_bwd1, origins, directions, viewdirs,
                             pixels, B, randomized, t_rand, u, sp_points, seed, grads, stats, ws, ws_bytes, grads0_ready, stream,
-                            sg_params, sg_grads, "pxo_sg_train_fwd_bwd");
+                            sg_params, sg_grads, nullptr, nullptr, "pxo_sg_train_fwd_bwd");
 }
 
 int pxo_sg_train_fwd_bwd(const PxoCfg* cfg, const float* params, const float* sg_params, const float* packed_fwd0,
@@ -966,197 +1002,13 @@ int pxo_train_fwd_bwd(const PxoCfg* cfg, const float* params, const float* packe
                                     nullptr, stream);
 }
 
-}  // extern "C"
-
-namespace pxo {
-
-// The record of a culled step (pxo_train_fwd_bwd_culled) in the step words: not kStepRecord, so that pxo_train_backward_work,
-// whose chunk totals are those of the dense row count, refuses such a workspace by name.
-constexpr unsigned int kStepRecordCulled = 0x5E7DC000u;
-
-// What pxo_train_fwd_bwd_culled keeps behind the TrainWs block (whose layout stays pxo_train_fwd_bwd's), after carve_cull: the
-// compact points, raw rows and upstream gradient of ONE level (the last level's size, sparsity points included; the coarse
-// level uses their head), the slots, the two counts and the cull's scratch
-struct TrainCullWs {
-  float *pts_live, *rgb_live, *sigma_live, *d_rgb_live, *d_sigma_live;
-  int32_t* slot;
-  int64_t* n_live;
-  void* cull;
-  size_t total;
-};
-static void carve_train_cull(const PxoCfg* cfg, int64_t B, void* ws, const TrainWs& t, TrainCullWs& k) {
-  Carver c(ws);
-  c.off = t.total;
-  const int C = rgb_channels(cfg->sh_deg);
-  const int64_t rows = B * (cfg->num_coarse_samples + cfg->num_fine_samples), M = rows + t.n_sp;
-  k.pts_live = c.take<float>(M * 3);
-  k.rgb_live = c.take<float>(M * C);
-  k.sigma_live = c.take<float>(M);
-  k.d_rgb_live = c.take<float>(M * C);
-  k.d_sigma_live = c.take<float>(M);
-  k.slot = c.take<int32_t>(M);
-  k.n_live = c.take<int64_t>(2);
-  k.cull = c.take<char>((int64_t)occ_cull_workspace_bytes(rows));
-  k.total = (c.off + 255) & ~(size_t)255;
-}
-
-// One level of the culled step between its sampling launch and its shade + composite launch: cull the B * p.S sample rows, read
-// n_live (synchronises), append the always-live rows behind the samples (the sparsity points of the last level: p.M - B * p.S
-// of them), the training forward on the compact rows -- acts / enc / mask in compact order -- and expand.  *M_live: the rows
-// the level's MLP launches run on.
-static int culled_train_forward(const PxoCfg* cfg, const PxoOccGrid& occ, TrainCullWs& k, int level, const float* packed_fwd,
-                                PassBuffers& p, int64_t B, int64_t* host_count, unsigned int* tile_counter, hipStream_t s,
-                                int64_t* M_live) {
-  const char* who = "pxo_train_fwd_bwd_culled";
-  const int64_t rows = B * p.S, extra = p.M - rows;
-  PXO_TRY(launch_occ_cull(occ, p.pts, rows, k.pts_live, k.slot, k.n_live + level, k.cull, s));
-  if (hipMemcpyAsync(host_count, k.n_live + level, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    set_error("%s: reading the live-row count: %s", who, hipGetErrorString(hipGetLastError()));
-    return PXO_ERR_HIP;
-  }
-  const int64_t n_live = *host_count;
-  if (n_live < 0 || n_live > rows) {
-    set_error("%s: live-row count %lld outside [0, %lld]", who, (long long)n_live, (long long)rows);
-    return PXO_ERR_HIP;
-  }
-  if (extra > 0) {                                    // slot[rows + j] = n_live + j <= p.M - 1: inside the compact arrays
-    if (hipMemcpyAsync(k.pts_live + 3 * n_live, p.pts + 3 * rows, (size_t)extra * 3 * sizeof(float), hipMemcpyDeviceToDevice, s) !=
-        hipSuccess) {
-      set_error("%s: hipMemcpyAsync(sparsity points) failed", who);
-      return PXO_ERR_HIP;
-    }
-    PXO_TRY(launch_occ_tail_slots(k.slot + rows, extra, n_live, s));
-  }
-  *M_live = n_live + extra;
-  if (*M_live > 0)
-    PXO_TRY(launch_mlp_fwd(cfg, packed_fwd, k.pts_live, *M_live, k.rgb_live, k.sigma_live, p.acts, p.enc, p.mask, s, tile_counter));
-  return launch_occ_expand(k.rgb_live, k.sigma_live, k.slot, p.M, rgb_channels(cfg->sh_deg), p.raw_rgb, p.raw_sigma, s);
-}
-
-// The reverse of that level: the dense d_raw_* of the shade launch gathered to compact order, then the existing backward(data)
-// and weight-gradient launches on M_live rows, with the split of that M.  No live row: no MLP launch, a zero gradient.
-static int culled_train_reverse(const PxoCfg* cfg, TrainWs& t, TrainCullWs& k, const float* packed_bwd, PassBuffers& p,
-                                int64_t M_live, float* grads, int64_t n_mlp, const StepPlan& plan, const Tuning& tu,
-                                unsigned int* tile_counter, hipStream_t s) {
-  if (M_live == 0) return launch_fill(grads, n_mlp, 0.f, s);
-  PXO_TRY(launch_occ_gather(p.d_raw_rgb, p.d_raw_sigma, k.slot, p.M, rgb_channels(cfg->sh_deg), k.d_rgb_live, k.d_sigma_live, s));
-  uint8_t* const live = plan.skip ? p.live : nullptr;
-  PXO_TRY(launch_mlp_bwd_data(cfg, packed_bwd, k.d_rgb_live, k.d_sigma_live, p.mask, M_live, p.dz, p.dbias, live, tile_counter, s,
-                              plan.bias_from_wgrad));
-  return launch_mlp_bwd_weights(cfg, p.acts, p.enc, p.dz, k.d_rgb_live, k.d_sigma_live, p.dbias, M_live, grads, t.wgrad_ws,
-                                t.wgrad_bytes, live, s, wgrad_split(M_live, num_cus(), tu), plan.x6_main, plan.bias_from_wgrad);
-}
-
-}  // namespace pxo
-
-extern "C" {
-
-int pxo_train_culled_workspace_bytes(const PxoCfg* cfg, int64_t B, size_t* bytes) {
-  PXO_TRY(validate_cfg(cfg));
-  PXO_REQUIRE(bytes && B >= 1, "pxo_train_culled_workspace_bytes: bad arguments");
-  TrainWs t;
-  carve_train(cfg, B, nullptr, true, t);
-  PXO_REQUIRE(B * (int64_t)(cfg->num_coarse_samples + cfg->num_fine_samples) + t.n_sp < ((int64_t)1 << 31),
-              "pxo_train_culled_workspace_bytes: %lld rays x %d samples exceed 2^31 rows", (long long)B,
-              cfg->num_coarse_samples + cfg->num_fine_samples);
-  TrainCullWs k;
-  carve_train_cull(cfg, B, nullptr, t, k);
-  *bytes = k.total;
-  return PXO_OK;
-}
-
-int pxo_train_fwd_bwd_culled(const PxoCfg* cfg, const PxoOccGrid* occ, const float* params, const float* packed_fwd0,
-                             const float* packed_bwd0, const float* packed_fwd1, const float* packed_bwd1, const float* origins,
-                             const float* directions, const float* viewdirs, const float* pixels, int64_t B, int randomized,
-                             const float* t_rand, const float* u, const float* sp_points, uint64_t seed, float* grads,
-                             float* stats, void* ws, size_t ws_bytes, void* grads0_ready, void* stream, int64_t live_rows[2]) {
-  const char* who = "pxo_train_fwd_bwd_culled";
-  PXO_TRY(validate_cfg(cfg));
-  PXO_TRY(occ_validate(occ, who));
-  if (cfg->mlp_precision != PXO_MLP_F32 && cfg->mlp_precision != PXO_MLP_BF16X6) {
-    set_error("%s: training runs in float32 or its float32-accurate bf16x6 emulation only (mlp_precision bf16x3 is an inference option)", who);
-    return PXO_ERR_UNSUPPORTED;
-  }
-  if (randomized && cfg->noise_std > 0.f) {
-    set_error("%s: noise_std > 0 with randomized sampling (noise on a culled sample's zero sigma would resurrect it)", who);
-    return PXO_ERR_UNSUPPORTED;
-  }
-  if (live_rows) live_rows[0] = live_rows[1] = 0;
-  const int Nc = cfg->num_coarse_samples, Nf = cfg->num_fine_samples;
-  PXO_REQUIRE(B >= 1 && params && packed_fwd0 && packed_bwd0 && origins && directions && viewdirs && pixels && grads && stats && ws,
-              "%s: bad arguments", who);
-  if (Nf > 0) PXO_REQUIRE(packed_fwd1 && packed_bwd1, "%s: MLP_1 images missing", who);
-  hipStream_t s = (hipStream_t)stream;
-  TrainWs t;
-  carve_train(cfg, B, ws, true, t);
-  PXO_REQUIRE(B * (int64_t)(Nc + Nf) + t.n_sp < ((int64_t)1 << 31), "%s: %lld rays x %d samples exceed 2^31 rows", who, (long long)B,
-              Nc + Nf);
-  TrainCullWs k;
-  carve_train_cull(cfg, B, ws, t, k);
-  if (ws_bytes < k.total) {
-    set_error("%s: workspace %zu < %zu", who, ws_bytes, k.total);
-    return PXO_ERR_WORKSPACE;
-  }
-  int64_t* host = pinned_counts();
-  if (!host) {
-    set_error("%s: hipHostMalloc of the count words failed", who);
-    return PXO_ERR_HIP;
-  }
-  const int64_t n_mlp = mlp_param_count(cfg->sh_deg);
-  const int64_t n_all = 2 * n_mlp;
-  const float wd_coef = 2.f * cfg->weight_decay_mult / (float)n_all;
-  // the dense step's decisions (one snapshot of the knobs), but for the weight-gradient splits, which follow the compact M of
-  // each level (a compact pass is no longer than the dense one: a dense split that fits the live lists stays fitting)
-  const Tuning tu = tuning_snapshot();
-  const StepPlan plan = plan_step(*cfg, t.c.M, Nf > 0 ? t.f.M : 0, num_cus(), tu);
-  float* const sumsq_partial = t.scalars;
-  unsigned int* const step_words = reinterpret_cast<unsigned int*>(t.scalars + kStepWordsAt);
-  unsigned int* const counters = step_words + 2;
-  unsigned int* const cnt_fwd_c = plan.dyn ? counters + 0 : nullptr;
-  unsigned int* const cnt_fwd_f = plan.dyn ? counters + 2 : nullptr;
-  unsigned int* const cnt_bwd_c = (plan.dyn || cfg->skip_zero_rows) ? counters + 1 : nullptr;
-  unsigned int* const cnt_bwd_f = (plan.dyn || cfg->skip_zero_rows) ? counters + 3 : nullptr;
-  Draws dr;
-  PXO_TRY(prepare_draws(cfg, t, B, randomized, t_rand, u, sp_points, seed, s, dr, params, 2 * n_mlp, sumsq_partial, step_words,
-                        kStepWords, kStepRecordCulled));
-  // coarse level
-  int64_t M_c = 0, M_f = 0;
-  PXO_TRY(launch_sample_along_rays(origins, directions, B, Nc, cfg->near_, cfg->far_, cfg->lindisp, dr.t_rand, t.c.z, t.c.pts, s));
-  PXO_TRY(culled_train_forward(cfg, *occ, k, 0, packed_fwd0, t.c, B, host, cnt_fwd_c, s, &M_c));
-  if (live_rows) live_rows[0] = host[0];
-  PXO_TRY(launch_shade_composite_train(cfg, t.c.raw_rgb, t.c.raw_sigma, t.c.z, directions, viewdirs, pixels, B, Nc, nullptr,
-                                       Nf > 0 ? t.c.weights : nullptr, t.c.ray_sse, t.c.d_raw_rgb, t.c.d_raw_sigma,
-                                       Nf > 0 ? 0 : t.n_sp, t.sp_exp, nullptr, nullptr, s));
-  PXO_TRY(culled_train_reverse(cfg, t, k, packed_bwd0, t.c, M_c, grads, n_mlp, plan, tu, cnt_bwd_c, s));
-  if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads, params, n_mlp, wd_coef, s));
-  if (grads0_ready && hipEventRecord((hipEvent_t)grads0_ready, s) != hipSuccess) {
-    set_error("%s: hipEventRecord(grads0_ready) failed", who);
-    return PXO_ERR_HIP;
-  }
-  if (Nf > 0) {
-    PXO_TRY(launch_sample_pdf(t.c.z, t.c.weights, origins, directions, B, Nc, Nf, dr.u, t.f.z, t.f.pts, s));
-    PXO_TRY(culled_train_forward(cfg, *occ, k, 1, packed_fwd1, t.f, B, host + 1, cnt_fwd_f, s, &M_f));
-    if (live_rows) live_rows[1] = host[1];
-    PXO_TRY(launch_shade_composite_train(cfg, t.f.raw_rgb, t.f.raw_sigma, t.f.z, directions, viewdirs, pixels, B, Nc + Nf, nullptr,
-                                         nullptr, t.f.ray_sse, t.f.d_raw_rgb, t.f.d_raw_sigma, t.n_sp, t.sp_exp, nullptr, nullptr,
-                                         s));
-    PXO_TRY(culled_train_reverse(cfg, t, k, packed_bwd1, t.f, M_f, grads + n_mlp, n_mlp, plan, tu, cnt_bwd_f, s));
-  } else {
-    PXO_TRY(launch_fill(grads + n_mlp, n_mlp, 0.f, s));
-  }
-  if (cfg->weight_decay_mult != 0.f) PXO_TRY(launch_axpy(grads + n_mlp, params + n_mlp, n_mlp, wd_coef, s));
-  return launch_finalize_stats(Nf > 0 ? t.f.ray_sse : nullptr, t.c.ray_sse, t.n_sp > 0 ? t.sp_exp : nullptr, sumsq_partial, B,
-                               t.n_sp, cfg->sparsity_weight, n_all, stats, s);
-}
-
 int pxo_train_backward_work(const PxoCfg* cfg, int64_t B, void* ws, size_t ws_bytes, int64_t* live_chunks,
                             int64_t* total_chunks, void* stream) {
   PXO_TRY(validate_cfg(cfg));
   PXO_REQUIRE(B >= 1 && ws && live_chunks && total_chunks, "pxo_train_backward_work: bad arguments");
-  TrainWs t;
-  carve_train(cfg, B, ws, true, t);
-  if (ws_bytes < t.total) { set_error("pxo_train_backward_work: workspace %zu < %zu", ws_bytes, t.total); return PXO_ERR_WORKSPACE; }
+  Layout L;
+  PXO_TRY(lay_out(cfg, B, ws, ws_bytes, true, false, false, "pxo_train_backward_work", L));
+  const TrainWs& t = L.t;
   hipStream_t s = (hipStream_t)stream;
   const int64_t nc = (t.c.M + kLiveRows - 1) / kLiveRows, nf = cfg->num_fine_samples > 0 ? (t.f.M + kLiveRows - 1) / kLiveRows : 0;
   *total_chunks = nc + nf;

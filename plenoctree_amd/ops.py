@@ -259,28 +259,42 @@ def train_workspace_bytes(cfg, B):
     return n.value
 
 
+def _check_lobes(cfg, lobes):
+    if lobes is not None:
+        K = (cfg.sh_deg + 1) ** 2
+        if lobes.dtype != torch.float32 or tuple(lobes.shape) != (K, 4) or not lobes.is_contiguous() or not lobes.is_cuda:
+            raise PxoError(f"SG lobes must be a contiguous float32 [{K}, 4] tensor on the GPU")
+
+
+def _render_outputs(cfg, B, dev):
+    """The [(rgb, disp, acc)] list of the levels a render returns, and the six pointers the library takes (NULL without a fine level)."""
+    outs = [(_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev)) for _ in range(2 if cfg.num_fine_samples > 0 else 1)]
+    return outs, [_f(x) for lvl in outs for x in lvl] + [None] * (6 - 3 * len(outs))
+
+
+def _train_args(packed, origins, directions, viewdirs, pixels, randomized, t_rand, u, sp_points, seed, grads, stats, ws, grads0_ready):
+    """What the three train entry points share: the arguments from the packed images to `grads`, and those from `stats` on."""
+    (f0, b0), (f1, b1) = packed
+    head = (_f(f0), _f(b0), _f(f1), _f(b1), _f(origins), _f(directions), _f(viewdirs), _f(pixels), origins.shape[0], int(randomized),
+            _f(t_rand), _f(u), _f(sp_points), seed, _f(grads))
+    return head, (_f(stats), _p(ws), ws.numel(), grads0_ready.handle if grads0_ready is not None else None, _stream())
+
+
 def render_fwd(cfg, packed_fwd0, packed_fwd1, origins, directions, viewdirs, randomized=False, t_rand=None, u=None,
                seed=0, ws=None, lobes=None):
     """NerfModel.__call__ forward: [(rgb,disp,acc)_coarse, (rgb,disp,acc)_fine].  lobes [K,4] with K = (cfg.sh_deg+1)^2: the
     model is a NeRF-SG with sg_dim = K (pxo_sg_render_fwd) and is shaded with that basis instead of SH."""
     _require_gpu()
-    if lobes is not None:
-        K = (cfg.sh_deg + 1) ** 2
-        if lobes.dtype != torch.float32 or tuple(lobes.shape) != (K, 4) or not lobes.is_contiguous() or not lobes.is_cuda:
-            raise PxoError(f"SG lobes must be a contiguous float32 [{K}, 4] tensor on the GPU")
+    _check_lobes(cfg, lobes)
     lib = _lib.load()
     B = origins.shape[0]
     dev = origins.device
     nbytes = render_workspace_bytes(cfg, B)
     if ws is None or ws.numel() < nbytes:
         ws = _new(max(nbytes, 16), device=dev, dtype=torch.uint8)
-    outs = [(_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev))]
-    fine = cfg.num_fine_samples > 0
-    if fine:
-        outs.append((_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev)))
-    f = outs[1] if fine else (None, None, None)
+    outs, out_ptrs = _render_outputs(cfg, B, dev)
     tail = (_f(packed_fwd0), _f(packed_fwd1), _f(origins), _f(directions), _f(viewdirs), B, int(randomized), _f(t_rand), _f(u),
-            seed, _f(outs[0][0]), _f(outs[0][1]), _f(outs[0][2]), _f(f[0]), _f(f[1]), _f(f[2]), _p(ws), ws.numel(), _stream())
+            seed, *out_ptrs, _p(ws), ws.numel(), _stream())
     if lobes is None:
         check(lib.pxo_render_fwd(ctypes.byref(cfg), *tail), "pxo_render_fwd")
     else:
@@ -294,14 +308,9 @@ def train_fwd_bwd(cfg, params, packed, origins, directions, viewdirs, pixels, gr
     grads0_ready: an `Event` recorded on the current stream once MLP_0's half of `grads` is final (the coarse level is
     reversed before the fine level starts), or None."""
     _require_gpu()
-    lib = _lib.load()
-    (f0, b0), (f1, b1) = packed
-    B = origins.shape[0]
-    check(lib.pxo_train_fwd_bwd_bucketed(ctypes.byref(cfg), _f(params), _f(f0), _f(b0), _f(f1), _f(b1), _f(origins),
-                                         _f(directions), _f(viewdirs), _f(pixels), B, int(randomized), _f(t_rand), _f(u),
-                                         _f(sp_points), seed, _f(grads), _f(stats), _p(ws), ws.numel(),
-                                         grads0_ready.handle if grads0_ready is not None else None, _stream()),
-          "pxo_train_fwd_bwd_bucketed")
+    head, tail = _train_args(packed, origins, directions, viewdirs, pixels, randomized, t_rand, u, sp_points, seed, grads, stats, ws,
+                             grads0_ready)
+    check(_lib.load().pxo_train_fwd_bwd_bucketed(ctypes.byref(cfg), _f(params), *head, *tail), "pxo_train_fwd_bwd_bucketed")
 
 
 # ---- training a NeRF-SG: the pxo_sg_* entry points beside the three above -----------------------------------------------------
@@ -347,13 +356,9 @@ def sg_train_fwd_bwd(cfg, params, sg_params, packed, origins, directions, viewdi
     """train_fwd_bwd of a NeRF-SG: sg_params [3K] in, sg_grads [3K] out (d total loss / d raw SG parameters, weight decay
     included); stats[5] counts the SG leaves."""
     _require_gpu()
-    lib = _lib.load()
-    (f0, b0), (f1, b1) = packed
-    B = origins.shape[0]
-    check(lib.pxo_sg_train_fwd_bwd_bucketed(ctypes.byref(cfg), _f(params), _f(sg_params), _f(f0), _f(b0), _f(f1), _f(b1),
-                                            _f(origins), _f(directions), _f(viewdirs), _f(pixels), B, int(randomized), _f(t_rand),
-                                            _f(u), _f(sp_points), seed, _f(grads), _f(sg_grads), _f(stats), _p(ws), ws.numel(),
-                                            grads0_ready.handle if grads0_ready is not None else None, _stream()),
+    head, tail = _train_args(packed, origins, directions, viewdirs, pixels, randomized, t_rand, u, sp_points, seed, grads, stats, ws,
+                             grads0_ready)
+    check(_lib.load().pxo_sg_train_fwd_bwd_bucketed(ctypes.byref(cfg), _f(params), _f(sg_params), *head, _f(sg_grads), *tail),
           "pxo_sg_train_fwd_bwd_bucketed")
 
 
@@ -789,23 +794,15 @@ def render_fwd_culled(cfg, occ, packed_fwd0, packed_fwd1, origins, directions, v
     _require_gpu()
     if not isinstance(occ, OccupancyGrid):
         raise PxoError("render_fwd_culled: occ must be an ops.OccupancyGrid")
-    if lobes is not None:
-        K = (cfg.sh_deg + 1) ** 2
-        if lobes.dtype != torch.float32 or tuple(lobes.shape) != (K, 4) or not lobes.is_contiguous() or not lobes.is_cuda:
-            raise PxoError(f"SG lobes must be a contiguous float32 [{K}, 4] tensor on the GPU")
+    _check_lobes(cfg, lobes)
     B, dev = origins.shape[0], origins.device
     ws = _ws(ws, render_culled_workspace_bytes(cfg, B), dev)
-    outs = [(_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev))]
-    fine = cfg.num_fine_samples > 0
-    if fine:
-        outs.append((_new(B, 3, device=dev), _new(B, device=dev), _new(B, device=dev)))
-    f = outs[1] if fine else (None, None, None)
+    outs, out_ptrs = _render_outputs(cfg, B, dev)
     rows = (ctypes.c_int64 * 2)(0, 0)
     g = occ.struct()
     check(_lib.load().pxo_render_fwd_culled(ctypes.byref(cfg), ctypes.byref(g), _f(lobes), _f(packed_fwd0), _f(packed_fwd1),
                                             _f(origins), _f(directions), _f(viewdirs), B, int(randomized), _f(t_rand), _f(u), seed,
-                                            _f(outs[0][0]), _f(outs[0][1]), _f(outs[0][2]), _f(f[0]), _f(f[1]), _f(f[2]), rows,
-                                            _p(ws), ws.numel(), _stream()), "pxo_render_fwd_culled")
+                                            *out_ptrs, rows, _p(ws), ws.numel(), _stream()), "pxo_render_fwd_culled")
     if live_rows is not None:
         live_rows[:] = [rows[0], rows[1]]
     return outs
@@ -849,15 +846,11 @@ def train_fwd_bwd_culled(cfg, occ, params, packed, origins, directions, viewdirs
     _require_gpu()
     if occ is not None and not isinstance(occ, OccupancyGrid):
         raise PxoError("train_fwd_bwd_culled: occ must be an ops.OccupancyGrid")
-    lib = _lib.load()
-    (f0, b0), (f1, b1) = packed
-    B = origins.shape[0]
+    head, tail = _train_args(packed, origins, directions, viewdirs, pixels, randomized, t_rand, u, sp_points, seed, grads, stats, ws,
+                             grads0_ready)
     rows = (ctypes.c_int64 * 2)(0, 0)
     g = occ.struct() if occ is not None else None
-    check(lib.pxo_train_fwd_bwd_culled(ctypes.byref(cfg), ctypes.byref(g) if g is not None else None, _f(params), _f(f0), _f(b0),
-                                       _f(f1), _f(b1), _f(origins), _f(directions), _f(viewdirs), _f(pixels), B, int(randomized),
-                                       _f(t_rand), _f(u), _f(sp_points), seed, _f(grads), _f(stats), _p(ws), ws.numel(),
-                                       grads0_ready.handle if grads0_ready is not None else None, _stream(), rows),
-          "pxo_train_fwd_bwd_culled")
+    check(_lib.load().pxo_train_fwd_bwd_culled(ctypes.byref(cfg), ctypes.byref(g) if g is not None else None, _f(params), *head,
+                                               *tail, rows), "pxo_train_fwd_bwd_culled")
     if live_rows is not None:
         live_rows[:] = [rows[0], rows[1]]
