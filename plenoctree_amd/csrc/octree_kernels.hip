@@ -807,8 +807,11 @@ __device__ __forceinline__ float row_sum(float v) {   // sum over the ROW lanes 
 
 // sh_basis_dyn / sg_basis_dyn, the per-ray basis of either tree format: pxo_sh.h (shared with pxo_shade_points)
 
-struct RenderArgs {
-  PxoTree tree;
+// The argument block of the renderers of a tree with float or float16 rows (Tree: PxoTree or PxoHalfTree).  The member order
+// is the kernels' kernarg layout: pinned below.
+template <typename Tree>
+struct FwdBlock {
+  Tree tree;
   PxoCamera cam;
   int has_cam;
   const float* origins;
@@ -819,8 +822,15 @@ struct RenderArgs {
   const float* lobes;                          // NULL: SH tree; else the [basis_dim,4] lobes of an SG tree (kernel-uniform)
   PxoNdc ndc;                                  // width == 0: world-space rays; else the NDC set-up of ndc_ray (kernel-uniform)
 };
+using RenderArgs = FwdBlock<PxoTree>;          // also what the backward and the counting kernel take
+static_assert(sizeof(RenderArgs) == 160 && offsetof(RenderArgs, opt) == 120 && offsetof(RenderArgs, lobes) == 136 &&
+              offsetof(RenderArgs, ndc) == 144, "kernarg layout of the float tree's renderers");
+static_assert(sizeof(FwdBlock<PxoHalfTree>) == 168 && offsetof(FwdBlock<PxoHalfTree>, opt) == 128 &&
+              offsetof(FwdBlock<PxoHalfTree>, lobes) == 144 && offsetof(FwdBlock<PxoHalfTree>, ndc) == 152,
+              "kernarg layout of the float16 tree's renderers");
 // the per-ray basis of either tree format; everything after it sees only basis[k]
-__device__ __forceinline__ void ray_basis(const RenderArgs& A, int basis_dim, const float (&vdir)[3], float* Y) {
+template <typename Tree>
+__device__ __forceinline__ void ray_basis(const FwdBlock<Tree>& A, int basis_dim, const float (&vdir)[3], float* Y) {
   if (A.lobes) sg_basis_dyn(basis_dim, A.lobes, vdir[0], vdir[1], vdir[2], Y);
   else sh_basis_dyn(basis_dim, vdir[0], vdir[1], vdir[2], Y);
 }
@@ -829,29 +839,10 @@ struct AuxOut {
   float* out;                                  // [B,3]: alpha, depth, surface (plenoctree_octree.h)
   float surface_thresh;
 };
-struct RenderAuxArgs : RenderArgs, AuxOut {};
-// The argument block of a float16 tree (PxoHalfTree): RenderArgs member for member with the other tree view, so that the
-// forward kernel reads A.tree / A.opt / A.lobes / A.ndc of either.
-struct HalfRenderArgs {
-  PxoHalfTree tree;
-  PxoCamera cam;
-  int has_cam;
-  const float* origins;
-  const float* dirs;
-  const float* viewdirs;
-  int64_t B;
-  PxoRenderOpts opt;
-  const float* lobes;
-  PxoNdc ndc;
-};
-__device__ __forceinline__ void ray_basis(const HalfRenderArgs& A, int basis_dim, const float (&vdir)[3], float* Y) {
-  if (A.lobes) sg_basis_dyn(basis_dim, A.lobes, vdir[0], vdir[1], vdir[2], Y);
-  else sh_basis_dyn(basis_dim, vdir[0], vdir[1], vdir[2], Y);
-}
-struct HalfRenderAuxArgs : HalfRenderArgs, AuxOut {};
+template <typename Block> struct WithAux : Block, AuxOut {};
+template <typename Block, bool AUX> using MaybeAux = std::conditional_t<AUX, WithAux<Block>, Block>;
 // ST: what a leaf row stores, float (PxoTree) or _Float16 (PxoHalfTree)
-template <typename ST, bool AUX> struct FwdArgs { using type = std::conditional_t<AUX, RenderAuxArgs, RenderArgs>; };
-template <bool AUX> struct FwdArgs<_Float16, AUX> { using type = std::conditional_t<AUX, HalfRenderAuxArgs, HalfRenderArgs>; };
+template <typename ST> using TreeOf = std::conditional_t<std::is_same<ST, float>::value, PxoTree, PxoHalfTree>;
 
 // Four consecutive halves of a float16 leaf row, widened (exactly) to float32.  ALIGN: what is known at compile time of the
 // first half's index modulo 4 -- rows start 8-byte aligned (row_stride is a multiple of 4).  0: one 8-byte load; 2: two
@@ -983,7 +974,8 @@ __device__ __forceinline__ RowId row_ray(const Args& A, int row, float (&origin)
 // K/4 whole groups and coefficient 4 (K/4) + l of the K % 4 left over, so the basis values a lane needs are the same for
 // the three channels: 4 ceil(K/4/ROW) + 1 registers instead of a selector-weighted triple per data element, and a third
 // of the FMAs.  KF = K (1, 4, 9, 16, 25) makes K a compile-time constant (SH16 at 4 lanes: one float4 per lane and channel,
-// 56 VGPRs - 8 waves per SIMD - against 112 for the index-ordered path); KF = -1 keeps it a run-time value.
+// 56 VGPRs - 8 waves per SIMD - against 112 for the index-ordered path); KF = -1 keeps it a run-time value (no
+// forward launch instantiates that: check_format admits the five formats only; octree_render_bwd4_kernel<-1> is launched).
 // AUX (forward only): three more row-uniform accumulators per ray -- alpha = sum of the weights, depth = sum of weight x
 // sample distance, surface = distance of the sample at which the transmittance first falls to A.surface_thresh -- written to
 // A.out[ray*3 + c] by the lanes that write out_rgb.  A sample's distance is (t + delta / 2) delta_scale with the sample's OWN
@@ -993,7 +985,7 @@ __device__ __forceinline__ RowId row_ray(const Args& A, int row, float (&origin)
 // the logical indices, multiplies and adds in the order of the float instantiation with the same MODE, ROW, KF and AUX: the
 // two return the same bits for a tree whose float data is the widened halves.
 template <int MODE, int ROW, bool VEC = false, int KF = 0, bool AUX = false, typename ST = float>
-__global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(typename FwdArgs<ST, AUX>::type A,
+__global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(MaybeAux<FwdBlock<TreeOf<ST>>, AUX> A,
                                                                         float* __restrict__ out_rgb,
                                                                         const float* __restrict__ fwd_rgb,
                                                                         const float* __restrict__ grad_out,
@@ -1731,7 +1723,6 @@ struct QuantRenderArgs {
   int64_t B;
   PxoRenderOpts opt;
 };
-struct QuantRenderAuxArgs : QuantRenderArgs, AuxOut {};
 
 // octree_render_kernel<0, ROW>'s rays, march and compositing; a shaded sample's colour comes through the palettes.  Plane
 // ownership inside a ray's ROW lanes: lane l owns the retained planes l, l + ROW, .. and the groups l, l + ROW, .. of four
@@ -1740,7 +1731,7 @@ struct QuantRenderAuxArgs : QuantRenderArgs, AuxOut {};
 // depends on (ROW, K, r) only.  AUX: the float kernel's three extra outputs, the same way (they depend on sigma and the
 // geometry only, and sigma is the float tree's).
 template <int ROW, bool AUX = false>
-__global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(std::conditional_t<AUX, QuantRenderAuxArgs, QuantRenderArgs> A,
+__global__ __launch_bounds__(kRenderThreads) void octree_render_quant_kernel(MaybeAux<QuantRenderArgs, AUX> A,
                                                                               float* __restrict__ out_rgb) {
   using G = RowGeom<ROW>;
   constexpr int kRow = ROW, kRaysPerBlock = G::kRaysPerBlock;
@@ -2020,8 +2011,8 @@ using namespace pxo;
 static inline int64_t blocks_for(int64_t n, int threads) { return (n + threads - 1) / threads; }
 
 // ---- renderer launches (templates: outside the C linkage block) ----
-// What the float and the palette renderers share of a launch at `row` lanes per ray: the checks on the camera or the ray
-// arrays, the rays' part of the argument block (Args: RenderArgs or QuantRenderArgs) and the block count.
+// What the renderers of every form share of a launch at `row` lanes per ray: the checks on the camera or the ray arrays,
+// the rays' part of the argument block (Args: a FwdBlock or QuantRenderArgs) and the block count.
 template <typename Args>
 static int launch_shape(const PxoCamera* cam, const float* origins, const float* dirs, const float* viewdirs, int64_t B, int row,
                         const char* who, Args& A, unsigned& grid) {
@@ -2047,52 +2038,31 @@ static int launch_shape(const PxoCamera* cam, const float* origins, const float*
   return PXO_OK;
 }
 
-// Forward launch of a float tree.  4 lanes per ray: the channel-aligned kernel with the tree's basis_dim as a compile-time
-// constant; 8 / 16 lanes: groups of four consecutive floats.
-template <bool AUX>
-static void launch_render_fwd(const std::conditional_t<AUX, RenderAuxArgs, RenderArgs>& A, int row, unsigned grid, float* out_rgb,
-                              void* stream) {
-  auto kernel = row == 8 ? octree_render_kernel<0, 8, true, 0, AUX> : octree_render_kernel<0, 16, true, 0, AUX>;
-  if (row == 4) {
-    switch (A.tree.basis_dim) {
-      case 1: kernel = octree_render_kernel<0, 4, true, 1, AUX>; break;
-      case 4: kernel = octree_render_kernel<0, 4, true, 4, AUX>; break;
-      case 9: kernel = octree_render_kernel<0, 4, true, 9, AUX>; break;
-      case 16: kernel = octree_render_kernel<0, 4, true, 16, AUX>; break;
-      case 25: kernel = octree_render_kernel<0, 4, true, 25, AUX>; break;
-      default: kernel = octree_render_kernel<0, 4, true, -1, AUX>; break;
+// The forward launch of one argument block at `row` lanes per ray.  Rows of float or float16, 4 lanes: the channel-aligned
+// kernel with the tree's basis_dim as a compile-time constant (check_format has admitted these five values only, so there
+// is no run-time-K variant); 8 / 16 lanes: groups of four consecutive floats.  The palette form has one kernel per `row`.
+template <typename Block, bool AUX>
+static void launch_fwd(const MaybeAux<Block, AUX>& A, int row, unsigned grid, float* out_rgb, void* stream) {
+  if constexpr (std::is_same<Block, QuantRenderArgs>::value) {
+    const auto kernel = row == 4   ? octree_render_quant_kernel<4, AUX>
+                        : row == 8 ? octree_render_quant_kernel<8, AUX>
+                                   : octree_render_quant_kernel<16, AUX>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb);
+  } else {
+    using ST = std::conditional_t<std::is_same<Block, RenderArgs>::value, float, _Float16>;
+    auto kernel = row == 8 ? octree_render_kernel<0, 8, true, 0, AUX, ST> : octree_render_kernel<0, 16, true, 0, AUX, ST>;
+    if (row == 4) {
+      switch (A.tree.basis_dim) {
+        case 1: kernel = octree_render_kernel<0, 4, true, 1, AUX, ST>; break;
+        case 4: kernel = octree_render_kernel<0, 4, true, 4, AUX, ST>; break;
+        case 9: kernel = octree_render_kernel<0, 4, true, 9, AUX, ST>; break;
+        case 16: kernel = octree_render_kernel<0, 4, true, 16, AUX, ST>; break;
+        default: kernel = octree_render_kernel<0, 4, true, 25, AUX, ST>; break;
+      }
     }
+    const float* none = nullptr;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr);
   }
-  const float* none = nullptr;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr);
-}
-
-// Forward launch of a float16 tree: launch_render_fwd's choice of instantiation, with float16 rows.  The caller has checked
-// basis_dim (check_format), so there is no run-time-K variant.
-template <bool AUX>
-static void launch_half_fwd(const std::conditional_t<AUX, HalfRenderAuxArgs, HalfRenderArgs>& A, int row, unsigned grid,
-                            float* out_rgb, void* stream) {
-  auto kernel = row == 8 ? octree_render_kernel<0, 8, true, 0, AUX, _Float16> : octree_render_kernel<0, 16, true, 0, AUX, _Float16>;
-  if (row == 4) {
-    switch (A.tree.basis_dim) {
-      case 1: kernel = octree_render_kernel<0, 4, true, 1, AUX, _Float16>; break;
-      case 4: kernel = octree_render_kernel<0, 4, true, 4, AUX, _Float16>; break;
-      case 9: kernel = octree_render_kernel<0, 4, true, 9, AUX, _Float16>; break;
-      case 16: kernel = octree_render_kernel<0, 4, true, 16, AUX, _Float16>; break;
-      default: kernel = octree_render_kernel<0, 4, true, 25, AUX, _Float16>; break;
-    }
-  }
-  const float* none = nullptr;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb, none, none, (float*)nullptr);
-}
-
-template <bool AUX>
-static void launch_quant_fwd(const std::conditional_t<AUX, QuantRenderAuxArgs, QuantRenderArgs>& A, int row, unsigned grid,
-                             float* out_rgb, void* stream) {
-  const auto kernel = row == 4   ? octree_render_quant_kernel<4, AUX>
-                      : row == 8 ? octree_render_quant_kernel<8, AUX>
-                                 : octree_render_quant_kernel<16, AUX>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb);
 }
 
 // The 4-lane backward kernel for `wc_rows` rows of write-combining cache (0: direct scatter) and the cache's update form.
@@ -2364,20 +2334,101 @@ static int check_format(int K, int data_dim, const char* name, const char* who) 
   return PXO_OK;
 }
 
-static int render_args(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
-                       const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const char* who, bool backward,
-                       RenderArgs& A, unsigned& grid, int& row) {
-  if (int rc = check_opts(opts, who)) return rc;
+static int check_n_internal(int64_t n_internal, const char* who) {
+  PXO_REQUIRE(n_internal >= 1 && n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
+  return PXO_OK;
+}
+
+// the palette form (octree/compression.py:88-139) has no data_dim of its own
+static int quant_format_ok(int64_t n_internal, int basis_dim, int n_retained, int bits, const char* who) {
+  const int K = basis_dim;
+  if (int rc = check_format(K, 3 * K + 1, "SH", who)) return rc;
+  PXO_REQUIRE(n_retained >= 0 && n_retained < K, "%s: n_retained %d must be in [0, basis_dim %d)", who, n_retained, K);
+  PXO_REQUIRE(bits >= 1 && bits <= 16, "%s: bits %d must be in 1..16 (the map is uint16)", who, bits);
+  return check_n_internal(n_internal, who);
+}
+
+// stop_thresh < surface_thresh < 1: an early stop (light <= stop_thresh) then never comes before the crossing
+static int check_surface_thresh(const PxoRenderOpts* o, float surface_thresh, const char* who) {
+  PXO_REQUIRE(o->stop_thresh < surface_thresh && surface_thresh < 1.0f,
+              "%s: surface_thresh %g must lie in (stop_thresh %g, 1)", who, (double)surface_thresh, (double)o->stop_thresh);
+  return PXO_OK;
+}
+
+extern "C++" {   // overloads and templates
+
+// What a tree of each form must satisfy before a renderer reads it.  lobes: non-NULL names SG in the format's message.
+template <typename Tree>   // rows of float or float16
+static int check_row_tree(const Tree* tree, const float* lobes, const char* who) {
   PXO_REQUIRE(tree && tree->child && tree->data, "%s: null tree", who);
-  if (int rc = check_format(tree->basis_dim, tree->data_dim, "SH", who)) return rc;
-  PXO_REQUIRE(tree->n_internal >= 1 && tree->n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
-  row = render_row(backward);
+  if (int rc = check_format(tree->basis_dim, tree->data_dim, lobes ? "SG" : "SH", who)) return rc;
+  return check_n_internal(tree->n_internal, who);
+}
+static int check_tree(const PxoTree* tree, const float* lobes, const char* who) { return check_row_tree(tree, lobes, who); }
+static int check_tree(const PxoHalfTree* tree, const float* lobes, const char* who) {
+  if (int rc = check_row_tree(tree, lobes, who)) return rc;
+  PXO_REQUIRE(tree->row_stride == ((tree->data_dim + 3) & ~3), "%s: row_stride %d is not that of pxo_octree_half_pack_bytes (%d)",
+              who, tree->row_stride, (tree->data_dim + 3) & ~3);
+  PXO_REQUIRE(((uintptr_t)tree->data & 7) == 0, "%s: data must be 8-byte aligned", who);
+  return PXO_OK;
+}
+static int check_tree(const PxoQuantTree* tree, const float*, const char* who) {
+  PXO_REQUIRE(tree && tree->child && tree->idx && tree->palette && tree->sigma, "%s: null tree", who);
+  if (int rc = quant_format_ok(tree->n_internal, tree->basis_dim, tree->n_retained, tree->bits, who)) return rc;
+  const int Kq = tree->basis_dim - tree->n_retained;
+  PXO_REQUIRE(tree->idx_stride == ((Kq + 3) & ~3) && tree->ret_stride == 4 * tree->n_retained,
+              "%s: strides (%d, %d) are not those of pxo_octree_quant_pack_bytes", who, tree->idx_stride, tree->ret_stride);
+  PXO_REQUIRE(tree->n_retained == 0 || tree->retained, "%s: n_retained %d but retained is null", who, tree->n_retained);
+  PXO_REQUIRE((((uintptr_t)tree->idx | (uintptr_t)tree->palette | (uintptr_t)tree->retained) & 7) == 0,
+              "%s: idx, palette and retained must be 8-byte aligned", who);
+  return PXO_OK;
+}
+
+// how a tree shades its rays: an SG tree's lobes, an NDC scene's projection (the palette form has neither)
+template <typename Tree>
+static void set_shading(FwdBlock<Tree>& A, const float* lobes, const PxoNdc* ndc) {
+  A.lobes = lobes;
+  A.ndc = ndc ? *ndc : kNoNdc;
+}
+static void set_shading(QuantRenderArgs&, const float*, const PxoNdc*) {}
+
+// The argument block of every renderer launch, forward, backward and counting, of every form: the checks on the options, the
+// tree (check_tree) and the rays (launch_shape), lanes per ray and block count.  The entry points check lobes and ndc first.
+template <typename Block>
+static int render_args(const decltype(Block::tree)* tree, const float* lobes, const PxoNdc* ndc, const PxoCamera* cam,
+                       const float* origins, const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts,
+                       const char* who, bool backward, Block& A, unsigned& grid, int& row) {
+  if (int rc = check_opts(opts, who)) return rc;
+  if (int rc = check_tree(tree, lobes, who)) return rc;
+  row = render_row(backward);                    // the palette kernel is unmeasured against 8 / 16 (see DESIGN): the float default
   A.tree = *tree;
   A.opt = *opts;
-  A.lobes = nullptr;                            // the SG entry points set it after their own checks
-  A.ndc = kNoNdc;                               // the NDC entry points set it after their own checks
+  set_shading(A, lobes, ndc);
   return launch_shape(cam, origins, dirs, viewdirs, B, row, who, A, grid);
 }
+
+// Every forward entry point after its own checks of lobes and ndc.  AUX: with the alpha / depth / surface outputs.
+template <typename Block, bool AUX>
+static int render_forward(const decltype(Block::tree)* tree, const float* lobes, const PxoNdc* ndc, const PxoCamera* cam,
+                          const float* origins, const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts,
+                          float surface_thresh, float* out_rgb, float* out_aux, void* stream, const char* who) {
+  MaybeAux<Block, AUX> A;
+  unsigned grid;
+  int row;
+  if (int rc = render_args<Block>(tree, lobes, ndc, cam, origins, dirs, viewdirs, B, opts, who, false, A, grid, row)) return rc;
+  if constexpr (AUX)
+    if (int rc = check_surface_thresh(opts, surface_thresh, who)) return rc;
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(out_rgb && (!AUX || out_aux), "%s: null output", who);
+  if constexpr (AUX) {
+    A.out = out_aux;
+    A.surface_thresh = surface_thresh;
+  }
+  launch_fwd<Block, AUX>(A, row, grid, out_rgb, stream);
+  return check_launch(who);
+}
+
+}  // extern "C++"
 
 int pxo_octree_set_lanes_per_ray(int forward, int backward) {
   auto ok = [](int v) { return v == 0 || v == 4 || v == 8 || v == 16; };
@@ -2423,8 +2474,7 @@ int pxo_octree_get_tuning(int knob, int* value) {
   }
 }
 
-// SG trees: the same launches with RenderArgs::lobes set.  The format is checked before render_args so that the message
-// names SG, not SH.
+// SG trees: the same launches with RenderArgs::lobes set.  The format is checked before anything else, in SG's name.
 static int check_sg(const PxoTree* tree, const float* lobes, const char* who) {
   PXO_REQUIRE(tree, "%s: null tree", who);
   if (int rc = check_format(tree->basis_dim, tree->data_dim, "SG", who)) return rc;
@@ -2432,67 +2482,35 @@ static int check_sg(const PxoTree* tree, const float* lobes, const char* who) {
   return PXO_OK;
 }
 
-static int octree_render_fwd_impl(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
-                                  const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* lobes,
-                                  float* out_rgb, void* stream, const char* who, const PxoNdc& ndc = kNoNdc) {
-  RenderArgs A;
-  unsigned grid;
-  int row;
-  if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, false, A, grid, row)) return rc;
-  A.lobes = lobes;
-  A.ndc = ndc;
-  if (B == 0) return PXO_OK;
-  PXO_REQUIRE(out_rgb, "%s: null output", who);
-  launch_render_fwd<false>(A, row, grid, out_rgb, stream);
-  return check_launch(who);
-}
-
 int pxo_octree_render_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                           const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
-  return octree_render_fwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, nullptr, out_rgb, stream, "pxo_octree_render_fwd");
+  return render_forward<RenderArgs, false>(tree, nullptr, nullptr, cam, origins, dirs, viewdirs, B, opts, 0.0f, out_rgb, nullptr,
+                                           stream, "pxo_octree_render_fwd");
 }
 
 int pxo_octree_render_sg_fwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
                              const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb,
                              void* stream) {
   if (int rc = check_sg(tree, lobes, "pxo_octree_render_sg_fwd")) return rc;
-  return octree_render_fwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, lobes, out_rgb, stream, "pxo_octree_render_sg_fwd");
-}
-
-// stop_thresh < surface_thresh < 1: an early stop (light <= stop_thresh) then never comes before the crossing
-static int check_surface_thresh(const PxoRenderOpts* o, float surface_thresh, const char* who) {
-  PXO_REQUIRE(o->stop_thresh < surface_thresh && surface_thresh < 1.0f,
-              "%s: surface_thresh %g must lie in (stop_thresh %g, 1)", who, (double)surface_thresh, (double)o->stop_thresh);
-  return PXO_OK;
+  return render_forward<RenderArgs, false>(tree, lobes, nullptr, cam, origins, dirs, viewdirs, B, opts, 0.0f, out_rgb, nullptr,
+                                           stream, "pxo_octree_render_sg_fwd");
 }
 
 int pxo_octree_render_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                               const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
                               float* out_rgb, float* out_aux, void* stream) {
-  const char* who = "pxo_octree_render_aux_fwd";
-  RenderAuxArgs A;
-  unsigned grid;
-  int row;
-  if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, false, A, grid, row)) return rc;
-  if (int rc = check_surface_thresh(opts, surface_thresh, who)) return rc;
-  if (B == 0) return PXO_OK;
-  PXO_REQUIRE(out_rgb && out_aux, "%s: null output", who);
-  A.out = out_aux;
-  A.surface_thresh = surface_thresh;
-  launch_render_fwd<true>(A, row, grid, out_rgb, stream);
-  return check_launch("octree_render_aux_fwd");
+  return render_forward<RenderArgs, true>(tree, nullptr, nullptr, cam, origins, dirs, viewdirs, B, opts, surface_thresh, out_rgb,
+                                          out_aux, stream, "pxo_octree_render_aux_fwd");
 }
 
 static int octree_render_bwd_impl(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                                   const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const float* lobes,
                                   const float* out_rgb, const float* grad_out, float* grad_data, void* stream,
-                                  const char* who, const PxoNdc& ndc = kNoNdc) {
+                                  const char* who, const PxoNdc* ndc = nullptr) {
   RenderArgs A;
   unsigned grid;
   int row;
-  if (int rc = render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, true, A, grid, row)) return rc;
-  A.lobes = lobes;
-  A.ndc = ndc;
+  if (int rc = render_args(tree, lobes, ndc, cam, origins, dirs, viewdirs, B, opts, who, true, A, grid, row)) return rc;
   if (B == 0) return PXO_OK;
   PXO_REQUIRE(grad_out && grad_data, "%s: null pointer", who);
   // the gradient pass marches exactly (no early stop, no 1/(1-T) rescale): a forward image made with
@@ -2521,13 +2539,13 @@ int pxo_octree_render_bwd(const PxoTree* tree, const PxoCamera* cam, const float
 }
 
 // NDC twins: every launch render_row / the PXO_TUNE_* knobs can select carries RenderArgs::ndc, so each of them runs the
-// NDC set-up (none falls back to the world-space march).  render_args checks the SH format.
+// NDC set-up (none falls back to the world-space march).  check_tree checks the SH format.
 int pxo_octree_render_ndc_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                               const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream,
                               const PxoNdc* ndc) {
   if (int rc = check_ndc(ndc, "pxo_octree_render_ndc_fwd")) return rc;
-  return octree_render_fwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, nullptr, out_rgb, stream,
-                                "pxo_octree_render_ndc_fwd", *ndc);
+  return render_forward<RenderArgs, false>(tree, nullptr, ndc, cam, origins, dirs, viewdirs, B, opts, 0.0f, out_rgb, nullptr,
+                                           stream, "pxo_octree_render_ndc_fwd");
 }
 
 int pxo_octree_render_ndc_bwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
@@ -2535,7 +2553,7 @@ int pxo_octree_render_ndc_bwd(const PxoTree* tree, const PxoCamera* cam, const f
                               const float* grad_out, float* grad_data, void* stream, const PxoNdc* ndc) {
   if (int rc = check_ndc(ndc, "pxo_octree_render_ndc_bwd")) return rc;
   return octree_render_bwd_impl(tree, cam, origins, dirs, viewdirs, B, opts, nullptr, out_rgb, grad_out, grad_data, stream,
-                                "pxo_octree_render_ndc_bwd", *ndc);
+                                "pxo_octree_render_ndc_bwd", ndc);
 }
 
 int pxo_octree_render_sg_bwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
@@ -2547,15 +2565,6 @@ int pxo_octree_render_sg_bwd(const PxoTree* tree, const float* lobes, const PxoC
 }
 
 // ---- compressed trees (octree/compression.py:88-139) ----
-static int quant_format_ok(int64_t n_internal, int basis_dim, int n_retained, int bits, const char* who) {
-  const int K = basis_dim;
-  if (int rc = check_format(K, 3 * K + 1, "SH", who)) return rc;        // (the palette form has no data_dim of its own)
-  PXO_REQUIRE(n_retained >= 0 && n_retained < K, "%s: n_retained %d must be in [0, basis_dim %d)", who, n_retained, K);
-  PXO_REQUIRE(bits >= 1 && bits <= 16, "%s: bits %d must be in 1..16 (the map is uint16)", who, bits);
-  PXO_REQUIRE(n_internal >= 1 && n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
-  return PXO_OK;
-}
-
 int pxo_octree_quant_pack_bytes(int64_t n_internal, int basis_dim, int n_retained, int bits, PxoQuantLayout* layout) {
   if (int rc = quant_format_ok(n_internal, basis_dim, n_retained, bits, "pxo_octree_quant_pack_bytes")) return rc;
   PXO_REQUIRE(layout, "pxo_octree_quant_pack_bytes: null layout");
@@ -2609,61 +2618,24 @@ int pxo_octree_quant_pack(const uint16_t* quant_map, const void* quant_colors, c
   return check_launch("octree_quant_pack");
 }
 
-// the argument checks and the launch shape of the palette renderers (with and without the extra outputs)
-static int quant_render_args(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
-                             const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const char* who, QuantRenderArgs& A,
-                             unsigned& grid, int& row) {
-  if (int rc = check_opts(opts, who)) return rc;
-  PXO_REQUIRE(tree && tree->child && tree->idx && tree->palette && tree->sigma, "%s: null tree", who);
-  if (int rc = quant_format_ok(tree->n_internal, tree->basis_dim, tree->n_retained, tree->bits, who)) return rc;
-  const int Kq = tree->basis_dim - tree->n_retained;
-  PXO_REQUIRE(tree->idx_stride == ((Kq + 3) & ~3) && tree->ret_stride == 4 * tree->n_retained,
-              "%s: strides (%d, %d) are not those of pxo_octree_quant_pack_bytes", who, tree->idx_stride, tree->ret_stride);
-  PXO_REQUIRE(tree->n_retained == 0 || tree->retained, "%s: n_retained %d but retained is null", who, tree->n_retained);
-  PXO_REQUIRE((((uintptr_t)tree->idx | (uintptr_t)tree->palette | (uintptr_t)tree->retained) & 7) == 0,
-              "%s: idx, palette and retained must be 8-byte aligned", who);
-  A.tree = *tree;
-  A.opt = *opts;
-  row = render_row(false);                             // unmeasured against 8 / 16 (see DESIGN): the float kernel's default
-  return launch_shape(cam, origins, dirs, viewdirs, B, row, who, A, grid);
-}
-
 int pxo_octree_render_quant_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                                 const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
-  const char* who = "pxo_octree_render_quant_fwd";
-  QuantRenderArgs A;
-  unsigned grid;
-  int row;
-  if (int rc = quant_render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, A, grid, row)) return rc;
-  if (B == 0) return PXO_OK;
-  PXO_REQUIRE(out_rgb, "%s: null output", who);
-  launch_quant_fwd<false>(A, row, grid, out_rgb, stream);
-  return check_launch("octree_render_quant_fwd");
+  return render_forward<QuantRenderArgs, false>(tree, nullptr, nullptr, cam, origins, dirs, viewdirs, B, opts, 0.0f, out_rgb,
+                                                nullptr, stream, "pxo_octree_render_quant_fwd");
 }
 
 int pxo_octree_render_quant_aux_fwd(const PxoQuantTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                                     const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
                                     float* out_rgb, float* out_aux, void* stream) {
-  const char* who = "pxo_octree_render_quant_aux_fwd";
-  QuantRenderAuxArgs A;
-  unsigned grid;
-  int row;
-  if (int rc = quant_render_args(tree, cam, origins, dirs, viewdirs, B, opts, who, A, grid, row)) return rc;
-  if (int rc = check_surface_thresh(opts, surface_thresh, who)) return rc;
-  if (B == 0) return PXO_OK;
-  PXO_REQUIRE(out_rgb && out_aux, "%s: null output", who);
-  A.out = out_aux;
-  A.surface_thresh = surface_thresh;
-  launch_quant_fwd<true>(A, row, grid, out_rgb, stream);
-  return check_launch("octree_render_quant_aux_fwd");
+  return render_forward<QuantRenderArgs, true>(tree, nullptr, nullptr, cam, origins, dirs, viewdirs, B, opts, surface_thresh,
+                                               out_rgb, out_aux, stream, "pxo_octree_render_quant_aux_fwd");
 }
 
 // ---- float16 trees rendered in place (the data array of the files N3Tree.save writes) ----
 static int half_format_ok(int64_t n_internal, int data_dim, const char* who) {
   PXO_REQUIRE(data_dim >= 4 && (data_dim - 1) % 3 == 0, "%s: data_dim %d is not 3*basis_dim+1", who, data_dim);
   if (int rc = check_format((data_dim - 1) / 3, data_dim, "SH", who)) return rc;
-  PXO_REQUIRE(n_internal >= 1 && n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
-  return PXO_OK;
+  return check_n_internal(n_internal, who);
 }
 
 int pxo_octree_half_pack_bytes(int64_t n_internal, int data_dim, int32_t* row_stride, int64_t* bytes) {
@@ -2690,25 +2662,6 @@ int pxo_octree_half_pack(const void* src, int64_t n_internal, int data_dim, void
   return check_launch("octree_half_pack");
 }
 
-// the argument checks and the launch shape of the float16 renderers: those of render_args, plus row_stride and alignment
-static int half_render_args(const PxoHalfTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
-                            const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, const char* who,
-                            HalfRenderArgs& A, unsigned& grid, int& row) {
-  if (int rc = check_opts(opts, who)) return rc;
-  PXO_REQUIRE(tree && tree->child && tree->data, "%s: null tree", who);
-  if (int rc = check_format(tree->basis_dim, tree->data_dim, lobes ? "SG" : "SH", who)) return rc;
-  PXO_REQUIRE(tree->n_internal >= 1 && tree->n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
-  PXO_REQUIRE(tree->row_stride == ((tree->data_dim + 3) & ~3), "%s: row_stride %d is not that of pxo_octree_half_pack_bytes (%d)",
-              who, tree->row_stride, (tree->data_dim + 3) & ~3);
-  PXO_REQUIRE(((uintptr_t)tree->data & 7) == 0, "%s: data must be 8-byte aligned", who);
-  row = render_row(false);
-  A.tree = *tree;
-  A.opt = *opts;
-  A.lobes = lobes;
-  A.ndc = kNoNdc;
-  return launch_shape(cam, origins, dirs, viewdirs, B, row, who, A, grid);
-}
-
 int pxo_octree_render_half_fwd(const PxoHalfTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
                                const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb,
                                void* stream, const PxoNdc* ndc) {
@@ -2716,46 +2669,29 @@ int pxo_octree_render_half_fwd(const PxoHalfTree* tree, const float* lobes, cons
   PXO_REQUIRE(!(lobes && ndc), "%s: SG trees have no NDC form (lobes and ndc are both set)", who);
   if (ndc)
     if (int rc = check_ndc(ndc, who)) return rc;
-  HalfRenderArgs A;
-  unsigned grid;
-  int row;
-  if (int rc = half_render_args(tree, lobes, cam, origins, dirs, viewdirs, B, opts, who, A, grid, row)) return rc;
-  if (ndc) A.ndc = *ndc;
-  if (B == 0) return PXO_OK;
-  PXO_REQUIRE(out_rgb, "%s: null output", who);
-  launch_half_fwd<false>(A, row, grid, out_rgb, stream);
-  return check_launch("octree_render_half_fwd");
+  return render_forward<FwdBlock<PxoHalfTree>, false>(tree, lobes, ndc, cam, origins, dirs, viewdirs, B, opts, 0.0f, out_rgb,
+                                                      nullptr, stream, who);
 }
 
 int pxo_octree_render_half_aux_fwd(const PxoHalfTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
                                    const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float surface_thresh,
                                    float* out_rgb, float* out_aux, void* stream) {
-  const char* who = "pxo_octree_render_half_aux_fwd";
-  HalfRenderAuxArgs A;
-  unsigned grid;
-  int row;
-  if (int rc = half_render_args(tree, nullptr, cam, origins, dirs, viewdirs, B, opts, who, A, grid, row)) return rc;
-  if (int rc = check_surface_thresh(opts, surface_thresh, who)) return rc;
-  if (B == 0) return PXO_OK;
-  PXO_REQUIRE(out_rgb && out_aux, "%s: null output", who);
-  A.out = out_aux;
-  A.surface_thresh = surface_thresh;
-  launch_half_fwd<true>(A, row, grid, out_rgb, stream);
-  return check_launch("octree_render_half_aux_fwd");
+  return render_forward<FwdBlock<PxoHalfTree>, true>(tree, nullptr, nullptr, cam, origins, dirs, viewdirs, B, opts, surface_thresh,
+                                                     out_rgb, out_aux, stream, "pxo_octree_render_half_aux_fwd");
 }
 
 int pxo_octree_count_work(const PxoTree* tree, const PxoCamera* cam, const PxoRenderOpts* opts, unsigned long long* counts,
                           uint8_t* leaf_seen, void* stream) {
-  PXO_REQUIRE(cam != nullptr && counts != nullptr, "pxo_octree_count_work: needs a camera and a counts[4] buffer");
+  const char* who = "pxo_octree_count_work";
+  PXO_REQUIRE(cam != nullptr && counts != nullptr, "%s: needs a camera and a counts[4] buffer", who);
   RenderArgs A;
   unsigned grid;
   int row;
-  if (int rc = render_args(tree, cam, nullptr, nullptr, nullptr, (int64_t)cam->width * cam->height, opts,
-                           "pxo_octree_count_work", false, A, grid, row)) return rc;
   const int64_t rays = (int64_t)cam->width * cam->height;
+  if (int rc = render_args(tree, nullptr, nullptr, cam, nullptr, nullptr, nullptr, rays, opts, who, false, A, grid, row)) return rc;
   hipLaunchKernelGGL(octree_count_kernel, dim3((unsigned)blocks_for(rays, 256)), dim3(256), 0, (hipStream_t)stream, A, counts,
                      leaf_seen);
-  return check_launch("octree_count_work");
+  return check_launch(who);
 }
 
 // what the two weight entry points share: the checks on tree / options / ndc / weights and the launch (op: checked by the
@@ -2765,7 +2701,7 @@ static int weight_accum_launch(const PxoTree* tree, WeightArgs& A, const PxoRend
   if (int rc = check_opts(opts, who)) return rc;
   PXO_REQUIRE(tree && tree->child && tree->data, "%s: null tree", who);
   PXO_REQUIRE(tree->data_dim >= 1, "%s: data_dim %d < 1", who, tree->data_dim);
-  PXO_REQUIRE(tree->n_internal >= 1 && tree->n_internal < ((int64_t)1 << 28), "%s: n_internal out of range", who);
+  if (int rc = check_n_internal(tree->n_internal, who)) return rc;
   PXO_REQUIRE(weights, "%s: null weights", who);
   if (ndc)
     if (int rc = check_ndc(ndc, who)) return rc;

@@ -370,6 +370,11 @@ class N3Tree:
     def view(self):
         return oops.tree_view(self.child, self.data.data, self.offset, self.invradius)
 
+    # what VolumeRenderer asks of a tree of any storage form (the read-only forms: _ReadOnlyTree)
+    render_view = view
+    ndc_refusal = None
+    requires_grad = property(lambda self: self.data.requires_grad)
+
     def basis_kwargs(self):
         """What selects the renderer of this tree's basis in octree_ops: the lobes of an SG tree, nothing for an SH tree."""
         return {} if self.extra_data is None else {"lobes": self.extra_data}
@@ -645,7 +650,56 @@ def _validated_quant(z, n):
             None if retained is None else np.ascontiguousarray(retained[:, :n].reshape(r, n * 8, 3)), bits)
 
 
-class QuantizedN3Tree:
+class _ReadOnlyTree:
+    """What QuantizedN3Tree and HalfN3Tree share: the geometry of an N3Tree, no float leaf data, and a refusal by name of
+    everything that reads or edits it.  A subclass gives its NOUN, the name of its WAY_OUT to a float N3Tree, and
+    render_view()."""
+
+    basis_dim = N3Tree.basis_dim
+    data_dim = N3Tree.data_dim
+    n_internal = N3Tree.n_internal
+    n_leaves = N3Tree.n_leaves
+    max_depth = N3Tree.max_depth
+    basis_kwargs = N3Tree.basis_kwargs
+    # what VolumeRenderer asks of a tree before it renders it
+    requires_grad = False                        # never differentiable
+    _weight_accum = None                         # no weight accumulation
+    ndc_refusal = None                           # why VolumeRenderer(ndc=...) refuses this form, if it does
+
+    @property
+    def device(self):
+        return self.child.device
+
+    @property
+    def float_nbytes(self):
+        """Device bytes the float form (what N3Tree.load makes of the same file) takes."""
+        return 4 * self.n_internal * 8 * self.data_dim + 4 * (self.child.numel() + self.parent_depth.numel())
+
+    def _device_form(self):
+        if self._packed is None:
+            raise PxoError(f"a {self.NOUN} renders on a ROCm device only (there is no CPU fallback): load it with map_location='cuda'")
+        return self._packed
+
+    def _read_only(self, what):
+        raise PxoError(f"{what}: a {self.NOUN} is read-only and has no float leaf data; call {self.WAY_OUT}() for an N3Tree")
+
+
+def _refused(what):
+    def stub(self, *args, **kwargs):
+        self._read_only(what)
+    return stub
+
+
+for _name, _what in (("parameters", "tree.parameters()"), ("__getitem__", "tree[...]"), ("__setitem__", "tree[...] = value"),
+                     ("refine", "refine"), ("refine_from_mask", "refine_from_mask"), ("relu_sigma_", "relu_sigma_"),
+                     ("accumulate_weights", "accumulate_weights"), ("prune_", "prune_"), ("refine_leaves", "refine_leaves"),
+                     ("view", "view()"), ("save", "save")):
+    setattr(_ReadOnlyTree, _name, _refused(_what))
+_ReadOnlyTree.data = property(_refused("tree.data"))
+del _name, _what
+
+
+class QuantizedN3Tree(_ReadOnlyTree):
     """A compressed tree (octree/compression.py) kept in its palette form: `N3Tree.load(path, keep_quantized=True)`.
 
     Read-only.  It has the geometry of an N3Tree (child, parent_depth, offset, invradius, depth_limit, data_format,
@@ -665,31 +719,20 @@ class QuantizedN3Tree:
             self._packed, _ = oops.quant_pack(up(qmap.view(np.int16)), up(colors), up(sigma), up(retained), n, self.basis_dim,
                                               self.n_retained, self.bits)
 
-    basis_dim = N3Tree.basis_dim
-    data_dim = N3Tree.data_dim
-    n_internal = N3Tree.n_internal
-    n_leaves = N3Tree.n_leaves
-    max_depth = N3Tree.max_depth
-
-    @property
-    def device(self):
-        return self.child.device
+    NOUN, WAY_OUT = "QuantizedN3Tree", "dequantize"
+    ndc_refusal = ("VolumeRenderer(ndc=...) on a QuantizedN3Tree: NDC rendering of the palette form is not built; load the tree "
+                   "without keep_quantized")
 
     @property
     def nbytes(self):
         """Device bytes of this form: the packed buffer (indices, palettes, sigma, retained planes) + child + parent_depth."""
         return int(self._layout.total_bytes) + 4 * (self.child.numel() + self.parent_depth.numel())
 
-    @property
-    def float_nbytes(self):
-        """Device bytes the float form (`dequantize()`, what N3Tree.load makes of the same file) takes."""
-        return 4 * self.n_internal * 8 * self.data_dim + 4 * (self.child.numel() + self.parent_depth.numel())
-
     def quant_view(self):
-        if self._packed is None:
-            raise PxoError("a QuantizedN3Tree renders on a ROCm device only (there is no CPU fallback): load it with map_location='cuda'")
-        return oops.quant_tree_view(self.child, self._packed, self._layout, self.basis_dim, self.n_retained, self.bits,
+        return oops.quant_tree_view(self.child, self._device_form(), self._layout, self.basis_dim, self.n_retained, self.bits,
                                     self.offset, self.invradius)
+
+    render_view = quant_view
 
     def dequantize(self):
         """The float N3Tree that `N3Tree.load(path)` makes of the same file, on this tree's device."""
@@ -699,48 +742,8 @@ class QuantizedN3Tree:
         return (f"svox.QuantizedN3Tree(N=2, data_format:{self.data_format}, n_internal:{self.n_internal}, bits:{self.bits}, "
                 f"retained:{self.n_retained}, {self.nbytes / 2 ** 20:.1f} MB on the device, float form {self.float_nbytes / 2 ** 20:.1f} MB)")
 
-    def _read_only(self, what):
-        raise PxoError(f"{what}: a QuantizedN3Tree is read-only and has no float leaf data; call dequantize() for an N3Tree")
 
-    @property
-    def data(self):
-        self._read_only("tree.data")
-
-    def parameters(self):
-        self._read_only("tree.parameters()")
-
-    def __getitem__(self, key):
-        self._read_only("tree[...]")
-
-    def __setitem__(self, key, value):
-        self._read_only("tree[...] = value")
-
-    def refine(self, *args, **kwargs):
-        self._read_only("refine")
-
-    def refine_from_mask(self, mask):
-        self._read_only("refine_from_mask")
-
-    def relu_sigma_(self):
-        self._read_only("relu_sigma_")
-
-    def accumulate_weights(self, op="sum"):
-        self._read_only("accumulate_weights")
-
-    def prune_(self, keep, collapse=True):
-        self._read_only("prune_")
-
-    def refine_leaves(self, mask):
-        self._read_only("refine_leaves")
-
-    def view(self):
-        self._read_only("view()")
-
-    def save(self, path, shrink=True, compress=True):
-        self._read_only("save")
-
-
-class HalfN3Tree:
+class HalfN3Tree(_ReadOnlyTree):
     """An uncompressed tree kept in the float16 of its file: `N3Tree.load(path, keep_half=True)`.
 
     Read-only.  It has the geometry of an N3Tree (child, parent_depth, offset, invradius, depth_limit, data_format,
@@ -761,31 +764,17 @@ class HalfN3Tree:
         else:
             self._half = half
 
-    basis_dim = N3Tree.basis_dim
-    data_dim = N3Tree.data_dim
-    n_internal = N3Tree.n_internal
-    n_leaves = N3Tree.n_leaves
-    max_depth = N3Tree.max_depth
-    basis_kwargs = N3Tree.basis_kwargs
-
-    @property
-    def device(self):
-        return self.child.device
+    NOUN, WAY_OUT = "HalfN3Tree", "to_float"
 
     @property
     def nbytes(self):
         """Device bytes of this form: the float16 rows at their stride + child + parent_depth."""
         return int(self._packed_bytes) + 4 * (self.child.numel() + self.parent_depth.numel())
 
-    @property
-    def float_nbytes(self):
-        """Device bytes the float form (`to_float()`, what N3Tree.load makes of the same file) takes."""
-        return 4 * self.n_internal * 8 * self.data_dim + 4 * (self.child.numel() + self.parent_depth.numel())
-
     def half_view(self):
-        if self._packed is None:
-            raise PxoError("a HalfN3Tree renders on a ROCm device only (there is no CPU fallback): load it with map_location='cuda'")
-        return oops.half_tree_view(self.child, self._packed, self.data_dim, self.offset, self.invradius)
+        return oops.half_tree_view(self.child, self._device_form(), self.data_dim, self.offset, self.invradius)
+
+    render_view = half_view
 
     def to_float(self):
         """The float N3Tree that `N3Tree.load(path)` makes of the same file, on this tree's device."""
@@ -803,46 +792,6 @@ class HalfN3Tree:
     def __repr__(self):
         return (f"svox.HalfN3Tree(N=2, data_format:{self.data_format}, n_internal:{self.n_internal}, row_stride:{self.row_stride}, "
                 f"{self.nbytes / 2 ** 20:.1f} MB on the device, float form {self.float_nbytes / 2 ** 20:.1f} MB)")
-
-    def _read_only(self, what):
-        raise PxoError(f"{what}: a HalfN3Tree is read-only and has no float leaf data; call to_float() for an N3Tree")
-
-    @property
-    def data(self):
-        self._read_only("tree.data")
-
-    def parameters(self):
-        self._read_only("tree.parameters()")
-
-    def __getitem__(self, key):
-        self._read_only("tree[...]")
-
-    def __setitem__(self, key, value):
-        self._read_only("tree[...] = value")
-
-    def refine(self, *args, **kwargs):
-        self._read_only("refine")
-
-    def refine_from_mask(self, mask):
-        self._read_only("refine_from_mask")
-
-    def relu_sigma_(self):
-        self._read_only("relu_sigma_")
-
-    def accumulate_weights(self, op="sum"):
-        self._read_only("accumulate_weights")
-
-    def prune_(self, keep, collapse=True):
-        self._read_only("prune_")
-
-    def refine_leaves(self, mask):
-        self._read_only("refine_leaves")
-
-    def view(self):
-        self._read_only("view()")
-
-    def save(self, path, shrink=True, compress=True):
-        self._read_only("save")
 
 
 def parent_depth_from_child(child):
@@ -900,9 +849,8 @@ class VolumeRenderer:
         if ndc is not None:
             if not isinstance(ndc, NDCConfig):
                 raise NotImplementedError(f"VolumeRenderer(ndc=...): NDC rendering takes an svox.NDCConfig, got {type(ndc).__name__}")
-            if isinstance(tree, QuantizedN3Tree):
-                raise NotImplementedError("VolumeRenderer(ndc=...) on a QuantizedN3Tree: NDC rendering of the palette form is not "
-                                          "built; load the tree without keep_quantized")
+            if tree.ndc_refusal:
+                raise NotImplementedError(tree.ndc_refusal)
             if getattr(tree, "extra_data", None) is not None:
                 raise NotImplementedError(f"VolumeRenderer(ndc=...) on an SG tree ({tree.data_format}): NDC rendering is built for "
                                           "SH trees only")
@@ -936,15 +884,9 @@ class VolumeRenderer:
         octree/optimization.py:216) is differentiable; the early-stopping preset (fast=True, evaluation) never is."""
         self._check_ndc_camera(width, height, fx, fy)
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.tree.device)
-        if isinstance(self.tree, QuantizedN3Tree):
-            # nothing in a compressed tree requires grad: rendered directly, with grad mode on as well, `fast` both ways
-            return oops.octree_render_quant_persp(self.tree.quant_view(), c2w, width, height, fx, self._opts(fast), fy)
-        if isinstance(self.tree, HalfN3Tree):
-            # read-only as well: the float tree's launch on the file's float16 rows, the same image bit for bit
-            return oops.octree_render_half_persp(self.tree.half_view(), c2w, width, height, fx, self._opts(fast), fy,
-                                                 **self._basis_kwargs())
-        data = self.tree.data
-        differentiable = torch.is_grad_enabled() and data.requires_grad
+        # nothing in a read-only tree (the palette form, the file's float16 rows) requires grad or accumulates weights: it is
+        # rendered directly, with grad mode on as well, `fast` both ways
+        differentiable = torch.is_grad_enabled() and self.tree.requires_grad
         accum = self.tree._weight_accum
         if accum is not None and not (differentiable and fast):
             # one more launch on the same camera and options; the rgb launches and their results are untouched
@@ -957,22 +899,18 @@ class VolumeRenderer:
                 # "does not require grad" error in the caller's backward
                 raise oops.PxoError("render_persp(fast=True) is not differentiable: call it under torch.no_grad(), "
                                     "or use fast=False to optimise the tree")
-            return _RenderPersp.apply(data, self, c2w, width, height, fx, fy, self._opts(False))
-        return oops.octree_render_persp(self.tree.view(), c2w, width, height, fx, self._opts(fast), fy, **self._basis_kwargs())
+            return _RenderPersp.apply(self.tree.data, self, c2w, width, height, fx, fy, self._opts(False))
+        return oops.octree_render_persp(self.tree.render_view(), c2w, width, height, fx, self._opts(fast), fy,
+                                        **self._basis_kwargs())
 
     def forward(self, origins, dirs, viewdirs, fast=False):
         """Colours [B,3] of explicit world-space rays (unit `dirs`); with `ndc` the rays are converted per ray and `viewdirs`
         (world space) shade them."""
-        if isinstance(self.tree, QuantizedN3Tree):
-            return oops.octree_render_quant_rays(self.tree.quant_view(), origins, dirs, viewdirs, self._opts(fast))
-        if isinstance(self.tree, HalfN3Tree):
-            return oops.octree_render_half_rays(self.tree.half_view(), origins, dirs, viewdirs, self._opts(fast),
-                                                **self._basis_kwargs())
         accum = self.tree._weight_accum
         if accum is not None:
             oops.octree_weight_accum_rays(self.tree.view(), origins, dirs, self._opts(fast), accum.op, accum._buffer(),
                                           ndc=self.ndc)
-        return oops.octree_render_rays(self.tree.view(), origins, dirs, viewdirs, self._opts(fast), **self._basis_kwargs())
+        return oops.octree_render_rays(self.tree.render_view(), origins, dirs, viewdirs, self._opts(fast), **self._basis_kwargs())
 
     __call__ = forward
 
@@ -984,14 +922,10 @@ class VolumeRenderer:
         if getattr(self.tree, "extra_data", None) is not None:
             raise NotImplementedError(f"{what} on an SG tree ({self.tree.data_format}): alpha / depth / surface are built for SH "
                                       "trees only")
-        if isinstance(self.tree, QuantizedN3Tree):
-            return self.tree.quant_view()
-        if isinstance(self.tree, HalfN3Tree):
-            return self.tree.half_view()
-        if torch.is_grad_enabled() and self.tree.data.requires_grad:
+        if torch.is_grad_enabled() and self.tree.requires_grad:
             raise oops.PxoError(f"{what} is not differentiable (alpha, depth and surface have no gradient kernel): call it "
                                 "under torch.no_grad()")
-        return self.tree.view()
+        return self.tree.render_view()
 
     @staticmethod
     def _aux_dict(rgb, aux):

@@ -140,21 +140,26 @@ def grid_weight_render(sigma_grid, reso, c2w_all, fx, fy, width, height, opts, o
     return grid_weight
 
 
+def _tree_fields(t, child, offset, invradius):
+    """What the three tree structs share: the child array, n_internal and the transform."""
+    if child.dtype != torch.int32:
+        raise PxoError("child must be int32")
+    t.child = _p(child).value
+    t.n_internal = child.shape[0]
+    t.offset = _vec3(offset)
+    t.invradius = _vec3(invradius)
+    return t
+
+
 def tree_view(child, data, offset, invradius):
     """PxoTree struct over torch storage (keeps no reference: the caller owns the tensors)."""
     data_dim = data.shape[-1]
     if (data_dim - 1) % 3:
         raise PxoError(f"data_dim {data_dim} is not 3*basis_dim+1")
-    if child.dtype != torch.int32:
-        raise PxoError("child must be int32")
-    t = _lib.PxoTree()
-    t.child = _p(child).value
+    t = _tree_fields(_lib.PxoTree(), child, offset, invradius)
     t.data = _f(data).value
-    t.n_internal = child.shape[0]
     t.data_dim = data_dim
     t.basis_dim = (data_dim - 1) // 3
-    t.offset = _vec3(offset)
-    t.invradius = _vec3(invradius)
     return t
 
 
@@ -172,26 +177,58 @@ def _no_sg_ndc(lobes, ndc):
                                   "trees only")
 
 
-def _render_entry(direction, tree, lobes, ndc):
-    """(entry point, its name, leading args, trailing args) of the float-tree renderer, direction "fwd" or "bwd":
-    pxo_octree_render_*; pxo_octree_render_sg_* when the tree's SG lobes are given (they follow the tree);
-    pxo_octree_render_ndc_* when the scene's NDC projection is (it ends the list)."""
+# The renderer entry points: (struct type, what) -> {shading: (name, takes lobes, takes ndc)}; what: "fwd", "aux" (forward with
+# the extra outputs) or "bwd"; shading: "" for SH in world space, "sg" with an SG tree's lobes, "ndc" with a scene's projection.
+# Every one takes, in this order: the tree[, lobes], the camera and rays of _rays, the options[, surface_thresh], out_rgb[,
+# out_aux] (backward: out_rgb, grad_out, grad_data), the stream[, ndc].  What a form has no row or shading for is not built.
+_ENTRIES = {
+    (_lib.PxoTree, "fwd"): {"": ("pxo_octree_render_fwd", False, False), "sg": ("pxo_octree_render_sg_fwd", True, False),
+                            "ndc": ("pxo_octree_render_ndc_fwd", False, True)},
+    (_lib.PxoTree, "bwd"): {"": ("pxo_octree_render_bwd", False, False), "sg": ("pxo_octree_render_sg_bwd", True, False),
+                            "ndc": ("pxo_octree_render_ndc_bwd", False, True)},
+    (_lib.PxoTree, "aux"): {"": ("pxo_octree_render_aux_fwd", False, False)},
+    (_lib.PxoQuantTree, "fwd"): {"": ("pxo_octree_render_quant_fwd", False, False)},
+    (_lib.PxoQuantTree, "aux"): {"": ("pxo_octree_render_quant_aux_fwd", False, False)},
+    (_lib.PxoHalfTree, "fwd"): dict.fromkeys(("", "sg", "ndc"), ("pxo_octree_render_half_fwd", True, True)),
+    (_lib.PxoHalfTree, "aux"): {"": ("pxo_octree_render_half_aux_fwd", False, False)},
+}
+_WHAT = {"fwd": "rendering", "aux": "rendering alpha / depth / surface", "bwd": "the gradient"}
+_SHADING = {"": "an SH tree in world space", "sg": "an SG tree (lobes)", "ndc": "an NDC scene (ndc)"}
+
+
+def _call(tree, what, lobes, ndc, rays, opts, outputs):
+    """Calls the renderer entry point of `tree`'s form; outputs: the arguments between the options and the stream."""
     _no_sg_ndc(lobes, ndc)
-    kind = "ndc_" if ndc is not None else ("" if lobes is None else "sg_")
-    name = f"pxo_octree_render_{kind}{direction}"
-    lead = (ctypes.byref(tree),) if lobes is None else (ctypes.byref(tree), _lobes(lobes, tree))
-    return getattr(_lib.load(), name), name, lead, () if ndc is None else (ctypes.byref(_ndc(ndc)),)
+    if not isinstance(tree, (_lib.PxoTree, _lib.PxoQuantTree, _lib.PxoHalfTree)):
+        raise PxoError(f"expected a PxoTree, a PxoQuantTree or a PxoHalfTree, got {type(tree).__name__}")
+    shading = "ndc" if ndc is not None else ("" if lobes is None else "sg")
+    row = _ENTRIES.get((type(tree), what), {})
+    if shading not in row:
+        raise NotImplementedError(f"{_WHAT[what]} of {_SHADING[shading]} is not built for a {type(tree).__name__}")
+    name, takes_lobes, takes_ndc = row[shading]
+    lead = (None if lobes is None else _lobes(lobes, tree),) if takes_lobes else ()
+    trail = (None if ndc is None else ctypes.byref(_ndc(ndc)),) if takes_ndc else ()
+    check(getattr(_lib.load(), name)(ctypes.byref(tree), *lead, *rays, ctypes.byref(opts), *outputs, _stream(), *trail), name)
 
 
-def _render_fwd(tree, lobes, rays, opts, out, ndc=None):
-    fn, name, lead, trail = _render_entry("fwd", tree, lobes, ndc)
-    check(fn(*lead, *rays, ctypes.byref(opts), _f(out), _stream(), *trail), name)
-    return out
+def _forward(tree, opts, camera=None, rays=None, lobes=None, ndc=None, surface_thresh=None):
+    """The forward render of a PxoTree, a PxoQuantTree or a PxoHalfTree from camera = (c2w, width, height, fx, fy) or rays =
+    (origins, dirs, viewdirs): rgb [H,W,3] or [B,3], and with surface_thresh (rgb, aux), aux of rgb's shape."""
+    _require_gpu()
+    if camera is not None:
+        cam, keep = _camera(*camera)
+        shape, device, rays = (cam.height, cam.width, 3), keep.device, _rays(cam)
+    else:
+        shape, device, rays = (rays[0].shape[0], 3), rays[0].device, _rays(None, *rays)
+    aux = surface_thresh is not None
+    outs = [_new(*shape, device=device) for _ in range(2 if aux else 1)]
+    _call(tree, "aux" if aux else "fwd", lobes, ndc, rays, opts,
+          ((float(surface_thresh),) if aux else ()) + tuple(_f(o) for o in outs))
+    return tuple(outs) if aux else outs[0]
 
 
 def _render_bwd(tree, lobes, rays, opts, out_rgb, grad_out, grad_data, ndc=None):
-    fn, name, lead, trail = _render_entry("bwd", tree, lobes, ndc)
-    check(fn(*lead, *rays, ctypes.byref(opts), _f(out_rgb), _f(grad_out), _f(grad_data), _stream(), *trail), name)
+    _call(tree, "bwd", lobes, ndc, rays, opts, (_f(out_rgb), _f(grad_out), _f(grad_data)))
     return grad_data
 
 
@@ -231,11 +268,9 @@ def set_tuning(knob, value):
 def octree_render_persp(tree, c2w, width, height, fx, opts, fy=None, lobes=None, ndc=None):
     """[H,W,3] image of a pinhole camera (VolumeRenderer.render_persp).  lobes: the [K,4] extra_data of an SG tree (the
     spherical-Gaussian basis instead of SH), None for an SH tree.  ndc: the projection (ndc_spec / NDCConfig) of a
-    forward-facing scene whose tree lives in the NDC cube, None for a world-space tree."""
-    _require_gpu()
-    cam, keep = _camera(c2w, width, height, fx, fy)
-    out = _new(height, width, 3, device=keep.device)
-    return _render_fwd(tree, lobes, _rays(cam), opts, out, ndc=ndc)
+    forward-facing scene whose tree lives in the NDC cube, None for a world-space tree.  tree: a PxoTree, or the struct of
+    another storage form (PxoQuantTree: SH in world space only; PxoHalfTree), rendered in place."""
+    return _forward(tree, opts, camera=(c2w, width, height, fx, fy), lobes=lobes, ndc=ndc)
 
 
 def octree_render_persp_bwd(tree, c2w, width, height, fx, opts, grad_out, grad_data, fy=None, out_rgb=None, lobes=None,
@@ -352,9 +387,7 @@ def tree_collapse(child, parent_depth, data, keep):
 def octree_render_rays(tree, origins, dirs, viewdirs, opts, lobes=None, ndc=None):
     """[B,3] colours of explicit world-space rays with unit dirs (VolumeRenderer.forward).  lobes, ndc: as in
     octree_render_persp (with ndc the rays are still given in world space; they are converted per ray)."""
-    _require_gpu()
-    out = _new(origins.shape[0], 3, device=origins.device)
-    return _render_fwd(tree, lobes, _rays(None, origins, dirs, viewdirs), opts, out, ndc=ndc)
+    return _forward(tree, opts, rays=(origins, dirs, viewdirs), lobes=lobes, ndc=ndc)
 
 
 # ---- compressed trees rendered in place (the palette form of octree/compression.py:88-139) ----
@@ -388,42 +421,27 @@ def quant_pack(quant_map, quant_colors, sigma, data_retained, n_internal, basis_
 
 def quant_tree_view(child, packed, lay, basis_dim, n_retained, bits, offset, invradius):
     """PxoQuantTree struct over torch storage (keeps no reference: the caller owns the tensors)."""
-    if child.dtype != torch.int32:
-        raise PxoError("child must be int32")
+    t = _tree_fields(_lib.PxoQuantTree(), child, offset, invradius)
     if packed.dtype != torch.uint8 or packed.numel() < lay.total_bytes:
         raise PxoError("packed buffer is smaller than its layout")
     base = _p(packed).value
-    t = _lib.PxoQuantTree()
-    t.child = _p(child).value
     t.idx = base + lay.idx_offset
     t.palette = base + lay.palette_offset
     t.sigma = base + lay.sigma_offset
     t.retained = base + lay.retained_offset
-    t.n_internal = child.shape[0]
     t.basis_dim, t.n_retained, t.bits = int(basis_dim), int(n_retained), int(bits)
     t.idx_stride, t.ret_stride = lay.idx_stride, lay.ret_stride
-    t.offset = _vec3(offset)
-    t.invradius = _vec3(invradius)
     return t
 
 
 def octree_render_quant_persp(qtree, c2w, width, height, fx, opts, fy=None):
     """octree_render_persp on a PxoQuantTree."""
-    _require_gpu()
-    cam, keep = _camera(c2w, width, height, fx, fy)
-    out = _new(height, width, 3, device=keep.device)
-    check(_lib.load().pxo_octree_render_quant_fwd(ctypes.byref(qtree), *_rays(cam), ctypes.byref(opts), _f(out), _stream()),
-          "pxo_octree_render_quant_fwd")
-    return out
+    return _forward(qtree, opts, camera=(c2w, width, height, fx, fy))
 
 
 def octree_render_quant_rays(qtree, origins, dirs, viewdirs, opts):
     """octree_render_rays on a PxoQuantTree."""
-    _require_gpu()
-    out = _new(origins.shape[0], 3, device=origins.device)
-    check(_lib.load().pxo_octree_render_quant_fwd(ctypes.byref(qtree), *_rays(None, origins, dirs, viewdirs), ctypes.byref(opts),
-                                                  _f(out), _stream()), "pxo_octree_render_quant_fwd")
-    return out
+    return _forward(qtree, opts, rays=(origins, dirs, viewdirs))
 
 
 # ---- float16 trees rendered in place (the data array of the files N3Tree.save writes) ----
@@ -453,45 +471,25 @@ def half_pack(data, n_internal):
 
 def half_tree_view(child, packed, data_dim, offset, invradius):
     """PxoHalfTree struct over torch storage (keeps no reference: the caller owns the tensors)."""
-    if child.dtype != torch.int32:
-        raise PxoError("child must be int32")
+    t = _tree_fields(_lib.PxoHalfTree(), child, offset, invradius)
     stride, nbytes = half_layout(child.shape[0], data_dim)
     if packed.dtype != torch.float16 or not packed.is_contiguous() or packed.numel() * 2 < nbytes:
         raise PxoError("packed buffer is smaller than its layout")
-    t = _lib.PxoHalfTree()
-    t.child = _p(child).value
     t.data = _p(packed).value
-    t.n_internal = child.shape[0]
     t.data_dim = int(data_dim)
     t.basis_dim = (int(data_dim) - 1) // 3
     t.row_stride = stride
-    t.offset = _vec3(offset)
-    t.invradius = _vec3(invradius)
     return t
-
-
-def _render_half_fwd(htree, lobes, rays, opts, out, ndc):
-    _no_sg_ndc(lobes, ndc)
-    check(_lib.load().pxo_octree_render_half_fwd(ctypes.byref(htree), None if lobes is None else _lobes(lobes, htree), *rays,
-                                                 ctypes.byref(opts), _f(out), _stream(),
-                                                 None if ndc is None else ctypes.byref(_ndc(ndc))),
-          "pxo_octree_render_half_fwd")
-    return out
 
 
 def octree_render_half_persp(htree, c2w, width, height, fx, opts, fy=None, lobes=None, ndc=None):
     """octree_render_persp on a PxoHalfTree: bit for bit the image of the float tree with the widened data."""
-    _require_gpu()
-    cam, keep = _camera(c2w, width, height, fx, fy)
-    out = _new(height, width, 3, device=keep.device)
-    return _render_half_fwd(htree, lobes, _rays(cam), opts, out, ndc)
+    return _forward(htree, opts, camera=(c2w, width, height, fx, fy), lobes=lobes, ndc=ndc)
 
 
 def octree_render_half_rays(htree, origins, dirs, viewdirs, opts, lobes=None, ndc=None):
     """octree_render_rays on a PxoHalfTree."""
-    _require_gpu()
-    out = _new(origins.shape[0], 3, device=origins.device)
-    return _render_half_fwd(htree, lobes, _rays(None, origins, dirs, viewdirs), opts, out, ndc)
+    return _forward(htree, opts, rays=(origins, dirs, viewdirs), lobes=lobes, ndc=ndc)
 
 
 def _half_only(htree):
@@ -511,38 +509,15 @@ def octree_render_half_aux_rays(htree, origins, dirs, viewdirs, opts, surface_th
     return octree_render_aux_rays(htree, origins, dirs, viewdirs, opts, surface_thresh)
 
 
-def _aux_entry(tree):
-    """(entry point, its name) of the renderer with the extra outputs for a PxoTree, a PxoQuantTree or a PxoHalfTree."""
-    if isinstance(tree, _lib.PxoQuantTree):
-        return _lib.load().pxo_octree_render_quant_aux_fwd, "pxo_octree_render_quant_aux_fwd"
-    if isinstance(tree, _lib.PxoHalfTree):
-        return _lib.load().pxo_octree_render_half_aux_fwd, "pxo_octree_render_half_aux_fwd"
-    if isinstance(tree, _lib.PxoTree):
-        return _lib.load().pxo_octree_render_aux_fwd, "pxo_octree_render_aux_fwd"
-    raise PxoError(f"expected a PxoTree, a PxoQuantTree or a PxoHalfTree, got {type(tree).__name__}")
-
-
 def octree_render_aux_persp(tree, c2w, width, height, fx, opts, fy=None, surface_thresh=0.5):
-    """(rgb [H,W,3], aux [H,W,3]) of a pinhole camera from one march: rgb is octree_render_persp's (octree_render_quant_persp's
-    for a PxoQuantTree), aux = (alpha, depth, surface) as defined at pxo_octree_render_aux_fwd.  Not differentiable."""
-    _require_gpu()
-    fn, name = _aux_entry(tree)
-    cam, keep = _camera(c2w, width, height, fx, fy)
-    out = _new(height, width, 3, device=keep.device)
-    aux = _new(height, width, 3, device=keep.device)
-    check(fn(ctypes.byref(tree), *_rays(cam), ctypes.byref(opts), float(surface_thresh), _f(out), _f(aux), _stream()), name)
-    return out, aux
+    """(rgb [H,W,3], aux [H,W,3]) of a pinhole camera from one march, for a PxoTree, a PxoQuantTree or a PxoHalfTree: rgb is
+    octree_render_persp's, aux = (alpha, depth, surface) as defined at pxo_octree_render_aux_fwd.  Not differentiable."""
+    return _forward(tree, opts, camera=(c2w, width, height, fx, fy), surface_thresh=surface_thresh)
 
 
 def octree_render_aux_rays(tree, origins, dirs, viewdirs, opts, surface_thresh=0.5):
     """(rgb [B,3], aux [B,3]) of explicit world-space rays with unit dirs; see octree_render_aux_persp."""
-    _require_gpu()
-    fn, name = _aux_entry(tree)
-    out = _new(origins.shape[0], 3, device=origins.device)
-    aux = _new(origins.shape[0], 3, device=origins.device)
-    check(fn(ctypes.byref(tree), *_rays(None, origins, dirs, viewdirs), ctypes.byref(opts), float(surface_thresh), _f(out),
-             _f(aux), _stream()), name)
-    return out, aux
+    return _forward(tree, opts, rays=(origins, dirs, viewdirs), surface_thresh=surface_thresh)
 
 
 def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None, lobes=None, ndc=None):
