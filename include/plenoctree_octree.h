@@ -398,6 +398,30 @@ int pxo_tree_collapse_emit(const int32_t* child, const int32_t* parent_depth, co
                            const uint8_t* keep, const uint8_t* node_dead, const int64_t* new_index, int64_t n, int64_t n_new,
                            int32_t* new_child, int32_t* new_parent_depth, float* new_data, int64_t* old2new, void* stream);
 
+/* ---- level of detail: a mean pyramid in the rows of the cells that have a child  (no svox counterpart; the reduction is
+ *      this project's definition, not svox's) ----
+ * `data` holds a row for every cell, also for the cells that have a child; no renderer reads those (a marcher stops where
+ * child == 0) and the extraction leaves them zero.  pxo_tree_lod_fill writes into each of them the VALUE of the child node,
+ * deepest level first.  The value of node n, from the rows (c_j[0..D-2], s_j) of its cells j = 0..7 in storage order (the row
+ * of a cell that has a child is that child's value, already written), D = data_dim, all in float32, one rounding per
+ * operation, no contraction:
+ *   w_j = max(s_j, 0)                                           (negative sigma left by fine-tuning must not cancel density)
+ *   S = ((((((w_0 + w_1) + w_2) + w_3) + w_4) + w_5) + w_6) + w_7           sigma = S * 0.125
+ *   c[k] = (((w_0 c_0[k] + w_1 c_1[k]) + ...) + w_7 c_7[k]) / S   if S > 0 (IEEE division), else 0
+ * The colour coefficients are weighted by density, so empty octants do not wash them out; SH and SG trees alike (the lobes
+ * are not touched).  Every node of depth d >= 1 (parent_depth[n, 1]) writes its value into the row of its parent cell
+ * (parent_depth[n, 0]), one pass per depth max_depth .. 1 in stream order; nodes are picked by their stored depth, so node
+ * order does not matter (a tree that is not breadth-first, or a collapsed one).  Rows of leaves are never written: a row is
+ * written only where child[parent cell] points back at the node.  A level reads only rows of its own depth and writes only
+ * rows one level up, and a parent cell has one child: no atomics, the result does not depend on scheduling.
+ * A copy of `child` with the pointers of all nodes of depth >= L zeroed then renders level L (2^(L+1) cells per axis) in place
+ * through every entry point above, from the same `data`.
+ * data: float32 [n_internal, 8, data_dim], updated in place.  max_depth: the deepest node's depth.  PXO_ERR_ARG: a null
+ * pointer, n_internal outside [1, 2^28), data_dim not 3 k + 1 with k in {1, 4, 9, 16, 25}, max_depth outside
+ * [0, PXO_TREE_MAX_DEPTH].  n_internal == 1 or max_depth == 0 (a root-only tree) returns 0 without a launch.  Asynchronous. */
+int pxo_tree_lod_fill(const int32_t* child, const int32_t* parent_depth, float* data, int64_t n_internal, int data_dim,
+                      int max_depth, void* stream);
+
 /* ---- isosurface meshing  (marching cubes on the device; the reference meshes on the host: nerf_sh/gen_mesh.py:88-130) ----
  * Definition and output order are those of plenoctree_amd/nerf_sh/isosurface.py:marching_cubes, so the arrays compare with ==:
  *   inside(p) = vol[p] >= (float)iso                      vol: float32 [nx, ny, nz], x slowest, finite values

@@ -7,9 +7,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libplenoctree_hip.so")
 SOURCES = ["pxo_api.hip", "mlp_kernels.hip", "mlp_x3_kernels.hip", "mlp_x6_kernels.hip", "wgrad_kernels.hip", "wgrad_x6_kernels.hip", "render_kernels.hip", "optim_kernels.hip",
-           "octree_kernels.hip", "viewdirs_kernels.hip", "mesh_kernels.hip", "occupancy_kernels.hip"]
-# per-source flags: the octree marchers and the marching cubes are compiled without fused contraction (see the file headers)
-SOURCE_FLAGS = {"octree_kernels.hip": ["-ffp-contract=off"], "mesh_kernels.hip": ["-ffp-contract=off"]}
+           "octree_kernels.hip", "viewdirs_kernels.hip", "mesh_kernels.hip", "occupancy_kernels.hip", "lod_kernels.hip"]
+# per-source flags: the octree marchers, the marching cubes and the level-of-detail fill are compiled without fused contraction
+# (see the file headers)
+SOURCE_FLAGS = {"octree_kernels.hip": ["-ffp-contract=off"], "mesh_kernels.hip": ["-ffp-contract=off"],
+                "lod_kernels.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

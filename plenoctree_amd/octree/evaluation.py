@@ -5,6 +5,8 @@ mean PSNR of its renders of the test split; test images are sharded over the GPU
         [--keep_compressed]     (a tree written by octree.compression is rendered from its palette form, in place)
         [--keep_half]           (an uncompressed tree is rendered from the float16 data of its file, in place: the images of
                                  the float tree bit for bit; SH, SG and NDC scenes, --write_aux / --write_points on SH trees)
+        [--max_depth L]         (the float tree rendered at level L in place, 2^(L+1) cells per axis, from the mean pyramid
+                                 N3Tree.fill_internal_ writes into its unused rows; refused with --keep_half / --keep_compressed)
         [--write_aux DIR]       (per view NNN_rgba.png, the render with its opacity as the alpha channel, and NNN_depth.npz
                                  with float32 depth / surface / alpha; distances are Euclidean, from the camera origin)
         [--write_points F.ply]  (every --points_stride-th pixel of every view whose transmittance falls to --surface_thresh,
@@ -37,6 +39,9 @@ def define_flags():
     a("--keep_half", action="store_true",
       help="evaluate an uncompressed tree from the float16 data of its file, in place, instead of widening it to float32 "
            "(the same images bit for bit, half the device memory)")
+    # not a reference flag: level of detail (VolumeRenderer(max_depth=...))
+    a("--max_depth", type=int, default=None,
+      help="render the float tree at this level in place, from the mean pyramid in its unused rows (0 = the root's 8 cells)")
     # not reference flags: the renderer's opacity / distance outputs (VolumeRenderer.render_persp_aux)
     a("--write_aux", type=str, default=None, help="directory for NNN_rgba.png and NNN_depth.npz of every test view")
     a("--write_points", type=str, default=None, help="binary PLY of the back-projected surface points of all test views")
@@ -98,6 +103,13 @@ def main(argv=None):
     if args.keep_half and args.keep_compressed:
         raise ValueError("--keep_half together with --keep_compressed: a file holds either float16 data or the palette form; "
                          "give the flag that matches --input")
+    if args.max_depth is not None:
+        bad = [f for f, on in (("--keep_half", args.keep_half), ("--keep_compressed", args.keep_compressed)) if on]
+        if bad:
+            raise NotImplementedError(f"octree.evaluation: --max_depth together with {', '.join(bad)}: a capped render reads the "
+                                      "mean pyramid in the float tree's unused rows; the float16 and palette forms have none")
+        if args.max_depth < 0:
+            raise ValueError(f"--max_depth {args.max_depth}: must be >= 0")
     extraction.check_octree_flags(args, "octree.evaluation", (("--keep_compressed", args.keep_compressed),
                                                               ("--write_aux", args.write_aux is not None),
                                                               ("--write_points", args.write_points is not None)))
@@ -121,11 +133,12 @@ def main(argv=None):
     if want_aux:
         sink = _AuxSink(args, dataset)
         psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True,
-                                                    aux_sink=sink, surface_thresh=args.surface_thresh)
+                                                    aux_sink=sink, surface_thresh=args.surface_thresh, max_depth=args.max_depth)
         if args.write_points is not None:
             sink.write_points(comm)
     else:
-        psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True)
+        psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True,
+                                                    max_depth=args.max_depth)
     if comm.rank == 0:
         print("Average PSNR", psnr, "SSIM", ssim, flush=True)
     if args.write_vid is not None and frames:

@@ -37,6 +37,11 @@ tests/golden/sg_reference.npz): basis_i(d) = exp(lambda_i (mu_i . d - 1)) / K, c
 extra_data is a buffer, not a parameter: it is saved, loaded, cloned and moved with the tree and never optimised.  An SG tree
 renders (render_persp, forward) and back-propagates; the extra outputs (render_persp_aux) and the palette form
 (keep_quantized) are not built for it.
+
+Level of detail (no svox counterpart; the reduction is this project's definition, include/plenoctree_octree.h "level of
+detail"): N3Tree.fill_internal_() writes the density-weighted mean of every subtree into the row of the
+cell that holds it -- rows no renderer reads --, N3Tree.lod(L) cuts a standalone tree at depth L from them, and
+VolumeRenderer(tree, max_depth=L) renders level L in place through a copy of `child` with the deeper pointers zeroed.
 """
 import re
 import types
@@ -149,8 +154,9 @@ class N3TreeView:
         t = self.tree
         ch = range(t.data_dim)[self.channels]
         if self._all() and list(ch) == [t.data_dim - 1]:
-            oops.tree_relu_sigma(t.data.data)
+            t.relu_sigma_()
             return self
+        t._lod_filled = False
         d = t.data.data.view(-1, t.data_dim)
         with torch.no_grad():
             if self._all():
@@ -163,6 +169,7 @@ class N3TreeView:
 
     def set(self, value):
         t = self.tree
+        t._lod_filled = False
         d = t.data.data.view(-1, t.data_dim)
         value = torch.as_tensor(value, dtype=d.dtype, device=d.device)
         with torch.no_grad():
@@ -211,6 +218,7 @@ class N3Tree:
         self._level_order = True       # nodes stored breadth-first, levels contiguous (fast-path methods need it)
         self._sample_seed, self._sample_calls = 0, 0
         self._weight_accum = None      # the active WeightAccumulator (accumulate_weights), if any
+        self._lod_filled = False       # the rows of cells that have a child hold the pyramid of fill_internal_()
 
     # ---- structure -------------------------------------------------------------------------------
     @property
@@ -303,6 +311,7 @@ class N3Tree:
             if k == 0:
                 return 0
             n0, D, dev = self.n_internal, self.data_dim, self.device
+            self._lod_filled = False
             if n0 + k >= 1 << 28:
                 raise PxoError(f"{n0 + k} nodes exceed the int32 packed-index range")
             if int(depth.min()) < self.max_depth:
@@ -330,7 +339,7 @@ class N3Tree:
             self.level_nodes.pop()
         self.data = torch.nn.Parameter(torch.zeros(self.n_internal, 2, 2, 2, self.data_dim, dtype=torch.float32,
                                                    device=mask.device), requires_grad=self.data.requires_grad)
-        self._leaves, self._level_order = None, True
+        self._leaves, self._level_order, self._lod_filled = None, True, False
         return self
 
     def _need_level_order(self, what):
@@ -357,11 +366,13 @@ class N3Tree:
         (octree/extraction.py:394)."""
         node0, total = self.max_depth_nodes()
         count = total - first if count is None else count
+        self._lod_filled = False                 # the view is there to be written
         return self.data.data[node0 + first: node0 + first + count].view(count * 8, self.data_dim)
 
     def relu_sigma_(self):
         """tree[:, -1:].relu_() (octree/extraction.py:503)."""
         oops.tree_relu_sigma(self.data.data)
+        self._lod_filled = False
         return self
 
     def shrink_to_fit(self):
@@ -423,6 +434,7 @@ class N3Tree:
         root stays).  Entries of `keep` at cells that are not leaves are ignored.  Returns the number of nodes removed."""
         keep = self._cell_mask(keep, "prune_")
         n0 = self.n_internal
+        self._lod_filled = False
         with torch.no_grad():
             if not collapse:
                 dead = (self.child.view(-1) == 0) & ~keep
@@ -440,6 +452,63 @@ class N3Tree:
         depth_limit stay.  Entries at cells that are not leaves are ignored.  Returns the number of nodes added."""
         mask = self._cell_mask(mask, "refine_leaves")
         return self._refine_packed(torch.nonzero(mask & (self.child.view(-1) == 0)).reshape(-1))
+
+    # ---- additions (no svox counterpart): level of detail from a mean pyramid in the rows no renderer reads -----------------
+    def fill_internal_(self):
+        """Writes into the row of every cell that has a child the density-weighted mean of the subtree below it, bottom-up
+        (pxo_tree_lod_fill: this project's reduction, not svox's; include/plenoctree_octree.h, "level of detail").  Leaf rows
+        and every full-depth render stay as they are.  The tree is then marked filled; every method of this class that changes
+        structure or data (refine, refine_from_mask, prune_, tree[...] = value, relu_, relu_sigma_, max_depth_data) clears the
+        mark.  Writes that bypass the class -- an optimizer step, a kernel writing through tree.data -- do not: call this again
+        after them (torch's version counter is no help, the kernels write through raw pointers)."""
+        oops.tree_lod_fill(self.child, self.parent_depth, self.data.data, self.max_depth)
+        self._lod_filled = True
+        return self
+
+    def _lod_depth(self, L, what):
+        if not isinstance(L, (int, np.integer)) or isinstance(L, bool) or not 0 <= L <= self.max_depth:
+            raise ValueError(f"{what}: depth {L!r} is outside [0, {self.max_depth}] (the tree's max_depth)")
+        return int(L)
+
+    def lod_child(self, L):
+        """A copy of `child` with the pointers of every node of depth >= L zeroed: rendered with the tree's own (filled) data,
+        it shows the tree at level L (2^(L+1) cells per axis), since a marcher stops wherever child == 0 and reads the row there."""
+        L = self._lod_depth(L, "lod_child")
+        return self.child * (self.parent_depth[:, 1] < L).to(torch.int32)[:, None, None, None]
+
+    def lod(self, L, fill=True):
+        """A new N3Tree holding the nodes of depth <= L in their original order, the cells of its depth-L nodes all leaves: a
+        cell that had a child carries the filled row of that child (the mean of its subtree), surviving leaves keep their rows
+        bit for bit, and the rows of cells that still have a child are zero, as the extraction leaves them.  Transform, format,
+        depth_limit, geom_resize_fact and a copy of extra_data are carried over.  fill=True runs fill_internal_() on THIS tree
+        first unless it is marked filled (a side effect on its unused rows only); fill=False takes the rows as they stand and
+        runs on a CPU tree."""
+        L = self._lod_depth(L, "lod")
+        if fill and not self._lod_filled:
+            self.fill_internal_()
+        with torch.no_grad():
+            depth = self.parent_depth[:, 1]
+            keep = depth <= L
+            new_index = torch.cumsum(keep.long(), 0) - 1                  # of survivors; unused elsewhere
+            old = torch.nonzero(keep).reshape(-1)
+            skip = self.child.view(-1, 8)[old].long()
+            inner = (skip != 0) & (depth[old] < L)[:, None]               # cells that still have a child
+            target = old[:, None] + skip                                  # == old where skip == 0: always a valid index
+            child = torch.where(inner, new_index[target] - new_index[old][:, None], torch.zeros_like(skip))
+            parent = self.parent_depth[old, 0].long()                     # the parent of a survivor survives; root: (0, 0)
+            pd = torch.stack([(new_index[parent >> 3] * 8 + (parent & 7)).int(), depth[old]], 1)
+            data = self.data.data.view(-1, 8, self.data_dim)[old]
+            data = torch.where(inner[:, :, None], torch.zeros_like(data), data)
+        t = object.__new__(N3Tree)
+        t.__dict__.update(self.__dict__)
+        t.child, t.parent_depth = child.int().reshape(-1, 2, 2, 2), pd
+        t.data = torch.nn.Parameter(data.reshape(-1, 2, 2, 2, self.data_dim), requires_grad=self.data.requires_grad)
+        t.invradius, t.offset = self.invradius.clone(), self.offset.clone()
+        t.extra_data = None if self.extra_data is None else self.extra_data.detach().clone()
+        t.level_nodes = list(self.level_nodes[:L + 1])
+        t._leaves, t._weight_accum, t._lod_filled = None, None, False
+        t._level_order = not bool((pd[1:, 1] < pd[:-1, 1]).any())
+        return t
 
     # ---- npz (svox N3Tree.save / load; keys as consumed by octree/compression.py:76-86) ------------------
     def save(self, path, shrink=True, compress=True):
@@ -843,9 +912,26 @@ class VolumeRenderer:
 
     A HalfN3Tree renders wherever the float tree of the same file does (SH and SG in world space, SH with ndc, the alpha /
     depth / surface outputs on SH in world space), the same values bit for bit, and is refused where that tree is, in the same
-    words.  It is never differentiable."""
+    words.  It is never differentiable.
 
-    def __init__(self, tree, step_size=1e-3, background_brightness=1.0, ndc=None):
+    max_depth (an addition, no svox counterpart): None, or the level L the tree is rendered at, in place: through a copy of
+    `child` with the pointers of depth >= L nodes zeroed (N3Tree.lod_child) and the tree's own data, whose unused rows
+    N3Tree.fill_internal_() has filled with the mean of the subtree below them.  The images are those of `tree.lod(L)`, bit for
+    bit, through the same launches (SH and SG, world space and ndc, the aux outputs).  The first capped render fills the tree
+    if it is not marked filled, and every capped render checks the mark and the identity of tree.child, so a change made
+    through the class is followed by a refill; a stale pyramid is never rendered.  max_depth >= tree.max_depth renders the
+    full tree.  Float N3Tree only; a capped render is refused by name while the tree requires grad with grad mode on
+    (fine-tune tree.lod(L) instead) and inside accumulate_weights."""
+
+    def __init__(self, tree, step_size=1e-3, background_brightness=1.0, ndc=None, max_depth=None):
+        if max_depth is not None:
+            if not isinstance(tree, N3Tree):
+                raise NotImplementedError(f"VolumeRenderer(max_depth=...) on a {type(tree).__name__}: capped rendering is built "
+                                          f"for the float N3Tree only; call {getattr(tree, 'WAY_OUT', 'to_float')}() first")
+            if not isinstance(max_depth, (int, np.integer)) or isinstance(max_depth, bool) or max_depth < 0:
+                raise ValueError(f"VolumeRenderer(max_depth={max_depth!r}): must be None or an integer >= 0")
+        self.max_depth = None if max_depth is None else int(max_depth)
+        self._lod_child, self._lod_of = None, None       # the capped child array and the tree.child it was made from
         if ndc is not None:
             if not isinstance(ndc, NDCConfig):
                 raise NotImplementedError(f"VolumeRenderer(ndc=...): NDC rendering takes an svox.NDCConfig, got {type(ndc).__name__}")
@@ -870,6 +956,25 @@ class VolumeRenderer:
             kw["ndc"] = self.ndc
         return kw
 
+    def _view(self, what):
+        """The view a forward launch of `what` renders: the tree's own, or with an active cap (max_depth below the tree's
+        depth) the capped child array over the tree's filled data, refilled / rebuilt if the tree changed since."""
+        t = self.tree
+        if self.max_depth is None or self.max_depth >= t.max_depth:
+            return t.render_view()
+        if torch.is_grad_enabled() and t.requires_grad:
+            raise NotImplementedError(f"{what} with max_depth={self.max_depth} on a tree that requires grad: there is no gradient "
+                                      f"through a capped view; fine-tune tree.lod({self.max_depth}) instead, or render under "
+                                      "torch.no_grad()")
+        if t._weight_accum is not None:
+            raise NotImplementedError(f"{what} with max_depth={self.max_depth} inside accumulate_weights: the weights address the "
+                                      f"full tree's leaves; accumulate them on tree.lod({self.max_depth})")
+        if not t._lod_filled:
+            t.fill_internal_()
+        if self._lod_of is not t.child:                  # every structure edit replaces tree.child by a new tensor
+            self._lod_child, self._lod_of = t.lod_child(self.max_depth).contiguous(), t.child
+        return oops.tree_view(self._lod_child, t.data.data, t.offset, t.invradius)
+
     def _check_ndc_camera(self, width, height, fx, fy):
         """An NDC tree was built for ONE projection: a camera of another size or focal length renders rubbish without a word."""
         n = self.ndc
@@ -884,6 +989,7 @@ class VolumeRenderer:
         octree/optimization.py:216) is differentiable; the early-stopping preset (fast=True, evaluation) never is."""
         self._check_ndc_camera(width, height, fx, fy)
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.tree.device)
+        view = self._view("render_persp")
         # nothing in a read-only tree (the palette form, the file's float16 rows) requires grad or accumulates weights: it is
         # rendered directly, with grad mode on as well, `fast` both ways
         differentiable = torch.is_grad_enabled() and self.tree.requires_grad
@@ -900,17 +1006,18 @@ class VolumeRenderer:
                 raise oops.PxoError("render_persp(fast=True) is not differentiable: call it under torch.no_grad(), "
                                     "or use fast=False to optimise the tree")
             return _RenderPersp.apply(self.tree.data, self, c2w, width, height, fx, fy, self._opts(False))
-        return oops.octree_render_persp(self.tree.render_view(), c2w, width, height, fx, self._opts(fast), fy,
+        return oops.octree_render_persp(view, c2w, width, height, fx, self._opts(fast), fy,
                                         **self._basis_kwargs())
 
     def forward(self, origins, dirs, viewdirs, fast=False):
         """Colours [B,3] of explicit world-space rays (unit `dirs`); with `ndc` the rays are converted per ray and `viewdirs`
         (world space) shade them."""
+        view = self._view("forward")
         accum = self.tree._weight_accum
         if accum is not None:
             oops.octree_weight_accum_rays(self.tree.view(), origins, dirs, self._opts(fast), accum.op, accum._buffer(),
                                           ndc=self.ndc)
-        return oops.octree_render_rays(self.tree.render_view(), origins, dirs, viewdirs, self._opts(fast), **self._basis_kwargs())
+        return oops.octree_render_rays(view, origins, dirs, viewdirs, self._opts(fast), **self._basis_kwargs())
 
     __call__ = forward
 
@@ -922,10 +1029,11 @@ class VolumeRenderer:
         if getattr(self.tree, "extra_data", None) is not None:
             raise NotImplementedError(f"{what} on an SG tree ({self.tree.data_format}): alpha / depth / surface are built for SH "
                                       "trees only")
+        view = self._view(what)                          # a capped view has refusals of its own, by name
         if torch.is_grad_enabled() and self.tree.requires_grad:
             raise oops.PxoError(f"{what} is not differentiable (alpha, depth and surface have no gradient kernel): call it "
                                 "under torch.no_grad()")
-        return self.tree.render_view()
+        return view
 
     @staticmethod
     def _aux_dict(rgb, aux):

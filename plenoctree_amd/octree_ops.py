@@ -384,6 +384,21 @@ def tree_collapse(child, parent_depth, data, keep):
     return new_child, new_pd, new_data, old2new
 
 
+def tree_lod_fill(child, parent_depth, data, max_depth):
+    """Writes into the row of every cell that has a child the density-weighted mean of that child's eight rows, deepest level
+    first, in place (pxo_tree_lod_fill; the definition is in include/plenoctree_octree.h, "level of detail").  Leaf rows are
+    not touched.  max_depth: the deepest node's depth.  Returns `data`."""
+    _require_gpu()
+    n, D = child.shape[0], data.shape[-1]
+    if child.dtype != torch.int32 or parent_depth.dtype != torch.int32 or data.dtype != torch.float32:
+        raise PxoError("tree_lod_fill: child / parent_depth must be int32, data float32")
+    if child.numel() != n * 8 or data.numel() != n * 8 * D or parent_depth.numel() != n * 2:
+        raise PxoError(f"tree_lod_fill: data / parent_depth do not match the {n} nodes of child")
+    check(_lib.load().pxo_tree_lod_fill(_p(child), _p(parent_depth), _f(data), n, D, int(max_depth), _stream()),
+          "pxo_tree_lod_fill")
+    return data
+
+
 def octree_render_rays(tree, origins, dirs, viewdirs, opts, lobes=None, ndc=None):
     """[B,3] colours of explicit world-space rays with unit dirs (VolumeRenderer.forward).  lobes, ndc: as in
     octree_render_persp (with ndc the rays are still given in world space; they are converted per ray)."""
