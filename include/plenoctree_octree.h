@@ -422,6 +422,42 @@ int pxo_tree_collapse_emit(const int32_t* child, const int32_t* parent_depth, co
 int pxo_tree_lod_fill(const int32_t* child, const int32_t* parent_depth, float* data, int64_t n_internal, int data_dim,
                       int max_depth, void* stream);
 
+/* ---- footprint: a depth chosen per sample by the width of the pixel there  (no svox counterpart; this project's definition) ----
+ * pxo_octree_render_fwd / pxo_octree_render_sg_fwd (lobes != NULL) / pxo_octree_render_aux_fwd on a tree whose `data`
+ * pxo_tree_lod_fill has filled, with every sample's descent stopped where the pixel is at least as wide as the cell.  Forward
+ * only, float rows, world space.  Per launch:
+ *   cone >= 0   world-space width of a pixel per unit of world distance along the ray (the caller has multiplied in how many
+ *               pixels a cell may span); one cone per launch
+ *   min_depth   in [0, PXO_TREE_MAX_DEPTH]: no sample stops above this depth on account of the footprint
+ * All in float32, one rounding per operation, no contraction:
+ *   g = fl(cone * m),  m = min(invradius[0..2])      once per launch, on the host.  The smallest invradius: a cell is folded
+ *                                                    only if its LONGEST world side is at most the footprint (on an
+ *                                                    anisotropic volume this errs towards detail)
+ *   k = fl(delta_scale * g)                          per ray; delta_scale: the world length of a unit tree-space step
+ *   f = fl(tt * k)                                   per sample, at the ray parameter tt the descent is made for: the
+ *                                                    footprint in tree units
+ *   cap = clamp(126 - (bits(f) >> 23), min_depth, PXO_TREE_MAX_DEPTH)
+ * bits(f) >> 23 is the biased exponent of f (f >= 0), so cap is the smallest depth d whose cell side 2^-(d+1) is <= f,
+ * integer-exact, no log2.  f = 0 or a denormal gives 126: no cap.  f >= 0.5 (also +inf) gives <= 0: min_depth.
+ * The descent stops at the first cell where child == 0 or depth >= cap (which subsumes the depth bound of the other marchers);
+ * the sample reads data[node * 8 + cell] of that cell -- the filled row where the cell has a child -- and steps to the exit of
+ * THAT cell: cell_exit(local) * 2^-(depth+1) + step_size with the depth the descent stopped at.  The descent resumes from the
+ * previous sample's path at min(common, last_depth, cap): without the clamp by cap, a ray whose cap falls between two samples
+ * inside one deep cell would read the fine cell.  Compositing, the early stop, its rescale and the aux distances are those
+ * of the entry points named above; there is no blending between levels (level changes along a ray are hard steps).
+ * Consequences: cone so small that f stays below 2^-(PXO_TREE_MAX_DEPTH+1), or min_depth >= the tree's depth, renders the
+ * uncapped image bit for bit; a huge cone renders the level-min_depth view of pxo_tree_lod_fill's closing paragraph bit for bit.
+ * The caller answers for `data` being filled; a stale pyramid renders without a word.
+ * lobes: NULL for an SH tree, else the [basis_dim,4] lobes of an SG tree (checked as pxo_octree_render_sg_fwd checks them).
+ * The aux entry is SH only, as pxo_octree_render_aux_fwd.  PXO_ERR_ARG before any launch: a null tree, cone negative or not
+ * finite, min_depth outside its range, and whatever the uncapped entry points refuse.  Asynchronous. */
+int pxo_octree_render_foot_fwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                               const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float cone,
+                               int min_depth, float* out_rgb, void* stream);
+int pxo_octree_render_foot_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                   const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float cone, int min_depth,
+                                   float surface_thresh, float* out_rgb, float* out_aux, void* stream);
+
 /* ---- isosurface meshing  (marching cubes on the device; the reference meshes on the host: nerf_sh/gen_mesh.py:88-130) ----
  * Definition and output order are those of plenoctree_amd/nerf_sh/isosurface.py:marching_cubes, so the arrays compare with ==:
  *   inside(p) = vol[p] >= (float)iso                      vol: float32 [nx, ny, nz], x slowest, finite values

@@ -240,6 +240,10 @@ SIGNATURES = {
     "pxo_tree_collapse_mark": (c_int, [P, P, P, c_int64, c_int, P, P]),
     "pxo_tree_collapse_emit": (c_int, [P, P, P, c_int, P, P, P, c_int64, c_int64, P, P, P, P, P]),
     "pxo_tree_lod_fill": (c_int, [P, P, P, c_int64, c_int, c_int, P]),
+    "pxo_octree_render_foot_fwd": (c_int, [POINTER(PxoTree), P, POINTER(PxoCamera), P, P, P, c_int64,
+                                           POINTER(PxoRenderOpts), c_float, c_int, P, P]),
+    "pxo_octree_render_foot_aux_fwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
+                                               POINTER(PxoRenderOpts), c_float, c_int, c_float, P, P, P]),
     "pxo_mc_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "pxo_mc_count": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_size_t, POINTER(c_int64), P]),
     "pxo_mc_emit": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_size_t, POINTER(c_int64), P, P, P, P]),

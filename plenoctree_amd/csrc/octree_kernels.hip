@@ -841,6 +841,13 @@ struct AuxOut {
 };
 template <typename Block> struct WithAux : Block, AuxOut {};
 template <typename Block, bool AUX> using MaybeAux = std::conditional_t<AUX, WithAux<Block>, Block>;
+// ... and a FOOT instantiation (a depth per sample from the pixel footprint; plenoctree_octree.h, "footprint")
+struct FootIn {
+  float foot_g;                                // fl(cone * min(invradius)): footprint per unit of world distance, in tree units
+  int foot_min_depth;
+};
+template <typename Block> struct WithFoot : Block, FootIn {};
+template <typename Block, bool FOOT> using MaybeFoot = std::conditional_t<FOOT, WithFoot<Block>, Block>;
 // ST: what a leaf row stores, float (PxoTree) or _Float16 (PxoHalfTree)
 template <typename ST> using TreeOf = std::conditional_t<std::is_same<ST, float>::value, PxoTree, PxoHalfTree>;
 
@@ -881,7 +888,12 @@ struct Marcher {
     s[0] = 0;
   }
   // finds the leaf containing pos (tree coords, clamped); returns flat cell index node*8+cell
-  __device__ __forceinline__ int64_t find(const int32_t* __restrict__ child, const float (&pos)[3], int& depth_out) {
+  // CAP (the footprint renderer; plenoctree_octree.h, "footprint"): the descent also stops at depth `cap` (0 <= cap <= kMaxD),
+  // at a cell that may have a child, WITHOUT reading that cell's child pointer; the descent resumes no deeper than `cap`
+  // either -- the previous sample may sit below it in the same cell, and its path would lead back into the fine cell.
+  template <bool CAP = false>
+  __device__ __forceinline__ int64_t find(const int32_t* __restrict__ child, const float (&pos)[3], int& depth_out,
+                                          int cap = kMaxD) {
     const uint32_t X = (uint32_t)(pos[0] * (float)(1u << kBits));
     const uint32_t Y = (uint32_t)(pos[1] * (float)(1u << kBits));
     const uint32_t Z = (uint32_t)(pos[2] * (float)(1u << kBits));
@@ -890,6 +902,7 @@ struct Marcher {
       const uint32_t diff = (X ^ pX) | (Y ^ pY) | (Z ^ pZ);
       const int common = diff ? (__clz((int)diff) - (32 - kBits)) : kBits;     // leading bit-levels shared
       depth = min(common, last_depth);
+      if constexpr (CAP) depth = min(depth, cap);
     }
     first = false;
     pX = X; pY = Y; pZ = Z;
@@ -899,9 +912,11 @@ struct Marcher {
     while (true) {
       const int bit = kBits - 1 - depth;
       cell = (int)(((X >> bit) & 1u) << 2 | ((Y >> bit) & 1u) << 1 | ((Z >> bit) & 1u));
+      if constexpr (CAP)
+        if (depth >= cap) break;                        // cap <= kMaxD: the depth bound below, and more
       const int skip = child[(int64_t)node * 8 + cell];
       ++loads;
-      if (skip == 0 || depth >= kMaxD) break;          // depth bound: a malformed file cannot spin the descent
+      if (skip == 0 || (!CAP && depth >= kMaxD)) break;   // depth bound: a malformed file cannot spin the descent
       node += skip;
       ++depth;
       stack[depth] = node;
@@ -914,13 +929,21 @@ struct Marcher {
 
 // One sample of a tree march: the leaf at parameter tt of ray r and the step to the next sample.  Neither depends on the
 // leaf's DATA, which is what the renderers' software pipeline rests on.
+// FOOT: the sample stops at the depth its pixel footprint allows (foot_cap) and steps to the exit of THAT cell; foot_k is the
+// ray's footprint per unit of tt, in tree units.
+__device__ __forceinline__ int foot_cap(float f, int min_depth) {
+  return max(min_depth, min(126 - (int)(__float_as_uint(f) >> 23), kMaxD));      // smallest d with 2^-(d+1) <= f, clamped
+}
+template <bool FOOT = false>
 __device__ __forceinline__ void locate_leaf(const TreeRay& r, const CellExit& cell_exit, Marcher& mk, const int32_t* child,
-                                            float step_size, float tt, int64_t& leaf, float& delta) {
+                                            float step_size, float tt, int64_t& leaf, float& delta, float foot_k = 0.0f,
+                                            int min_depth = 0) {
   float pos[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) pos[a] = clamp_coord(r.o[a] + tt * r.d[a]);
   int depth;
-  leaf = mk.find(child, pos, depth);
+  if constexpr (FOOT) leaf = mk.find<true>(child, pos, depth, foot_cap(tt * foot_k, min_depth));
+  else leaf = mk.find(child, pos, depth);
   const float cube = (float)(2u << depth);
   float local[3];
 #pragma unroll
@@ -984,8 +1007,11 @@ __device__ __forceinline__ RowId row_ray(const Args& A, int row, float (&origin)
 // coefficient and sigma are widened to float32 as they are loaded (load_half4 for the groups of four), and every lane owns
 // the logical indices, multiplies and adds in the order of the float instantiation with the same MODE, ROW, KF and AUX: the
 // two return the same bits for a tree whose float data is the widened halves.
-template <int MODE, int ROW, bool VEC = false, int KF = 0, bool AUX = false, typename ST = float>
-__global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(MaybeAux<FwdBlock<TreeOf<ST>>, AUX> A,
+// FOOT (forward, float rows): every sample stops its descent at the depth its pixel footprint allows and reads the row there,
+// the filled row of pxo_tree_lod_fill where the cell has a child (locate_leaf<true>).  One register per ray (foot_k); per
+// sample a multiply, a shift, a subtract and a clamp.  Nothing else in the kernel knows of it.
+template <int MODE, int ROW, bool VEC = false, int KF = 0, bool AUX = false, typename ST = float, bool FOOT = false>
+__global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(MaybeFoot<MaybeAux<FwdBlock<TreeOf<ST>>, AUX>, FOOT> A,
                                                                         float* __restrict__ out_rgb,
                                                                         const float* __restrict__ fwd_rgb,
                                                                         const float* __restrict__ grad_out,
@@ -1011,6 +1037,13 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(MaybeAux<
   cell_exit.init(r.invdir);
   const bool miss = ndc_miss || r.tmax < 0.0f || r.tmin > r.tmax;
   static_assert(!AUX || MODE == 0, "alpha / depth / surface: forward only");
+  static_assert(!FOOT || (MODE == 0 && std::is_same_v<ST, float>), "footprint depth: forward, float rows");
+  float foot_k = 0.0f;
+  int foot_min = 0;
+  if constexpr (FOOT) {
+    foot_k = r.delta_scale * A.foot_g;
+    foot_min = A.foot_min_depth;
+  }
   if (MODE == 0 && miss) {
     for (int c = l; c < 3; c += kRow) out_rgb[ray * 3 + c] = bg;
     if constexpr (AUX)
@@ -1082,7 +1115,7 @@ __global__ __launch_bounds__(kRenderThreads) void octree_render_kernel(MaybeAux<
     // travel together with the sigma request), and only then is the current sample shaded -- per sample one dependent L2 round
     // trip less (lookup || sigma -> coefficients instead of lookup -> sigma -> coefficients).  Same samples, same arithmetic.
     auto locate = [&](float tt, int64_t& leaf_o, float& delta_o) {
-      locate_leaf(r, cell_exit, mk, child, A.opt.step_size, tt, leaf_o, delta_o);
+      locate_leaf<FOOT>(r, cell_exit, mk, child, A.opt.step_size, tt, leaf_o, delta_o, foot_k, foot_min);
     };
     int64_t leaf = 0;
     float delta_t = 0.0f;
@@ -2041,8 +2074,9 @@ static int launch_shape(const PxoCamera* cam, const float* origins, const float*
 // The forward launch of one argument block at `row` lanes per ray.  Rows of float or float16, 4 lanes: the channel-aligned
 // kernel with the tree's basis_dim as a compile-time constant (check_format has admitted these five values only, so there
 // is no run-time-K variant); 8 / 16 lanes: groups of four consecutive floats.  The palette form has one kernel per `row`.
-template <typename Block, bool AUX>
-static void launch_fwd(const MaybeAux<Block, AUX>& A, int row, unsigned grid, float* out_rgb, void* stream) {
+template <typename Block, bool AUX, bool FOOT = false>
+static void launch_fwd(const MaybeFoot<MaybeAux<Block, AUX>, FOOT>& A, int row, unsigned grid, float* out_rgb, void* stream) {
+  static_assert(!FOOT || std::is_same<Block, RenderArgs>::value, "footprint depth: the float tree only");
   if constexpr (std::is_same<Block, QuantRenderArgs>::value) {
     const auto kernel = row == 4   ? octree_render_quant_kernel<4, AUX>
                         : row == 8 ? octree_render_quant_kernel<8, AUX>
@@ -2050,14 +2084,14 @@ static void launch_fwd(const MaybeAux<Block, AUX>& A, int row, unsigned grid, fl
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, A, out_rgb);
   } else {
     using ST = std::conditional_t<std::is_same<Block, RenderArgs>::value, float, _Float16>;
-    auto kernel = row == 8 ? octree_render_kernel<0, 8, true, 0, AUX, ST> : octree_render_kernel<0, 16, true, 0, AUX, ST>;
+    auto kernel = row == 8 ? octree_render_kernel<0, 8, true, 0, AUX, ST, FOOT> : octree_render_kernel<0, 16, true, 0, AUX, ST, FOOT>;
     if (row == 4) {
       switch (A.tree.basis_dim) {
-        case 1: kernel = octree_render_kernel<0, 4, true, 1, AUX, ST>; break;
-        case 4: kernel = octree_render_kernel<0, 4, true, 4, AUX, ST>; break;
-        case 9: kernel = octree_render_kernel<0, 4, true, 9, AUX, ST>; break;
-        case 16: kernel = octree_render_kernel<0, 4, true, 16, AUX, ST>; break;
-        default: kernel = octree_render_kernel<0, 4, true, 25, AUX, ST>; break;
+        case 1: kernel = octree_render_kernel<0, 4, true, 1, AUX, ST, FOOT>; break;
+        case 4: kernel = octree_render_kernel<0, 4, true, 4, AUX, ST, FOOT>; break;
+        case 9: kernel = octree_render_kernel<0, 4, true, 9, AUX, ST, FOOT>; break;
+        case 16: kernel = octree_render_kernel<0, 4, true, 16, AUX, ST, FOOT>; break;
+        default: kernel = octree_render_kernel<0, 4, true, 25, AUX, ST, FOOT>; break;
       }
     }
     const float* none = nullptr;
@@ -2408,11 +2442,13 @@ static int render_args(const decltype(Block::tree)* tree, const float* lobes, co
 }
 
 // Every forward entry point after its own checks of lobes and ndc.  AUX: with the alpha / depth / surface outputs.
-template <typename Block, bool AUX>
+// FOOT: with a depth per sample from the pixel footprint (cone, min_depth: already checked by check_foot).
+template <typename Block, bool AUX, bool FOOT = false>
 static int render_forward(const decltype(Block::tree)* tree, const float* lobes, const PxoNdc* ndc, const PxoCamera* cam,
                           const float* origins, const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts,
-                          float surface_thresh, float* out_rgb, float* out_aux, void* stream, const char* who) {
-  MaybeAux<Block, AUX> A;
+                          float surface_thresh, float* out_rgb, float* out_aux, void* stream, const char* who,
+                          float cone = 0.0f, int min_depth = 0) {
+  MaybeFoot<MaybeAux<Block, AUX>, FOOT> A;
   unsigned grid;
   int row;
   if (int rc = render_args<Block>(tree, lobes, ndc, cam, origins, dirs, viewdirs, B, opts, who, false, A, grid, row)) return rc;
@@ -2424,7 +2460,11 @@ static int render_forward(const decltype(Block::tree)* tree, const float* lobes,
     A.out = out_aux;
     A.surface_thresh = surface_thresh;
   }
-  launch_fwd<Block, AUX>(A, row, grid, out_rgb, stream);
+  if constexpr (FOOT) {
+    A.foot_g = cone * fminf(fminf(tree->invradius[0], tree->invradius[1]), tree->invradius[2]);
+    A.foot_min_depth = min_depth;
+  }
+  launch_fwd<Block, AUX, FOOT>(A, row, grid, out_rgb, stream);
   return check_launch(who);
 }
 
@@ -2501,6 +2541,35 @@ int pxo_octree_render_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const f
                               float* out_rgb, float* out_aux, void* stream) {
   return render_forward<RenderArgs, true>(tree, nullptr, nullptr, cam, origins, dirs, viewdirs, B, opts, surface_thresh, out_rgb,
                                           out_aux, stream, "pxo_octree_render_aux_fwd");
+}
+
+// ---- a depth per sample from the pixel footprint (plenoctree_octree.h, "footprint") ----
+static int check_foot(const PxoTree* tree, float cone, int min_depth, const char* who) {
+  PXO_REQUIRE(tree && tree->child && tree->data, "%s: null tree", who);
+  PXO_REQUIRE(cone >= 0.0f && cone < INFINITY, "%s: cone %g must be finite and >= 0", who, (double)cone);
+  PXO_REQUIRE(min_depth >= 0 && min_depth <= PXO_TREE_MAX_DEPTH, "%s: min_depth %d is outside [0, %d]", who, min_depth,
+              PXO_TREE_MAX_DEPTH);
+  return PXO_OK;
+}
+
+int pxo_octree_render_foot_fwd(const PxoTree* tree, const float* lobes, const PxoCamera* cam, const float* origins,
+                               const float* dirs, const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float cone,
+                               int min_depth, float* out_rgb, void* stream) {
+  const char* who = "pxo_octree_render_foot_fwd";
+  if (int rc = check_foot(tree, cone, min_depth, who)) return rc;
+  if (lobes)                                     // an SG tree: its format is checked in SG's name, as pxo_octree_render_sg_fwd does
+    if (int rc = check_sg(tree, lobes, who)) return rc;
+  return render_forward<RenderArgs, false, true>(tree, lobes, nullptr, cam, origins, dirs, viewdirs, B, opts, 0.0f, out_rgb,
+                                                 nullptr, stream, who, cone, min_depth);
+}
+
+int pxo_octree_render_foot_aux_fwd(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,
+                                   const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float cone, int min_depth,
+                                   float surface_thresh, float* out_rgb, float* out_aux, void* stream) {
+  const char* who = "pxo_octree_render_foot_aux_fwd";
+  if (int rc = check_foot(tree, cone, min_depth, who)) return rc;
+  return render_forward<RenderArgs, true, true>(tree, nullptr, nullptr, cam, origins, dirs, viewdirs, B, opts, surface_thresh,
+                                                out_rgb, out_aux, stream, who, cone, min_depth);
 }
 
 static int octree_render_bwd_impl(const PxoTree* tree, const PxoCamera* cam, const float* origins, const float* dirs,

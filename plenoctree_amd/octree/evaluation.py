@@ -7,6 +7,11 @@ mean PSNR of its renders of the test split; test images are sharded over the GPU
                                  the float tree bit for bit; SH, SG and NDC scenes, --write_aux / --write_points on SH trees)
         [--max_depth L]         (the float tree rendered at level L in place, 2^(L+1) cells per axis, from the mean pyramid
                                  N3Tree.fill_internal_ writes into its unused rows; refused with --keep_half / --keep_compressed)
+        [--lod_pixels P [--lod_min_depth M]]
+                                (the float tree with every sample read at the first level whose cells are no wider than P
+                                 pixels where the sample lies, never above depth M, from the same pyramid; composes with
+                                 --max_depth, --write_aux and --write_points; refused with --keep_half / --keep_compressed
+                                 and on an NDC scene)
         [--write_aux DIR]       (per view NNN_rgba.png, the render with its opacity as the alpha channel, and NNN_depth.npz
                                  with float32 depth / surface / alpha; distances are Euclidean, from the camera origin)
         [--write_points F.ply]  (every --points_stride-th pixel of every view whose transmittance falls to --surface_thresh,
@@ -23,6 +28,7 @@ import numpy as np
 from .. import dist
 from ..nerf_sh.nerf import llff, utils
 from . import aux_io, extraction
+from .._lib import TREE_MAX_DEPTH
 from .svox import N3Tree
 
 
@@ -42,6 +48,10 @@ def define_flags():
     # not a reference flag: level of detail (VolumeRenderer(max_depth=...))
     a("--max_depth", type=int, default=None,
       help="render the float tree at this level in place, from the mean pyramid in its unused rows (0 = the root's 8 cells)")
+    # not reference flags: a depth per sample from the pixel footprint (VolumeRenderer(lod_pixels=..., lod_min_depth=...))
+    a("--lod_pixels", type=float, default=None,
+      help="stop every sample's descent at the first cell no wider than this many pixels there (0 or unset: full depth)")
+    a("--lod_min_depth", type=int, default=None, help=f"with --lod_pixels: never fold above this depth (0..{TREE_MAX_DEPTH}, default 0)")
     # not reference flags: the renderer's opacity / distance outputs (VolumeRenderer.render_persp_aux)
     a("--write_aux", type=str, default=None, help="directory for NNN_rgba.png and NNN_depth.npz of every test view")
     a("--write_points", type=str, default=None, help="binary PLY of the back-projected surface points of all test views")
@@ -63,6 +73,26 @@ def check_sg_flags(args):
     if bad:
         raise NotImplementedError(f"{args.input} is an SG tree ({fmt}): {', '.join(bad)} not built for SG trees (palette-form "
                                   "rendering and the alpha / depth / surface outputs are SH only)")
+
+
+def check_lod_flags(args):
+    """--lod_pixels / --lod_min_depth: what they are refused with, by name, before anything is loaded."""
+    if args.lod_pixels is None:
+        if args.lod_min_depth is not None:
+            raise ValueError("--lod_min_depth without --lod_pixels: it bounds the footprint render only")
+        return
+    if not 0 <= args.lod_pixels < float("inf"):
+        raise ValueError(f"--lod_pixels {args.lod_pixels}: must be a finite number >= 0")
+    if args.lod_min_depth is not None and not 0 <= args.lod_min_depth <= TREE_MAX_DEPTH:
+        raise ValueError(f"--lod_min_depth {args.lod_min_depth}: must be in [0, {TREE_MAX_DEPTH}]")
+    bad = [f for f, on in (("--keep_half", args.keep_half), ("--keep_compressed", args.keep_compressed)) if on]
+    if bad:
+        raise NotImplementedError(f"octree.evaluation: --lod_pixels together with {', '.join(bad)}: a footprint render reads "
+                                  "the mean pyramid in the float tree's unused rows; the float16 and palette forms have none")
+    if extraction.uses_ndc(args):
+        raise NotImplementedError("octree.evaluation: --lod_pixels not built for an NDC scene (--dataset llff without "
+                                  "--spherify): a ray parameter there is an NDC length, a pixel footprint along it has no "
+                                  "meaning")
 
 
 class _AuxSink:
@@ -110,6 +140,7 @@ def main(argv=None):
                                       "mean pyramid in the float tree's unused rows; the float16 and palette forms have none")
         if args.max_depth < 0:
             raise ValueError(f"--max_depth {args.max_depth}: must be >= 0")
+    check_lod_flags(args)
     extraction.check_octree_flags(args, "octree.evaluation", (("--keep_compressed", args.keep_compressed),
                                                               ("--write_aux", args.write_aux is not None),
                                                               ("--write_points", args.write_points is not None)))
@@ -130,15 +161,17 @@ def main(argv=None):
         print(f"float16 tree kept in place: {tree.nbytes / 2 ** 20:.1f} MB on the device "
               f"(float form: {tree.float_nbytes / 2 ** 20:.1f} MB)", flush=True)
     want_frames = args.write_images is not None or args.write_vid is not None
+    lod = {"lod_pixels": args.lod_pixels, "lod_min_depth": args.lod_min_depth or 0}
     if want_aux:
         sink = _AuxSink(args, dataset)
         psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True,
-                                                    aux_sink=sink, surface_thresh=args.surface_thresh, max_depth=args.max_depth)
+                                                    aux_sink=sink, surface_thresh=args.surface_thresh, max_depth=args.max_depth,
+                                                    **lod)
         if args.write_points is not None:
             sink.write_points(comm)
     else:
         psnr, ssim, frames = extraction.eval_octree(tree, dataset, args, comm, want_frames=want_frames, want_ssim=True,
-                                                    max_depth=args.max_depth)
+                                                    max_depth=args.max_depth, **lod)
     if comm.rank == 0:
         print("Average PSNR", psnr, "SSIM", ssim, flush=True)
     if args.write_vid is not None and frames:

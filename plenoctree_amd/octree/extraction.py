@@ -251,15 +251,18 @@ def tree_center_radius(tree):
 
 @torch.no_grad()
 def eval_octree(tree, dataset, args, comm=None, want_frames=False, want_ssim=False, aux_sink=None, surface_thresh=0.5,
-                max_depth=None):
+                max_depth=None, lod_pixels=None, lod_min_depth=0):
     """eval_octree (octree/nerf/utils.py:448-497): mean PSNR (and SSIM if asked) of the octree renders of a split;
     images are sharded over the ranks.  LPIPS needs pretrained VGG weights, which cannot be fetched here.
     aux_sink (off by default): called as aux_sink(idx, c2w, res) for every view of this rank with the dict of
     VolumeRenderer.render_persp_aux; the view is then rendered by that call (same rgb) instead of render_persp.
     An LLFF scene that is not --spherify is rendered in NDC (octree/nerf/utils.py:451-457).
-    max_depth (off by default): the level the float tree is rendered at, in place (VolumeRenderer(max_depth=...))."""
+    max_depth (off by default): the level the float tree is rendered at, in place (VolumeRenderer(max_depth=...)).
+    lod_pixels, lod_min_depth (off by default): every sample at the depth its pixel footprint allows
+    (VolumeRenderer(lod_pixels=...))."""
     comm = comm or dist.Comm()
-    r = VolumeRenderer(tree, step_size=args.renderer_step_size, ndc=ndc_config(args, dataset), max_depth=max_depth)
+    foot = {"lod_pixels": lod_pixels, "lod_min_depth": lod_min_depth} if lod_pixels else {}    # unset: the call of before
+    r = VolumeRenderer(tree, step_size=args.renderer_step_size, ndc=ndc_config(args, dataset), max_depth=max_depth, **foot)
     acc = torch.zeros(3, dtype=torch.float64, device=tree.device)
     frames = []
     for idx in range(comm.rank, dataset.size, comm.world):

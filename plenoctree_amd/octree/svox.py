@@ -921,9 +921,35 @@ class VolumeRenderer:
     if it is not marked filled, and every capped render checks the mark and the identity of tree.child, so a change made
     through the class is followed by a refill; a stale pyramid is never rendered.  max_depth >= tree.max_depth renders the
     full tree.  Float N3Tree only; a capped render is refused by name while the tree requires grad with grad mode on
-    (fine-tune tree.lod(L) instead) and inside accumulate_weights."""
+    (fine-tune tree.lod(L) instead) and inside accumulate_weights.
 
-    def __init__(self, tree, step_size=1e-3, background_brightness=1.0, ndc=None, max_depth=None):
+    lod_pixels (an addition, no svox counterpart): None or 0 for the launches above, or P > 0: every sample stops its descent
+    at the first cell that is no wider than P pixels where the sample lies, and reads the filled row there (the definition:
+    include/plenoctree_octree.h, "footprint"; forward only, hard steps between levels).  render_persp / render_persp_aux take
+    the width of a pixel from the camera, cone = P / max(fx, fy); forward / forward_aux need pixel_angle, radians per pixel
+    for unit dirs, cone = P * pixel_angle.  lod_min_depth: no sample is folded above this depth.  The tree is filled and
+    refilled as for max_depth, with which it composes (the footprint march then runs on the capped child array).  Float
+    N3Tree in world space only; refused by name for the other forms, with ndc, while the tree requires grad with grad mode
+    on, and inside accumulate_weights."""
+
+    def __init__(self, tree, step_size=1e-3, background_brightness=1.0, ndc=None, max_depth=None, lod_pixels=None,
+                 lod_min_depth=0):
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+        if lod_pixels is not None and not (number(lod_pixels) and 0 <= lod_pixels < float("inf")):
+            raise ValueError(f"VolumeRenderer(lod_pixels={lod_pixels!r}): must be None or a finite number >= 0")
+        if not isinstance(lod_min_depth, (int, np.integer)) or isinstance(lod_min_depth, bool) or \
+                not 0 <= lod_min_depth <= TREE_MAX_DEPTH:
+            raise ValueError(f"VolumeRenderer(lod_min_depth={lod_min_depth!r}): must be an integer in [0, {TREE_MAX_DEPTH}]")
+        self.lod_pixels = float(lod_pixels) if lod_pixels else None          # None and 0: the launches without a footprint
+        self.lod_min_depth = int(lod_min_depth)
+        if self.lod_pixels is not None:
+            if not isinstance(tree, N3Tree):
+                raise NotImplementedError(f"VolumeRenderer(lod_pixels=...) on a {type(tree).__name__}: footprint rendering is "
+                                          f"built for the float N3Tree only; call {getattr(tree, 'WAY_OUT', 'to_float')}() first")
+            if ndc is not None:
+                raise NotImplementedError("VolumeRenderer(lod_pixels=...) with ndc: footprint rendering is not built for an NDC "
+                                          "scene (a ray parameter there is an NDC length, and a pixel footprint along it has no "
+                                          "meaning)")
         if max_depth is not None:
             if not isinstance(tree, N3Tree):
                 raise NotImplementedError(f"VolumeRenderer(max_depth=...) on a {type(tree).__name__}: capped rendering is built "
@@ -960,20 +986,46 @@ class VolumeRenderer:
         """The view a forward launch of `what` renders: the tree's own, or with an active cap (max_depth below the tree's
         depth) the capped child array over the tree's filled data, refilled / rebuilt if the tree changed since."""
         t = self.tree
-        if self.max_depth is None or self.max_depth >= t.max_depth:
+        capped = self.max_depth is not None and self.max_depth < t.max_depth
+        if not capped and self.lod_pixels is None:
             return t.render_view()
-        if torch.is_grad_enabled() and t.requires_grad:
-            raise NotImplementedError(f"{what} with max_depth={self.max_depth} on a tree that requires grad: there is no gradient "
-                                      f"through a capped view; fine-tune tree.lod({self.max_depth}) instead, or render under "
-                                      "torch.no_grad()")
-        if t._weight_accum is not None:
-            raise NotImplementedError(f"{what} with max_depth={self.max_depth} inside accumulate_weights: the weights address the "
-                                      f"full tree's leaves; accumulate them on tree.lod({self.max_depth})")
+        if capped:
+            if torch.is_grad_enabled() and t.requires_grad:
+                raise NotImplementedError(f"{what} with max_depth={self.max_depth} on a tree that requires grad: there is no "
+                                          f"gradient through a capped view; fine-tune tree.lod({self.max_depth}) instead, or "
+                                          "render under torch.no_grad()")
+            if t._weight_accum is not None:
+                raise NotImplementedError(f"{what} with max_depth={self.max_depth} inside accumulate_weights: the weights address "
+                                          f"the full tree's leaves; accumulate them on tree.lod({self.max_depth})")
+        if self.lod_pixels is not None:                  # a footprint render reads the filled rows as well, cap or no cap
+            if torch.is_grad_enabled() and t.requires_grad:
+                raise NotImplementedError(f"{what} with lod_pixels={self.lod_pixels:g} on a tree that requires grad: there is no "
+                                          "gradient through a footprint render; render under torch.no_grad()")
+            if t._weight_accum is not None:
+                raise NotImplementedError(f"{what} with lod_pixels={self.lod_pixels:g} inside accumulate_weights: the weights "
+                                          "address leaves, a footprint render also reads the rows of cells that have a child")
         if not t._lod_filled:
             t.fill_internal_()
+        if not capped:
+            return t.render_view()
         if self._lod_of is not t.child:                  # every structure edit replaces tree.child by a new tensor
             self._lod_child, self._lod_of = t.lod_child(self.max_depth).contiguous(), t.child
         return oops.tree_view(self._lod_child, t.data.data, t.offset, t.invradius)
+
+    def _cone(self, what, pixel_angle):
+        """The cone of a footprint launch on explicit rays; None without lod_pixels (pixel_angle is then not looked at)."""
+        if self.lod_pixels is None:
+            return None
+        if pixel_angle is None:
+            raise ValueError(f"{what} with lod_pixels={self.lod_pixels:g} needs pixel_angle (radians per pixel for unit dirs): "
+                             "explicit rays carry no pixel size")
+        if isinstance(pixel_angle, bool) or not isinstance(pixel_angle, (int, float, np.integer, np.floating)) or \
+                not 0 <= pixel_angle < float("inf"):
+            raise ValueError(f"{what}(pixel_angle={pixel_angle!r}): must be a finite number >= 0")
+        return self.lod_pixels * float(pixel_angle)
+
+    def _camera_cone(self, fx, fy):
+        return None if self.lod_pixels is None else self.lod_pixels / max(float(fx), float(fx if fy is None else fy))
 
     def _check_ndc_camera(self, width, height, fx, fy):
         """An NDC tree was built for ONE projection: a camera of another size or focal length renders rubbish without a word."""
@@ -1006,13 +1058,20 @@ class VolumeRenderer:
                 raise oops.PxoError("render_persp(fast=True) is not differentiable: call it under torch.no_grad(), "
                                     "or use fast=False to optimise the tree")
             return _RenderPersp.apply(self.tree.data, self, c2w, width, height, fx, fy, self._opts(False))
+        if self.lod_pixels is not None:
+            return oops.octree_render_foot_persp(view, c2w, width, height, fx, self._opts(fast), self._camera_cone(fx, fy),
+                                                 self.lod_min_depth, fy, **self.tree.basis_kwargs())
         return oops.octree_render_persp(view, c2w, width, height, fx, self._opts(fast), fy,
                                         **self._basis_kwargs())
 
-    def forward(self, origins, dirs, viewdirs, fast=False):
+    def forward(self, origins, dirs, viewdirs, fast=False, pixel_angle=None):
         """Colours [B,3] of explicit world-space rays (unit `dirs`); with `ndc` the rays are converted per ray and `viewdirs`
-        (world space) shade them."""
+        (world space) shade them.  pixel_angle: with lod_pixels, the angle between neighbouring rays, radians per pixel."""
+        cone = self._cone("forward", pixel_angle)
         view = self._view("forward")
+        if cone is not None:
+            return oops.octree_render_foot_rays(view, origins, dirs, viewdirs, self._opts(fast), cone, self.lod_min_depth,
+                                                **self.tree.basis_kwargs())
         accum = self.tree._weight_accum
         if accum is not None:
             oops.octree_weight_accum_rays(self.tree.view(), origins, dirs, self._opts(fast), accum.op, accum._buffer(),
@@ -1046,11 +1105,20 @@ class VolumeRenderer:
         Distances are Euclidean, in world units, from the ray origin.  Not differentiable."""
         view = self._aux_view("render_persp_aux")
         c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.tree.device)
+        if self.lod_pixels is not None:
+            return self._aux_dict(*oops.octree_render_foot_persp(view, c2w, width, height, fx, self._opts(fast),
+                                                                 self._camera_cone(fx, fy), self.lod_min_depth, fy,
+                                                                 surface_thresh=surface_thresh))
         return self._aux_dict(*oops.octree_render_aux_persp(view, c2w, width, height, fx, self._opts(fast), fy, surface_thresh))
 
-    def forward_aux(self, origins, dirs, viewdirs, fast=False, surface_thresh=0.5):
-        """render_persp_aux for explicit world-space rays (unit `dirs`): rgb [B,3], alpha / depth / surface [B]."""
+    def forward_aux(self, origins, dirs, viewdirs, fast=False, surface_thresh=0.5, pixel_angle=None):
+        """render_persp_aux for explicit world-space rays (unit `dirs`): rgb [B,3], alpha / depth / surface [B].  pixel_angle:
+        as in forward."""
+        cone = self._cone("forward_aux", pixel_angle)
         view = self._aux_view("forward_aux")
+        if cone is not None:
+            return self._aux_dict(*oops.octree_render_foot_rays(view, origins, dirs, viewdirs, self._opts(fast), cone,
+                                                                self.lod_min_depth, surface_thresh=surface_thresh))
         return self._aux_dict(*oops.octree_render_aux_rays(view, origins, dirs, viewdirs, self._opts(fast), surface_thresh))
 
 

@@ -179,20 +179,25 @@ def _no_sg_ndc(lobes, ndc):
 
 # The renderer entry points: (struct type, what) -> {shading: (name, takes lobes, takes ndc)}; what: "fwd", "aux" (forward with
 # the extra outputs) or "bwd"; shading: "" for SH in world space, "sg" with an SG tree's lobes, "ndc" with a scene's projection.
-# Every one takes, in this order: the tree[, lobes], the camera and rays of _rays, the options[, surface_thresh], out_rgb[,
-# out_aux] (backward: out_rgb, grad_out, grad_data), the stream[, ndc].  What a form has no row or shading for is not built.
+# "foot" / "foot_aux" are "fwd" / "aux" at a depth per sample from the pixel footprint (float trees in world space only).
+# Every one takes, in this order: the tree[, lobes], the camera and rays of _rays, the options[, cone, min_depth][,
+# surface_thresh], out_rgb[, out_aux] (backward: out_rgb, grad_out, grad_data), the stream[, ndc].  What a form has no row or shading for is not built.
 _ENTRIES = {
     (_lib.PxoTree, "fwd"): {"": ("pxo_octree_render_fwd", False, False), "sg": ("pxo_octree_render_sg_fwd", True, False),
                             "ndc": ("pxo_octree_render_ndc_fwd", False, True)},
     (_lib.PxoTree, "bwd"): {"": ("pxo_octree_render_bwd", False, False), "sg": ("pxo_octree_render_sg_bwd", True, False),
                             "ndc": ("pxo_octree_render_ndc_bwd", False, True)},
     (_lib.PxoTree, "aux"): {"": ("pxo_octree_render_aux_fwd", False, False)},
+    (_lib.PxoTree, "foot"): dict.fromkeys(("", "sg"), ("pxo_octree_render_foot_fwd", True, False)),
+    (_lib.PxoTree, "foot_aux"): {"": ("pxo_octree_render_foot_aux_fwd", False, False)},
     (_lib.PxoQuantTree, "fwd"): {"": ("pxo_octree_render_quant_fwd", False, False)},
     (_lib.PxoQuantTree, "aux"): {"": ("pxo_octree_render_quant_aux_fwd", False, False)},
     (_lib.PxoHalfTree, "fwd"): dict.fromkeys(("", "sg", "ndc"), ("pxo_octree_render_half_fwd", True, True)),
     (_lib.PxoHalfTree, "aux"): {"": ("pxo_octree_render_half_aux_fwd", False, False)},
 }
-_WHAT = {"fwd": "rendering", "aux": "rendering alpha / depth / surface", "bwd": "the gradient"}
+_WHAT = {"fwd": "rendering", "aux": "rendering alpha / depth / surface", "bwd": "the gradient",
+         "foot": "rendering at a depth per sample from the pixel footprint",
+         "foot_aux": "rendering alpha / depth / surface at a depth per sample from the pixel footprint"}
 _SHADING = {"": "an SH tree in world space", "sg": "an SG tree (lobes)", "ndc": "an NDC scene (ndc)"}
 
 
@@ -211,9 +216,10 @@ def _call(tree, what, lobes, ndc, rays, opts, outputs):
     check(getattr(_lib.load(), name)(ctypes.byref(tree), *lead, *rays, ctypes.byref(opts), *outputs, _stream(), *trail), name)
 
 
-def _forward(tree, opts, camera=None, rays=None, lobes=None, ndc=None, surface_thresh=None):
+def _forward(tree, opts, camera=None, rays=None, lobes=None, ndc=None, surface_thresh=None, foot=None):
     """The forward render of a PxoTree, a PxoQuantTree or a PxoHalfTree from camera = (c2w, width, height, fx, fy) or rays =
-    (origins, dirs, viewdirs): rgb [H,W,3] or [B,3], and with surface_thresh (rgb, aux), aux of rgb's shape."""
+    (origins, dirs, viewdirs): rgb [H,W,3] or [B,3], and with surface_thresh (rgb, aux), aux of rgb's shape.  foot: None, or
+    (cone, min_depth) of the footprint launches (include/plenoctree_octree.h, "footprint"); the tree's data must be filled."""
     _require_gpu()
     if camera is not None:
         cam, keep = _camera(*camera)
@@ -222,7 +228,8 @@ def _forward(tree, opts, camera=None, rays=None, lobes=None, ndc=None, surface_t
         shape, device, rays = (rays[0].shape[0], 3), rays[0].device, _rays(None, *rays)
     aux = surface_thresh is not None
     outs = [_new(*shape, device=device) for _ in range(2 if aux else 1)]
-    _call(tree, "aux" if aux else "fwd", lobes, ndc, rays, opts,
+    what = ("aux" if aux else "fwd") if foot is None else ("foot_aux" if aux else "foot")
+    _call(tree, what, lobes, ndc, rays, opts, (() if foot is None else (float(foot[0]), int(foot[1]))) +
           ((float(surface_thresh),) if aux else ()) + tuple(_f(o) for o in outs))
     return tuple(outs) if aux else outs[0]
 
@@ -533,6 +540,20 @@ def octree_render_aux_persp(tree, c2w, width, height, fx, opts, fy=None, surface
 def octree_render_aux_rays(tree, origins, dirs, viewdirs, opts, surface_thresh=0.5):
     """(rgb [B,3], aux [B,3]) of explicit world-space rays with unit dirs; see octree_render_aux_persp."""
     return _forward(tree, opts, rays=(origins, dirs, viewdirs), surface_thresh=surface_thresh)
+
+
+def octree_render_foot_persp(tree, c2w, width, height, fx, opts, cone, min_depth=0, fy=None, lobes=None, surface_thresh=None):
+    """octree_render_persp (surface_thresh None) or octree_render_aux_persp of a PxoTree whose data tree_lod_fill has filled,
+    every sample at the depth its pixel footprint allows (pxo_octree_render_foot_fwd / _foot_aux_fwd).  cone: world-space
+    width of a pixel per unit of distance along the ray; min_depth: no sample is folded above this depth."""
+    return _forward(tree, opts, camera=(c2w, width, height, fx, fy), lobes=lobes, surface_thresh=surface_thresh,
+                    foot=(cone, min_depth))
+
+
+def octree_render_foot_rays(tree, origins, dirs, viewdirs, opts, cone, min_depth=0, lobes=None, surface_thresh=None):
+    """octree_render_foot_persp for explicit world-space rays [B,3] with unit dirs."""
+    return _forward(tree, opts, rays=(origins, dirs, viewdirs), lobes=lobes, surface_thresh=surface_thresh,
+                    foot=(cone, min_depth))
 
 
 def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_data, out_rgb=None, lobes=None, ndc=None):
