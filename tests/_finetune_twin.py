@@ -1,13 +1,12 @@
 """The float64 twin of octree fine-tuning (plenoctree_amd/octree/optimization.py; reference octree/optimization.py:176-243) and
 the cases it is run on.  Shared by tests/test_finetune_twin_cpu.py (the conditions that keep the GPU tests honest, on the twin
 alone) and tests/test_gpu_octree_finetune.py (the HIP path against the twin).  Nothing here touches the GPU or the code under
-test: the renders are oracle/octree_oracle.py:render_rays_torch (SH), tests/_octree_sg_oracle.py (SG) and
-tests/_octree_ndc_oracle.py (NDC), the optimisers are torch.optim.SGD and torch.optim.Adam.
+test: the renders are oracle/octree_oracle.py:render_rays_torch (SH, SG with lobes, NDC), the optimisers are torch.optim.SGD
+and torch.optim.Adam.
 
-The oracle's march (the sample sequence of a ray) depends on the tree's structure only, never on its data, so every ray is
-marched once per process and the sequence reused by every later render of the same ray (`_marches_reused`).
+The oracle's march (the sample sequence of a ray) depends on the tree's structure only, never on its data, so a case marches
+every ray of a view once (Case.marches) and hands the marches to every render of that view.
 """
-import contextlib
 import functools
 import math
 import types
@@ -17,7 +16,7 @@ import torch
 
 import _octree_ndc_oracle as N
 import _octree_sg_cases as G
-import _octree_sg_oracle as S
+from _octree_cases import pose, random_tree
 from oracle import octree_oracle as T
 
 f32 = np.float32
@@ -74,38 +73,16 @@ def mode_args(mode, lr, **kw):
 
 
 # ---- cases ----------------------------------------------------------------------------------------------------------------
-def random_tree(depth, seed, K, p=0.15, center=(0.1, 0.0, -0.2), radius=(1.4, 1.5, 1.3)):
-    """tests/test_gpu_octree.py:_random_tree, value for value (the GPU test compares the two): random mask, random data,
-    about a third of the leaves empty (sigma <= 0)."""
-    reso = 2 ** (depth + 1)
-    mask = np.random.RandomState(seed).rand(reso, reso, reso) < p
-    t = T.build_from_mask(mask, depth, 3 * K + 1, center, radius)
-    rs = np.random.RandomState(seed + 100)
-    t.data[:] = (rs.randn(*t.data.shape) * 0.7).astype(f32)
-    t.data[..., -1] = ((rs.rand(*t.data.shape[:-1]) - 0.35) * 12.0).astype(f32)
-    return t
-
-
-def _pose(theta, phi, radius=4.0):
-    from plenoctree_amd.nerf_sh.nerf.datasets import pose_spherical
-    return np.asarray(pose_spherical(theta, phi, radius), f32)
-
-
-def _camera_rays(c2w, W, H, fx):
-    """(origins, unit directions) [H*W,3] of T.cam2world_ray, row-major, as test_octree_render_gradient_matches_oracle."""
-    rays = [T.cam2world_ray(ix, iy, c2w, W, H, fx, fx) for iy in range(H) for ix in range(W)]
-    return np.stack([r[0] for r in rays]).astype(f32), np.stack([r[1] for r in rays]).astype(f32)
-
-
 class Case:
-    """tree: the oracle tree (its .data is the start); lobes / ndc: None or what the SG / NDC oracle takes; poses, gt, rays per
-    split ("train", "val", "val_mid", "val_back"): c2w [n,3 or 4,4] float32, float32 [H,W,3] images, (origins, dirs) per view."""
+    """tree: the oracle tree (its .data is the start); lobes / ndc: None or what the oracle takes for an SG tree / an NDC scene;
+    poses, gt, rays, marches per split ("train", "val", "val_mid", "val_back"): c2w [n,3 or 4,4] float32, float32 [H,W,3]
+    images, (origins, dirs) per view, and per view the oracle's march of every ray."""
 
     def __init__(self, name, family, tree, W, H, fx, lobes=None, ndc=None):
         self.name, self.family, self.tree, self.W, self.H, self.fx, self.lobes, self.ndc = name, family, tree, W, H, fx, lobes, ndc
         self.opt = T.RenderOptions(1e-3)
         self.data0 = tree.data.copy()
-        self.poses, self.gt, self.rays = {}, {}, {}
+        self.poses, self.gt, self.rays, self.marches = {}, {}, {}, {}
 
     @property
     def n(self):
@@ -115,50 +92,19 @@ class Case:
         """Views whose ground truth is the float64 render of the tree holding `target`, rounded to float32."""
         rays_of = rays_of or split
         if rays_of not in self.rays:
-            self.rays[rays_of] = [_camera_rays(c, self.W, self.H, self.fx) for c in poses]
-        self.poses[split], self.rays[split] = np.stack(poses).astype(f32), self.rays[rays_of]
+            self.rays[rays_of] = [T.camera_rays(c, self.W, self.H, self.fx) for c in poses]
+            self.marches[rays_of] = [[T.march(self.tree, o, d, self.opt.step_size, ndc=self.ndc) for o, d in zip(*rays)]
+                                     for rays in self.rays[rays_of]]
+        self.poses[split], self.rays[split], self.marches[split] = np.stack(poses).astype(f32), self.rays[rays_of], self.marches[rays_of]
         with torch.no_grad():
             d = torch.from_numpy(target.astype(np.float64))
             self.gt[split] = [render(self, d, split, j, torch.float64).clamp(0.0, 1.0).float().numpy() for j in range(len(poses))]
 
 
-@functools.lru_cache(maxsize=None)
-def _march_of(tree_id, o, d, step):
-    tree, opt = _march_of.trees[tree_id], T.RenderOptions(step)
-    return _march_of.plain(tree, np.frombuffer(o, f32), np.frombuffer(d, f32), opt)
-
-
-_march_of.trees = {}
-_march_of.plain = T.march_tree
-
-
-@contextlib.contextmanager
-def _marches_reused():
-    """While active, T.march_tree answers a ray it has marched before (same tree object, origin, direction, step size, no
-    thresholds) from a table.  The sequence is a function of exactly these, so the renders are unchanged."""
-    def march(tree, origin, direction, opt):
-        if opt.sigma_thresh != 0.0 or opt.stop_thresh != 0.0:
-            return _march_of.plain(tree, origin, direction, opt)
-        _march_of.trees[id(tree)] = tree
-        return _march_of(id(tree), np.asarray(origin, f32).tobytes(), np.asarray(direction, f32).tobytes(), float(opt.step_size))
-    before = T.march_tree
-    T.march_tree = march
-    try:
-        yield
-    finally:
-        T.march_tree = before
-
-
 def render(case, data, split, j, dtype):
     """[H,W,3] image of view j of a split from `data` (a torch tensor shaped like tree.data), composited in dtype."""
     o, d = case.rays[split][j]
-    with _marches_reused():
-        if case.lobes is not None:
-            out = S.render_rays_torch(case.tree, case.lobes, data, o, d, d, case.opt, dtype=dtype)
-        elif case.ndc is not None:
-            out = N.render_rays_torch(case.tree, data, o, d, d, case.opt, case.ndc, dtype=dtype)
-        else:
-            out = T.render_rays_torch(case.tree, data, o, d, d, case.opt, dtype=dtype)
+    out = T.render_rays_torch(case.tree, data, o, d, d, case.opt, dtype=dtype, lobes=case.lobes, marches=case.marches[split][j])
     return out.reshape(case.H, case.W, 3)
 
 
@@ -188,16 +134,16 @@ def case(name):
             _plant_sigma(t)
         c = Case(name, "sg" if name == "sg4" else "sh", t, 12, 9, 11.0, lobes=G.lobes(4) if name == "sg4" else None)
         target = _target(t, seed + 200)
-        c.add_views("train", [_pose(*a) for a in TRAIN_POSES], target)
+        c.add_views("train", [pose(*a) for a in TRAIN_POSES], target)
         if name == "sh4":
-            val = [_pose(*a) for a in VAL_POSES]
+            val = [pose(*a) for a in VAL_POSES]
             d0 = t.data.astype(np.float64)
             c.add_views("val", val, target)
             c.add_views("val_mid", val, d0 + VAL_MID * (target - d0), rays_of="val")
             c.add_views("val_back", val, d0 + VAL_BACK * (target - d0), rays_of="val")
         return c
     if name == "ndc":
-        t = N.random_tree(4, 1)
+        t = N.box_tree(4, 1)
         c = Case(name, "ndc", t, N.W, N.H, N.FX, ndc=N.Ndc())
         c.add_views("train", [N.camera_a(), N.camera_b()], _target(t, 300))
         return c
@@ -245,42 +191,38 @@ def _loss_backward_one_sweep(c, p, split, j):
     K = (D - 1) // 3
     flat = p.detach().numpy().reshape(-1, D)
     grad = np.zeros_like(flat)
-    o, d = c.rays[split][j]
+    _, d = c.rays[split][j]
     gt = c.gt[split][j].reshape(-1, 3)
     scale = f32(f32(2.0) / f32(c.n))
     one, bg = f32(1.0), f32(c.opt.background_brightness)
     sse = f32(0.0)
-    with _marches_reused():
-        for r in range(len(o)):
-            ro, rd, hit = (o[r], d[r], True) if c.ndc is None else N.ndc_ray(o[r], d[r], c.ndc)
-            with np.errstate(over="ignore"):
-                samples = T.march_tree(t, ro, rd, c.opt) if hit else None
-            basis = S.sg_basis_np(c.lobes, d[r]) if c.lobes is not None else T.sh_basis_np(K, d[r])
-            live = []
-            out, light = np.zeros(3, f32), one
-            for leaf, dtw in samples or []:
-                val = flat[leaf]
-                if val[-1] > 0:
-                    att = f32(np.exp(f32(-dtw * val[-1]), dtype=f32))
-                    weight = f32(light * f32(one - att))
-                    col = (one / (one + np.exp(-(val[:-1].reshape(3, K) * basis).sum(-1, dtype=f32), dtype=f32))).astype(f32)
-                    out = (out + weight * col).astype(f32)
-                    light = f32(light * att)
-                    live.append((leaf, dtw, att, weight, col))
-            out = (out + f32(light * bg)).astype(f32)
-            clamped = np.clip(out, f32(0.0), one)
-            e = (clamped - gt[r]).astype(f32)
-            sse = f32(sse + f32(f32(f32(e[0] * e[0]) + f32(e[1] * e[1])) + f32(e[2] * e[2])))
-            g = np.where((out >= 0) & (out <= 1), scale * e, f32(0.0)).astype(f32)
-            accum = f32(f32(f32(g[0] * out[0]) + f32(g[1] * out[1])) + f32(g[2] * out[2]))
-            light = one
-            for leaf, dtw, att, weight, col in live:
-                total = f32(f32(f32(g[0] * col[0]) + f32(g[1] * col[1])) + f32(g[2] * col[2]))
-                dcol = (weight * g * col * (one - col)).astype(f32)
-                grad[leaf, :-1] += (dcol[:, None] * basis[None, :]).astype(f32).reshape(-1)
+    for r, m in enumerate(c.marches[split][j]):
+        basis = T.view_basis(t, d[r], c.lobes)
+        live = []
+        out, light = np.zeros(3, f32), one
+        for leaf, dtw in (() if m is None else zip(m.flat.tolist(), m.dtw)):
+            val = flat[leaf]
+            if val[-1] > 0:
+                att = f32(np.exp(f32(-dtw * val[-1]), dtype=f32))
+                weight = f32(light * f32(one - att))
+                col = (one / (one + np.exp(-(val[:-1].reshape(3, K) * basis).sum(-1, dtype=f32), dtype=f32))).astype(f32)
+                out = (out + weight * col).astype(f32)
                 light = f32(light * att)
-                accum = f32(accum - f32(weight * total))
-                grad[leaf, -1] += f32(dtw * f32(f32(total * light) - accum))
+                live.append((leaf, dtw, att, weight, col))
+        out = (out + f32(light * bg)).astype(f32)
+        clamped = np.clip(out, f32(0.0), one)
+        e = (clamped - gt[r]).astype(f32)
+        sse = f32(sse + f32(f32(f32(e[0] * e[0]) + f32(e[1] * e[1])) + f32(e[2] * e[2])))
+        g = np.where((out >= 0) & (out <= 1), scale * e, f32(0.0)).astype(f32)
+        accum = f32(f32(f32(g[0] * out[0]) + f32(g[1] * out[1])) + f32(g[2] * out[2]))
+        light = one
+        for leaf, dtw, att, weight, col in live:
+            total = f32(f32(f32(g[0] * col[0]) + f32(g[1] * col[1])) + f32(g[2] * col[2]))
+            dcol = (weight * g * col * (one - col)).astype(f32)
+            grad[leaf, :-1] += (dcol[:, None] * basis[None, :]).astype(f32).reshape(-1)
+            light = f32(light * att)
+            accum = f32(accum - f32(weight * total))
+            grad[leaf, -1] += f32(dtw * f32(f32(total * light) - accum))
     g_new = torch.from_numpy(grad.reshape(p.shape))
     p.grad = g_new if p.grad is None else p.grad + g_new
     return float(sse)

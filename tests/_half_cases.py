@@ -15,7 +15,6 @@ import numpy as np
 import _octree_aux_cases as A
 import _octree_cases as C
 import _octree_sg_cases as G
-import _octree_sg_oracle as S
 from oracle import octree_oracle as T
 
 f32, f16 = np.float32, np.float16
@@ -91,15 +90,13 @@ def rays(K):
 
 @functools.lru_cache(maxsize=None)
 def want(kind, K, fast):
-    """(image [H,W,3], rays [50,3]) of the oracle on the widened data; kind "SH" (oracle/octree_oracle.py) or "SG"
-    (tests/_octree_sg_oracle.py with the fixture's lobes)."""
+    """(image [H,W,3], rays [50,3]) of the oracle on the widened data; kind "SH" or "SG" (oracle/octree_oracle.py with the
+    fixture's lobes)."""
     t, opt = sg_tree(K), options(fast)
     o, d, v, _ = rays(K)
-    if kind == "SG":
-        img = S.render_persp(t, G.lobes(K), VIEW["c2w"], VIEW["W"], VIEW["H"], VIEW["fx"], opt, VIEW["fy"], dtype=f32)
-        return img, S.render_rays(t, G.lobes(K), o, d, v, opt, dtype=f32)
-    img = T.render_persp(t, VIEW["c2w"], VIEW["W"], VIEW["H"], VIEW["fx"], opt, VIEW["fy"])
-    return img, np.stack([T.render_ray(t, oo, dd, vv, opt) for oo, dd, vv in zip(o, d, v)])
+    lobes = G.lobes(K) if kind == "SG" else None
+    img = T.render_persp(t, VIEW["c2w"], VIEW["W"], VIEW["H"], VIEW["fx"], opt, VIEW["fy"], lobes=lobes)
+    return img, T.render_rays(t, o, d, v, opt, lobes=lobes)
 
 
 # ---- aux: the _octree_aux_cases configurations --------------------------------------------------------------------------

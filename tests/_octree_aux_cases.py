@@ -1,12 +1,13 @@
 """The cases of tests/test_octree_aux_cpu.py and tests/test_gpu_octree_aux.py: the shapes of
 tests/test_gpu_octree.py::test_octree_render_matches_oracle (depth-3 trees with a third of their leaves empty, a 14 x 10
 camera at radius 4, 25 explicit rays with origins inside the volume and one ray that misses), with the references of
-tests/_octree_aux_oracle.py computed once per case and shared."""
+oracle/octree_oracle.py (through tests/_octree_aux_oracle.py) computed once per case and shared."""
 import functools
 
 import numpy as np
 
 import _octree_aux_oracle as A
+from _octree_cases import pose, random_tree
 from oracle import octree_oracle as T
 
 f32 = np.float32
@@ -17,24 +18,7 @@ SURFACE_THRESH = 0.5
 CONFIGS = {"exact": ((20.0, 30.0), 1e-3, 1.0, False), "fast": ((250.0, -5.0), 1e-3, 1.0, True), "rays": (None, 2e-3, 0.5, False)}
 
 
-def pose(theta, phi, radius=4.0):
-    from plenoctree_amd.nerf_sh.nerf.datasets import pose_spherical
-    return pose_spherical(theta, phi, radius)
-
-
 @functools.lru_cache(maxsize=None)
-def random_tree(depth, seed, K, p=0.15, center=(0.1, 0.0, -0.2), radius=(1.4, 1.5, 1.3)):
-    """Local copy of tests/test_gpu_octree.py `_random_tree`: oracle tree with random SH data, about a third of the leaves
-    empty (sigma <= 0)."""
-    reso = 2 ** (depth + 1)
-    mask = np.random.RandomState(seed).rand(reso, reso, reso) < p
-    t = T.build_from_mask(mask, depth, 3 * K + 1, center, radius)
-    rs = np.random.RandomState(seed + 100)
-    t.data[:] = (rs.randn(*t.data.shape) * 0.7).astype(f32)
-    t.data[..., -1] = ((rs.rand(*t.data.shape[:-1]) - 0.35) * 12.0).astype(f32)
-    return t
-
-
 def tree(K):
     return random_tree(3, 10 + K, K)
 

@@ -9,7 +9,6 @@ import os
 import numpy as np
 
 import _octree_cases as C
-import _octree_sg_oracle as S
 from oracle import octree_oracle as T
 
 f32 = np.float32
@@ -67,14 +66,14 @@ def ray_batch(K):
 
 @functools.lru_cache(maxsize=None)
 def want_image(K, fast, dtype="f32"):
-    return S.render_persp(tree(K), lobes(K), VIEW["c2w"], VIEW["W"], VIEW["H"], VIEW["fx"], options(fast), VIEW["fy"],
+    return T.render_persp(tree(K), VIEW["c2w"], VIEW["W"], VIEW["H"], VIEW["fx"], options(fast), VIEW["fy"], lobes=lobes(K),
                           dtype=f32 if dtype == "f32" else np.float64)
 
 
 @functools.lru_cache(maxsize=None)
 def want_rays(K, fast, dtype="f32"):
     o, d, v = ray_batch(K)
-    return S.render_rays(tree(K), lobes(K), o, d, v, options(fast), dtype=f32 if dtype == "f32" else np.float64)
+    return T.render_rays(tree(K), o, d, v, options(fast), lobes=lobes(K), dtype=f32 if dtype == "f32" else np.float64)
 
 
 @functools.lru_cache(maxsize=None)
@@ -85,5 +84,8 @@ def sh_image(K):
 
 @functools.lru_cache(maxsize=None)
 def view_alphas(K):
-    o, d = S.camera_rays(VIEW["c2w"], VIEW["W"], VIEW["H"], VIEW["fx"], VIEW["fy"])
-    return np.array([S.ray_alpha(tree(K), oo, dd, options(False)) for oo, dd in zip(o, d)])
+    """Accumulated opacity 1 - light of every ray of the view (float64 over march's samples, no early stop); 0 for a miss."""
+    t, opt = tree(K), options(False)
+    rows = t.data.reshape(-1, t.data_dim)
+    o, d = T.camera_rays(**VIEW)
+    return np.array([1.0 - T.composite(rows, T.march(t, oo, dd, opt.step_size), None, opt, np.float64).light for oo, dd in zip(o, d)])

@@ -1,9 +1,8 @@
 """Test-side oracle of the per-leaf weight accumulation (pxo_octree_weight_accum_*) and of the structural collapse
-(pxo_tree_collapse_*): numpy only, built on oracle/octree_oracle.py's march_tree and tests/_octree_ndc_oracle.py's conversion.
+(pxo_tree_collapse_*): numpy only, built on oracle/octree_oracle.py's march and composite.
 
-Weights.  march_tree gives a ray's (leaf, dtw) sequence; over it the compositing weight of every shaded sample is restated
-twice: in float32 with the operation order of oracle.render_ray (att = exp(-dtw sigma), w = light (1 - att), light *= att,
-stop once light <= stop_thresh), and in float64 over the SAME sample sequence (the float32 restatement decides where an
+Weights.  A ray's compositing weights are composite's, taken twice: in float32 (the operation order of oracle.render_ray,
+stop once light <= stop_thresh), and in float64 over the SAME samples (the float32 compositing decides where an
 early-stopped ray ends, so that both see the same samples).  Per leaf: max and sum of either, and the sample count.
 
 Collapse.  A recursion on the definition (include/plenoctree_octree.h): dead(node) = every cell is a leaf with keep == 0 or
@@ -21,7 +20,7 @@ f32 = np.float32
 
 
 class LeafWeights:
-    """Per flat cell index: max32 / sum32 (float32 restatement), max64 / sum64 (float64), count (shaded samples); floor = the
+    """Per flat cell index: max32 / sum32 (float32 compositing), max64 / sum64 (float64), count (shaded samples); floor = the
     largest |float32 - float64| of a single sample's weight."""
 
     def __init__(self, cells):
@@ -30,41 +29,33 @@ class LeafWeights:
         self.count = np.zeros(cells, np.int64)
         self.floor = 0.0
 
-    def add_ray(self, flat_sigma, samples, opt):
-        light32, light64 = f32(1.0), 1.0
-        for leaf, dtw in samples or ():
-            sigma = flat_sigma[leaf]
-            if not sigma > opt.sigma_thresh:
-                continue
-            att32 = f32(np.exp(f32(-dtw * sigma), dtype=f32))
-            w32 = f32(light32 * f32(f32(1.0) - att32))
-            att64 = np.exp(-float(dtw) * float(sigma))
-            w64 = light64 * (1.0 - att64)
-            self.max32[leaf] = max(self.max32[leaf], w32)
-            self.sum32[leaf] = f32(self.sum32[leaf] + w32)
-            self.max64[leaf] = max(self.max64[leaf], w64)
-            self.sum64[leaf] += w64
-            self.count[leaf] += 1
-            self.floor = max(self.floor, abs(float(w32) - w64))
-            light32, light64 = f32(light32 * att32), light64 * att64
-            if light32 <= opt.stop_thresh:
-                break
+    def add_ray(self, rows, m, opt):
+        if m is None:
+            return
+        r32 = T.composite(rows, m, None, opt)
+        r64 = T.composite(rows, m, None, T.RenderOptions(opt.step_size, 1.0, opt.sigma_thresh, 0.0), np.float64)
+        leaf, w32, w64 = m.flat[r32.shaded], r32.weight[r32.shaded], r64.weight[r32.shaded]
+        if not len(leaf):
+            return
+        np.maximum.at(self.max32, leaf, w32)
+        np.add.at(self.sum32, leaf, w32)                 # unbuffered and in sample order: one float32 rounding per sample
+        np.maximum.at(self.max64, leaf, w64)
+        np.add.at(self.sum64, leaf, w64)
+        np.add.at(self.count, leaf, 1)
+        self.floor = max(self.floor, float(np.abs(w32.astype(np.float64) - w64).max()))
 
 
 def march_rays(tree, origins, dirs, step_size, ndc=None):
-    """The sample sequence of every ray (None for a miss); it depends on the step size only, not on the thresholds."""
-    opt = T.RenderOptions(step_size)
-    if ndc is None:
-        return [T.march_tree(tree, o, d, opt) for o, d in zip(np.asarray(origins, f32), np.asarray(dirs, f32))]
-    return [N.march(tree, o, d, opt, ndc) for o, d in zip(np.asarray(origins, f32), np.asarray(dirs, f32))]
+    """The March of every ray (None for a miss); it depends on the step size only, not on the thresholds."""
+    return [T.march(tree, o, d, step_size, ndc=ndc) for o, d in zip(np.asarray(origins, f32), np.asarray(dirs, f32))]
 
 
 def leaf_weights(tree, marches, opt):
-    """LeafWeights of the given per-ray sample sequences (march_rays) under the thresholds of `opt`."""
-    flat_sigma = tree.data.reshape(-1, tree.data_dim)[:, -1]
+    """LeafWeights of the given per-ray marches (march_rays) under the thresholds of `opt`."""
+    rows = tree.data.reshape(-1, tree.data_dim)
     lw = LeafWeights(tree.n_internal * 8)
-    for samples in marches:
-        lw.add_ray(flat_sigma, samples, opt)
+    for m in marches:
+        lw.add_ray(rows, m, opt)
     return lw
 
 
@@ -211,7 +202,7 @@ def ray_marches(name):
 @functools.lru_cache(maxsize=None)
 def camera_marches(name, cam):
     view = dict(c2w=camera(cam), W=CAM_W, H=CAM_H, fx=CAM_FX, fy=CAM_FY)
-    o, d = C.camera_rays(view)
+    o, d = T.camera_rays(**view)
     return tuple(march_rays(case_tree(name), o, d, TREES[name][3]))
 
 
@@ -232,13 +223,13 @@ NDC_K, NDC_BOX = 4, 1
 
 
 def ndc_tree():
-    return N.random_tree(NDC_K, NDC_BOX)
+    return N.box_tree(NDC_K, NDC_BOX)
 
 
 @functools.lru_cache(maxsize=None)
 def ndc_rays():
     """Camera B's rays, then five rays with d_z >= 0 (NDC misses) aimed at the tree's box from either side."""
-    o, d = N.camera_rays(N.camera_b())
+    o, d = T.camera_rays(N.camera_b(), N.W, N.H, N.FX)
     back_d = np.array([[0.0, 0.0, 1.0], [0.3, 0.1, 0.9], [0.6, -0.8, 0.0], [-0.2, 0.4, 0.5], [1.0, 0.0, 0.0]], np.float64)
     back_d = (back_d / np.linalg.norm(back_d, axis=1, keepdims=True)).astype(f32)
     back_o = (np.array(N.BOXES[NDC_BOX][0], f32) - 3.0 * back_d).astype(f32)
@@ -252,8 +243,8 @@ def ndc_case(mode):
     if mode == "rays":
         o, d = ndc_rays()
     else:
-        oa, da = N.camera_rays(N.camera_a())
-        ob, db = N.camera_rays(N.camera_b())
+        oa, da = T.camera_rays(N.camera_a(), N.W, N.H, N.FX)
+        ob, db = T.camera_rays(N.camera_b(), N.W, N.H, N.FX)
         o, d = np.concatenate([oa, ob]), np.concatenate([da, db])
     marches = march_rays(t, o, d, STEP, ndc)
     return leaf_weights(t, marches, opt), sum(m is None for m in marches)

@@ -1,5 +1,5 @@
 """The footprint render without a GPU: known answers of the cap, a hand-marched tree, the conditions the GPU fixtures must
-meet (asserted on the twin, tests/_footprint_oracle.py), every refusal that comes before a launch -- VolumeRenderer's by name,
+meet (asserted on the twin, oracle/octree_oracle.py's march with a footprint, and tests/_footprint_oracle.py's counts), every refusal that comes before a launch -- VolumeRenderer's by name,
 the entry points' own with pointers nothing reads -- and the flags of octree.evaluation."""
 import ctypes
 
@@ -17,19 +17,19 @@ PTR = 0x10000                                    # a 256-byte aligned address no
 
 # ---- the cap ---------------------------------------------------------------------------------------------------------------
 def test_cap_known_answers():
-    assert F.MAX_DEPTH == 10
-    assert F.cap_of(f32(2.0 ** -5)) == 4                                  # side 2^-(4+1) <= f
-    assert F.cap_of(np.nextafter(f32(2.0 ** -5), f32(0))) == 5            # the float just below: one level deeper
-    assert F.cap_of(f32(0.0)) == F.MAX_DEPTH and F.cap_of(f32(1e-40)) == F.MAX_DEPTH      # 0 and a denormal: no cap
+    assert T.MAX_DEPTH == 10
+    assert T.cap_of(f32(2.0 ** -5)) == 4                                  # side 2^-(4+1) <= f
+    assert T.cap_of(np.nextafter(f32(2.0 ** -5), f32(0))) == 5            # the float just below: one level deeper
+    assert T.cap_of(f32(0.0)) == T.MAX_DEPTH and T.cap_of(f32(1e-40)) == T.MAX_DEPTH      # 0 and a denormal: no cap
     assert f32(1e-40) > 0 and f32(1e-40) < np.finfo(f32).tiny
-    assert F.cap_of(f32(0.5)) == 0 and F.cap_of(f32(1e30)) == 0 and F.cap_of(f32(np.inf)) == 0
-    assert F.cap_of(np.nextafter(f32(0.5), f32(0))) == 1
-    for d in range(F.MAX_DEPTH + 1):                                      # every cell side, and the float below it
+    assert T.cap_of(f32(0.5)) == 0 and T.cap_of(f32(1e30)) == 0 and T.cap_of(f32(np.inf)) == 0
+    assert T.cap_of(np.nextafter(f32(0.5), f32(0))) == 1
+    for d in range(T.MAX_DEPTH + 1):                                      # every cell side, and the float below it
         side = f32(2.0 ** -(d + 1))
-        assert F.cap_of(side) == d and F.cap_of(np.nextafter(side, f32(0))) == min(d + 1, F.MAX_DEPTH)
+        assert T.cap_of(side) == d and T.cap_of(np.nextafter(side, f32(0))) == min(d + 1, T.MAX_DEPTH)
     # the clamp from below
-    assert F.cap_of(f32(0.5), min_depth=3) == 3 and F.cap_of(f32(2.0 ** -5), min_depth=3) == 4
-    assert F.cap_of(f32(0.0), min_depth=F.MAX_DEPTH) == F.MAX_DEPTH and F.cap_of(f32(np.inf), min_depth=F.MAX_DEPTH) == F.MAX_DEPTH
+    assert T.cap_of(f32(0.5), min_depth=3) == 3 and T.cap_of(f32(2.0 ** -5), min_depth=3) == 4
+    assert T.cap_of(f32(0.0), min_depth=T.MAX_DEPTH) == T.MAX_DEPTH and T.cap_of(f32(np.inf), min_depth=T.MAX_DEPTH) == T.MAX_DEPTH
 
 
 # ---- a tree of three levels, one axis-parallel ray, by hand -----------------------------------------------------------------
@@ -56,37 +56,38 @@ def test_hand_marched_ray():
     t = _hand_tree()
     o, d = np.array([-7.5, 1 / 32, 1 / 32], f32), np.array([1.0, 0.0, 0.0], f32)
     step = 2.0 ** -10
-    samples, delta_scale = F.march(t.child, t.offset, t.invradius, o, d, step, cone=2.0 ** -4)
-    assert delta_scale == 1.0
-    assert [s.flat for s in samples] == [8, 12, 4]
-    assert [float(s.t) for s in samples] == [7.5, 7.7509765625, 8.0009765625]
-    assert [float(s.delta) for s in samples] == [0.2509765625, 0.25, 0.5]
-    assert [float(s.dtw) for s in samples] == [0.2509765625, 0.25, 0.5]
-    assert [s.depth for s in samples] == [1, 1, 0] and [s.cap for s in samples] == [1, 1, 0]
-    assert [s.has_child for s in samples] == [True, False, True]
-    assert F.reuse_counts((samples, delta_scale)) == (3, 2, 0, True)
+    tree, foot = (t.child, t.offset, t.invradius), lambda cone, min_depth=0: (cone, min_depth)
+    m = T.march(tree, o, d, step, foot=foot(2.0 ** -4))
+    assert m.delta_scale == 1.0 and not m.guard
+    assert m.flat.tolist() == [8, 12, 4]
+    assert m.t.tolist() == [7.5, 7.7509765625, 8.0009765625]
+    assert m.delta.tolist() == [0.2509765625, 0.25, 0.5]
+    assert m.dtw.tolist() == [0.2509765625, 0.25, 0.5]
+    assert m.depth.tolist() == [1, 1, 0] and m.cap.tolist() == [1, 1, 0]
+    assert m.has_child.tolist() == [True, False, True]
+    assert F.reuse_counts(m) == (3, 2, 0, True)
     # no cone: the plain march of the oracle, down to the depth-2 cells of node 3 (flat 24 .., side 1/8)
-    plain, _ = F.march(t.child, t.offset, t.invradius, o, d, step, cone=0.0)
+    plain = T.march(tree, o, d, step, foot=foot(0.0))
     want = T.march_tree(t, o, d, T.RenderOptions(step))
-    assert [(s.flat, s.dtw) for s in plain] == want and [s.flat for s in plain][:2] == [24, 28]
-    assert [float(s.delta) for s in plain][:2] == [0.1259765625, 0.125]
-    assert not any(s.has_child for s in plain) and {s.cap for s in plain} == {F.MAX_DEPTH}
+    assert list(zip(plain.flat.tolist(), plain.dtw)) == want and plain.flat.tolist()[:2] == [24, 28]
+    assert plain.delta.tolist()[:2] == [0.1259765625, 0.125]
+    assert not plain.has_child.any() and set(plain.cap.tolist()) == {T.MAX_DEPTH}
     # min_depth holds the cap up: at 2 the ray is the plain one, at 1 only the last sample differs from cone 2^-4
-    held, _ = F.march(t.child, t.offset, t.invradius, o, d, step, cone=2.0 ** -4, min_depth=2)
-    assert [(s.flat, s.delta) for s in held] == [(s.flat, s.delta) for s in plain]
-    one, _ = F.march(t.child, t.offset, t.invradius, o, d, step, cone=2.0 ** -4, min_depth=1)
-    assert [s.flat for s in one][:2] == [8, 12] and one[2].flat == 2 * 8 + 0 and one[2].depth == 1
+    held = T.march(tree, o, d, step, foot=foot(2.0 ** -4, 2))
+    assert held.flat.tolist() == plain.flat.tolist() and held.delta.tolist() == plain.delta.tolist()
+    one = T.march(tree, o, d, step, foot=foot(2.0 ** -4, 1))
+    assert one.flat.tolist()[:2] == [8, 12] and one.flat[2] == 2 * 8 + 0 and one.depth[2] == 1
     # a huge cone is the constant cap min_depth
-    flat0, _ = F.march(t.child, t.offset, t.invradius, o, d, step, cone=1e9)
-    assert [s.flat for s in flat0] == [0, 4] and [float(s.delta) for s in flat0] == [0.5009765625, 0.5]
+    flat0 = T.march(tree, o, d, step, foot=foot(1e9))
+    assert flat0.flat.tolist() == [0, 4] and flat0.delta.tolist() == [0.5009765625, 0.5]
     # compositing: sigma chosen so that exp is exact (0), colour sigmoid(0) = 1/2 from the stopped cell's own row
     data = np.zeros((4 * 8, 4), f32)
     data[8, -1] = np.inf
     basis = T.sh_basis_np(1, d)
-    r = F.composite(data, (samples, delta_scale), basis, T.RenderOptions(step))
+    r = T.composite(data, m, basis, T.RenderOptions(step), surface_thresh=0.5)
     assert r.rgb.tolist() == [0.5, 0.5, 0.5] and r.alpha == 1.0 and r.pick == 0
     assert float(r.depth) == float(r.surface) == 7.5 + 0.5 * 0.2509765625
-    assert F.composite(data, None, basis, T.RenderOptions(step, 0.25)).rgb.tolist() == [0.25] * 3
+    assert T.composite(data, None, basis, T.RenderOptions(step, 0.25), surface_thresh=0.5).rgb.tolist() == [0.25] * 3
 
 
 # ---- the conditions of the GPU fixtures -------------------------------------------------------------------------------------
@@ -100,7 +101,7 @@ def test_fixture_conditions(family, depth):
     clamp case of the path reuse, rays whose cap changes.  The figures were worked out before the kernel ran."""
     t = LOD._case(family, depth, 1)
     o, d = LOD._rays()
-    marches = [F.march(t.child, t.offset, t.invradius, o[i], d[i], LOD.STEP, 0.1) for i in range(60)]
+    marches = [T.march((t.child, t.offset, t.invradius), o[i], d[i], LOD.STEP, foot=(0.1, 0)) for i in range(60)]
     c = F.case_counts(marches)
     print(family, depth, c)
     assert all(v > 0 for v in c.values()), c

@@ -4,7 +4,7 @@ in which EVERY row is random, so a sample that reads a row nothing filled, or a 
 
 What pins the kernel, in this order: a cap that never binds is the existing render bit for bit; a constant cap is the capped view
 of VolumeRenderer(max_depth=L) and the standalone tree.lod(L) bit for bit; a cap that varies along the rays is held to the numpy
-twin tests/_footprint_oracle.py, which descends from the root for every sample and so cannot share the kernel's path-reuse trap.
+twin (oracle/octree_oracle.py's march with a footprint), which descends from the root for every sample and so cannot share the kernel's path-reuse trap.
 The twin is given the DEVICE's filled rows, so the rounding of the fill plays no part.  Bounds of the third check (fixed before
 any GPU run): rgb rtol 0, atol 2e-5, what tests/test_gpu_octree.py holds the uncapped forward to, for the same reason -- the
 steps are identical, only exp, sigmoid and the order of the K-term sums differ; alpha atol 2e-5, depth atol 2e-5 s_max, surface
@@ -23,7 +23,6 @@ import torch
 
 import _footprint_oracle as F
 import _octree_cases as C
-import _octree_sg_oracle as SG
 import test_gpu_lod as LOD
 from _helpers import _gpu, close
 from oracle import octree_oracle as T
@@ -122,7 +121,7 @@ def test_constant_cap_is_the_capped_view(family, depth, K):
 # ---- 3: the varying cap against the twin -------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _ray_sets():
-    co, cd = C.camera_rays(VIEW)
+    co, cd = T.camera_rays(**VIEW)
     return {"rays": LOD._rays(), "persp": (co.astype(f32), cd.astype(f32))}
 
 
@@ -133,7 +132,7 @@ def _cone(which):
 
 def _march_all(child, offset, invradius, which, min_depth=0):
     o, d = _ray_sets()[which]
-    return [F.march(child, offset, invradius, o[i], d[i], STEP, _cone(which), min_depth) for i in range(o.shape[0])]
+    return [T.march((child, offset, invradius), o[i], d[i], STEP, foot=(_cone(which), min_depth)) for i in range(o.shape[0])]
 
 
 @functools.lru_cache(maxsize=None)
@@ -145,7 +144,7 @@ def _fixture_marches(family, depth, which):
 
 def _bases(which, K, lobes):
     _, d = _ray_sets()[which]
-    return [T.sh_basis_np(K, v) if lobes is None else SG.sg_basis_np(lobes, v) for v in d]
+    return [T.sh_basis_np(K, v) if lobes is None else T.sg_basis_np(lobes, v) for v in d]
 
 
 def _check_against_twin(name, got, data, marches_of, K, lobes, aux, min_surface=0):
@@ -156,7 +155,7 @@ def _check_against_twin(name, got, data, marches_of, K, lobes, aux, min_surface=
         assert all(v > 0 for v in counts.values()), f"{name} {which}: the case is empty somewhere: {counts}"
         bases = _bases(which, K, lobes)
         for fast in (False, True):
-            b32, b64 = F.render(data, marches, bases, T.RenderOptions.for_renderer(STEP, fast), SURFACE)
+            b32, b64 = T.composite_batches(data, marches, bases, T.RenderOptions.for_renderer(STEP, fast), SURFACE)
             what = f"{name} {which} fast={fast}"
             rgb = got[f"{which}.{fast}"].reshape(-1, 3)
             print(f"{what}: max |rgb - twin| {np.abs(rgb.cpu().numpy() - b32.rgb).max():.3g} (bound 2e-5), {counts}")
@@ -167,7 +166,7 @@ def _check_against_twin(name, got, data, marches_of, K, lobes, aux, min_surface=
             alpha, depth, surface = (got[f"{which}_aux.{fast}.{k}"].reshape(-1).cpu().numpy() for k in ("alpha", "depth", "surface"))
             close(f"{what} alpha", torch.from_numpy(alpha), torch.from_numpy(b32.aux[:, 0]), rtol=0, atol=2e-5)
             close(f"{what} depth", torch.from_numpy(depth), torch.from_numpy(b32.aux[:, 1]), rtol=0, atol=2e-5 * b32.s_max)
-            left_out = F.surface_excluded(b32, b64, SURFACE)
+            left_out = T.surface_excluded(b32, b64, SURFACE)
             assert left_out.mean() <= 0.02, what
             want = b32.aux[:, 2]
             inf = np.isinf(want)

@@ -128,13 +128,13 @@ def test_half_render_ndc(tmp_path):
     float tree bit for bit at every lane count and the composed NDC oracle on the widened data to 2e-5."""
     svox = _svox(); oops = _oops(); dev = _gpu()
     K = 16
-    t = N.random_tree(K, 1)
+    t = N.box_tree(K, 1)
     h, f = _load_both(tmp_path, t, f"SH{K}")
     w = H.widened(t)
     ndc = svox.NDCConfig(N.W, N.H, N.FX)
     rh, rf = svox.VolumeRenderer(h, step_size=1e-3, ndc=ndc), svox.VolumeRenderer(f, step_size=1e-3, ndc=ndc)
     c2w = torch.from_numpy(N.camera_b())
-    co, cd = N.camera_rays(N.camera_b())
+    co, cd = T.camera_rays(N.camera_b(), N.W, N.H, N.FX)
     rs = np.random.RandomState(5)
     cv = rs.randn(*cd.shape)
     cv = (cv / np.linalg.norm(cv, axis=1, keepdims=True)).astype(f32)
@@ -142,8 +142,8 @@ def test_half_render_ndc(tmp_path):
     try:
         for fast in (False, True):
             opt = T.RenderOptions.for_renderer(1e-3, fast)
-            want = torch.from_numpy(N.render_persp(w, N.camera_b(), opt, N.Ndc()))
-            want_r = torch.from_numpy(N.render_rays(w, co[50:87], cd[50:87], cv[:37], opt, N.Ndc()))
+            want = torch.from_numpy(T.render_persp(w, N.camera_b(), N.W, N.H, N.FX, opt, ndc=N.Ndc()))
+            want_r = torch.from_numpy(T.render_rays(w, co[50:87], cd[50:87], cv[:37], opt, ndc=N.Ndc()))
             bg = (want == 1.0).all(-1)
             assert float((want - 1.0).abs().max()) > 0.5 and bg.any()
             for lanes in H.LANES:

@@ -21,6 +21,7 @@ import _lod_oracle as L
 import _octree_cases as C
 import _octree_ndc_oracle as N
 from _helpers import _gpu
+from oracle import octree_oracle as T
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -223,10 +224,10 @@ def test_fill_widest_rows():
 def test_ndc_capped_view():
     """A tree in the NDC cube (tests/test_gpu_octree_ndc.py's set-up): render_persp and forward with ndc=..."""
     svox = _svox(); dev = _gpu()
-    tree = _svox_tree(N.random_tree(4, 1, depth=3, seed=77, p=0.2), dev)
+    tree = _svox_tree(N.box_tree(4, 1, depth=3, seed=77, p=0.2), dev)
     view = dict(c2w=N.camera_b(), W=N.W, H=N.H, fx=N.FX)
     _check_capped_equals_standalone("ndc", tree, dev, aux=False, ndc=svox.NDCConfig(N.W, N.H, N.FX), view=view,
-                                    rays=N.camera_rays(N.camera_b()))
+                                    rays=T.camera_rays(N.camera_b(), N.W, N.H, N.FX))
     _check_fill("ndc", tree)
 
 

@@ -1,5 +1,5 @@
 """The octree renderer's extra outputs on the device (pxo_octree_render_aux_fwd / pxo_octree_render_quant_aux_fwd: alpha, depth,
-surface distance) against the CPU restatement of their definitions, tests/_octree_aux_oracle.py.
+surface distance) against the CPU restatement of their definitions, oracle/octree_oracle.py's composite.
 
 Cases (tests/_octree_aux_cases.py): the shapes of test_gpu_octree.py::test_octree_render_matches_oracle -- depth-3 trees with a
 third of their leaves empty, a 14 x 10 camera (exact options and the early-stopping preset), 25 explicit rays with background
@@ -21,9 +21,9 @@ import pytest
 import torch
 
 import _octree_aux_cases as C
-import _octree_aux_oracle as A
 import _quant_cases as Q
 from _helpers import _gpu, close
+from oracle import octree_oracle as T
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -86,7 +86,7 @@ def _check_case(K, lanes, dev):
         else:
             assert not b32.stopped.any()
         # 2. surface distance
-        left_out = A.surface_excluded(b32, b64, C.SURFACE_THRESH)
+        left_out = T.surface_excluded(b32, b64, C.SURFACE_THRESH)
         assert left_out.mean() <= 0.02, what
         want = b32.aux[:, 2]
         inf = np.isinf(want)

@@ -1,6 +1,6 @@
 """GPU tests of the NDC launches of the octree side (pxo_octree_render_ndc_fwd / _bwd, pxo_grid_weight_render_ndc) against the
-composed oracle of tests/_octree_ndc_oracle.py: the reference's convert_to_ndc (pinned by tests/golden/octree_ndc.npz), then
-oracle/octree_oracle.py unchanged.  Bounds are those of the world-space tests in tests/test_gpu_octree.py: the march takes
+oracle's `ndc=` argument on the shapes of tests/_octree_ndc_oracle.py: the reference's convert_to_ndc (pinned by
+tests/golden/octree_ndc.npz), then the oracle's march unchanged.  Bounds are those of the world-space tests in tests/test_gpu_octree.py: the march takes
 identical steps, only exp / sigmoid and the summation order differ."""
 import os
 
@@ -41,11 +41,11 @@ def _want_image(K, box, cam, fast):
     """The oracle image of one of the shared views, computed once per session."""
     key = (K, box, cam, fast)
     if key not in _WANT:
-        t = N.random_tree(K, box)
+        t = N.box_tree(K, box)
         opt = T.RenderOptions.for_renderer(1e-3, fast)
-        o, d = N.camera_rays(N.CAMERAS[cam]())
-        hits = sum(N.march(t, oo, dd, opt, N.Ndc()) is not None for oo, dd in zip(o, d))
-        img = N.render_persp(t, N.CAMERAS[cam](), opt, N.Ndc())
+        o, d = T.camera_rays(N.CAMERAS[cam](), N.W, N.H, N.FX)
+        hits = sum(T.march(t, oo, dd, opt.step_size, ndc=N.Ndc()) is not None for oo, dd in zip(o, d))
+        img = T.render_persp(t, N.CAMERAS[cam](), N.W, N.H, N.FX, opt, ndc=N.Ndc())
         assert hits >= 20 and float(np.abs(img - 1.0).max()) > 0.5
         assert (hits == N.W * N.H) if (box, cam) == (0, "A") else (hits < N.W * N.H)         # misses are in the picture too
         _WANT[key] = (t, opt, img)
@@ -96,11 +96,11 @@ def test_ndc_forward_explicit_rays(B):
     finite); and the camera's own rays give the camera-mode image bit for bit."""
     oops = _oops(); dev = _gpu()
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    t = N.random_tree(16, 1)
+    t = N.box_tree(16, 1)
     view, keep = _device_tree(t, dev)
     opt = T.RenderOptions(2e-3, background_brightness=0.5)
     o, d = _frustum_rays(B, 7)
-    want = N.render_rays(t, o, d, d, opt, N.Ndc())
+    want = T.render_rays(t, o, d, d, opt, ndc=N.Ndc())
     got = oops.octree_render_rays(view, to(o), to(d), to(d), _dopts(opt), ndc=N.Ndc())
     close(f"NDC rays B={B}", got, torch.from_numpy(want), rtol=0, atol=2e-5)
     if B > 1:
@@ -112,11 +112,11 @@ def test_ndc_forward_explicit_rays(B):
         got2 = oops.octree_render_rays(view, to(o2), to(d2), to(d2), _dopts(opt), ndc=N.Ndc())
         assert bool(torch.isfinite(got2).all()) and torch.equal(got2[-2:].cpu(), torch.full((2, 3), 0.5))
         assert torch.equal(got2[:-2], got[:-2])
-        want2 = N.render_rays(t, o2[-2:], d2[-2:], d2[-2:], opt, N.Ndc())
+        want2 = T.render_rays(t, o2[-2:], d2[-2:], d2[-2:], opt, ndc=N.Ndc())
         assert np.array_equal(want2, np.full((2, 3), 0.5, f32))
     if B == 65:
         for cam in "AB":
-            co, cd = N.camera_rays(N.CAMERAS[cam]())
+            co, cd = T.camera_rays(N.CAMERAS[cam](), N.W, N.H, N.FX)
             img = oops.octree_render_persp(view, to(N.CAMERAS[cam]()), N.W, N.H, N.FX, _dopts(opt), ndc=N.Ndc())
             rays = oops.octree_render_rays(view, to(co), to(cd), to(cd), _dopts(opt), ndc=N.Ndc())
             assert torch.equal(rays.reshape(N.H, N.W, 3), img), cam
@@ -147,14 +147,14 @@ def _want_grad(K):
     """float64 autograd through render_rays_torch over the NDC sample sequence of camera B's rays (hits and misses) on a
     depth-2 tree in the off-centre box; once per K."""
     if K not in _WANT_GRAD:
-        t = N.random_tree(K, 1, depth=2, seed=30 + K, p=0.3)
-        o, d = N.camera_rays(N.camera_b())
+        t = N.box_tree(K, 1, depth=2, seed=30 + K, p=0.3)
+        o, d = T.camera_rays(N.camera_b(), N.W, N.H, N.FX)
         g = np.random.RandomState(K + 1).randn(o.shape[0], 3).astype(f32)
         opt = T.RenderOptions(1e-3)
         dd = torch.tensor(t.data.astype(np.float64), requires_grad=True)
-        out = N.render_rays_torch(t, dd, o, d, d, opt, N.Ndc())
+        out = T.render_rays_torch(t, dd, o, d, d, opt, ndc=N.Ndc())
         (out * torch.from_numpy(g.astype(np.float64))).sum().backward()
-        hit = np.array([N.march(t, oo, dd_, opt, N.Ndc()) is not None for oo, dd_ in zip(o, d)])
+        hit = np.array([T.march(t, oo, dd_, opt.step_size, ndc=N.Ndc()) is not None for oo, dd_ in zip(o, d)])
         assert 20 <= hit.sum() < hit.size
         _WANT_GRAD[K] = (t, o, d, g, opt, dd.grad.float(), out.detach(), hit)
     return _WANT_GRAD[K]
@@ -234,7 +234,7 @@ def test_ndc_grid_weight_render_matches_oracle(reso):
     opt = T.RenderOptions(step_size=1e-3)
     want = np.zeros_like(sigma)
     for c in cams:
-        N.grid_weight_render(sigma, c, W, H, fx, opt, t.offset, t.invradius, ndc, weight=want)
+        T.grid_weight_render(sigma, c, W, H, fx, opt, t.offset, t.invradius, weight=want, ndc=ndc)
     sig_d, cams_d = torch.from_numpy(sigma).to(dev), torch.from_numpy(cams).to(dev)
     call = lambda c=cams_d, acc=None: oops.grid_weight_render(sig_d, reso, c, fx, fx, W, H, oops.render_opts(1e-3), t.offset,
                                                               t.invradius, grid_weight=acc, ndc=ndc)
@@ -281,7 +281,7 @@ def test_world_space_launches_are_untouched_by_an_ndc_call():
     bit-equal.  The gradient view is 4 x 4 pixels -- one wave, whose atomics execute in program order -- so that bit equality
     is a property of the code and not of the order in which waves happen to run."""
     oops = _oops(); dev = _gpu()
-    t = N.random_tree(16, 1)
+    t = N.box_tree(16, 1)
     view, (child, data) = _device_tree(t, dev)
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     from plenoctree_amd.nerf_sh.nerf.datasets import pose_spherical

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import _quant_cases as Q
+from _octree_cases import pose as _pose
 from oracle import octree_oracle as T
 from _helpers import _gpu, close
 
@@ -28,11 +29,6 @@ W, H, FX, STEP = 13, 9, 12.0, 1e-3
 LANES = (4, 8, 16)
 # (theta, phi) of the camera per `fast`
 POSES = {False: (20.0, 30.0), True: (250.0, -5.0)}
-
-
-def _pose(theta, phi, radius=4.0):
-    from plenoctree_amd.nerf_sh.nerf.datasets import pose_spherical
-    return pose_spherical(theta, phi, radius)
 
 
 def _svox():

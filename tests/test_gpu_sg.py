@@ -1,5 +1,5 @@
-"""GPU tests of the spherical-Gaussian (SG) chain: pxo_octree_render_sg_fwd / _bwd against the CPU helper
-tests/_octree_sg_oracle.py, pxo_sg_render_fwd against the fixture-pinned eval_sg restatement over the kernel's own samples, and
+"""GPU tests of the spherical-Gaussian (SG) chain: pxo_octree_render_sg_fwd / _bwd against oracle/octree_oracle.py with the
+fixture's lobes, pxo_sg_render_fwd against the fixture-pinned eval_sg restatement over the kernel's own samples, and
 checkpoint -> octree.extraction -> octree.evaluation -> octree.optimization end to end.
 
 Bounds are those of the corresponding SH tests, taken over unchanged: colours atol 2e-5 (tests/test_gpu_octree.py: the march
@@ -14,7 +14,6 @@ import pytest
 import torch
 
 import _octree_sg_cases as G
-import _octree_sg_oracle as S
 from oracle import nerf_oracle as O
 from oracle import octree_oracle as T
 from _helpers import _gpu, _psnr, close, make_params
@@ -107,12 +106,12 @@ def test_sg_octree_gradient_matches_float64_autograd(K, lanes_reset):
     rs = np.random.RandomState(70 + K)
     o, d, v = G.ray_batch(K)
     V = G.VIEW
-    co, cd = S.camera_rays(V["c2w"], V["W"], V["H"], V["fx"], V["fy"])
+    co, cd = T.camera_rays(**V)
     cases = {"rays": (o, d, v, rs.randn(len(o), 3).astype(f32)), "view": (co, cd, cd, rs.randn(len(co), 3).astype(f32))}
     want = {}
     for name, (oo, dd, vv, g) in cases.items():
         x = torch.tensor(t.data.astype(np.float64), requires_grad=True)
-        out = S.render_rays_torch(t, G.lobes(K), x, oo, dd, vv, opt)
+        out = T.render_rays_torch(t, x, oo, dd, vv, opt, lobes=G.lobes(K))
         (out * torch.from_numpy(g.astype(np.float64))).sum().backward()
         want[name] = x.grad.float()
         assert float(want[name].abs().max()) > 1e-3
@@ -171,8 +170,8 @@ def test_sg_tree_renders_and_backpropagates_through_the_svox_mirror():
     loss = ((r.render_persp(c2w, width=V["W"], height=V["H"], fx=V["fx"], fast=False) - gt) ** 2).mean()
     loss.backward()
     x = torch.tensor(t.data.astype(np.float64), requires_grad=True)
-    co, cd = S.camera_rays(V["c2w"], V["W"], V["H"], V["fx"], V["fy"])
-    ref = ((S.render_rays_torch(t, G.lobes(K), x, co, cd, cd, G.options(False)).reshape(V["H"], V["W"], 3) - gt.cpu().double()) ** 2).mean()
+    co, cd = T.camera_rays(**V)
+    ref = ((T.render_rays_torch(t, x, co, cd, cd, G.options(False), lobes=G.lobes(K)).reshape(V["H"], V["W"], 3) - gt.cpu().double()) ** 2).mean()
     ref.backward()
     assert abs(float(loss) - float(ref)) < 1e-6
     close("svox SG grad", host.data.grad, x.grad.float(), rtol=2e-3, atol=2e-6 * float(x.grad.abs().max()) + 1e-9)
@@ -183,10 +182,10 @@ def test_sg_tree_renders_and_backpropagates_through_the_svox_mirror():
 
 # ---- NeRF-SG ray rendering ------------------------------------------------------------------------------------------
 def _sg_shade_f64(raw_rgb, raw_sigma, lobes, viewdirs, z, dirs, white):
-    """eval_sg (the fixture-pinned restatement S.sg_basis_f64) -> sigmoid / relu -> oracle volumetric rendering, float64."""
+    """eval_sg (the fixture-pinned restatement T.sg_basis_f64) -> sigmoid / relu -> oracle volumetric rendering, float64."""
     B, Sn = z.shape
     K = lobes.shape[0]
-    basis = torch.from_numpy(S.sg_basis_f64(lobes, viewdirs.numpy()))                       # [B,K]
+    basis = torch.from_numpy(T.sg_basis_f64(lobes, viewdirs.numpy()))                       # [B,K]
     pre = (raw_rgb.double().reshape(B, Sn, 3, K) * basis[:, None, None, :]).sum(-1)
     return O.volumetric_rendering(torch.sigmoid(pre), torch.relu(raw_sigma.double().reshape(B, Sn, 1)), z.double(), dirs.double(), white)
 

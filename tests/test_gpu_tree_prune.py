@@ -423,7 +423,7 @@ def test_accumulate_weights_on_the_differentiable_path():
         outs.append((im.detach(), tree.data.grad.clone()))
     assert torch.equal(outs[0][0], outs[1][0])
     close("gradient with the accumulator active", outs[1][1], outs[0][1], rtol=1e-5, atol=1e-7)      # atomics: order only
-    o, d = C.camera_rays(V)
+    o, d = T.camera_rays(**V)
     lw = P.leaf_weights(t, P.march_rays(t, o, d, P.STEP), T.RenderOptions(P.STEP))
     _check_weights("differentiable path", accum.value, lw, "sum", t.child)
 

@@ -132,7 +132,7 @@ def test_helper_is_consistent_with_the_oracle_and_the_definitions(K):
         assert np.abs(b32.aux[:, 1] - b64.aux[:, 1]).max() < 1e-6 * b32.s_max
         # the case shows what the GPU test wants to see, and leaves at most 2 % of its rays out of the surface comparison
         assert b32.aux[:, 0].max() > 0.5 and (b32.aux[:, 0] == 0).any()
-        left_out = A.surface_excluded(b32, b64, C.SURFACE_THRESH)
+        left_out = T.surface_excluded(b32, b64, C.SURFACE_THRESH)
         assert left_out.mean() <= 0.02, (config, int(left_out.sum()))
         assert np.isfinite(b32.aux[~left_out, 2]).sum() >= 20
     o, d = C.explicit_rays(K)
@@ -149,13 +149,14 @@ def test_helper_sample_distance_is_measured_from_the_origin():
     t.data[..., -1] = 1e4
     opt = T.RenderOptions(1e-3)
     o, d = np.array([-3.0, 0.1, 0.2], f32), np.array([1.0, 0.0, 0.0], f32)
-    (samples, scale) = A.march(t, o, d, opt)
+    m = T.march(t, o, d, opt.step_size)
     r32, r64 = A.render_ray_aux(t, o, d, d, opt)
-    first = 2.0 + 0.5 * float(samples[0][2]) * float(scale)
+    first = 2.0 + 0.5 * float(m.delta[0]) * float(m.delta_scale)
     for r in (r32, r64):
         assert abs(float(r.surface) - first) < 1e-6 and r.pick == 0
         assert abs(float(r.alpha) - 1.0) < 1e-6 and abs(float(r.depth) - first) < 1e-5
-    assert [(leaf, float(dt * scale)) for leaf, _, dt in samples] == [(leaf, float(dtw)) for leaf, dtw in T.march_tree(t, o, d, opt)]
+    assert [(leaf, float(dt * m.delta_scale)) for leaf, dt in zip(m.flat.tolist(), m.delta)] == \
+        [(leaf, float(dtw)) for leaf, dtw in T.march_tree(t, o, d, opt)]
 
 
 # ---- writers ------------------------------------------------------------------------------------------------------------

@@ -63,7 +63,7 @@ def test_rod_view_reuses_the_path(depth):
     t = C.make_tree("rod", depth, 4)
     view = C.rod_view(t)
     opt = T.RenderOptions(C.ROD_STEP)
-    o, d = C.camera_rays(view)
+    o, d = T.camera_rays(**view)
     axis = view["W"] * (view["H"] // 2) + view["W"] // 2
     _, _, per_ray = C.depth_coverage(t, o[axis:axis + 1], d[axis:axis + 1], opt)
     need = 1000 if depth >= 8 else 300

@@ -31,18 +31,18 @@ def test_restatement_is_the_reference_convert_to_ndc(golden):
     z = golden
     ndc = N.Ndc(int(z["width"]), int(z["height"]), float(z["focal"]))
     assert (ndc.width, ndc.height, ndc.focal) == (N.W, N.H, N.FX) and z["origins"].shape[0] == 2 * N.W * N.H + 6
-    got = [N.convert_to_ndc_f32(o, d, ndc) for o, d in zip(z["origins"], z["directions"])]
+    got = [T.convert_to_ndc_f32(o, d, ndc) for o, d in zip(z["origins"], z["directions"])]
     go, gd = np.stack([g[0] for g in got]), np.stack([g[1] for g in got])
     assert go.dtype == np.float32 and np.array_equal(go, z["o32"]) and np.array_equal(gd, z["d32"])
     e_o, e_d = float(z["e_ref_o"]), float(z["e_ref_d"])
     assert 0 < e_o < 1e-5 and 0 < e_d < 1e-5
     assert np.abs(go - z["o64"]).max() <= 4 * e_o and np.abs(gd - z["d64"]).max() <= 4 * e_d
     # the fixture's camera rays are the ones the tests render
-    o, d = N.camera_rays(N.camera_b())
+    o, d = T.camera_rays(N.camera_b(), N.W, N.H, N.FX)
     assert np.array_equal(z["origins"][N.W * N.H: 2 * N.W * N.H], o) and np.array_equal(z["directions"][N.W * N.H: 2 * N.W * N.H], d)
     # item 3: the direction that marches is a unit vector and every ray of a forward-facing camera is a hit
     for oo, dd in zip(o[::7], d[::7]):
-        no, nd, ok = N.ndc_ray(oo, dd, ndc)
+        no, nd, ok = T.ndc_ray(oo, dd, ndc)
         assert ok and abs(float(np.linalg.norm(nd.astype(np.float64))) - 1.0) < 1e-6 and nd[2] > 0
 
 
@@ -51,36 +51,36 @@ def test_shared_views_have_hits_and_misses():
     which fills the frustum by construction; at most 21 samples per ray; every image far from the background."""
     ndc = N.Ndc()
     for box in (0, 1):
-        t = N.random_tree(16, box)
+        t = N.box_tree(16, box)
         for cam in "AB":
-            o, d = N.camera_rays(N.CAMERAS[cam]())
+            o, d = T.camera_rays(N.CAMERAS[cam](), N.W, N.H, N.FX)
             for fast in (False, True):
                 opt = T.RenderOptions.for_renderer(1e-3, fast)
-                seqs = [N.march(t, oo, dd, opt, ndc) for oo, dd in zip(o, d)]
+                seqs = [T.march(t, oo, dd, opt.step_size, ndc=ndc) for oo, dd in zip(o, d)]
                 hits = sum(s is not None for s in seqs)
                 assert hits >= 20 and max(len(s) for s in seqs if s is not None) <= 21
                 assert (hits == N.W * N.H) if (box, cam) == (0, "A") else (hits < N.W * N.H), (box, cam, hits)
-                img = N.render_rays(t, o, d, d, opt, ndc)
+                img = T.render_rays(t, o, d, d, opt, ndc=ndc)
                 assert float(np.abs(img - 1.0).max()) > 0.5
 
 
 def test_known_answer_chord_and_world_space_shading():
-    worst, bound = N.known_answer_check(lambda t, o, d, opt: N.render_rays(t, o, d, d, opt, N.Ndc()))
+    worst, bound = N.known_answer_check(lambda t, o, d, opt: T.render_rays(t, o, d, d, opt, ndc=N.Ndc()))
     print(f"known answer: max error {worst:.3g}, bound {bound:.3g}")
     assert bound < 5e-3
 
 
 def test_rays_that_cannot_be_converted_give_the_background():
     ndc = N.Ndc()
-    t = N.random_tree(4, 0)
+    t = N.box_tree(4, 0)
     opt = T.RenderOptions(1e-3, background_brightness=0.25)
     for dz in (0.0, 0.5, -1e-38):
         d = np.array([0.1, -0.2, dz], f32)
         for o in ([0.0, 0.0, 0.0], [0.2, 0.1, -0.5]):
-            assert N.march(t, np.array(o, f32), d, opt, ndc) is None
-            assert np.array_equal(N.render_ray(t, np.array(o, f32), d, d, opt, ndc), np.full(3, 0.25, f32))
+            assert T.march(t, np.array(o, f32), d, opt.step_size, ndc=ndc) is None
+            assert np.array_equal(T.render_ray(t, np.array(o, f32), d, d, opt, ndc=ndc), np.full(3, 0.25, f32))
     # ... while the same origins looking down -z are hits that see the tree
-    assert N.march(t, np.zeros(3, f32), np.array([0.0, 0.0, -1.0], f32), opt, ndc) is not None
+    assert T.march(t, np.zeros(3, f32), np.array([0.0, 0.0, -1.0], f32), opt.step_size, ndc=ndc) is not None
 
 
 # ---- the Python surface ---------------------------------------------------------------------------------------------------

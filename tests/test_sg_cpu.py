@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import _octree_sg_cases as G
-import _octree_sg_oracle as S
+from oracle import octree_oracle as T
 from plenoctree_amd import _lib, build
 from plenoctree_amd.nerf_sh.nerf import checkpoints, families, models, sg, utils
 from plenoctree_amd.octree import compression, evaluation, extraction, svox
@@ -63,13 +63,13 @@ def test_sg_basis_matches_the_references_eval_sg():
         assert lobes[0].tolist() == [30.0, 0.0, 0.0, 1.0] and float(np.abs(fx[f"coeffs_{K}"]).max()) <= c
         lam_max = float(lobes[1:, 0].max()) if K > 1 else 0.0          # lambda_eff: the lobes whose dot product is rounded
         assert lam_max <= 4.02
-        basis = np.stack([S.sg_basis_np(lobes, d) for d in dirs])
+        basis = np.stack([T.sg_basis_np(lobes, d) for d in dirs])
         assert basis.dtype == f32
         tol_basis = (8 * lam_max + 5) * EPS / K
         err = np.abs(basis.astype(np.float64) - fx[f"basis_{K}"])
         print(f"K={K}: basis err {err.max():.3g} (bound {tol_basis:.3g})")
         assert err.max() <= tol_basis, (K, err.max(), tol_basis)
-        assert np.abs(S.sg_basis_f64(lobes, dirs) - fx[f"basis_{K}"]).max() <= tol_basis
+        assert np.abs(T.sg_basis_f64(lobes, dirs) - fx[f"basis_{K}"]).max() <= tol_basis
         # parallel to the sharp lobe: exactly 1/K; anti-parallel: exp(-60), towards 0 without becoming inf / nan
         assert basis[0, 0] == f32(1.0) / f32(K) and 0.0 <= basis[1, 0] < 1e-25
         if K >= 4:                                                  # the nearly flat lobe: 1/K everywhere to 1.4 %
