@@ -352,9 +352,6 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[RBN][CBN]) {
       for (int i = 0; i < 16; ++i) acc[r][c][i] = 0.f;
 }
 
-// accumulator register `reg` of a 32x32 tile holds row (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-__device__ __forceinline__ int frag_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
-
 // Copy of ONE wave's 32 columns of the finished (32*RBN) x 256 LDS tile to a row-major [M,256] global array, by the wave
 // that has just written them (no cross-wave ordering needed: a wave's LDS operations execute in order): per
 // instruction 8 rows x 128 B (whole 128-byte lines).  A workgroup-wide copy of whole 1 KiB rows needs a barrier between
@@ -385,6 +382,48 @@ __device__ __forceinline__ float mask_pop(uint32_t& mw, float x) {
   float r;
   asm volatile("v_add_co_u32 %0, vcc, %0, %0\n\tv_cndmask_b32 %1, 0, %2, vcc" : "+v"(mw), "=v"(r) : "v"(x) : "vcc");
   return r;
+}
+
+// ReLU of an accumulator element as ONE v_max_f32.  fmaxf() on an MFMA result costs two: hipcc canonicalises the operand
+// first (v_max_f32 x, x, x -- it cannot see that an MFMA never returns a signalling NaN; fmed3, a select, an assumption
+// that x is no NaN all end in the same pair), on the f32 lanes the MFMAs run on.  Same bits for everything an MFMA can
+// return: -0 and every negative -> +0, a quiet NaN -> 0 (IEEE mode returns the other operand), denormals kept.  (gfx950
+// has no packed form: v_pk_max exists for f16 only.)
+// REQUIREMENT: hipcc's hazard recognizer does not look into inline asm, so it inserts no wait states between an MFMA
+// and a relu_acc that reads its result (a VALU read of a 16-pass MFMA's destination needs 18).  Every value handed to
+// relu_acc must therefore come out of mfma_results_ready(), never straight from the accumulators.
+__device__ __forceinline__ float relu_acc(float x) {
+  float r;
+  asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+// The wait states relu_acc needs, placed by data dependence and not by the surrounding schedule: the asm takes the
+// accumulator fragments as in/out operands, so it is issued after the last MFMA that writes them and before the first
+// instruction that reads them, wherever the scheduler puts either.  18 idle cycles per fragment, once per layer.
+template <int RBN, int CBN>
+__device__ __forceinline__ void mfma_results_ready(f32x16 (&acc)[RBN][CBN]) {
+#pragma unroll
+  for (int r = 0; r < RBN; ++r)
+#pragma unroll
+    for (int c = 0; c < CBN; ++c) asm volatile("s_nop 15\n\ts_nop 1" : "+v"(acc[r][c]));
+}
+
+// Accumulator register `reg` of a 32x32 tile holds row (reg&3) + 8*(reg>>2) + 4*(lane>>5).  EpiRows: float offsets of
+// this lane's element of register 0 in the LDS tile, for the epilogues' ds_write_b32.  The instruction's immediate
+// offset has 16 bits (65,535 B): it reaches all of row blocks 0-1 from `lo`; row blocks 2-3 start 66,560 B further on
+// and get a second register (as ARows::hi).  Off ONE base hipcc spends a v_add_u32 on each of their 32 stores.
+struct EpiRows {
+  uint32_t lo, hi;
+};
+__device__ __forceinline__ EpiRows make_epi_rows(int col, int lane) {
+  EpiRows e{(uint32_t)(4 * (lane >> 5) * kLDA + col), 0u};
+  e.hi = e.lo + 2 * 32 * kLDA;
+  asm volatile("" : "+v"(e.hi));
+  return e;
+}
+// element `reg` of row block r (the lane part of the row is in make_epi_rows)
+__device__ __forceinline__ uint32_t epi_off(const EpiRows& e, int r, int reg) {
+  return (r < 2 ? e.lo : e.hi) + ((r & 1) * 32 + (reg & 3) + 8 * (reg >> 2)) * kLDA;
 }
 
 constexpr int kRB = kTM / 32;                    // row blocks of a full tile (all owned by every wave)
@@ -497,16 +536,16 @@ __device__ __forceinline__ void fwd_tile(float* __restrict__ lds, const float* _
     uint32_t mw[kMaskWords];
 #pragma unroll
     for (int w = 0; w < kMaskWords; ++w) mw[w] = 0u;
+    mfma_results_ready(acc);     // relu_acc below reads the accumulators through inline asm
 #pragma unroll
     for (int r = 0; r < RBN; ++r)
 #pragma unroll
       for (int c = 0; c < kCB; ++c) {
-        const int col = (wave * kCB + c) * 32 + (lane_e & 31);
+        const EpiRows er = make_epi_rows((wave * kCB + c) * 32 + (lane_e & 31), lane_e);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-          const int row = r * 32 + frag_row(reg, lane_e);
-          const float v = fmaxf(acc[r][c][reg], 0.f);
-          lds[row * kLDA + col] = v;
+          const float v = relu_acc(acc[r][c][reg]);
+          lds[epi_off(er, r, reg)] = v;
           if (SAVE) mask_push(mw[((r * kCB + c) * 16 + reg) >> 5], v);
         }
       }
@@ -677,16 +716,55 @@ __device__ __forceinline__ int bwd_tile(float* __restrict__ lds, float* __restri
   if (SKIP && tid < kChunks) nz[tid] = 0;
   if (SKIP) lds_barrier();
   // d_raw tile -> lds[:, 0:NH] with the head's column order (d_raw_rgb == NULL: sigma-only rows)
-  for (int idx = tid; idx < kRows * NH; idx += kMlpThreads) {
-    const int row = idx / NH, col = idx - row * NH;
-    const int64_t grow = row0 + row;
-    float v = 0.f;
-    if (grow < M) {
-      if (col < C) { if (d_raw_rgb) v = d_raw_rgb[grow * C + col]; }
-      else if (col == C) v = d_raw_sigma[grow];
+  if constexpr (SKIP) {
+    // the skipping instantiations keep the loop below: with the staging of the dense ones their first train step ended in
+    // an illegal memory access whose cause is not found (profiles/EXPERIMENTS.md, "Vector work between the GEMMs")
+    for (int idx = tid; idx < kRows * NH; idx += kMlpThreads) {
+      const int row = idx / NH, col = idx - row * NH;
+      const int64_t grow = row0 + row;
+      float v = 0.f;
+      if (grow < M) {
+        if (col < C) { if (d_raw_rgb) v = d_raw_rgb[grow * C + col]; }
+        else if (col == C) v = d_raw_sigma[grow];
+      }
+      lds[row * kLDA + col] = v;
+      if (v != 0.f) nz[row / kLiveRows] = 1;                        // same value from every writer
     }
-    lds[row * kLDA + col] = v;
-    if (SKIP && v != 0.f) nz[row / kLiveRows] = 1;                // same value from every writer
+  } else {
+    // A thread keeps one column of each 32-column head block and every 16th row.  Its source (an rgb column, the sigma
+    // column, or none) is fixed per block, so the kPer loads of a block are issued back to back -- rows past the tile's last
+    // valid one read that row instead and are zeroed afterwards, no per-element branch -- and waited for once.  (A loop over
+    // idx = tid, tid + 512, .. with idx / NH and one guarded load per trip waited for every load's round trip to HBM in turn:
+    // 16 of them per full SH16 tile, with all eight waves idle.)
+    constexpr int kPer = kRows / (kMlpThreads / 32);          // rows per thread and column block
+    const int c = tid & 31, rsub = tid >> 5;
+    const int last = (int)(M - row0 < kRows ? M - row0 : kRows) - 1;       // the tile's last valid row (>= 0)
+    float v[NHB][kPer];
+#pragma unroll
+    for (int cb = 0; cb < NHB; ++cb) {
+      const int col = cb * 32 + c;
+      const float* __restrict__ src = nullptr;                // this lane's column of the tile's first row
+      int stride = 0;
+      if (col < C) { if (d_raw_rgb) { src = d_raw_rgb + row0 * C + col; stride = C; } }
+      else if (col == C) { src = d_raw_sigma + row0; stride = 1; }
+#pragma unroll
+      for (int i = 0; i < kPer; ++i) v[cb][i] = 0.f;
+      if (src) {
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+          const int row = rsub + kLiveRows * i;
+          v[cb][i] = src[(row < last ? row : last) * stride];
+        }
+      }
+    }
+#pragma unroll
+    for (int cb = 0; cb < NHB; ++cb)
+#pragma unroll
+      for (int i = 0; i < kPer; ++i) {
+        const int row = rsub + kLiveRows * i;
+        const float x = row <= last ? v[cb][i] : 0.f;
+        lds[row * kLDA + cb * 32 + c] = x;
+      }
   }
   lds_barrier();
   if (SKIP) {
@@ -742,14 +820,16 @@ __device__ __forceinline__ int bwd_tile(float* __restrict__ lds, float* __restri
 #pragma unroll
     for (int c = 0; c < kCB; ++c) {
       const int col = (wave * kCB + c) * 32 + (lane_e & 31);
+      EpiRows er{};
+      if constexpr (!SKIP) er = make_epi_rows(col, lane_e);
       float colsum = 0.f;
 #pragma unroll
       for (int r = 0; r < RBN; ++r)
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-          const int row = r * 32 + frag_row(reg, lane_e);
           const float v = mask_pop(mw[((r * kCB + c) * 16 + reg) >> 5], acc[r][c][reg]);
-          lds[row * kLDA + col] = v;
+          if constexpr (SKIP) lds[(r * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane_e >> 5)) * kLDA + col] = v;
+          else lds[epi_off(er, r, reg)] = v;
           colsum += v;
         }
       colsum += __shfl_xor(colsum, 32);
