@@ -458,6 +458,66 @@ int pxo_octree_render_foot_aux_fwd(const PxoTree* tree, const PxoCamera* cam, co
                                    const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float cone, int min_depth,
                                    float surface_thresh, float* out_rgb, float* out_aux, void* stream);
 
+/* ---- scene: several trees in one world, each under its own similarity transform  (no svox counterpart; this project's
+ *      definition -- the "object insertion" of the PlenOctree paper) ----
+ * A scene is n instances, 1 <= n <= PXO_SCENE_MAX_INSTANCES.  Instance i is a float SH tree (PxoTree, any of SH1/4/9/16/25,
+ * formats may differ between instances) and a transform world <- object, x_w = s R x_o + t, R a rotation, s > 0.  A ray is
+ * carried into every object's frame -- the view direction rotates with it, so no coefficient is touched -- and all trees are
+ * marched together, one compositing sample per round.  Forward only.  All in float32, one rounding per operation, no
+ * contraction, in this order (o, d, vdir: the world ray of camera_ray or the explicit arrays; M = rot_t, row-major R^T;
+ * M v means ((M[a][0] v_0 + M[a][1] v_1) + M[a][2] v_2) per row a):
+ *   Set-up, per instance:  o_i = (M (o - t)) * inv_scale,  d_i = M d,  v_i = M vdir;  the tree transform and slab test of the
+ *     single-tree renderer on (o_i, d_i) give o, d, invdir, delta_scale_i, tmin_i, tmax_i.  The instance is hit unless
+ *     tmax_i < 0 or tmin_i > tmax_i or !(tmin_i < tmax_i); a hit instance WAITS.  c_i = scale * delta_scale_i (tree parameter
+ *     -> world length),  enter_i = tmin_i * c_i.  The SH basis of instance i is evaluated on v_i.
+ *   State:  a world parameter w, starting at the smallest enter_i of the waiting instances (none: the ray gets the
+ *     background), light = 1, and per instance a tree parameter tt_i.
+ *   Round:  (1) every waiting instance with enter_i <= w becomes INSIDE at tt_i = tmin_i.  (2) Every inside instance is located
+ *     exactly as the single-tree marchers do it (position o + tt d clamped to [0, 1 - 1e-6], descent, delta_i =
+ *     cell_exit * 2^-(depth+1) + step_size) and offers step_i = delta_i * c_i; every waiting instance offers the gap
+ *     enter_i - w.  D = the minimum of all offers.  With nothing inside, w jumps to the smallest enter_i of the waiting
+ *     instances and the round starts over; with nothing waiting either, the ray ends.
+ *   Sample:  for every inside instance with sigma_i > sigma_thresh (a LIVE instance), tau_i = (D * inv_scale_i) * sigma_i --
+ *     a scaled object keeps its opacity.  tau = ((0 + tau_a) + tau_b) + .. over the live instances in instance order.  If
+ *     tau > 0:  att = expf(-tau),  weight = light * (1 - att),  every live instance in instance order adds
+ *     (weight * (tau_i / tau)) * sigmoid(logit_i,c) to channel c (logit: the 4-lane channel-aligned sum of
+ *     pxo_octree_render_fwd at its default lanes per ray),  light = light * att;  once light <= stop_thresh the colour is
+ *     multiplied by 1 / (1 - light) and the ray ends without a background term.  tau == 0 adds nothing.
+ *   Advance:  an inside instance whose own step_i == D goes to tt_i + delta_i (its exact cell exit: instances of identical
+ *     structure stay in lockstep); every other inside instance goes to tt_i + D / c_i.  An instance leaves when the new
+ *     parameter is >= tmax_i or is not greater than the old one (the no-progress guard of the single-tree marchers).  If the
+ *     gap of a waiting instance was D, w becomes the largest enter_i among those instances, exactly; otherwise w = w + D.
+ *   End:  a ray that did not stop early adds light * background_brightness.
+ * Consequences, all bit for bit: one instance under the identity renders the image of pxo_octree_render_fwd; a tree cut into
+ * two trees of the same structure with complementary sigma renders the whole tree (x / x = 1); an instance under a signed
+ * permutation R and a power-of-two scale seen from the camera carried along renders the plain image.
+ * Out of scope, refused where a caller can reach them: gradients, alpha / depth / surface outputs, float16 / palette / SG
+ * instances, NDC, a depth cap or footprint, non-uniform scale or shear, more than PXO_SCENE_MAX_INSTANCES instances.  There is
+ * no acceleration structure over instances: the per-ray slab tests are the cull. */
+#define PXO_SCENE_MAX_INSTANCES 8
+typedef struct PxoInstance {
+  PxoTree tree;
+  float rot_t[9];               /* R^T, row-major */
+  float trans[3];               /* t */
+  float scale, inv_scale;       /* s and fl(1 / s) */
+} PxoInstance;
+/* Checks n HOST records before the caller uploads them (host only, no launch).  The renderer reads trees, formats and scales
+ * from the device array, which the host cannot inspect at launch: this is where they are refused.  PXO_ERR_ARG: n outside
+ * [1, PXO_SCENE_MAX_INSTANCES], a null pointer, a tree the single-tree renderer would refuse (check_tree: null arrays,
+ * basis_dim outside {1, 4, 9, 16, 25}, data_dim != 3 basis_dim + 1, n_internal out of range), a scale that is not finite or
+ * not > 0, an inv_scale that is not fl(1 / scale), a non-finite rot_t or trans.  Orthonormality of rot_t is the caller's to
+ * ensure. */
+int pxo_scene_check(const PxoInstance* instances, int n);
+/* out_rgb [B,3] (camera mode: [H,W,3]) of the scene in d_instances, the device copy of n records pxo_scene_check has passed;
+ * rays and options as pxo_octree_render_fwd takes them.  Always the scene kernel: a one-instance scene is not forwarded to the single-tree
+ * renderer.  4 lanes per ray whatever pxo_octree_set_lanes_per_ray says; LDS is sized by n (bytes per workgroup:
+ * pxo_scene_lds_bytes).  PXO_ERR_ARG: n outside [1, PXO_SCENE_MAX_INSTANCES], null d_instances, and the option / camera / ray
+ * checks of pxo_octree_render_fwd.  Asynchronous; B == 0 launches nothing. */
+int pxo_scene_render_fwd(const PxoInstance* d_instances, int n, const PxoCamera* cam, const float* origins, const float* dirs,
+                         const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream);
+/* Dynamic LDS of one workgroup (64 rays) of pxo_scene_render_fwd at n instances (host only). */
+int pxo_scene_lds_bytes(int n, size_t* bytes);
+
 /* ---- isosurface meshing  (marching cubes on the device; the reference meshes on the host: nerf_sh/gen_mesh.py:88-130) ----
  * Definition and output order are those of plenoctree_amd/nerf_sh/isosurface.py:marching_cubes, so the arrays compare with ==:
  *   inside(p) = vol[p] >= (float)iso                      vol: float32 [nx, ny, nz], x slowest, finite values

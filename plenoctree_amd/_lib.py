@@ -68,6 +68,14 @@ class PxoTree(Structure):
                 ("basis_dim", c_int32), ("offset", c_float * 3), ("invradius", c_float * 3)]
 
 
+class PxoInstance(Structure):
+    """A tree placed in a scene: x_w = scale * R x_o + trans; rot_t = R^T, row-major (include/plenoctree_octree.h, "scene")."""
+    _fields_ = [("tree", PxoTree), ("rot_t", c_float * 9), ("trans", c_float * 3), ("scale", c_float), ("inv_scale", c_float)]
+
+
+SCENE_MAX_INSTANCES = 8             # PXO_SCENE_MAX_INSTANCES
+
+
 class PxoCamera(Structure):
     _fields_ = [("c2w", c_void_p), ("fx", c_float), ("fy", c_float), ("width", c_int32), ("height", c_int32)]
 
@@ -244,6 +252,9 @@ SIGNATURES = {
                                            POINTER(PxoRenderOpts), c_float, c_int, P, P]),
     "pxo_octree_render_foot_aux_fwd": (c_int, [POINTER(PxoTree), POINTER(PxoCamera), P, P, P, c_int64,
                                                POINTER(PxoRenderOpts), c_float, c_int, c_float, P, P, P]),
+    "pxo_scene_check": (c_int, [POINTER(PxoInstance), c_int]),
+    "pxo_scene_render_fwd": (c_int, [P, c_int, POINTER(PxoCamera), P, P, P, c_int64, POINTER(PxoRenderOpts), P, P]),
+    "pxo_scene_lds_bytes": (c_int, [c_int, POINTER(c_size_t)]),
     "pxo_mc_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "pxo_mc_count": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_size_t, POINTER(c_int64), P]),
     "pxo_mc_emit": (c_int, [P, c_int, c_int, c_int, c_double, P, P, c_size_t, POINTER(c_int64), P, P, P, P]),

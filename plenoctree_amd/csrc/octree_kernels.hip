@@ -2034,6 +2034,250 @@ __global__ void tree_collapse_data_kernel(const int32_t* __restrict__ child, con
   new_data[(new_index[node] * 8 + (cell & 7)) * D + (i - cell * D)] = v;
 }
 
+// ------------------------------------------------------------------------------------------
+// scene: several trees under similarity transforms, marched together (plenoctree_octree.h, "scene")
+// ------------------------------------------------------------------------------------------
+// One ray per row of 4 lanes, 64 rays per workgroup, as the forward renderer at its default; row_ray deals the rays.  The four
+// lanes of a row run the same march (row-uniform control flow) and split a leaf's coefficients exactly as
+// octree_render_kernel<0, 4, true, K> does, with K a run-time value: the same products in the same order, so a one-instance
+// identity scene returns that kernel's bits.
+// Eight instances' ray constants and march state do not fit in registers beside an SH25 dot, and a loop over instances cannot
+// index registers: all per-instance state of a ray lives in dynamic LDS, sized by the launch's instance count.  Per instance:
+//   stack  int   [64 rays][kMaxD + 2]   the Marcher's node path (ray stride 12 words: 16 rays of a wave on 16 distinct banks)
+//   basis  float [64 rays][25]          SH basis on the rotated view direction (stride 25: odd)
+//   field  word  [kSceneFields][64 rays] ray constants, march state and the round's offers, field-major (a wave's 16 rays read
+//                                        16 consecutive words; the 4 lanes of a row the same word: a broadcast)
+// = 4 * (12 + 25 + kSceneFields) = 236 bytes per ray and instance, 15104 per workgroup and instance (8 instances: 120832).
+// Every lane of a row writes the same values to the row's words, so no lane waits for another except for the basis (lane
+// i % 4 evaluates instance i's), which a wave barrier orders.
+constexpr int kSceneRow = 4;
+constexpr int kSceneRays = kRenderThreads / kSceneRow;
+enum SceneField {
+  kScO = 0, kScD = 3, kScInv = 6,               // tree-space origin, unit direction, 1 / (d + 1e-9)
+  kScTmax = 9, kScC, kScEnter, kScT,           // tmax, c = scale * delta_scale, enter = tmin * c, tt (tmin until entered)
+  kScPX, kScPY, kScPZ, kScDepth,               // Marcher: the previous sample's quantised position and depth (-1: no sample yet)
+  kScState,                                    // 0 done, 1 waiting, 2 inside, 3 inside and live in this round
+  kScLeaf, kScDelta, kScStep,                  // this round: leaf, tree-space step, the offer (step or gap) in world length
+  kScTau,                                      // this round: tau_i of a live instance
+  kSceneFields
+};
+constexpr int kSceneWordsPerRay = kMaxD + 2 + 25 + kSceneFields;
+static_assert(kSceneFields == 22 && kSceneWordsPerRay == 59, "scene LDS layout (plenoctree_octree.h, DESIGN)");
+
+struct SceneArgs {
+  const PxoInstance* inst;                     // device array [n]
+  int n;
+  PxoCamera cam;
+  int has_cam;
+  const float* origins;
+  const float* dirs;
+  const float* viewdirs;
+  int64_t B;
+  PxoRenderOpts opt;
+};
+
+__global__ __launch_bounds__(kRenderThreads) void scene_render_kernel(SceneArgs A, float* __restrict__ out_rgb) {
+  extern __shared__ __attribute__((aligned(16))) int s_scene[];
+  const int n = A.n;
+  const int row = threadIdx.x / kSceneRow, l = threadIdx.x % kSceneRow;
+  int* const s_stack = s_scene + row * (kMaxD + 2);                                  // + i * kSceneRays * (kMaxD + 2)
+  float* const s_basis = reinterpret_cast<float*>(s_scene + n * kSceneRays * (kMaxD + 2)) + row * 25;   // + i * kSceneRays * 25
+  int* const s_field = s_scene + n * kSceneRays * (kMaxD + 2 + 25) + row;            // + (i * kSceneFields + f) * kSceneRays
+  auto fi = [&](int i, int f) -> int& { return s_field[(i * kSceneFields + f) * kSceneRays]; };
+  auto ff = [&](int i, int f) -> float& { return reinterpret_cast<float*>(s_field)[(i * kSceneFields + f) * kSceneRays]; };
+
+  float origin[3], dir[3], vdir[3];
+  const RowId id = row_ray<kSceneRow>(A, row, origin, dir, vdir);
+  if (!id.active) return;                      // whole rows leave together; only wave barriers below
+  const int64_t ray = id.ray;
+  const float bg = A.opt.background_brightness;
+
+  // ---- set-up: the ray in every instance's frame ----
+  float w = INFINITY;
+  for (int i = 0; i < n; ++i) {
+    const PxoInstance& I = A.inst[i];
+    float q[3], oi[3], di[3], vi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a] = origin[a] - I.trans[a];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float* m = I.rot_t + 3 * a;
+      oi[a] = ((m[0] * q[0] + m[1] * q[1]) + m[2] * q[2]) * I.inv_scale;
+      di[a] = (m[0] * dir[0] + m[1] * dir[1]) + m[2] * dir[2];
+      vi[a] = (m[0] * vdir[0] + m[1] * vdir[1]) + m[2] * vdir[2];
+    }
+    TreeRay r;
+    to_tree_ray(oi, di, I.tree.offset, I.tree.invradius, r);
+    const bool hit = !(r.tmax < 0.0f || r.tmin > r.tmax) && r.tmin < r.tmax;
+    const float c = I.scale * r.delta_scale;
+    const float enter = r.tmin * c;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      ff(i, kScO + a) = r.o[a];
+      ff(i, kScD + a) = r.d[a];
+      ff(i, kScInv + a) = r.invdir[a];
+    }
+    ff(i, kScTmax) = r.tmax;
+    ff(i, kScC) = c;
+    ff(i, kScEnter) = enter;
+    ff(i, kScT) = r.tmin;
+    fi(i, kScPX) = 0; fi(i, kScPY) = 0; fi(i, kScPZ) = 0;
+    fi(i, kScDepth) = -1;
+    fi(i, kScState) = hit ? 1 : 0;
+    s_stack[i * kSceneRays * (kMaxD + 2)] = 0;
+    if (hit) w = fminf(w, enter);
+    if (hit && l == (i & (kSceneRow - 1))) sh_basis_dyn(I.tree.basis_dim, vi[0], vi[1], vi[2], s_basis + i * kSceneRays * 25);
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (!(w < INFINITY)) {                       // no instance is hit
+    for (int c = l; c < 3; c += kSceneRow) out_rgb[ray * 3 + c] = bg;
+    return;
+  }
+
+  float light = 1.0f;
+  float out[3] = {0.f, 0.f, 0.f};
+  bool stopped = false;
+  while (true) {
+    // ---- offers: a located step from every inside instance, the gap from every waiting one ----
+    float d_min = INFINITY, next_enter = INFINITY;
+    bool any_inside = false;
+    for (int i = 0; i < n; ++i) {
+      int st = fi(i, kScState);
+      if (st == 0) continue;
+      const float enter = ff(i, kScEnter);
+      if (st == 1 && enter <= w) st = 2;
+      if (st >= 2) {
+        TreeRay r;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          r.o[a] = ff(i, kScO + a);
+          r.d[a] = ff(i, kScD + a);
+          r.invdir[a] = ff(i, kScInv + a);
+        }
+        CellExit cell_exit;
+        cell_exit.init(r.invdir);
+        Marcher mk;
+        mk.stack = s_stack + i * kSceneRays * (kMaxD + 2);
+        mk.last_depth = fi(i, kScDepth);
+        mk.first = mk.last_depth < 0;
+        mk.pX = (uint32_t)fi(i, kScPX); mk.pY = (uint32_t)fi(i, kScPY); mk.pZ = (uint32_t)fi(i, kScPZ);
+        int64_t leaf;
+        float delta;
+        locate_leaf(r, cell_exit, mk, A.inst[i].tree.child, A.opt.step_size, ff(i, kScT), leaf, delta);
+        fi(i, kScPX) = (int)mk.pX; fi(i, kScPY) = (int)mk.pY; fi(i, kScPZ) = (int)mk.pZ;
+        fi(i, kScDepth) = mk.last_depth;
+        const float step = delta * ff(i, kScC);
+        fi(i, kScLeaf) = (int)leaf;             // n_internal < 2^28: node * 8 + cell fits
+        ff(i, kScDelta) = delta;
+        ff(i, kScStep) = step;
+        fi(i, kScState) = 2;
+        d_min = fminf(d_min, step);
+        any_inside = true;
+      } else {
+        const float gap = enter - w;
+        ff(i, kScStep) = gap;
+        d_min = fminf(d_min, gap);
+        next_enter = fminf(next_enter, enter);
+      }
+    }
+    if (!any_inside) {
+      if (!(next_enter < INFINITY)) break;      // nothing waiting either
+      w = next_enter;
+      continue;
+    }
+
+    // ---- one sample ----
+    float tau = 0.0f;
+    bool any_live = false;
+    for (int i = 0; i < n; ++i) {
+      if (fi(i, kScState) != 2) continue;
+      const PxoInstance& I = A.inst[i];
+      const float sg = I.tree.data[(int64_t)fi(i, kScLeaf) * I.tree.data_dim + I.tree.data_dim - 1];
+      if (sg > A.opt.sigma_thresh) {
+        const float tau_i = (d_min * I.inv_scale) * sg;
+        ff(i, kScTau) = tau_i;
+        fi(i, kScState) = 3;
+        tau = tau + tau_i;
+        any_live = true;
+      }
+    }
+    if (any_live && tau > 0.0f) {
+      const float att = expf(-tau);
+      const float weight = light * (1.0f - att);
+      for (int i = 0; i < n; ++i) {
+        if (fi(i, kScState) != 3) continue;
+        const PxoInstance& I = A.inst[i];
+        const int K = I.tree.basis_dim;
+        const float* __restrict__ val = I.tree.data + (int64_t)fi(i, kScLeaf) * I.tree.data_dim;
+        const float* Y = s_basis + i * kSceneRays * 25;
+        const int chG = K >> 2, chR = K & 3;
+        float p0 = 0.f, p1 = 0.f, p2 = 0.f;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {           // K <= 25: at most 6 whole groups of four, 2 per lane
+          const int g = l + kSceneRow * m;
+          if (g < chG) {
+            const f32x4u c0 = *reinterpret_cast<const f32x4u*>(val + 4 * g);
+            const f32x4u c1 = *reinterpret_cast<const f32x4u*>(val + K + 4 * g);
+            const f32x4u c2 = *reinterpret_cast<const f32x4u*>(val + 2 * K + 4 * g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float b = Y[4 * g + e];
+              p0 += c0[e] * b;
+              p1 += c1[e] * b;
+              p2 += c2[e] * b;
+            }
+          }
+        }
+        if (l < chR) {
+          const int k = 4 * chG + l;
+          const float b = Y[k];
+          p0 += val[k] * b;
+          p1 += val[K + k] * b;
+          p2 += val[2 * K + k] * b;
+        }
+        p0 = row_sum<kSceneRow>(p0);
+        p1 = row_sum<kSceneRow>(p1);
+        p2 = row_sum<kSceneRow>(p2);
+        const float c0 = 1.0f / (1.0f + expf(-p0)), c1 = 1.0f / (1.0f + expf(-p1)), c2 = 1.0f / (1.0f + expf(-p2));
+        const float share = weight * (ff(i, kScTau) / tau);
+        out[0] += share * c0;
+        out[1] += share * c1;
+        out[2] += share * c2;
+      }
+      light = light * att;
+      if (light <= A.opt.stop_thresh) {
+        const float scale = 1.0f / (1.0f - light);
+        out[0] *= scale; out[1] *= scale; out[2] *= scale;
+        stopped = true;
+        break;
+      }
+    }
+
+    // ---- advance ----
+    float snap = -INFINITY;
+    for (int i = 0; i < n; ++i) {
+      const int st = fi(i, kScState);
+      if (st >= 2) {
+        const float tt = ff(i, kScT);
+        const float tn = ff(i, kScStep) == d_min ? tt + ff(i, kScDelta) : tt + d_min / ff(i, kScC);
+        if (!(tn > tt) || tn >= ff(i, kScTmax)) {
+          fi(i, kScState) = 0;
+        } else {
+          ff(i, kScT) = tn;
+          fi(i, kScState) = 2;
+        }
+      } else if (st == 1 && ff(i, kScStep) == d_min) {
+        snap = fmaxf(snap, ff(i, kScEnter));
+      }
+    }
+    w = snap > -INFINITY ? snap : w + d_min;
+  }
+  if (!stopped) {
+    out[0] += light * bg; out[1] += light * bg; out[2] += light * bg;
+  }
+  for (int c = l; c < 3; c += kSceneRow) out_rgb[ray * 3 + c] = c == 0 ? out[0] : (c == 1 ? out[1] : out[2]);
+}
+
 }  // namespace pxo
 
 // ==========================================================================================
@@ -2865,6 +3109,61 @@ int pxo_grid_weight_count_work(const float* sigma_grid, int reso, const float* c
   hipLaunchKernelGGL(grid_count_kernel, dim3((unsigned)blocks_for(rays, 256)), dim3(256), 0, (hipStream_t)stream, sigma_grid, reso,
                      c2w_all, n_cams, fx, fy, width, height, *opts, o, ir, counts, voxel_seen);
   return check_launch("grid_weight_count_work");
+}
+
+// ---- scene (plenoctree_octree.h, "scene") ----
+static int check_scene_n(int n, const char* who) {
+  PXO_REQUIRE(n >= 1 && n <= PXO_SCENE_MAX_INSTANCES, "%s: %d instances, a scene takes 1 .. %d", who, n, PXO_SCENE_MAX_INSTANCES);
+  return PXO_OK;
+}
+
+int pxo_scene_lds_bytes(int n, size_t* bytes) {
+  if (int rc = check_scene_n(n, "pxo_scene_lds_bytes")) return rc;
+  PXO_REQUIRE(bytes, "pxo_scene_lds_bytes: null pointer");
+  *bytes = (size_t)n * kSceneRays * kSceneWordsPerRay * sizeof(int);
+  return PXO_OK;
+}
+
+int pxo_scene_check(const PxoInstance* instances, int n) {
+  const char* who = "pxo_scene_check";
+  if (int rc = check_scene_n(n, who)) return rc;
+  PXO_REQUIRE(instances, "%s: null instances", who);
+  for (int i = 0; i < n; ++i) {
+    const PxoInstance& I = instances[i];
+    if (int rc = check_tree(&I.tree, nullptr, who)) return rc;
+    PXO_REQUIRE(I.scale > 0.0f && I.scale < INFINITY, "%s: instance %d: scale %g must be finite and > 0", who, i, (double)I.scale);
+    PXO_REQUIRE(I.inv_scale == 1.0f / I.scale, "%s: instance %d: inv_scale %g is not 1 / scale", who, i, (double)I.inv_scale);
+    bool finite = true;
+    for (int k = 0; k < 9; ++k) finite = finite && fabsf(I.rot_t[k]) < INFINITY;
+    for (int k = 0; k < 3; ++k) finite = finite && fabsf(I.trans[k]) < INFINITY;
+    PXO_REQUIRE(finite, "%s: instance %d: rot_t / trans must be finite", who, i);
+  }
+  return PXO_OK;
+}
+
+int pxo_scene_render_fwd(const PxoInstance* d_instances, int n, const PxoCamera* cam, const float* origins, const float* dirs,
+                         const float* viewdirs, int64_t B, const PxoRenderOpts* opts, float* out_rgb, void* stream) {
+  const char* who = "pxo_scene_render_fwd";
+  if (int rc = check_scene_n(n, who)) return rc;
+  PXO_REQUIRE(d_instances, "%s: null instances", who);
+  if (int rc = check_opts(opts, who)) return rc;
+  SceneArgs A;
+  unsigned grid;
+  if (int rc = launch_shape(cam, origins, dirs, viewdirs, B, kSceneRow, who, A, grid)) return rc;
+  if (B == 0) return PXO_OK;
+  PXO_REQUIRE(out_rgb, "%s: null output", who);
+  A.inst = d_instances;
+  A.n = n;
+  A.opt = *opts;
+  const size_t lds = (size_t)n * kSceneRays * kSceneWordsPerRay * sizeof(int);
+  // more than 64 KB of dynamic LDS (5 instances and up) has to be allowed per function and device; a host-side setting
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(scene_render_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess) {
+    set_error("%s: %zu bytes of LDS for %d instances refused by the device", who, lds, n);
+    return PXO_ERR_HIP;
+  }
+  hipLaunchKernelGGL(scene_render_kernel, dim3(grid), dim3(kRenderThreads), lds, (hipStream_t)stream, A, out_rgb);
+  return check_launch(who);
 }
 
 int pxo_image_mse(const float* im, const float* gt, int64_t n, float* grad, float* sse_out, void* stream) {

@@ -1122,6 +1122,128 @@ class VolumeRenderer:
         return self._aux_dict(*oops.octree_render_aux_rays(view, origins, dirs, viewdirs, self._opts(fast), surface_thresh))
 
 
+# ---- scenes (an addition, no svox counterpart): several trees in one world, each under its own transform ------------------
+class Instance:
+    """A tree placed in a scene: x_world = scale * rotation @ x_object + translation.
+
+    rotation: 3x3, orthonormal with det +1 (within 1e-5, checked in float64); translation: 3 finite numbers; scale: finite, > 0.
+    matrix=: instead of the three, a 3x3 (scale * rotation) or 4x4 ([scale * rotation | translation; 0 0 0 1]) matrix, from
+    which the uniform scale is extracted (cbrt of the determinant); non-uniform scale and shear fail the rotation check.
+    Float SH N3Tree only: a QuantizedN3Tree, a HalfN3Tree and an SG tree are refused by name."""
+
+    def __init__(self, tree, rotation=None, translation=None, scale=None, matrix=None):
+        if isinstance(tree, _ReadOnlyTree):
+            raise NotImplementedError(f"Instance of a {tree.NOUN}: a scene renders float SH trees only; call tree.{tree.WAY_OUT}() "
+                                      "for an N3Tree")
+        if not isinstance(tree, N3Tree):
+            raise TypeError(f"Instance(tree): expected an svox.N3Tree, got {type(tree).__name__}")
+        if getattr(tree, "extra_data", None) is not None:
+            raise NotImplementedError(f"Instance of an SG tree ({tree.data_format}): a scene renders SH trees only")
+        if matrix is not None:
+            if rotation is not None or translation is not None or scale is not None:
+                raise ValueError("Instance(matrix=...) excludes rotation, translation and scale")
+            m = np.asarray(matrix, np.float64)
+            if m.shape == (4, 4):
+                if not np.array_equal(m[3], [0.0, 0.0, 0.0, 1.0]):
+                    raise ValueError(f"Instance(matrix=...): the last row of a 4x4 matrix must be (0, 0, 0, 1), got {m[3].tolist()}")
+                translation, m = m[:3, 3], m[:3, :3]
+            elif m.shape != (3, 3):
+                raise ValueError(f"Instance(matrix=...): expected a 3x3 or 4x4 matrix, got shape {m.shape}")
+            det = np.linalg.det(m) if np.isfinite(m).all() else np.nan
+            if not (np.isfinite(det) and det > 0):
+                raise ValueError(f"Instance(matrix=...): determinant {det} is not finite and > 0 (no reflection, no collapse)")
+            scale = float(np.cbrt(det))
+            rotation = m / scale
+        self.tree = tree
+        self.rotation = np.eye(3) if rotation is None else np.asarray(rotation, np.float64)
+        self.translation = np.zeros(3) if translation is None else np.asarray(translation, np.float64)
+        self.scale = 1.0 if scale is None else scale
+        if isinstance(self.scale, bool) or not isinstance(self.scale, (int, float, np.integer, np.floating)) or \
+                not (np.isfinite(self.scale) and self.scale > 0 and np.isfinite(np.float32(self.scale))
+                     and np.float32(self.scale) > 0):
+            raise ValueError(f"Instance(scale={scale!r}): must be a finite number > 0")
+        self.scale = float(self.scale)
+        R = self.rotation
+        if R.shape != (3, 3) or not np.isfinite(R).all():
+            raise ValueError(f"Instance(rotation=...): expected a finite 3x3 matrix, got shape {R.shape}")
+        if np.abs(R.T @ R - np.eye(3)).max() > 1e-5 or abs(np.linalg.det(R) - 1.0) > 1e-5:
+            raise ValueError("Instance(rotation=...): not a rotation (R^T R = I and det R = +1 within 1e-5); non-uniform scale, "
+                             "shear and reflections are not built")
+        if self.translation.shape != (3,) or not np.isfinite(self.translation).all():
+            raise ValueError(f"Instance(translation=...): expected 3 finite numbers, got {self.translation!r}")
+
+    def __repr__(self):
+        return f"svox.Instance({self.tree!r}, scale={self.scale:g}, translation={self.translation.tolist()})"
+
+
+class SceneRenderer:
+    """Renders 1 .. 8 Instances together (the definition: include/plenoctree_octree.h, "scene"): every ray is
+    carried into each object's frame, the view direction with it, and the trees are marched in one loop with one compositing
+    sample per round, so overlapping objects blend by density and a scaled object keeps its opacity.  Forward only.
+
+    Refused by name: ndc, max_depth / lod_pixels, a tree that requires grad with grad mode on, a render inside
+    accumulate_weights, and (by Instance) the read-only and SG forms.  A one-instance scene still runs the scene kernel.
+    The device records are rebuilt whenever a tree's `child` or `data` tensor has been replaced since the last render."""
+
+    def __init__(self, instances, step_size=1e-3, background_brightness=1.0, ndc=None, max_depth=None, lod_pixels=None):
+        if ndc is not None:
+            raise NotImplementedError("SceneRenderer(ndc=...): NDC scenes are not built (an NDC tree lives in one camera's "
+                                      "projection, not in a world that objects can share)")
+        if max_depth is not None or lod_pixels:
+            raise NotImplementedError("SceneRenderer(max_depth=... / lod_pixels=...): level of detail is not built for a scene; "
+                                      "place tree.lod(L) as the instance instead")
+        instances = list(instances)
+        if not 1 <= len(instances) <= oops._lib.SCENE_MAX_INSTANCES:
+            raise ValueError(f"SceneRenderer: a scene takes 1 .. {oops._lib.SCENE_MAX_INSTANCES} instances, got {len(instances)}")
+        for i in instances:
+            if not isinstance(i, Instance):
+                raise TypeError(f"SceneRenderer: expected svox.Instance objects, got {type(i).__name__}")
+        if len({i.tree.device for i in instances}) != 1:
+            raise ValueError("SceneRenderer: the instances' trees must live on one device")
+        self.instances = instances
+        self.step_size = float(step_size)
+        self.background_brightness = float(background_brightness)
+        self._scene, self._scene_of = None, None
+
+    @property
+    def device(self):
+        return self.instances[0].tree.device
+
+    def _opts(self, fast):
+        thr = 1e-2 if fast else 0.0
+        return oops.render_opts(self.step_size, self.background_brightness, thr, thr)
+
+    def _records(self, what):
+        for k, i in enumerate(self.instances):
+            t = i.tree
+            if torch.is_grad_enabled() and t.requires_grad:
+                raise NotImplementedError(f"SceneRenderer.{what}: instance {k}'s tree requires grad and there is no gradient "
+                                          "through a scene; render under torch.no_grad()")
+            if t._weight_accum is not None:
+                raise NotImplementedError(f"SceneRenderer.{what} inside accumulate_weights (instance {k}): the weights of a "
+                                          "scene's samples are shared between trees; accumulate them with a VolumeRenderer")
+        # a structure edit replaces tree.child, an assignment to tree.data the parameter, one to tree.data.data its storage
+        now = tuple((i.tree.child, i.tree.data, i.tree.data.data_ptr()) for i in self.instances)
+        if self._scene_of is None or any(a[0] is not b[0] or a[1] is not b[1] or a[2] != b[2]
+                                         for a, b in zip(now, self._scene_of)):
+            self._scene = oops.scene_instances([(i.tree.view(), i.rotation, i.translation, i.scale) for i in self.instances],
+                                               self.device)
+            self._scene_of = now                     # also keeps the tensors the records point into alive
+        return self._scene
+
+    def render_persp(self, c2w, width=800, height=800, fx=1111.111, fy=None, fast=False):
+        """[H,W,3] image of the scene from a world-space pinhole camera."""
+        scene = self._records("render_persp")
+        c2w = torch.as_tensor(c2w, dtype=torch.float32, device=self.device)
+        return oops.scene_render_persp(scene, c2w, width, height, fx, self._opts(fast), fy)
+
+    def forward(self, origins, dirs, viewdirs, fast=False):
+        """Colours [B,3] of explicit world-space rays (unit `dirs`); `viewdirs` shade them, rotated into each object's frame."""
+        return oops.scene_render_rays(self._records("forward"), origins, dirs, viewdirs, self._opts(fast))
+
+    __call__ = forward
+
+
 # ---- svox.helpers._get_c_extension(): the slice of svox's native module the reference touches ---------------------------
 class _RenderOptions:
     """svox.csrc RenderOptions as filled in by octree/extraction.py:184-195."""

@@ -561,6 +561,75 @@ def octree_render_rays_bwd(tree, origins, dirs, viewdirs, opts, grad_out, grad_d
     return _render_bwd(tree, lobes, _rays(None, origins, dirs, viewdirs), opts, out_rgb, grad_out, grad_data, ndc=ndc)
 
 
+# ---- scene: several float SH trees in one world, each under a similarity transform (include/plenoctree_octree.h, "scene") ----
+class SceneInstances:
+    """The device array of a scene's PxoInstance records (`records`: uint8 on the trees' device) and their count.  Keeps no
+    reference to the trees' tensors: the caller owns them for as long as the scene is rendered."""
+
+    def __init__(self, records, n):
+        self.records, self.n = records, n
+
+
+def scene_instances(instances, device=None):
+    """instances: a sequence of (PxoTree, rotation 3x3, translation 3, scale) with rotation R of x_w = scale R x_o +
+    translation (float64 on the host; orthonormality is the caller's to check, svox.Instance does).  Checked by
+    pxo_scene_check -- count, tree formats, scales -- and uploaded: a SceneInstances."""
+    import numpy as np
+    n = len(instances)
+    if not 1 <= n <= _lib.SCENE_MAX_INSTANCES:
+        raise PxoError(f"a scene takes 1 .. {_lib.SCENE_MAX_INSTANCES} instances, got {n}")
+    host = (_lib.PxoInstance * n)()
+    for rec, (tree, rotation, translation, scale) in zip(host, instances):
+        if not isinstance(tree, _lib.PxoTree):
+            raise NotImplementedError(f"a scene instance must be a float SH tree (PxoTree), got {type(tree).__name__}: float16, "
+                                      "palette and SG instances are not built")
+        rec.tree = tree
+        rot_t = np.asarray(rotation, np.float64).reshape(3, 3).T.astype(np.float32)
+        rec.rot_t = (ctypes.c_float * 9)(*rot_t.reshape(-1).tolist())
+        rec.trans = _vec3(np.asarray(translation, np.float64).reshape(3))
+        s = np.float32(scale)
+        rec.scale = float(s)
+        with np.errstate(all="ignore"):
+            rec.inv_scale = float(np.float32(1.0) / s)
+    check(_lib.load().pxo_scene_check(host, n), "pxo_scene_check")
+    _require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    records = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
+    return SceneInstances(records, n)
+
+
+def _scene_forward(scene, opts, camera=None, rays=None):
+    _require_gpu()
+    if not isinstance(scene, SceneInstances):
+        raise PxoError(f"expected the SceneInstances of scene_instances(), got {type(scene).__name__}")
+    if camera is not None:
+        cam, keep = _camera(*camera)
+        shape, rays = (cam.height, cam.width, 3), _rays(cam)
+    else:
+        shape, rays = (rays[0].shape[0], 3), _rays(None, *rays)
+    out = _new(*shape, device=scene.records.device)
+    check(_lib.load().pxo_scene_render_fwd(_p(scene.records), scene.n, *rays, ctypes.byref(opts), _f(out), _stream()),
+          "pxo_scene_render_fwd")
+    return out
+
+
+def scene_render_persp(scene, c2w, width, height, fx, opts, fy=None):
+    """[H,W,3] image of the scene (a SceneInstances) from a pinhole camera.  Always the scene kernel, also for one instance."""
+    return _scene_forward(scene, opts, camera=(c2w, width, height, fx, fy))
+
+
+def scene_render_rays(scene, origins, dirs, viewdirs, opts):
+    """[B,3] colours of explicit world-space rays with unit dirs through the scene."""
+    return _scene_forward(scene, opts, rays=(origins, dirs, viewdirs))
+
+
+def scene_lds_bytes(n):
+    """Dynamic LDS per workgroup of the scene kernel at n instances (host only)."""
+    v = ctypes.c_size_t(0)
+    check(_lib.load().pxo_scene_lds_bytes(int(n), ctypes.byref(v)), "pxo_scene_lds_bytes")
+    return v.value
+
+
 MSE_BLOCK, MSE_PER_THREAD, MSE_MAX_BLOCKS = 256, 8, 4096     # pxo_image_mse's launch (kMseBlock, kMsePerThread, kMseMaxBlocks)
 
 
